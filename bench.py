@@ -1,14 +1,24 @@
 """bench.py -- Mrays/s and ms/frame of the rayca hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload atrium|soup|cornell|box|atrium4k] [--no-others]
+    python bench.py --gpus N --steps K --warmup W [--workload atrium|soup|cornell|box|atrium4k] [--dump-outputs DIR]
+                    [--full [--no-others] [--no-latency] [--no-cpu-baseline]]
 
 A "step" is one frame: every rank renders its rows of the frame with the HIP kernels (scene and BVH already resident
 in HBM) and rank 0 receives the gathered RGBA8 frame (N > 1: ONE RCCL gather per frame, at frame end).  Default
 workload = the configuration BASELINE.json's metric is quoted on: 1920x1080, primary + 1 shadow ray per hit (Pathtracer
 max_depth=1, NEE, one point light), 1 spp, on the ~272k-triangle procedural atrium -- a STAND-IN for Sponza, which is
-not available offline.  The default run then times BASELINE's other GPU configurations the same way, shorter, and
-reports them under `config.other_workloads` (each with its own roofline): the 1M-triangle soup at 4096x4096 (Flat), the
-Cornell room at 1080p (Flat), the atrium at 3840x2160 with four bounces.
+not available offline.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `config`).  `--full` adds
+everything else below: `roofline`, `latency`, `cpu_baseline`, for N > 1 the gathered-frame check and the batched-gather
+run, and (default workload) BASELINE's other GPU configurations timed the same way, shorter, under
+`config.other_workloads` (each with its own roofline): the 1M-triangle soup at 4096x4096 (Flat), the Cornell room at
+1080p (Flat), the atrium at 3840x2160 with four bounces.
+
+`--dump-outputs DIR` writes, after the timed steps, the frame the timed path delivered in its last step (rank 0's
+frame, RGBA8 values as float32) to DIR/frame.npy: the whole (H, W, 4) frame when it fits in DUMP_LIMIT_BYTES, else a
+fixed, seeded sample of its pixels, (n, 4), with their flat pixel indices (y * W + x) in DIR/frame_pixels.npy
+(float64).  The scenes are procedural with fixed seeds, so the same arguments give the same inputs on every run.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (rayca_amd/launcher.py: plain
 child processes, started before anything touches a GPU); under `python -m torch.distributed.run` the ranks come from
@@ -16,9 +26,10 @@ the launcher's environment as usual.
 
 One JSON line on rank 0:
   value         whole-job Mrays/s = rays traced by all ranks in K steps / max-over-ranks wall time, with ONE gather per
-                frame for N > 1 (`config.frame_gather`); the same K steps with four frames per collective are timed as
-                well and reported next to it (`config.gather_batched`) -- never as `value`
-  roofline      the kernel the frame spends most of its time in (RaycaStats.class_ms: HIP events around every launch,
+                frame for N > 1 (`config.frame_gather`); with --full the same K steps with four frames per collective
+                are timed as well and reported next to it (`config.gather_batched`) -- never as `value`
+  ms_per_step   max-over-ranks wall time of the K timed steps / K, in milliseconds
+  roofline      (--full) the kernel the frame spends most of its time in (RaycaStats.class_ms: HIP events around every launch,
                 on the launch stream, by kernel class): its average launch duration, priced against every hardware limit
                 it could hit -- VALU issue, L1 (vector cache) accesses, L2 fill, HBM traffic, compulsory HBM bytes; `bound`
                 names the one it is closest to and `frac` is that fraction.  The per-launch counter values come from the
@@ -28,10 +39,10 @@ One JSON line on rank 0:
                 (profiles/peaks_r03.json).  SURVEY 8(d)'s algorithmic bytes (32 B per box test + 36 B per triangle test
                 + 272 B per shaded hit + 4 B per pixel, counted by the instrumented instantiation of the same kernels)
                 are kept as `algorithmic_access_rate`: they are served by L1/L2, not by HBM.
-  latency       N = 1: one frame at a time -- kernels only (HIP events), through rayca_hip_render_device + a synchronise,
+  latency       (--full) N = 1: one frame at a time -- kernels only (HIP events), through rayca_hip_render_device + a synchronise,
                 and through rayca_hip_render, the drop-in draw(): kernels + the copy into the caller's host image
                 (what scene.rs:101-152 times), into ordinary and into page-locked host memory
-  cpu_baseline  the CPU oracle (port of the reference algorithm, per-test vertex transforms, all host cores of this
+  cpu_baseline  (--full) the CPU oracle (port of the reference algorithm, per-test vertex transforms, all host cores of this
                 job's share) on an evenly spaced subset of the same frame's rows; rank 0, N = 1, main workload only
 """
 from __future__ import annotations
@@ -59,8 +70,12 @@ L1_ACCESSES_PER_CLK_CU_DEFAULT = 0.99
 
 KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill", "k_wf_shade", "k_wf_shadow", "k_shadow_refill", "other")
 
-# the other BASELINE GPU configurations the default run times after the main one: (workload, steps, warmup)
+# the other BASELINE GPU configurations --full times after the main one: (workload, steps, warmup)
 OTHER_WORKLOADS = (("soup", 24, 4), ("cornell", 200, 8), ("atrium4k", 16, 4))
+
+# --dump-outputs: at most this many bytes of .npy payload (the 1080p frame as float32 is 33 MB); larger frames are sampled
+DUMP_LIMIT_BYTES = 60_000_000
+DUMP_SEED = 0x5EED0D
 
 
 def workload_config(name):
@@ -89,7 +104,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)   # (0.4 ms each: long enough that filling and draining four frames in flight is noise)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--workload", default="atrium")
-    ap.add_argument("--no-others", action="store_true", help="only the main workload (the default run adds soup, cornell and atrium4k under config.other_workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, latency, CPU baseline, the N > 1 frame check and "
+                         "batched gather, and (default workload) soup, cornell and atrium4k under config.other_workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; see the module docstring)")
+    ap.add_argument("--no-others", action="store_true", help="--full: only the main workload (no config.other_workloads)")
     ap.add_argument("--band-rows", type=int, default=8)
     ap.add_argument("--builder", default="sah", choices=["sah", "reference"],
                     help="sah: SAH tree with empty-seeded candidate boxes (default); reference: the reference's tree, quirks included")
@@ -100,7 +120,26 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the RGBA8 frame (H, W, 4) the timed path delivered, as float32 -- whole, or a fixed seeded sample of
+    its pixels when the whole frame would exceed DUMP_LIMIT_BYTES (then with the pixels' flat indices, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.asarray(frame)
+    if frame.size * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame.astype(np.float32))
+        return
+    pixels = frame.reshape(-1, 4)
+    n = DUMP_LIMIT_BYTES // (4 * 4 + 8)   # an RGBA float32 sample + its float64 index per pixel
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame.npy"), pixels[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_pixels.npy"), idx.astype(np.float64))
 
 
 def measured_peaks():
@@ -316,6 +355,7 @@ def run_workload(env, args, name, steps, warmup, main):
         def step(self):
             c = self.counter % F
             self.counter += 1
+            self.last = c
             self.issue[c]()
             return outs[c]
 
@@ -359,12 +399,20 @@ def run_workload(env, args, name, steps, warmup, main):
     algo_bytes = 32 * counted["boxes_tested"] + 36 * counted["triangles_tested"] + 272 * counted["hits_shaded"] + 4 * my_rows * W
 
     frame_check = None
+    full = args.full
     if world == 1:
-        elapsed = timed(LocalLoop())
+        loop = LocalLoop()
+        elapsed = timed(loop)
+        last_frame = outs[loop.last]
         elapsed_batched, B2 = None, 1
     else:
         sg = StreamGatherLoop()
         elapsed = timed(sg)                                  # `value`: one gather per frame
+        last_frame = sg.frames[sg.last]
+        elapsed_batched, B2 = None, 1
+    if main and args.dump_outputs and rank == 0:   # what the caller of the timed path received in its last step
+        dump_outputs(args.dump_outputs, last_frame.cpu().numpy())
+    if world > 1 and full:
         if rank == 0:   # the frame rank 0 holds after the last gather == the frame one GPU renders on its own, bit for bit
             whole = torch.empty((H, W, 4), dtype=torch.uint8, device=dev)
             ds.render_device(cfg, W, H, whole.data_ptr(), 0, stream=stream.cuda_stream)
@@ -373,37 +421,38 @@ def run_workload(env, args, name, steps, warmup, main):
         B2 = max(1, min(args.gather_batch, 8))
         elapsed_batched = timed(GatherLoop(B2)) if (B2 > 1 and main) else None
 
-    # kernel durations with HIP events on the launch stream, one frame at a time (separate loop: the events force a sync
-    # per step), by kernel class: RaycaStats.class_ms / class_launches
-    kms, tms = [], []
-    class_ms = np.zeros(8)
-    class_n = np.zeros(8)
-    launches_per_frame = 1
-    for _ in range(4):   # (the scene sizes its grids by the frame contexts of the last four calls: from here on there is one)
-        ds.render_device(cfg, W, H, out.data_ptr(), 0, tile=tile, stream=stream.cuda_stream, want_stats=True)
-    n_probe = max(3, min(steps, 20))
-    for _ in range(n_probe):
-        st = ds.render_device(cfg, W, H, out.data_ptr(), 0, tile=tile, stream=stream.cuda_stream, want_stats=True)
-        kms.append(st["kernel_ms"])
-        tms.append(st["trace_kernel_ms"])
-        class_ms += np.array(st["class_ms"])
-        class_n += np.array(st["class_launches"])
-        launches_per_frame = max(int(st["trace_kernel_launches"]), 1)
-    class_ms /= n_probe
-    class_n /= n_probe
-    frame_kernel_ms = float(np.mean(kms))
-    trace_frame_ms = float(np.mean(tms))     # all traversal launches of a frame
-    traversal = [k for k in range(7) if k != 4 and class_n[k] > 0]   # (4 = k_wf_shade, 7 = other: not traversal kernels)
-    dominant = max(traversal, key=lambda k: class_ms[k]) if traversal else 7
-    dom_name = KERNEL_NAMES[dominant]
-    dom_launch_ms = float(class_ms[dominant] / max(class_n[dominant], 1.0))
-    kernels = {KERNEL_NAMES[k]: {"launches_per_frame": round(float(class_n[k]), 2), "avg_launch_ms": round(float(class_ms[k] / class_n[k]), 4),
-                                 "ms_per_frame": round(float(class_ms[k]), 4), "share_of_frame_kernel_time": round(float(class_ms[k] / max(frame_kernel_ms, 1e-9)), 3)}
-               for k in range(8) if class_n[k] > 0}
+    if full:
+        # kernel durations with HIP events on the launch stream, one frame at a time (separate loop: the events force a sync
+        # per step), by kernel class: RaycaStats.class_ms / class_launches
+        kms, tms = [], []
+        class_ms = np.zeros(8)
+        class_n = np.zeros(8)
+        launches_per_frame = 1
+        for _ in range(4):   # (the scene sizes its grids by the frame contexts of the last four calls: from here on there is one)
+            ds.render_device(cfg, W, H, out.data_ptr(), 0, tile=tile, stream=stream.cuda_stream, want_stats=True)
+        n_probe = max(3, min(steps, 20))
+        for _ in range(n_probe):
+            st = ds.render_device(cfg, W, H, out.data_ptr(), 0, tile=tile, stream=stream.cuda_stream, want_stats=True)
+            kms.append(st["kernel_ms"])
+            tms.append(st["trace_kernel_ms"])
+            class_ms += np.array(st["class_ms"])
+            class_n += np.array(st["class_launches"])
+            launches_per_frame = max(int(st["trace_kernel_launches"]), 1)
+        class_ms /= n_probe
+        class_n /= n_probe
+        frame_kernel_ms = float(np.mean(kms))
+        trace_frame_ms = float(np.mean(tms))     # all traversal launches of a frame
+        traversal = [k for k in range(7) if k != 4 and class_n[k] > 0]   # (4 = k_wf_shade, 7 = other: not traversal kernels)
+        dominant = max(traversal, key=lambda k: class_ms[k]) if traversal else 7
+        dom_name = KERNEL_NAMES[dominant]
+        dom_launch_ms = float(class_ms[dominant] / max(class_n[dominant], 1.0))
+        kernels = {KERNEL_NAMES[k]: {"launches_per_frame": round(float(class_n[k]), 2), "avg_launch_ms": round(float(class_ms[k] / class_n[k]), 4),
+                                     "ms_per_frame": round(float(class_ms[k]), 4), "share_of_frame_kernel_time": round(float(class_ms[k] / max(frame_kernel_ms, 1e-9)), 3)}
+                   for k in range(8) if class_n[k] > 0}
 
     # one frame at a time, end to end (N = 1): what a host that calls draw() per frame sees
     latency = None
-    if world == 1 and not args.no_latency:
+    if world == 1 and full and not args.no_latency:
         import ctypes as C
         reps = max(3, min(steps, 10))
         issue1 = ds.prepare_device(cfg, W, H, out.data_ptr(), 0, tile=tile, stream=stream.cuda_stream, context=0)
@@ -477,15 +526,6 @@ def run_workload(env, args, name, steps, warmup, main):
     if rank != 0:
         return None
     mrays = rays_total * steps / elapsed_max / 1e6
-    algo_rate = algo_bytes / (max(trace_frame_ms, 1e-9) * 1e-3) / 1e9
-    # what MUST cross the HBM interface once per frame: the scene's arrays in (nodes, 48-B primitive records, shading
-    # records), path records and pixels out -- per launch of
-    # the dominant kernel: its share of the frame's traversal launches
-    records = (16 + 16 + 4) * my_rows * W * max(wl_generations, 1) if is_path else 0   # direct colour, radiance factor, state per pixel and depth
-    n_nodes, n_tris = int(info["node_count"]), int(info["triangle_count"])
-    node_bytes = {0: (48 if node_format & 4096 else 64) * n_nodes, 1: 128 * n_nodes // 3, 4: 32 * n_nodes, 5: 64 * n_nodes // 3}[node_format & 5]
-    compulsory_frame = node_bytes + (48 + 256 + 8) * n_tris + records + 4 * my_rows * W
-    compulsory = compulsory_frame if launches_per_frame == 1 else (node_bytes + 48 * n_tris + (records + 4 * my_rows * W) // max(launches_per_frame, 1))
     fmt = lambda w, h: ("4-wide" if w else "binary") + (" fp16" if h else " f32")   # noqa: E731
     result = {
         "metric": "Mrays/sec (primary+shadow), 1920x1080 Sponza 1spp" if name == "atrium" else f"Mrays/sec ({name})",
@@ -513,45 +553,55 @@ def run_workload(env, args, name, steps, warmup, main):
                    "frame_gather": (f"torch.distributed.gather ({'RCCL' if backend == 'nccl' else backend}) to rank 0, ONE collective per frame at frame end, behind the frame on the frame's own stream"
                                     if world > 1 else "none"),
                    "launched_by": "torch.distributed.run / environment" if os.environ.get("TORCHELASTIC_RUN_ID") else ("bench.py (rayca_amd/launcher.py)" if world > 1 else "single process")},
-        "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": None, "peak": None, "unit": "GB/s", "frac": None, "traffic": None,
-                     "launch_ms": round(dom_launch_ms, 4), "launches_per_frame": round(float(class_n[dominant]), 2), "frame_kernel_ms": round(frame_kernel_ms, 4),
-                     "kernels": kernels,
-                     "algorithmic_access_rate": {"bytes_per_frame": int(algo_bytes), "GBps": round(algo_rate, 1), "x_hbm_peak": round(algo_rate / HBM_PEAK_GBS, 3),
-                                                 "note": "SURVEY 8(d): every node and triangle a ray touches, over the frame's traversal kernels; served by L1/L2 (the tree is cache resident), so this is an access rate, not an HBM fraction",
-                                                 "boxes_tested": int(counted["boxes_tested"]), "triangles_tested": int(counted["triangles_tested"]),
-                                                 "hits_shaded": int(counted["hits_shaded"])},
-                     "compulsory_bytes_per_launch": int(compulsory)},
     }
     if world > 1 and elapsed_batched is not None:
         result["config"]["gather_batched"] = {"frames_per_collective": B2, "ms_per_step": round(elapsed_batched_max / steps * 1e3, 4),
                                               "Mrays_per_s": round(rays_total * steps / elapsed_batched_max / 1e6, 3),
                                               "note": "the same K frames, B finished frames per collective (fewer rendezvous); reported for comparison, not as `value`"}
-    rl = result["roofline"]
-    counters, pmc_ms, src = pmc_for(name, args.builder, dom_name, node_format & 5, 48 if node_format & 4096 else 64) if world == 1 else (None, None, "counters describe the whole frame on one GPU")
-    if counters:
-        lim = roofline_limits(counters, dom_launch_ms, compulsory)
-        rl.update(lim)
-        rl["pmc_source"] = src
-        rl["pmc_launch_ms"] = pmc_ms
-        top_name, top = max(lim["limits"].items(), key=lambda kv: kv[1]["frac"])
-        rl["bound"] = {"valu_issue": "valu", "l1_accesses": "l1", "l2_fill": "l2", "hbm_traffic": "hbm", "hbm_compulsory": "hbm"}[top_name]
-        rl["achieved"], rl["peak"], rl["unit"], rl["frac"] = top["achieved"], top["peak"], top["unit"], top["frac"]
-        rl["traffic"] = lim["hbm_traffic_bytes"]
-        rl["hbm_frac"] = lim["limits"]["hbm_traffic"]["frac"]
-        # the same limits over the TIMED REGION: with frames in flight the launches overlap, a frame completes every
-        # ms_per_step, and the chip issues launches_per_frame x the per-launch counters in that time -- the fraction of the
-        # limit the bench's operating point runs at, next to `frac` (one launch alone on the chip, with its tail)
-        step_s = elapsed_max / steps
-        if launches_per_frame == 1 and step_s > 0:
-            rl["over_timed_region"] = {k: round(v["frac"] * (dom_launch_ms * 1e-3) / step_s, 4) for k, v in lim["limits"].items()}
-            rl["over_timed_region"]["note"] = f"per-launch counters / ms_per_step ({F} frames in flight): what the chip sustains while frames overlap"
-    else:   # no usable counters for this kernel / format / rank count: the compulsory-bytes HBM figure is what can be stated
-        a = compulsory / (dom_launch_ms * 1e-3) / 1e9
-        rl["achieved"], rl["peak"], rl["frac"] = round(a, 1), HBM_PEAK_GBS, round(a / HBM_PEAK_GBS, 4)
-        rl["note"] = f"{src}: frac prices the compulsory HBM bytes only"
+    if full:
+        algo_rate = algo_bytes / (max(trace_frame_ms, 1e-9) * 1e-3) / 1e9
+        # what MUST cross the HBM interface once per frame: the scene's arrays in (nodes, 48-B primitive records, shading
+        # records), path records and pixels out -- per launch of
+        # the dominant kernel: its share of the frame's traversal launches
+        records = (16 + 16 + 4) * my_rows * W * max(wl_generations, 1) if is_path else 0   # direct colour, radiance factor, state per pixel and depth
+        n_nodes, n_tris = int(info["node_count"]), int(info["triangle_count"])
+        node_bytes = {0: (48 if node_format & 4096 else 64) * n_nodes, 1: 128 * n_nodes // 3, 4: 32 * n_nodes, 5: 64 * n_nodes // 3}[node_format & 5]
+        compulsory_frame = node_bytes + (48 + 256 + 8) * n_tris + records + 4 * my_rows * W
+        compulsory = compulsory_frame if launches_per_frame == 1 else (node_bytes + 48 * n_tris + (records + 4 * my_rows * W) // max(launches_per_frame, 1))
+        result["roofline"] = {"bound": "hbm", "kernel": dom_name, "achieved": None, "peak": None, "unit": "GB/s", "frac": None, "traffic": None,
+                              "launch_ms": round(dom_launch_ms, 4), "launches_per_frame": round(float(class_n[dominant]), 2), "frame_kernel_ms": round(frame_kernel_ms, 4),
+                              "kernels": kernels,
+                              "algorithmic_access_rate": {"bytes_per_frame": int(algo_bytes), "GBps": round(algo_rate, 1), "x_hbm_peak": round(algo_rate / HBM_PEAK_GBS, 3),
+                                                          "note": "SURVEY 8(d): every node and triangle a ray touches, over the frame's traversal kernels; served by L1/L2 (the tree is cache resident), so this is an access rate, not an HBM fraction",
+                                                          "boxes_tested": int(counted["boxes_tested"]), "triangles_tested": int(counted["triangles_tested"]),
+                                                          "hits_shaded": int(counted["hits_shaded"])},
+                              "compulsory_bytes_per_launch": int(compulsory)}
+        rl = result["roofline"]
+        counters, pmc_ms, src = pmc_for(name, args.builder, dom_name, node_format & 5, 48 if node_format & 4096 else 64) if world == 1 else (None, None, "counters describe the whole frame on one GPU")
+        if counters:
+            lim = roofline_limits(counters, dom_launch_ms, compulsory)
+            rl.update(lim)
+            rl["pmc_source"] = src
+            rl["pmc_launch_ms"] = pmc_ms
+            top_name, top = max(lim["limits"].items(), key=lambda kv: kv[1]["frac"])
+            rl["bound"] = {"valu_issue": "valu", "l1_accesses": "l1", "l2_fill": "l2", "hbm_traffic": "hbm", "hbm_compulsory": "hbm"}[top_name]
+            rl["achieved"], rl["peak"], rl["unit"], rl["frac"] = top["achieved"], top["peak"], top["unit"], top["frac"]
+            rl["traffic"] = lim["hbm_traffic_bytes"]
+            rl["hbm_frac"] = lim["limits"]["hbm_traffic"]["frac"]
+            # the same limits over the TIMED REGION: with frames in flight the launches overlap, a frame completes every
+            # ms_per_step, and the chip issues launches_per_frame x the per-launch counters in that time -- the fraction of the
+            # limit the bench's operating point runs at, next to `frac` (one launch alone on the chip, with its tail)
+            step_s = elapsed_max / steps
+            if launches_per_frame == 1 and step_s > 0:
+                rl["over_timed_region"] = {k: round(v["frac"] * (dom_launch_ms * 1e-3) / step_s, 4) for k, v in lim["limits"].items()}
+                rl["over_timed_region"]["note"] = f"per-launch counters / ms_per_step ({F} frames in flight): what the chip sustains while frames overlap"
+        else:   # no usable counters for this kernel / format / rank count: the compulsory-bytes HBM figure is what can be stated
+            a = compulsory / (dom_launch_ms * 1e-3) / 1e9
+            rl["achieved"], rl["peak"], rl["frac"] = round(a, 1), HBM_PEAK_GBS, round(a / HBM_PEAK_GBS, 4)
+            rl["note"] = f"{src}: frac prices the compulsory HBM bytes only"
     if latency:
         result["latency"] = latency
-    if main and world == 1 and not args.no_cpu_baseline:
+    if main and world == 1 and full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(desc, cfg, W, H, args.cpu_seconds)
     return result
 
@@ -599,7 +649,7 @@ def main():
 
     result = run_workload(env, args, args.workload, args.steps, args.warmup, main=True)
     others = []
-    if args.workload == "atrium" and not args.no_others:
+    if args.workload == "atrium" and args.full and not args.no_others:
         for name, k, w in OTHER_WORKLOADS:
             r = run_workload(env, args, name, k, w, main=False)
             if r is not None:
