@@ -65,7 +65,7 @@ struct FrameCtx {
                                       // previous frame cleared them): generation 0 needs no memset launch
   hipEvent_t ev_done = nullptr;       // recorded behind the last kernel of every frame of this context
   bool frame_pending = false;         // ev_done has been recorded at least once
-  std::vector<hipEvent_t> ev_trace;   // pairs around each generation kernel
+  std::vector<hipEvent_t> ev_trace;   // pairs around the timed launches of a frame (LaunchLog)
   std::mutex mu;
 };
 
@@ -320,6 +320,10 @@ void make_scene_streams(RaycaScene* s, bool all) {
   (void)hipGetLastError();
 }
 
+// one allocation: TraceCounters, then (128-B aligned) the 64 statistics lines of k_wf_shade
+constexpr size_t kShadeStatsOffset = ((sizeof(TraceCounters) + 127) / 128) * 128;
+constexpr size_t kCountersBytes = kShadeStatsOffset + 64 * 16 * sizeof(unsigned long long);
+
 // first use of a frame context: stream, counters, events
 int32_t ensure_ctx(RaycaScene* s, FrameCtx* c) {
   if (c->ready) return RAYCA_OK;
@@ -338,13 +342,11 @@ int32_t ensure_ctx(RaycaScene* s, FrameCtx* c) {
     HIP_TRY(hipMemset(c->heads_alloc, 0, (16 * 64 + 64) * sizeof(uint32_t)));
   }
   if (!c->counters) {
-    constexpr size_t off = ((sizeof(TraceCounters) + 127) / 128) * 128;
-    constexpr size_t bytes = off + 64 * 16 * sizeof(unsigned long long);
     void* ctr = nullptr;
-    HIP_TRY(hipMalloc(&ctr, bytes));
+    HIP_TRY(hipMalloc(&ctr, kCountersBytes));
     c->counters = static_cast<TraceCounters*>(ctr);
-    c->shade_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctr) + off);
-    HIP_TRY(hipMemset(c->counters, 0, bytes));
+    c->shade_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctr) + kShadeStatsOffset);
+    HIP_TRY(hipMemset(c->counters, 0, kCountersBytes));
   }
   // hipMemset of device memory is asynchronous (null stream) and the frame streams are non-blocking: without this
   // the zeroing could land in the middle of the first kernel and hand out batches twice
@@ -377,18 +379,6 @@ bool is_emissive(const RaycaMaterial& m) {  // phong.rs:54-56, Color::close colo
   return !close_to_black;
 }
 
-// one allocation: TraceCounters, then (128-B aligned) the 64 statistics lines of k_wf_shade
-constexpr size_t kShadeStatsOffset = ((sizeof(TraceCounters) + 127) / 128) * 128;
-constexpr size_t kCountersBytes = kShadeStatsOffset + 64 * 16 * sizeof(unsigned long long);
-
-// Single-generation path frames (primary + shadow rays, one sample): fold the vertex and write the pixel in k_generation
-// itself instead of records + k_resolve.  Measured twice, lost twice: round 1 with the fold inside the divergent state
-// machine (0.734 vs 0.695 ms), round 2 with the fold at the reconverged point behind the ray loop (two frames in flight:
-// 0.4727 vs 0.4222 ms, same pixels) -- the 8x8-tile pixel stores and the longer tail of the persistent kernel cost more
-// than k_resolve's coalesced pass.  Off; kept so that the measurement can be repeated (-DRAYCA_FUSE_PATH1=1).
-#ifndef RAYCA_FUSE_PATH1
-#define RAYCA_FUSE_PATH1 0
-#endif
 #ifndef RAYCA_WF_LDS_ENTRIES
 #define RAYCA_WF_LDS_ENTRIES 16u
 #endif
@@ -437,9 +427,6 @@ GenKernel gen_kernel2(Trav t, bool sph, bool stats) {
 // use the instantiation without them
 GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats) {
   if (mode == kModeFlat) return fused ? gen_kernel2<kModeFlat, true, true>(t, sph, stats) : gen_kernel2<kModeFlat, true, false>(t, sph, stats);
-#if RAYCA_FUSE_PATH1
-  if (fused) return gen_kernel2<kModePath, true, true>(t, sph, stats);  // a single-generation path frame: pixels straight from generation 0
-#endif
   return gen0 ? gen_kernel2<kModePath, true, false>(t, sph, stats) : gen_kernel2<kModePath, false, false>(t, sph, stats);
 }
 
@@ -462,23 +449,17 @@ TraceKernel trace_kernel(Trav t) {
 // Which node format a generation traverses.  Measured on MI355X (atrium, 1080p, A/B in one run):
 // coherent camera/shadow rays are VALU-bound and the binary tree wins (0.37 vs 0.43 ms for the primary
 // generation: the 4-wide node tests more boxes and sorts), incoherent bounce rays are latency-bound
-// and the 4-wide tree wins (-9 % on the 4-bounce frame).  RAYCA_WIDE=0/1 forces one format.
+// and the 4-wide tree wins (-9 % on the 4-bounce frame).
 // RAYCA_NODE_FORMAT=0..3 pins the node format of every generation (bit 0 = 4-wide, bit 1 = fp16 boxes) instead of
 // letting the scene time them; RAYCA_WIDE=0/1 is the older spelling for the f32 formats.  For profiling sessions,
 // where counter collection perturbs the timing.
 int format_forced() {
-#if defined(RAYCA_WIDE_ALWAYS)
-  return 1;
-#elif defined(RAYCA_WIDE_NEVER)
-  return 0;
-#else
   static const int forced = [] {
     if (const char* e = getenv("RAYCA_NODE_FORMAT")) return atoi(e) & 3;
     if (const char* e = getenv("RAYCA_WIDE")) return atoi(e) ? 1 : 0;
     return -1;
   }();
   return forced;
-#endif
 }
 int wide_forced() {
   const int f = format_forced();
@@ -486,14 +467,7 @@ int wide_forced() {
 }
 bool use_wide(uint32_t generation) {
   const int forced = wide_forced();
-  if (forced >= 0) return forced != 0;
-#if defined(RAYCA_WIDE_ALWAYS)
-  return true;
-#elif defined(RAYCA_WIDE_NEVER)
-  return false;
-#else
-  return generation > 0;
-#endif
+  return forced >= 0 ? forced != 0 : generation > 0;
 }
 
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
@@ -514,6 +488,19 @@ StackPlan plan_stack(uint32_t need, uint32_t max_entries = kMaxLdsEntries) {
   p.spill_entries = want > p.lds_entries ? want - p.lds_entries : 0u;
   p.lds_bytes = (size_t)p.lds_entries * kBlock * 4u;
   return p;
+}
+// A launch's node stack: the LDS part, and the spill area (a column per thread of the grid: entry e of thread t at
+// ovf[e * ovf_stride + t]) when the plan needs one.  The context's one spill area grows to the largest launch.
+int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch& tl) {
+  tl = TraceLaunch{};
+  tl.lds_entries = sp.lds_entries;
+  if (sp.spill_entries) {
+    tl.ovf_stride = grid * kBlock;
+    const int32_t rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
+    if (rc != RAYCA_OK) return rc;
+    tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
+  }
+  return RAYCA_OK;
 }
 
 #ifndef RAYCA_PATH_LDS_ENTRIES
@@ -600,6 +587,35 @@ int32_t kernel_registers(const void* k, uint32_t& regs) {
   return RAYCA_OK;
 }
 
+// Grid of a persistent kernel, whose blocks take batches (64 rays or one 8x8 tile) off a work counter until none are
+// left.  Persistent blocks need no co-residency (there are no inter-block waits), so the grid only has to fill every CU:
+// blocks per CU = what registers and LDS admit (one 256-thread block = one wave per SIMD; 512 VGPRs per lane per SIMD,
+// allocated in granules of 8; 160 KiB of LDS per CU), and no more blocks than the batches fill (4 per block).
+// `per_cu_forced` != 0 replaces the blocks per CU (RAYCA_GRID_MULT, for experiments).
+// `capped`: at most 8 blocks per CU, and fewer with frames in flight (the stack machine goes without both).  A frame
+// that takes every block slot of the chip keeps the next frame's blocks out until its own retire; with fewer slots per
+// frame the blocks of two frames are resident side by side and one frame's slow tiles run under the other's work
+// (DESIGN.md, "the frames leave each other room"; tests/gpu_inflight_probe.py with RAYCA_GRID_MULT).
+int32_t persistent_grid(const RaycaScene* s, const void* kernel, size_t lds_bytes, uint32_t batches, bool capped, uint32_t in_flight,
+                        uint32_t per_cu_forced, uint32_t& grid) {
+  uint32_t per_cu = per_cu_forced;
+  if (per_cu == 0) {
+    uint32_t regs = 0;
+    const int32_t rc = kernel_registers(kernel, regs);
+    if (rc != RAYCA_OK) return rc;
+    per_cu = std::min(512u / (((regs + 7u) / 8u) * 8u), lds_bytes ? (uint32_t)((160u * 1024u) / lds_bytes) : 8u);
+    if (capped) {
+      per_cu = std::max(1u, std::min(per_cu, 8u));
+      if (in_flight >= 4u) per_cu = (per_cu + 1u) / 2u;
+      else if (in_flight >= 2u) per_cu = (per_cu * 3u + 3u) / 4u;
+    }
+    per_cu = std::max(1u, per_cu);
+  }
+  const uint32_t need = (batches + 3u) / 4u;
+  grid = std::min((uint32_t)s->cu_count * per_cu, need ? need : 1u);
+  return RAYCA_OK;
+}
+
 // ---- wavefront engine: one generation = k_wf_trace, k_wf_shade, k_wf_shadow (wavefront.inc) -------------------
 using WfTraceKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, TraceCounters*, TraceLaunch);
 using WfShadowKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, TraceCounters*, TraceLaunch);
@@ -637,27 +653,256 @@ WfShadeKernel pick_wf_shade(int mode, bool gen0, bool fused, bool sph) {
   return sph ? k_wf_shade<kModePath, false, false, true> : k_wf_shade<kModePath, false, false, false>;
 }
 
+// ---- one frame: render_body drives the per-engine launch steps below ------------------------------------------------
+
+// The launches of one frame: how many, and the event pairs around the timed ones (the i-th timed launch, of class
+// ev_class[i], sits between events 2i and 2i + 1 of the context's ev_trace, which are made on first use and kept).
+struct LaunchLog {
+  FrameCtx* c = nullptr;
+  size_t ev_used = 0;
+  std::vector<int> ev_class;   // kernel class (RAYCA_KERNEL_*) per event pair
+  uint32_t launches = 0, trace_launches = 0;
+};
+// One launch: `launch()` issues it and returns RAYCA_OK or an error.  `timed`: bracketed by an event pair of kernel class
+// `cls`, whose index in ev_trace (of its first event) goes to *pair.  `trace`: it counts as a traversal launch.
+template <typename Launch>
+int32_t timed_launch(LaunchLog& log, hipStream_t stream, int cls, bool timed, bool trace, Launch&& launch, size_t* pair = nullptr) {
+  std::vector<hipEvent_t>& ev = log.c->ev_trace;
+  if (timed) {
+    for (hipEvent_t e; ev.size() < log.ev_used + 2;) {
+      HIP_TRY(hipEventCreate(&e));
+      ev.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(ev[log.ev_used], stream));
+    log.ev_class.push_back(cls);
+    if (pair) *pair = log.ev_used;
+    log.ev_used += 2;
+  }
+  const int32_t rc = launch();
+  if (rc != RAYCA_OK) return rc;
+  HIP_TRY(hipGetLastError());
+  if (timed) HIP_TRY(hipEventRecord(ev[log.ev_used - 1], stream));
+  ++log.launches;
+  if (trace) ++log.trace_launches;
+  return RAYCA_OK;
+}
+
+// generation class, index of the event pair, the format launched; refill: -1 = a format calibration, 0/1 = a kernel calibration
+struct TuneEvent { int cls; size_t ev; int format; int refill; };
+
+// What the steps of one frame share.
+struct Frame {
+  RaycaScene* s;
+  FrameCtx* c;
+  RaycaConfig cfg;
+  RaycaRenderOptions opts;
+  LaunchPlan plan;
+  FrameParams fp;
+  PathBuffers pb;
+  hipStream_t stream;
+  const DevScene* dscene;           // s->dev_full once the other node formats are there, else s->dev
+  uint8_t* rgba8;
+  float4* rgba32f;
+  uint32_t in_flight;               // frames_in_flight_hint
+  bool fused;                       // one generation, one sample: the generation kernel writes the pixel (no k_resolve)
+  bool timing;                      // RaycaStats asked for: every launch timed
+  bool all_formats;                 // formats_ready
+  uint32_t node_format;             // RaycaStats.node_format
+  int frame_format[2] = {-2, -2};   // node format of this frame per generation class (-2 = not asked yet, -1 = default)
+  bool frame_calibrates[2] = {false, false};
+  std::vector<TuneEvent> tune_events;   // calibration launches of this frame
+  LaunchLog log;
+};
+
+// generation g reads queue (g - 1) & 1 and writes queue g & 1; their counters sit behind the 8 padded work counters
+struct GenQueues {
+  QueuedRay* in;
+  uint32_t* in_count;
+  QueuedRay* out;
+  uint32_t* out_count;
+};
+
+// One generation of the wavefront engine: closest hits, shading, then shadow rays + direct lighting when there are any.
+int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
+  RaycaScene* s = f.s;
+  FrameCtx* c = f.c;
+  const bool sph = s->host.sphere_count != 0, fast = s->dev.ref_leaf_of != nullptr, stats = f.plan.stats;
+  if (fast)   // (the formats these kernels are compiled for: RAYCA_WF_*, trace_core.inc)
+    f.node_format |= g == 0 ? ((RAYCA_WF_PRIMARY_WIDE ? 1u : 0u) | (RAYCA_WF_PRIMARY_HALF ? 4u : 0u)) : ((RAYCA_WF_BOUNCE_WIDE ? 2u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 8u : 0u));
+  // 16 LDS entries per lane (16 KiB per block) so that the lean kernels' occupancy is set by registers
+  // (the wide tree never needs more pending entries than the binary one: one plan serves both)
+  const StackPlan sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
+  const int flavour = !fast ? 2 : (sp.spill_entries ? 1 : 0);
+  const uint32_t npix = f.pb.npix;
+  const uint32_t batches = g == 0 ? f.fp.tile_count : (npix + 63u) / 64u;
+  const uint32_t grid = (batches + 3u) / 4u;  // one thread per ray, four 8x8 tiles per block
+  const uint32_t nls = (f.plan.mode == kModePath && f.cfg.direct_sampler == RAYCA_SAMPLER_NEE) ? (uint32_t)s->host.lights.size() * f.cfg.light_samples : 0u;
+  int32_t rc;
+  WfBuffers wb{};
+  if ((rc = ensure(c->wf_hits, (size_t)npix * 16u)) != RAYCA_OK) return rc;
+  wb.hits = static_cast<float4*>(c->wf_hits.ptr);
+  wb.nls = nls;
+  if (nls) {
+    if ((rc = ensure(c->wf_sh_ray, (size_t)npix * nls * 32u)) != RAYCA_OK) return rc;
+    if ((rc = ensure(c->wf_sh_x, (size_t)npix * nls * 16u)) != RAYCA_OK) return rc;
+    wb.sh_ray = static_cast<float4*>(c->wf_sh_ray.ptr);
+    wb.sh_x = static_cast<float4*>(c->wf_sh_x.ptr);
+  }
+  // On a SAH scene the bounce generations' closest hits run on persistent lanes that take the next queue entry when their
+  // ray is done (refill.hip k_queue_refill; RAYCA_WF_REFILL=0 keeps one ray per lane, k_wf_trace), and so do the shadow
+  // rays (k_shadow_refill; RAYCA_WF_SHADOW_REFILL: 0 never, 1 bounce generations, 2 every generation), on the second
+  // set of work counters.  The work counters are cleared by render_body, every generation.
+  static const bool wf_refill = [] { const char* e = getenv("RAYCA_WF_REFILL"); return e ? atoi(e) != 0 : true; }();
+  static const int shadow_refill_mode = [] { const char* e = getenv("RAYCA_WF_SHADOW_REFILL"); return e ? atoi(e) : 1; }();
+  TraceLaunch tl{};
+  uint32_t lgrid = grid;
+  bool refill = wf_refill && g != 0 && fast;
+  if (refill && (rc = persistent_grid(s, queue_refill_kernel(sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
+  if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
+  if (refill) tl.ticket = 1u;
+  WfTraceKernel kt = g == 0 ? pick_wf_trace<true>(flavour, sph, stats) : pick_wf_trace<false>(flavour, sph, stats);
+  rc = timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_QUEUE_REFILL : RAYCA_KERNEL_WF_TRACE, f.timing, true, [&] {
+    if (refill)
+      launch_queue_refill(sph, stats, lgrid, sp.lds_bytes, f.stream, *f.dscene, q.in, q.in_count, wb.hits, c->heads, c->counters, tl);
+    else
+      hipLaunchKernelGGL(kt, dim3(lgrid), dim3(kBlock), sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, wb, c->counters, tl);
+    return RAYCA_OK;
+  });
+  if (rc != RAYCA_OK) return rc;
+  WfShadeKernel ks = pick_wf_shade(f.plan.mode, g == 0, f.fused, sph);
+  const uint32_t shade_grid = ((g == 0 ? f.fp.tile_count * 64u : npix) + kShadeBlock - 1) / kShadeBlock;
+  rc = timed_launch(f.log, f.stream, RAYCA_KERNEL_WF_SHADE, f.timing, false, [&] {
+    hipLaunchKernelGGL(ks, dim3(shade_grid), dim3(kShadeBlock), 0, f.stream, *f.dscene, f.fp, q.in, q.in_count, q.out, q.out_count, wb, f.pb, g,
+                       f.rgba8, f.rgba32f, c->shade_stats);
+    return RAYCA_OK;
+  });
+  if (rc != RAYCA_OK || !nls) return rc;
+  lgrid = grid;
+  refill = wf_refill && fast && (g != 0 ? shadow_refill_mode >= 1 : shadow_refill_mode >= 2);
+  if (refill && (rc = persistent_grid(s, shadow_refill_kernel(g == 0, sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
+  if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
+  if (refill) tl.ticket = 1u;
+  WfShadowKernel kh = g == 0 ? pick_wf_shadow<true>(flavour, sph, stats) : pick_wf_shadow<false>(flavour, sph, stats);
+  const ShadowRefillArgs sa{wb.sh_ray, wb.sh_x, wb.nls, f.pb.direct, f.pb.state, f.pb.npix};
+  return timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_SHADOW_REFILL : RAYCA_KERNEL_WF_SHADOW, f.timing, true, [&] {
+    if (refill)
+      launch_shadow_refill(g == 0, sph, stats, lgrid, sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, sa, g, c->heads_b, c->counters, tl);
+    else
+      hipLaunchKernelGGL(kh, dim3(lgrid), dim3(kBlock), sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, wb, f.pb, g, c->counters, tl);
+    return RAYCA_OK;
+  });
+}
+
+// What one generation of the fused engine launches: its node format (decided by timing on this scene, RaycaScene::Tune, or
+// forced by RAYCA_NODE_FORMAT / RAYCA_WIDE), and for Flat camera rays k_generation or the lane-refill kernel.
+struct GenChoice {
+  int format;          // -1 = default, else bit 0 = 4-wide nodes, bit 1 = fp16 nodes
+  bool calibrating;    // a node-format calibration launch
+  bool refill;         // k_flat_refill instead of k_generation
+  bool refill_cal;     // a kernel calibration launch
+};
+GenChoice choose_generation(Frame& f, uint32_t g) {
+  RaycaScene* s = f.s;
+  const LaunchPlan& plan = f.plan;
+  RaycaScene::Tune& tu = s->tune[plan.mode == kModePath ? 1 : 0][g == 0 ? 0 : 1];
+  GenChoice ch{f.all_formats ? format_forced() : 0, false, false, false};  // (binary f32 until the other formats are there)
+  // Flat camera rays on a SAH scene: k_generation, or the lane-refill kernel (refill.hip)?  Decided per scene by timing
+  // eight frames (RAYCA_REFILL=0/1 pins it) -- BEFORE the node format is timed, on 4-wide f32 nodes: the kernels differ
+  // by far more than the formats do (soup: 6.2 against 11 ms), and the formats rank differently under the two (soup:
+  // binary and 4-wide fp16 nodes tie under k_generation, 7.2 against 6.2 ms under lane refill), so the format has to be
+  // timed on the kernel that will run it.
+  static const int refill_env = [] { const char* e = getenv("RAYCA_REFILL"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+  const bool refill_possible = f.fused && plan.mode == kModeFlat && plan.ordered && s->dev.ref_leaf_of != nullptr;
+  const int refill_forced = !refill_possible ? 0 : (f.opts.camera_rays == RAYCA_CAMERA_REFILL ? 1 : (f.opts.camera_rays == RAYCA_CAMERA_GENERATION ? 0 : refill_env));
+  ch.refill = refill_forced > 0;
+  bool kernel_pending = false;
+  if (refill_possible && f.all_formats && refill_forced < 0) {   // (the timing runs on 4-wide nodes: once they are there)
+    std::lock_guard<std::mutex> tune_lock(s->tune_mu);
+    if (tu.refill >= 0) ch.refill = tu.refill != 0;
+    else if (f.pb.npix >= 65536u && !plan.stats && tu.refill_launched < 8u) {
+      ch.refill = (tu.refill_launched++ & 1u) != 0;
+      ch.refill_cal = true;
+      if (ch.format < 0) ch.format = 1;
+    } else {
+      kernel_pending = true;
+    }
+  }
+  const bool can_tune = plan.ordered && s->dev.ref_leaf_of != nullptr && wide_forced() < 0 && f.all_formats;
+  if (can_tune && !ch.refill_cal && !kernel_pending) {
+    const int cls = g == 0 ? 0 : 1;
+    if (f.frame_format[cls] == -2) {  // one decision per frame and class: all bounce generations of a frame use one format
+      std::lock_guard<std::mutex> tune_lock(s->tune_mu);
+      f.frame_format[cls] = -1;
+      if (tu.decided >= 0) f.frame_format[cls] = tu.decided;
+      else if (f.pb.npix >= 65536u && !plan.stats && tu.launched < 16u) {  // the counting instantiation is slower: never timed
+        f.frame_format[cls] = (int)(tu.launched++ & 3u);
+        f.frame_calibrates[cls] = true;
+      }
+    }
+    if (f.frame_format[cls] >= 0) ch.format = f.frame_format[cls];
+    ch.calibrating = f.frame_calibrates[cls];
+  }
+  return ch;
+}
+
+// One generation of the fused engine: one k_generation (or k_flat_refill) launch.
+int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
+  RaycaScene* s = f.s;
+  FrameCtx* c = f.c;
+  const GenChoice ch = choose_generation(f, g);
+  // path frames park each lane's ShadeCtx behind the stack rows (kernels.hip, RAYCA_PARK_CTX): 7 KiB per wave.  Their
+  // LDS part of the stack is capped at path_lds_entries() so that four blocks per CU still fit 160 KiB; deeper
+  // entries go to the (cold) spill area.
+  const bool park = RAYCA_PARK_CTX && f.plan.mode == kModePath;
+  const TravPlan tp = plan_traversal(s, f.plan.ordered, g, ch.format, park ? path_lds_entries() : kMaxLdsEntries);
+  f.node_format |= (tp.wide ? (g == 0 ? 1u : 2u) : 0u) | (tp.half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
+                   (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u);
+  const StackPlan sp = tp.stack;
+  const size_t lds_bytes = sp.lds_bytes + (park ? (size_t)kCtxQuads * 16u * kBlock : 0u);
+  const bool sph = s->host.sphere_count != 0;
+  GenKernel k = pick_kernel(f.plan.mode, g == 0, f.fused, tp.trav, sph, f.plan.stats);
+  const RefillFlavour rf{sph, tp.wide, tp.wide || sp.spill_entries != 0, f.plan.stats, tp.half};
+  const uint32_t batches = g == 0 ? f.fp.tile_count : (f.pb.npix + 63u) / 64u;
+  static const uint32_t grid_mult = [] { const char* e = getenv("RAYCA_GRID_MULT"); return e ? (uint32_t)atoi(e) : 0u; }();
+  uint32_t grid = 0;
+  TraceLaunch tl{};
+  int32_t rc = persistent_grid(s, ch.refill ? flat_refill_kernel(rf) : reinterpret_cast<const void*>(k), lds_bytes, batches, true, f.in_flight, grid_mult, grid);
+  if (rc != RAYCA_OK || (rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
+  // work tickets (next_batch): pairs of batches while every wave still gets several, single batches for small frames
+  static const uint32_t ticket_forced = [] { const char* e = getenv("RAYCA_TICKET"); return e ? (uint32_t)atoi(e) : 0u; }();
+  tl.ticket = ticket_forced ? ticket_forced : (batches >= 16u * grid ? 2u : 1u);
+  size_t ev = 0;
+  rc = timed_launch(f.log, f.stream, ch.refill ? RAYCA_KERNEL_FLAT_REFILL : RAYCA_KERNEL_GENERATION, f.timing || ch.calibrating || ch.refill_cal, true, [&] {
+    if (ch.refill)
+      launch_flat_refill(rf, grid, lds_bytes, f.stream, *f.dscene, f.fp, c->heads, f.rgba8, f.rgba32f, c->counters, tl);
+    else
+      hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds_bytes, f.stream, *f.dscene, f.fp, c->heads, q.in, q.in_count, q.out, q.out_count, f.pb, g,
+                         f.rgba8, f.rgba32f, c->counters, tl);
+    return RAYCA_OK;
+  }, &ev);
+  if (rc != RAYCA_OK) return rc;
+  if (ch.calibrating) f.tune_events.push_back({g == 0 ? 0 : 1, ev, ch.format, -1});
+  if (ch.refill_cal) f.tune_events.push_back({0, ev, ch.format, ch.refill ? 1 : 0});
+  return RAYCA_OK;
+}
+
 // One launch of the per-pixel stack machine (general.inc) for one sample of the frame.
 using GeneralKernel = void (*)(DevScene, FrameParams, uint32_t*, PathBuffers, GFrameStore, TraceCounters*, TraceLaunch);
 template <bool SPH, bool STATS>
 GeneralKernel general_kernel(bool fast) {
   return fast ? k_general<true, true, SPH, true, STATS> : k_general<true, false, SPH, true, STATS>;
 }
-int32_t launch_general(RaycaScene* s, FrameCtx* c, const RaycaConfig& cfg, const FrameParams& fp, const PathBuffers& pb, bool stats, hipStream_t stream) {
-  int32_t rc;
-  const bool fast = s->dev.ref_leaf_of != nullptr, sph = s->host.sphere_count != 0;
+int32_t stack_machine(Frame& f) {
+  RaycaScene* s = f.s;
+  FrameCtx* c = f.c;
+  const RaycaConfig& cfg = f.cfg;
+  const bool fast = s->dev.ref_leaf_of != nullptr, sph = s->host.sphere_count != 0, stats = f.plan.stats;
   GeneralKernel k = sph ? (stats ? general_kernel<true, true>(fast) : general_kernel<true, false>(fast))
                         : (stats ? general_kernel<false, true>(fast) : general_kernel<false, false>(fast));
   const StackPlan sp = plan_stack(s->host.max_depth);
-  uint32_t regs = 0;
-  if ((rc = kernel_registers(reinterpret_cast<const void*>(k), regs)) != RAYCA_OK) return rc;
-  uint32_t per_cu = 512u / (((regs + 7u) / 8u) * 8u);
-  const uint32_t by_lds = (uint32_t)((160u * 1024u) / sp.lds_bytes);
-  if (per_cu > by_lds) per_cu = by_lds;
-  if (per_cu < 1u) per_cu = 1u;
-  uint32_t grid = (uint32_t)s->cu_count * per_cu;
-  const uint32_t need = (fp.tile_count + 3u) / 4u;
-  if (grid > need) grid = need ? need : 1u;
+  uint32_t grid = 0;
+  int32_t rc = persistent_grid(s, reinterpret_cast<const void*>(k), sp.lds_bytes, f.fp.tile_count, false, 1u, 0u, grid);
+  if (rc != RAYCA_OK) return rc;
   // recursion depth of the reference's integrators: Pathtracer vertices live at depth < max_depth (unbounded
   // under roulette: capped, overflow is reported), Raytracer/Scratcher at depth <= max_depth, the others at 0
   uint32_t levels = 1;
@@ -674,17 +919,119 @@ int32_t launch_general(RaycaScene* s, FrameCtx* c, const RaycaConfig& cfg, const
     store.samples = static_cast<float4*>(c->mis_samples.ptr);
   }
   TraceLaunch tl{};
-  tl.lds_entries = sp.lds_entries;
-  tl.ticket = fp.tile_count >= 16u * grid ? 2u : 1u;
-  if (sp.spill_entries) {
-    tl.ovf_stride = grid * kBlock;
-    if ((rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u)) != RAYCA_OK) return rc;
-    tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
-  }
+  if ((rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
+  tl.ticket = f.fp.tile_count >= 16u * grid ? 2u : 1u;
   c->heads_clean = false;
-  HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), sp.lds_bytes, stream, s->dev, fp, c->heads, pb, store, c->counters, tl);
-  HIP_TRY(hipGetLastError());
+  return timed_launch(f.log, f.stream, RAYCA_KERNEL_OTHER, f.timing, true, [&]() -> int32_t {
+    HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), f.stream));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), sp.lds_bytes, f.stream, s->dev, f.fp, c->heads, f.pb, store, c->counters, tl);
+    return RAYCA_OK;
+  });
+}
+// The reference panics (todo!(), unwrap on the wrong material kind, stack overflow under roulette) where the stack machine
+// raises these flags; the frame is not usable then.
+int32_t stack_machine_status(Frame& f) {
+  HIP_TRY(hipStreamSynchronize(f.stream));
+  TraceCounters tc{};
+  HIP_TRY(hipMemcpy(&tc, f.c->counters, sizeof tc, hipMemcpyDeviceToHost));
+  if (tc.flags & kFlagTooDeep) return fail(RAYCA_ERR_UNSUPPORTED, "path recursion deeper than the path-vertex stack (Russian roulette did not terminate within 64 bounces)");
+  if (tc.flags & kFlagUnsupported)
+    return fail(RAYCA_ERR_UNSUPPORTED, "this Config reaches a todo!()/panic arm of the reference on this scene (e.g. directional light under NEE, quad light under Raytracer/Scratcher, get_t of a Pbr material, Whitted radiance of a Ggx material)");
+  return RAYCA_OK;
+}
+
+// k_resolve: the path records of one sample into the pixels.  On the generation engines the same launch clears the work
+// counters for the next frame of this context (see k_resolve).
+int32_t resolve(Frame& f) {
+  FrameCtx* c = f.c;
+  const bool general = f.plan.mode == kModeGeneral;
+  const int32_t rc = timed_launch(f.log, f.stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
+    hipLaunchKernelGGL(k_resolve, dim3((f.pb.npix + kBlock - 1) / kBlock), dim3(kBlock), 0, f.stream, f.fp, f.pb, f.plan.generations,
+                       static_cast<float4*>(c->accum.ptr), f.rgba8, f.rgba32f, general ? nullptr : c->heads_b, 17u * kHeadStride);
+    return RAYCA_OK;
+  });
+  if (rc == RAYCA_OK && !general) c->heads_clean = true;
+  return rc;
+}
+
+// A calibration frame: book its kernel time for the node format (or camera-ray kernel) it was launched with.
+int32_t book_calibration(Frame& f) {
+  RaycaScene* s = f.s;
+  HIP_TRY(hipStreamSynchronize(f.stream));
+  float sum[2] = {0.0f, 0.0f};
+  int fmt[2] = {-1, -1};
+  int refill_choice = -1;
+  float refill_ms = 0.0f;
+  for (const TuneEvent& te : f.tune_events) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, f.c->ev_trace[te.ev], f.c->ev_trace[te.ev + 1]));
+    if (te.refill >= 0) {
+      refill_choice = te.refill;
+      refill_ms = ms;
+      continue;
+    }
+    sum[te.cls] += ms;
+    fmt[te.cls] = te.format;  // all bounce generations of one frame are launched with one format
+  }
+  std::lock_guard<std::mutex> tune_lock(s->tune_mu);
+  if (refill_choice >= 0) {
+    RaycaScene::Tune& tu = s->tune[0][0];
+    if (refill_ms < tu.refill_best[refill_choice]) tu.refill_best[refill_choice] = refill_ms;
+    if (++tu.refill_booked == 8u) tu.refill = tu.refill_best[1] < tu.refill_best[0] ? 1 : 0;
+  }
+  for (int cls = 0; cls < 2; ++cls) {
+    if (fmt[cls] < 0) continue;
+    RaycaScene::Tune& tu = s->tune[f.plan.mode == kModePath ? 1 : 0][cls];
+    if (sum[cls] < tu.best[fmt[cls] & 3]) tu.best[fmt[cls] & 3] = sum[cls];
+    if (++tu.booked == 16u) {
+      int pick = 0;
+      for (int p = 1; p < 4; ++p)
+        if (tu.best[p] < tu.best[pick]) pick = p;
+      tu.decided = pick;
+    }
+  }
+  return RAYCA_OK;
+}
+
+int32_t fill_stats(Frame& f, RaycaStats* out) {
+  FrameCtx* c = f.c;
+  const bool general = f.plan.mode == kModeGeneral;
+  HIP_TRY(hipStreamSynchronize(f.stream));
+  TraceCounters tc{};
+  HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
+  if (f.plan.wavefront && !general) {
+    std::vector<unsigned long long> lines(64 * 16);
+    HIP_TRY(hipMemcpy(lines.data(), c->shade_stats, lines.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t l = 0; l < 64; ++l) {
+      tc.shaded += lines[l * 16 + 0];
+      tc.shadow += lines[l * 16 + 1];
+      tc.bounce += lines[l * 16 + 2];
+    }
+  }
+  std::memset(out, 0, sizeof *out);
+  out->rays_primary = (uint64_t)f.pb.npix * f.cfg.samples_per_pixel;
+  out->rays_shadow = tc.shadow;
+  out->rays_bounce = tc.bounce;
+  out->boxes_tested = tc.boxes;
+  out->triangles_tested = tc.tris;
+  out->hits_shaded = tc.shaded;
+  out->wave_box_slots = tc.box_slots;
+  out->wave_triangle_slots = tc.tri_slots;
+  HIP_TRY(hipEventElapsedTime(&out->kernel_ms, c->ev_begin, c->ev_end));
+  float tsum = 0.0f;
+  for (size_t i = 0; i + 1 < f.log.ev_used; i += 2) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[i], c->ev_trace[i + 1]));
+    const int cls = i / 2 < f.log.ev_class.size() ? f.log.ev_class[i / 2] : RAYCA_KERNEL_OTHER;
+    out->class_ms[cls] += ms;
+    out->class_launches[cls] += 1u;
+    if (cls != RAYCA_KERNEL_WF_SHADE && (cls != RAYCA_KERNEL_OTHER || general)) tsum += ms;   // the traversal kernels (the stack machine is one)
+  }
+  out->trace_kernel_ms = tsum;
+  out->kernel_launches = f.log.launches;
+  out->trace_kernel_launches = f.log.trace_launches;
+  out->rows_rendered = f.fp.rows;
+  out->node_format = f.node_format;
   return RAYCA_OK;
 }
 
@@ -696,10 +1043,11 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
   if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
   if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
-  const RaycaConfig cfg = *cfg_in;
-  RaycaRenderOptions opts{};
-  if (opts_in) opts = *opts_in;
-  LaunchPlan plan{};
+  Frame f{};
+  const RaycaConfig& cfg = f.cfg = *cfg_in;
+  const RaycaRenderOptions& opts = f.opts;
+  if (opts_in) f.opts = *opts_in;
+  LaunchPlan& plan = f.plan;
   plan.ordered = opts.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
   plan.stats = opts.collect_stats != 0;
   int32_t rc = validate_config(s, cfg, opts.engine, plan);
@@ -715,10 +1063,11 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     return RAYCA_OK;
   }
   if (opts.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  FrameCtx* c = &s->ctx[opts.context];
+  FrameCtx* c = f.c = f.log.c = &s->ctx[opts.context];
+  f.s = s;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
-  hipStream_t stream = opts.stream ? static_cast<hipStream_t>(opts.stream) : c->stream;
+  const hipStream_t stream = f.stream = opts.stream ? static_cast<hipStream_t>(opts.stream) : c->stream;
   // Calls on one context are serialised on the DEVICE too: the previous frame of this context may still be running
   // on another stream (asynchronous rayca_hip_render_device calls with different opts->stream) and owns the same
   // queues, path records and spill area.
@@ -727,11 +1076,14 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   // The wavefront engine's kernels are tied to the 4-wide / fp16 nodes, and so is a pinned format: those wait for the thread
   // that makes them.  Everything else renders on the binary f32 nodes until they are there (node_format bit 2048).
   if ((plan.wavefront || format_forced() > 0) && (rc = formats_wait(s)) != RAYCA_OK) return rc;
-  const bool all_formats = formats_ready(s);
-  const DevScene& dscene = all_formats ? s->dev_full : s->dev;
-  const uint32_t in_flight = frames_in_flight_hint(s, opts.context, opts.stream != nullptr);
+  f.all_formats = formats_ready(s);
+  f.dscene = f.all_formats ? &s->dev_full : &s->dev;
+  f.in_flight = frames_in_flight_hint(s, opts.context, opts.stream != nullptr);
+  f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
+  f.rgba8 = static_cast<uint8_t*>(d_rgba8);
+  f.rgba32f = static_cast<float4*>(d_rgba32f);
 
-  FrameParams fp{};
+  FrameParams& fp = f.fp;
   fp.width = width; fp.height = height; fp.rows = rows;
   fp.part = tile.part; fp.parts = tile.parts; fp.band = tile.band_rows;
   fp.tiles_x = (width + kTileW - 1u) / kTileW;
@@ -750,14 +1102,11 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   const float strate = sqrtf((float)cfg.samples_per_pixel);  // scene.rs:125-127
   const float sub_offset = 0.5f / strate, sub_step = 1.0f / strate;
 
-  const uint32_t npix = rows * width;
-  // one generation and one sample: the generation kernel writes the pixel itself (no k_resolve)
-  // Flat, one sample: the generation kernel writes the pixel itself (no k_resolve).  The same fusion was
-  // measured for the depth-1 path frame and LOST 5 % against generation + k_resolve (atrium 1080p, A/B in
-  // one process: 0.734 vs 0.695 ms), so path frames always resolve in their own pass.
-  const bool fused = cfg.samples_per_pixel == 1 && (plan.mode == kModeFlat || (RAYCA_FUSE_PATH1 && plan.mode == kModePath && plan.generations == 1 && !plan.wavefront));
-  const uint32_t depths = plan.generations;
-  PathBuffers pb{};
+  // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
+  // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
+  const uint32_t npix = rows * width, depths = plan.generations;
+  const bool fused = f.fused = cfg.samples_per_pixel == 1 && plan.mode == kModeFlat;
+  PathBuffers& pb = f.pb;
   pb.npix = npix;
   if (!fused) {
     const uint32_t dalloc = depths ? depths : 1;
@@ -774,29 +1123,11 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     pb.state = static_cast<uint32_t*>(c->path_state.ptr);
   }
 
-  const bool timing = stats_out != nullptr;
+  const bool timing = f.timing = stats_out != nullptr;
   const bool general = plan.mode == kModeGeneral;
   if (timing || general) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
   if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  uint32_t launches = 0, trace_launches = 0;
-  size_t ev_used = 0;
-  std::vector<int> ev_class;   // kernel class (RAYCA_KERNEL_*) of the launch between event pair i (events 2i, 2i + 1)
-  auto next_event = [&](hipEvent_t& ev) -> int32_t {
-    if (ev_used == c->ev_trace.size()) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->ev_trace.push_back(e);
-    }
-    ev = c->ev_trace[ev_used++];
-    return RAYCA_OK;
-  };
-  uint32_t node_format = (all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && dscene.nodes_ch ? 4096u : 0u);
-  int frame_format[2] = {-2, -2};  // node format of this frame per generation class (-2 = not asked yet, -1 = default)
-  bool frame_calibrates[2] = {false, false};
-  struct TuneEvent { int cls; size_t ev; int format; int refill; };  // generation class, index of the event pair, the format launched; refill: -1 = a format calibration, 0/1 = a kernel calibration
-  std::vector<TuneEvent> tune_events;                   // calibration launches of this frame
-  uint32_t* q_count = c->heads + 8 * kHeadStride;  // two queue counters, behind the 8 padded work counters
-
+  uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
   for (uint32_t sample = 0; sample < cfg.samples_per_pixel; ++sample) {
     fp.sample = sample;
     const uint32_t sc_i = (uint32_t)strate;
@@ -805,369 +1136,29 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     fp.sub_step_y = iy * sub_step;
     fp.sub_offset = sub_offset;
     if (!fused && depths > 1) HIP_TRY(hipMemsetAsync(pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
-    if (general) {
-      hipEvent_t g0 = nullptr, g1 = nullptr;
-      if (timing) {
-        if ((rc = next_event(g0)) != RAYCA_OK || (rc = next_event(g1)) != RAYCA_OK) return rc;
-        HIP_TRY(hipEventRecord(g0, stream));
-        ev_class.push_back(RAYCA_KERNEL_OTHER);
-      }
-      if ((rc = launch_general(s, c, cfg, fp, pb, plan.stats, stream)) != RAYCA_OK) return rc;
-      if (timing) HIP_TRY(hipEventRecord(g1, stream));
-      ++launches;
-      ++trace_launches;
-    }
+    if (general && (rc = stack_machine(f)) != RAYCA_OK) return rc;
     for (uint32_t g = 0; !general && g < depths; ++g) {
-      // generation 0 clears the work counters and both queue counters in one go; later generations
-      // must keep the input queue's counter
-      // one memset clears both counter sets (the second one is only used by the wavefront engine)
-      // (whole lines: a size that is not a multiple of the fill kernel's granule costs a second fill launch, ~5 us)
+      // generation 0 clears the work counters and both queue counters in one go (unless k_resolve of the previous frame
+      // left them clean); later generations must keep the input queue's counter.  One memset clears both counter sets (the
+      // second one is only used by the wavefront engine), in whole lines: a size that is not a multiple of the fill
+      // kernel's granule costs a second fill launch, ~5 us.
       if (!(g == 0 && c->heads_clean))
         HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
       c->heads_clean = false;
-      QueuedRay* qin = g ? static_cast<QueuedRay*>(c->queue[(g - 1) & 1].ptr) : nullptr;
-      QueuedRay* qout = static_cast<QueuedRay*>(c->queue[g & 1].ptr);
-      uint32_t* cin = g ? q_count + ((g - 1) & 1) : nullptr;
-      uint32_t* cout = q_count + (g & 1);
-      if (g != 0) HIP_TRY(hipMemsetAsync(cout, 0, sizeof(uint32_t), stream));
-      if (plan.wavefront) {
-        const bool sph = s->host.sphere_count != 0, fast = s->dev.ref_leaf_of != nullptr;
-        if (fast)   // (the formats these kernels are compiled for: RAYCA_WF_*, trace_core.inc)
-          node_format |= g == 0 ? ((RAYCA_WF_PRIMARY_WIDE ? 1u : 0u) | (RAYCA_WF_PRIMARY_HALF ? 4u : 0u)) : ((RAYCA_WF_BOUNCE_WIDE ? 2u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 8u : 0u));
-        // 16 LDS entries per lane (16 KiB per block) so that the lean kernels' occupancy is set by registers
-        // (the wide tree never needs more pending entries than the binary one: one plan serves both)
-        const StackPlan sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
-        const int flavour = !fast ? 2 : (sp.spill_entries ? 1 : 0);
-        const uint32_t batches = g == 0 ? fp.tile_count : (npix + 63u) / 64u;
-        const uint32_t nls = (plan.mode == kModePath && cfg.direct_sampler == RAYCA_SAMPLER_NEE) ? (uint32_t)s->host.lights.size() * cfg.light_samples : 0u;
-        WfBuffers wb{};
-        if ((rc = ensure(c->wf_hits, (size_t)npix * 16u)) != RAYCA_OK) return rc;
-        wb.hits = static_cast<float4*>(c->wf_hits.ptr);
-        wb.nls = nls;
-        if (nls) {
-          if ((rc = ensure(c->wf_sh_ray, (size_t)npix * nls * 32u)) != RAYCA_OK) return rc;
-          if ((rc = ensure(c->wf_sh_x, (size_t)npix * nls * 16u)) != RAYCA_OK) return rc;
-          wb.sh_ray = static_cast<float4*>(c->wf_sh_ray.ptr);
-          wb.sh_x = static_cast<float4*>(c->wf_sh_x.ptr);
-        }
-        auto stack_for = [&](uint32_t grid, TraceLaunch& tl) -> int32_t {
-          tl = TraceLaunch{};
-          tl.lds_entries = sp.lds_entries;
-          if (sp.spill_entries) {
-            tl.ovf_stride = grid * kBlock;
-            int32_t r2 = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
-            if (r2 != RAYCA_OK) return r2;
-            tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
-          }
-          return RAYCA_OK;
-        };
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        // closest hits
-        WfTraceKernel kt = g == 0 ? pick_wf_trace<true>(flavour, sph, plan.stats) : pick_wf_trace<false>(flavour, sph, plan.stats);
-        const uint32_t grid = (batches + 3u) / 4u;  // one thread per ray, four 8x8 tiles per block
-        TraceLaunch tl{};
-        // bounce generations on a SAH scene: persistent lanes that take the next queue entry when their ray is done
-        // (refill.hip k_queue_refill; RAYCA_WF_REFILL=0 keeps one ray per lane, k_wf_trace)
-        static const bool wf_refill = [] { const char* e = getenv("RAYCA_WF_REFILL"); return e ? atoi(e) != 0 : true; }();
-        const bool queue_refill = wf_refill && g != 0 && fast;
-        if (queue_refill) {
-          uint32_t regs = 0;
-          if ((rc = kernel_registers(queue_refill_kernel(sph, plan.stats), regs)) != RAYCA_OK) return rc;
-          uint32_t per_cu = 512u / (((regs + 7u) / 8u) * 8u);
-          const uint32_t by_lds = sp.lds_bytes ? (uint32_t)((160u * 1024u) / sp.lds_bytes) : 8u;
-          per_cu = std::max(1u, std::min(std::min(per_cu, by_lds), 8u));
-          if (in_flight >= 4u) per_cu = std::max(1u, (per_cu + 1u) / 2u);   // (frames in flight leave each other room: see the generation kernels' grid below)
-          else if (in_flight >= 2u) per_cu = std::max(1u, (per_cu * 3u + 3u) / 4u);
-          uint32_t rgrid = (uint32_t)s->cu_count * per_cu;
-          if (rgrid > grid) rgrid = grid ? grid : 1u;
-          if ((rc = stack_for(rgrid, tl)) != RAYCA_OK) return rc;
-          tl.ticket = 1u;
-          if (timing) {
-            if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-            HIP_TRY(hipEventRecord(e0, stream));
-            ev_class.push_back(RAYCA_KERNEL_QUEUE_REFILL);
-          }
-          launch_queue_refill(sph, plan.stats, rgrid, sp.lds_bytes, stream, dscene, qin, cin, wb.hits, c->heads, c->counters, tl);   // (work counters: cleared above, every generation)
-        } else {
-          if ((rc = stack_for(grid, tl)) != RAYCA_OK) return rc;
-          if (timing) {
-            if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-            HIP_TRY(hipEventRecord(e0, stream));
-            ev_class.push_back(RAYCA_KERNEL_WF_TRACE);
-          }
-          hipLaunchKernelGGL(kt, dim3(grid), dim3(kBlock), sp.lds_bytes, stream, dscene, fp, qin, cin, wb, c->counters, tl);
-        }
-        HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(e1, stream));
-        // shading
-        WfShadeKernel ks = pick_wf_shade(plan.mode, g == 0, fused, sph);
-        if (timing) {
-          if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-          HIP_TRY(hipEventRecord(e0, stream));
-          ev_class.push_back(RAYCA_KERNEL_WF_SHADE);
-        }
-        hipLaunchKernelGGL(ks, dim3(((g == 0 ? fp.tile_count * 64u : npix) + kShadeBlock - 1) / kShadeBlock), dim3(kShadeBlock), 0, stream, dscene, fp, qin, cin, qout, cout, wb, pb, g,
-                           static_cast<uint8_t*>(d_rgba8), static_cast<float4*>(d_rgba32f), c->shade_stats);
-        HIP_TRY(hipGetLastError());
-        if (timing) HIP_TRY(hipEventRecord(e1, stream));
-        launches += 2;
-        ++trace_launches;
-        // shadow rays + direct lighting
-        if (nls) {
-          WfShadowKernel kh = g == 0 ? pick_wf_shadow<true>(flavour, sph, plan.stats) : pick_wf_shadow<false>(flavour, sph, plan.stats);
-          // on a SAH scene with lane refill too (refill.hip k_shadow_refill; RAYCA_WF_SHADOW_REFILL: 0 never, 1 bounce
-          // generations, 2 every generation), on the second set of work counters
-          static const int shadow_refill_mode = [] { const char* e = getenv("RAYCA_WF_SHADOW_REFILL"); return e ? atoi(e) : 1; }();
-          const bool shadow_refill = wf_refill && fast && (g != 0 ? shadow_refill_mode >= 1 : shadow_refill_mode >= 2);
-          if (shadow_refill) {
-            uint32_t regs = 0;
-            if ((rc = kernel_registers(shadow_refill_kernel(g == 0, sph, plan.stats), regs)) != RAYCA_OK) return rc;
-            uint32_t per_cu = 512u / (((regs + 7u) / 8u) * 8u);
-            const uint32_t by_lds = sp.lds_bytes ? (uint32_t)((160u * 1024u) / sp.lds_bytes) : 8u;
-            per_cu = std::max(1u, std::min(std::min(per_cu, by_lds), 8u));
-            if (in_flight >= 4u) per_cu = std::max(1u, (per_cu + 1u) / 2u);
-            else if (in_flight >= 2u) per_cu = std::max(1u, (per_cu * 3u + 3u) / 4u);
-            uint32_t rgrid = (uint32_t)s->cu_count * per_cu;
-            if (rgrid > grid) rgrid = grid ? grid : 1u;
-            if ((rc = stack_for(rgrid, tl)) != RAYCA_OK) return rc;
-            tl.ticket = 1u;
-            if (timing) {
-              if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-              HIP_TRY(hipEventRecord(e0, stream));
-              ev_class.push_back(RAYCA_KERNEL_SHADOW_REFILL);
-            }
-            const ShadowRefillArgs sa{wb.sh_ray, wb.sh_x, wb.nls, pb.direct, pb.state, pb.npix};
-            launch_shadow_refill(g == 0, sph, plan.stats, rgrid, sp.lds_bytes, stream, dscene, fp, qin, cin, sa, g, c->heads_b, c->counters, tl);
-          } else {
-            if ((rc = stack_for(grid, tl)) != RAYCA_OK) return rc;
-            if (timing) {
-              if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-              HIP_TRY(hipEventRecord(e0, stream));
-              ev_class.push_back(RAYCA_KERNEL_WF_SHADOW);
-            }
-            hipLaunchKernelGGL(kh, dim3(grid), dim3(kBlock), sp.lds_bytes, stream, dscene, fp, qin, cin, wb, pb, g, c->counters, tl);
-          }
-          HIP_TRY(hipGetLastError());
-          if (timing) HIP_TRY(hipEventRecord(e1, stream));
-          ++launches;
-          ++trace_launches;
-        }
-        continue;
-      }
-      // node format: decided by measurement on this scene (RaycaScene::Tune), or forced by RAYCA_WIDE
-      RaycaScene::Tune& tu = s->tune[plan.mode == kModePath ? 1 : 0][g == 0 ? 0 : 1];
-      const bool can_tune = plan.ordered && s->dev.ref_leaf_of != nullptr && wide_forced() < 0 && all_formats;
-      int format_choice = all_formats ? format_forced() : 0;  // (binary f32 until the others are there)
-      bool calibrating = false;
-      // Flat camera rays on a SAH scene: k_generation, or the lane-refill kernel (refill.hip)?  Decided per scene by timing
-      // eight frames (RAYCA_REFILL=0/1 pins it) -- BEFORE the node format is timed, on 4-wide f32 nodes: the kernels differ
-      // by far more than the formats do (soup: 6.2 against 11 ms), and the formats rank differently under the two (soup:
-      // binary and 4-wide fp16 nodes tie under k_generation, 7.2 against 6.2 ms under lane refill), so the format has to be
-      // timed on the kernel that will run it.
-      static const int refill_env = [] { const char* e = getenv("RAYCA_REFILL"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-      const bool refill_possible = fused && plan.mode == kModeFlat && plan.ordered && s->dev.ref_leaf_of != nullptr;
-      const int refill_forced = !refill_possible ? 0 : (opts.camera_rays == RAYCA_CAMERA_REFILL ? 1 : (opts.camera_rays == RAYCA_CAMERA_GENERATION ? 0 : refill_env));
-      const bool refill_candidate = refill_possible && all_formats;   // (the timing runs on 4-wide nodes: once they are there)
-      bool refill = refill_forced > 0, refill_cal = false;
-      if (refill_candidate && refill_forced < 0) {
-        std::lock_guard<std::mutex> tune_lock(s->tune_mu);
-        if (tu.refill >= 0) refill = tu.refill != 0;
-        else if (npix >= 65536u && !plan.stats && tu.refill_launched < 8u) {
-          refill = (tu.refill_launched++ & 1u) != 0;
-          refill_cal = true;
-          if (format_choice < 0) format_choice = 1;
-        }
-      }
-      const bool kernel_pending = refill_candidate && refill_forced < 0 && !refill_cal && [&] {
-        std::lock_guard<std::mutex> tune_lock(s->tune_mu);
-        return tu.refill < 0;
-      }();
-      if (can_tune && !refill_cal && !kernel_pending) {
-        const int cls = g == 0 ? 0 : 1;
-        if (frame_format[cls] == -2) {  // one decision per frame and class: all bounce generations of a frame use one format
-          std::lock_guard<std::mutex> tune_lock(s->tune_mu);
-          frame_format[cls] = -1;
-          if (tu.decided >= 0) frame_format[cls] = tu.decided;
-          else if (npix >= 65536u && !plan.stats && tu.launched < 16u) {  // the counting instantiation is slower: never timed
-            frame_format[cls] = (int)(tu.launched++ & 3u);
-            frame_calibrates[cls] = true;
-          }
-        }
-        if (frame_format[cls] >= 0) format_choice = frame_format[cls];
-        calibrating = frame_calibrates[cls];
-      }
-      // path frames park each lane's ShadeCtx behind the stack rows (kernels.hip, RAYCA_PARK_CTX): 7 KiB per wave.  Their
-      // LDS part of the stack is capped at path_lds_entries() so that four blocks per CU still fit 160 KiB; deeper
-      // entries go to the (cold) spill area.
-      const bool park = RAYCA_PARK_CTX && plan.mode == kModePath;
-      const TravPlan tp = plan_traversal(s, plan.ordered, g, format_choice, park ? path_lds_entries() : kMaxLdsEntries);
-      node_format |= (tp.wide ? (g == 0 ? 1u : 2u) : 0u) | (tp.half ? (g == 0 ? 4u : 8u) : 0u) | (calibrating ? 256u : 0u);
-      const StackPlan sp = tp.stack;
-      const size_t lds_bytes = sp.lds_bytes + (park ? (size_t)kCtxQuads * 16u * kBlock : 0u);
-      GenKernel k = pick_kernel(plan.mode, g == 0, fused, tp.trav, s->host.sphere_count != 0, plan.stats);
-      const RefillFlavour rf{s->host.sphere_count != 0, tp.wide, tp.wide || sp.spill_entries != 0, plan.stats, tp.half};
-      const void* kernel_ptr = refill ? flat_refill_kernel(rf) : reinterpret_cast<const void*>(k);
-      node_format |= (refill_cal ? 512u : 0u) | (refill ? 1024u : 0u);
-      // Persistent blocks need no co-residency (there are no inter-block waits), so the grid only has
-      // to be large enough to fill every CU: blocks per CU = what registers and LDS admit (one
-      // 256-thread block = one wave per SIMD; 512 VGPRs per lane per SIMD, allocated in granules of 8;
-      // 160 KiB of LDS per CU).  RAYCA_GRID_MULT overrides for experiments.
-      const uint32_t batches = g == 0 ? fp.tile_count : (npix + 63u) / 64u;
-      static const uint32_t grid_mult = [] { const char* e = getenv("RAYCA_GRID_MULT"); return e ? (uint32_t)atoi(e) : 0u; }();
-      uint32_t per_cu = grid_mult;
-      if (per_cu == 0) {
-        uint32_t regs = 0;
-        if ((rc = kernel_registers(kernel_ptr, regs)) != RAYCA_OK) return rc;
-        const uint32_t alloc = ((regs + 7u) / 8u) * 8u;
-        per_cu = 512u / alloc;
-        const uint32_t by_lds = lds_bytes ? (uint32_t)((160u * 1024u) / lds_bytes) : 8u;
-        if (per_cu > by_lds) per_cu = by_lds;
-        if (per_cu > 8u) per_cu = 8u;
-        if (per_cu < 1u) per_cu = 1u;
-        // With frames in flight a frame that takes every block slot of the chip keeps the next frame's blocks out until
-        // its own retire, and the frames overlap at their tails only; with half the slots per frame the blocks of two
-        // frames are resident side by side and one frame's slow tiles run under the other's work.  Measured (atrium
-        // depth-1 frame, ms per frame, blocks per CU 4 / 3 / 2; tests/gpu_inflight_probe.py with RAYCA_GRID_MULT): one
-        // frame at a time 0.506 / 0.543 / 0.653; two in flight 0.420 / 0.391 / 0.401; four in flight 0.380 / 0.380 / 0.378
-        // for the whole frame, a rank's quarter 0.117 / 0.110 / 0.106, eighth 0.070 / 0.071 / 0.062.
-        if (in_flight >= 4u) per_cu = std::max(1u, (per_cu + 1u) / 2u);
-        else if (in_flight >= 2u) per_cu = std::max(1u, (per_cu * 3u + 3u) / 4u);
-      }
-      uint32_t grid = (uint32_t)s->cu_count * per_cu;
-      const uint32_t need = (batches + 3u) / 4u;  // 4 waves per block
-      if (grid > need) grid = need ? need : 1u;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (timing || calibrating || refill_cal) {
-        if ((rc = next_event(e0)) != RAYCA_OK || (rc = next_event(e1)) != RAYCA_OK) return rc;
-        HIP_TRY(hipEventRecord(e0, stream));
-        ev_class.push_back(refill ? RAYCA_KERNEL_FLAT_REFILL : RAYCA_KERNEL_GENERATION);
-        if (calibrating) tune_events.push_back({g == 0 ? 0 : 1, ev_used - 2, format_choice, -1});
-        if (refill_cal) tune_events.push_back({0, ev_used - 2, format_choice, refill ? 1 : 0});
-      }
-      TraceLaunch tl{};
-      tl.lds_entries = sp.lds_entries;
-      // work tickets (next_batch): pairs of batches while every wave still gets several, single batches for small frames
-      static const uint32_t ticket_forced = [] { const char* e = getenv("RAYCA_TICKET"); return e ? (uint32_t)atoi(e) : 0u; }();
-      tl.ticket = ticket_forced ? ticket_forced : (batches >= 16u * grid ? 2u : 1u);
-      if (sp.spill_entries) {
-        tl.ovf_stride = grid * kBlock;
-        if ((rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u)) != RAYCA_OK) return rc;
-        tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
-      }
-      if (refill)
-        launch_flat_refill(rf, grid, lds_bytes, stream, dscene, fp, c->heads, static_cast<uint8_t*>(d_rgba8), static_cast<float4*>(d_rgba32f), c->counters, tl);
-      else
-        hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds_bytes, stream, dscene, fp, c->heads, qin, cin, qout, cout, pb, g,
-                           static_cast<uint8_t*>(d_rgba8), static_cast<float4*>(d_rgba32f), c->counters, tl);
-      HIP_TRY(hipGetLastError());
-      if (timing || calibrating || refill_cal) HIP_TRY(hipEventRecord(e1, stream));
-      ++launches;
-      ++trace_launches;
+      const GenQueues q{g ? static_cast<QueuedRay*>(c->queue[(g - 1) & 1].ptr) : nullptr, g ? q_count + ((g - 1) & 1) : nullptr,
+                        static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
+      if (g != 0) HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
+      if ((rc = plan.wavefront ? wavefront_generation(f, g, q) : fused_generation(f, g, q)) != RAYCA_OK) return rc;
     }
-    if (!fused) {
-      hipEvent_t r0 = nullptr, r1 = nullptr;
-      if (timing) {
-        if ((rc = next_event(r0)) != RAYCA_OK || (rc = next_event(r1)) != RAYCA_OK) return rc;
-        HIP_TRY(hipEventRecord(r0, stream));
-        ev_class.push_back(RAYCA_KERNEL_OTHER);
-      }
-      // (the counters are cleared for the next frame of this context by the same launch: see k_resolve)
-      hipLaunchKernelGGL(k_resolve, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, fp, pb, depths, static_cast<float4*>(c->accum.ptr),
-                         static_cast<uint8_t*>(d_rgba8), static_cast<float4*>(d_rgba32f), general ? nullptr : c->heads_b, 17u * kHeadStride);
-      HIP_TRY(hipGetLastError());
-      if (timing) HIP_TRY(hipEventRecord(r1, stream));
-      if (!general) c->heads_clean = true;
-      ++launches;
-    }
+    if (!fused && (rc = resolve(f)) != RAYCA_OK) return rc;
   }
   if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
   HIP_TRY(hipEventRecord(c->ev_done, stream));
   if (opts.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opts.record_event), stream));
   c->frame_pending = true;
-  if (!tune_events.empty()) {  // calibration frame: book this frame's kernel time for the node format it was launched with
-    HIP_TRY(hipStreamSynchronize(stream));
-    float sum[2] = {0.0f, 0.0f};
-    int fmt[2] = {-1, -1};
-    int refill_choice = -1;
-    float refill_ms = 0.0f;
-    for (const TuneEvent& te : tune_events) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[te.ev], c->ev_trace[te.ev + 1]));
-      if (te.refill >= 0) {
-        refill_choice = te.refill;
-        refill_ms = ms;
-        continue;
-      }
-      sum[te.cls] += ms;
-      fmt[te.cls] = te.format;  // all bounce generations of one frame are launched with one format
-    }
-    std::lock_guard<std::mutex> tune_lock(s->tune_mu);
-    if (refill_choice >= 0) {
-      RaycaScene::Tune& tu = s->tune[0][0];
-      if (refill_ms < tu.refill_best[refill_choice]) tu.refill_best[refill_choice] = refill_ms;
-      if (++tu.refill_booked == 8u) tu.refill = tu.refill_best[1] < tu.refill_best[0] ? 1 : 0;
-    }
-    for (int cls = 0; cls < 2; ++cls) {
-      if (fmt[cls] < 0) continue;
-      RaycaScene::Tune& tu = s->tune[plan.mode == kModePath ? 1 : 0][cls];
-      if (sum[cls] < tu.best[fmt[cls] & 3]) tu.best[fmt[cls] & 3] = sum[cls];
-      if (++tu.booked == 16u) {
-        int pick = 0;
-        for (int f = 1; f < 4; ++f)
-          if (tu.best[f] < tu.best[pick]) pick = f;
-        tu.decided = pick;
-      }
-    }
-  }
-  if (general) {
-    // the reference panics (todo!(), unwrap on the wrong material kind, stack overflow under roulette) where
-    // these flags are raised; the frame is not usable then
-    HIP_TRY(hipStreamSynchronize(stream));
-    TraceCounters tc{};
-    HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
-    if (tc.flags & kFlagTooDeep) return fail(RAYCA_ERR_UNSUPPORTED, "path recursion deeper than the path-vertex stack (Russian roulette did not terminate within 64 bounces)");
-    if (tc.flags & kFlagUnsupported)
-      return fail(RAYCA_ERR_UNSUPPORTED, "this Config reaches a todo!()/panic arm of the reference on this scene (e.g. directional light under NEE, quad light under Raytracer/Scratcher, get_t of a Pbr material, Whitted radiance of a Ggx material)");
-  }
-  if (timing) {
-    HIP_TRY(hipStreamSynchronize(stream));
-    TraceCounters tc{};
-    HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
-    if (plan.wavefront && !general) {
-      std::vector<unsigned long long> lines(64 * 16);
-      HIP_TRY(hipMemcpy(lines.data(), c->shade_stats, lines.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      for (size_t l = 0; l < 64; ++l) {
-        tc.shaded += lines[l * 16 + 0];
-        tc.shadow += lines[l * 16 + 1];
-        tc.bounce += lines[l * 16 + 2];
-      }
-    }
-    std::memset(stats_out, 0, sizeof *stats_out);
-    stats_out->rays_primary = (uint64_t)npix * cfg.samples_per_pixel;
-    stats_out->rays_shadow = tc.shadow;
-    stats_out->rays_bounce = tc.bounce;
-    stats_out->boxes_tested = tc.boxes;
-    stats_out->triangles_tested = tc.tris;
-    stats_out->hits_shaded = tc.shaded;
-    stats_out->wave_box_slots = tc.box_slots;
-    stats_out->wave_triangle_slots = tc.tri_slots;
-    HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
-    float tsum = 0.0f;
-    for (size_t i = 0; i + 1 < ev_used; i += 2) {
-      float ms = 0.0f;
-      HIP_TRY(hipEventElapsedTime(&ms, c->ev_trace[i], c->ev_trace[i + 1]));
-      const int cls = i / 2 < ev_class.size() ? ev_class[i / 2] : RAYCA_KERNEL_OTHER;
-      stats_out->class_ms[cls] += ms;
-      stats_out->class_launches[cls] += 1u;
-      if (cls != RAYCA_KERNEL_WF_SHADE && (cls != RAYCA_KERNEL_OTHER || general)) tsum += ms;   // the traversal kernels (the stack machine is one)
-    }
-    stats_out->trace_kernel_ms = tsum;
-    stats_out->kernel_launches = launches;
-    stats_out->trace_kernel_launches = trace_launches;
-    stats_out->rows_rendered = rows;
-    stats_out->node_format = node_format;
-  }
-  return RAYCA_OK;
+  if (!f.tune_events.empty() && (rc = book_calibration(f)) != RAYCA_OK) return rc;
+  if (general && (rc = stack_machine_status(f)) != RAYCA_OK) return rc;
+  return timing ? fill_stats(f, stats_out) : RAYCA_OK;
 }
 
 // rayca_hip_render_device: takes the context's mutex around the frame.  With opts->stream == NULL the frame runs on the
@@ -2413,12 +2404,7 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
                                        : (stats ? trace_kernel<false, true>(tp.trav) : trace_kernel<false, false>(tp.trav));
   const uint32_t tgrid = (count + kBlock - 1) / kBlock;
   TraceLaunch tl{};
-  tl.lds_entries = sp.lds_entries;
-  if (sp.spill_entries) {
-    tl.ovf_stride = tgrid * kBlock;
-    if ((rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u)) != RAYCA_OK) return rc;
-    tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
-  }
+  if ((rc = bind_stack(c, sp, tgrid, tl)) != RAYCA_OK) return rc;
   HIP_TRY(hipEventRecord(c->ev_begin, stream));
   hipLaunchKernelGGL(k, dim3(tgrid), dim3(kBlock), lds_bytes, stream, s->dev_full, d_rays, count, d_t, d_prim, d_uv, c->counters, tl);
   HIP_TRY(hipGetLastError());
