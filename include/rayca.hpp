@@ -654,6 +654,12 @@ class DeviceScene {
   DeviceScene(const DeviceScene&) = delete;
   DeviceScene& operator=(const DeviceScene&) = delete;
   RaycaScene* handle() const { return handle_; }
+  // rayca_hip_scene_update: the camera, lights and materials of the edited scene, without a rebuild.  Throws Error with
+  // RAYCA_ERR_UNSUPPORTED when the edit would move geometry (recreate the DeviceScene then); a refused edit changes nothing.
+  void update(const FlatScene& flat) {
+    const RaycaSceneDesc d = flat.desc();
+    check(rayca_hip_scene_update(handle_, &d));
+  }
   RaycaStats draw(const Config& config, Image& image, const RaycaRenderOptions* opts = nullptr) {
     const RaycaConfig c = config.to_abi();
     RaycaStats st;

@@ -36,7 +36,8 @@ extern "C" {
 #endif
 
 #define RAYCA_ABI_VERSION 2u   /* 2: RaycaRenderOptions.wait_event / record_event, RaycaStats.class_ms / class_launches,
-                                  RaycaMultiOptions.context, rayca_hip_render_multi_issue / _wait, rayca_hip_scene_reap */
+                                  RaycaMultiOptions.context, rayca_hip_render_multi_issue / _wait, rayca_hip_scene_reap.
+                                  Added since, without a new version (no layout changed): rayca_hip_scene_update */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -437,6 +438,26 @@ int32_t rayca_hip_scene_info(const RaycaScene* scene, RaycaSceneInfo* out);
  * that want every frame from the first on to be eligible for every format (benchmarks, tests).  Never required:
  * the pixels are the same with every format.  No reference counterpart. */
 int32_t rayca_hip_scene_finish(RaycaScene* scene);
+
+/* Re-reads from `desc` what SceneDrawInfo::new re-reads per draw (scene.rs:88-115, 190-282) and what does not move
+ * geometry: the camera, the lights, the materials.  `desc` is the whole descriptor the caller would hand to
+ * rayca_hip_scene_create for the edited scene; read are only `nodes` (of which only `trs` may differ from creation),
+ * `cameras`, `lights`, `materials` and `texture_count`.  The vertex, index, texture and image arrays are NOT read.  Every
+ * count (node, mesh, primitive, vertex, index byte, material, texture, image, image byte, camera, light) must equal the
+ * scene's, a node's parent / model / mesh / camera / light must be those it was created with, and a material's texture
+ * indices must be RAYCA_NONE or in range: else RAYCA_ERR_BAD_ARG.
+ *
+ * After RAYCA_OK every frame rendered from the handle (any engine, any Config, every render entry point) is bit-identical,
+ * RGBA8, RGBA32F and error codes alike, to the same frame rendered from a new rayca_hip_scene_create(desc) with the same
+ * cfg->bvh and builder.  An edit that would move geometry is refused with RAYCA_ERR_UNSUPPORTED and a message naming the first
+ * offending node or light: the world transform of a node with a mesh changes (a moved ancestor counts), or the local or world
+ * transform of a quad light's node, its ab, ac or material, or a light's kind changes to or from RAYCA_LIGHT_QUAD (the quad's
+ * two triangles are in the BVH).  A refused edit changes nothing.
+ *
+ * Frames issued before the call render the old state, frames issued after it the new one.  A camera-only edit waits for
+ * nothing and touches no device memory; a light or material edit first waits for the scene's frames in flight, then
+ * overwrites the device tables in place.  No reference counterpart (the reference rebuilds everything per draw). */
+int32_t rayca_hip_scene_update(RaycaScene* scene, const RaycaSceneDesc* desc);
 
 /* The second half of SoftRenderer::draw (scene.rs:101-150): the pixel loop.  Renders
  * width x height with camera_draw_infos[0] and writes RGBA8 (rgba8.rs:75-84) and/or the

@@ -318,6 +318,7 @@ extern "C" {
     pub fn rayca_hip_scene_reap() -> i32;
     pub fn rayca_hip_scene_info(scene: *const RaycaScene, out: *mut RaycaSceneInfo) -> i32;
     pub fn rayca_hip_scene_finish(scene: *mut RaycaScene) -> i32;
+    pub fn rayca_hip_scene_update(scene: *mut RaycaScene, desc: *const RaycaSceneDesc) -> i32;
     pub fn rayca_hip_render(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaRenderOptions, rgba8_out: *mut u8, rgba32f_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_render_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaRenderOptions, d_rgba8_out: *mut c_void, d_rgba32f_out: *mut c_void, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_render_multi(scenes: *const *mut RaycaScene, count: u32, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaMultiOptions, rgba8_out: *mut c_void, stats_out: *mut RaycaStats) -> i32;
@@ -684,6 +685,18 @@ impl DeviceScene {
         let mut handle: *mut RaycaScene = std::ptr::null_mut();
         check(unsafe { rayca_hip_scene_create(&flat.desc(), &cfg, &opts, &mut handle) });
         Self { handle }
+    }
+
+    /// rayca_hip_scene_update: the camera, lights and materials of the edited scene, without a rebuild (a viewer's frame
+    /// loop).  Err(RAYCA_ERR_UNSUPPORTED): the edit moves geometry and changed nothing -- recreate the DeviceScene.  Every
+    /// other error panics like `check` does.
+    pub fn update(&mut self, flat: &FlatScene) -> Result<(), i32> {
+        let rc = unsafe { rayca_hip_scene_update(self.handle, &flat.desc()) };
+        if rc == RAYCA_ERR_UNSUPPORTED {
+            return Err(rc);
+        }
+        check(rc);
+        Ok(())
     }
 
     pub fn draw(&mut self, config: &Config, image: &mut Image) -> RaycaStats {

@@ -138,6 +138,7 @@ struct MultiCtx {
 
 struct RaycaScene {
   int device = 0;
+  RaycaSceneDesc counts{};   // the creation descriptor with its pointers cleared: the counts rayca_hip_scene_update holds to
   HostScene host;
   DevScene dev{};
   std::vector<void*> allocations;
@@ -377,6 +378,43 @@ bool is_emissive(const RaycaMaterial& m) {  // phong.rs:54-56, Color::close colo
   const bool close_to_black = fabsf(m.emission[0] - 0.0f) < FLT_EPSILON && fabsf(m.emission[1] - 0.0f) < FLT_EPSILON &&
                               fabsf(m.emission[2] - 0.0f) < FLT_EPSILON && fabsf(m.emission[3] - 1.0f) < FLT_EPSILON;
   return !close_to_black;
+}
+
+// The device records of a material and a light (scene_create and rayca_hip_scene_update: the same bits).  Zero-filled
+// first, so that two records compare equal with memcmp exactly when the kernels read the same values.
+DevMaterial dev_material(const RaycaMaterial& m) {
+  DevMaterial d;
+  std::memset(&d, 0, sizeof d);
+  std::memcpy(d.color, m.color, 16); std::memcpy(d.ambient, m.ambient, 16); std::memcpy(d.emission, m.emission, 16);
+  std::memcpy(d.diffuse, m.diffuse, 16); std::memcpy(d.specular, m.specular, 16);
+  d.kind = m.kind; d.albedo_texture = m.albedo_texture; d.normal_texture = m.normal_texture;
+  d.metallic_roughness_texture = m.metallic_roughness_texture;
+  d.metallic_factor = m.metallic_factor; d.roughness_factor = m.roughness_factor; d.shininess = m.shininess;
+  d.emissive = is_emissive(m) ? 1u : 0u;
+  return d;
+}
+
+DevLight dev_light(const HostLight& l) {
+  DevLight d;
+  std::memset(&d, 0, sizeof d);
+  d.kind = l.kind; d.material = l.material; d.intensity = l.intensity;
+  d.color[0] = l.color.r; d.color[1] = l.color.g; d.color[2] = l.color.b; d.color[3] = l.color.a;
+  d.attenuation[0] = l.attenuation.x; d.attenuation[1] = l.attenuation.y; d.attenuation[2] = l.attenuation.z;
+  d.ab[0] = l.ab.x; d.ab[1] = l.ab.y; d.ab[2] = l.ab.z;
+  d.ac[0] = l.ac.x; d.ac[1] = l.ac.y; d.ac[2] = l.ac.z;
+  const F4 pos = to_point(trs_world_translation(l.local));  // Point3::from(light_node.trs.get_translation())
+  d.position[0] = pos.x; d.position[1] = pos.y; d.position[2] = pos.z; d.position[3] = pos.w;
+  const F4 dir = -rotate(vec3(1.0f, 0.0f, 0.0f), l.local.rotation);  // DirectionalLight::get_direction  directional.rs:47-51
+  d.direction[0] = dir.x; d.direction[1] = dir.y; d.direction[2] = dir.z;
+  d.trs_translation[0] = l.local.translation.x; d.trs_translation[1] = l.local.translation.y; d.trs_translation[2] = l.local.translation.z;
+  d.trs_rotation[0] = l.local.rotation.x; d.trs_rotation[1] = l.local.rotation.y; d.trs_rotation[2] = l.local.rotation.z; d.trs_rotation[3] = l.local.rotation.w;
+  d.trs_scale[0] = l.local.scale.x; d.trs_scale[1] = l.local.scale.y; d.trs_scale[2] = l.local.scale.z;
+  if (l.kind == RAYCA_LIGHT_QUAD) {
+    const F4 n = normalized(cross(l.ab, l.ac));
+    d.normal[0] = n.x; d.normal[1] = n.y; d.normal[2] = n.z;
+    d.area = quad_area(l.ab, l.ac);
+  }
+  return d;
 }
 
 #ifndef RAYCA_WF_LDS_ENTRIES
@@ -1486,6 +1524,17 @@ int32_t rayca_hip_scene_create(const RaycaSceneDesc* desc, const RaycaConfig* cf
   auto t0 = std::chrono::steady_clock::now();
   RaycaScene* s = new RaycaScene();
   s->device = device;
+  s->counts.node_count = desc->node_count;
+  s->counts.mesh_count = desc->mesh_count;
+  s->counts.primitive_count = desc->primitive_count;
+  s->counts.vertex_count = desc->vertex_count;
+  s->counts.index_byte_count = desc->index_byte_count;
+  s->counts.material_count = desc->material_count;
+  s->counts.texture_count = desc->texture_count;
+  s->counts.image_count = desc->image_count;
+  s->counts.image_byte_count = desc->image_byte_count;
+  s->counts.camera_count = desc->camera_count;
+  s->counts.light_count = desc->light_count;
   s->runtime_init_ms = std::chrono::duration<float, std::milli>(t0 - t_init).count();
   std::string err;
   set_device_blas_builder((opts && opts->build_on_host) ? nullptr : &gpu_build_blas, (uint32_t)device);
@@ -1649,16 +1698,7 @@ int32_t rayca_hip_scene_create(const RaycaSceneDesc* desc, const RaycaConfig* cf
   const HostScene& h = s->host;
   const uint32_t P = (uint32_t)h.prim_order.size();
   std::vector<DevMaterial> mats(h.materials.size());
-  for (size_t i = 0; i < mats.size(); ++i) {
-    const RaycaMaterial& m = h.materials[i];
-    DevMaterial& d = mats[i];
-    std::memcpy(d.color, m.color, 16); std::memcpy(d.ambient, m.ambient, 16); std::memcpy(d.emission, m.emission, 16);
-    std::memcpy(d.diffuse, m.diffuse, 16); std::memcpy(d.specular, m.specular, 16);
-    d.kind = m.kind; d.albedo_texture = m.albedo_texture; d.normal_texture = m.normal_texture;
-    d.metallic_roughness_texture = m.metallic_roughness_texture;
-    d.metallic_factor = m.metallic_factor; d.roughness_factor = m.roughness_factor; d.shininess = m.shininess;
-    d.emissive = is_emissive(m) ? 1u : 0u;
-  }
+  for (size_t i = 0; i < mats.size(); ++i) mats[i] = dev_material(h.materials[i]);
   std::vector<DevTexture> texs(h.textures.size());
   for (size_t i = 0; i < texs.size(); ++i) {
     const uint32_t im = h.textures[i].image;
@@ -1667,28 +1707,7 @@ int32_t rayca_hip_scene_create(const RaycaSceneDesc* desc, const RaycaConfig* cf
     if (texs[i].width == 0 || texs[i].height == 0) return cleanup(fail(RAYCA_ERR_BAD_ARG, "empty texture image"));
   }
   std::vector<DevLight> lights(h.lights.size());
-  for (size_t i = 0; i < lights.size(); ++i) {
-    const HostLight& l = h.lights[i];
-    DevLight& d = lights[i];
-    std::memset(&d, 0, sizeof d);
-    d.kind = l.kind; d.material = l.material; d.intensity = l.intensity;
-    d.color[0] = l.color.r; d.color[1] = l.color.g; d.color[2] = l.color.b; d.color[3] = l.color.a;
-    d.attenuation[0] = l.attenuation.x; d.attenuation[1] = l.attenuation.y; d.attenuation[2] = l.attenuation.z;
-    d.ab[0] = l.ab.x; d.ab[1] = l.ab.y; d.ab[2] = l.ab.z;
-    d.ac[0] = l.ac.x; d.ac[1] = l.ac.y; d.ac[2] = l.ac.z;
-    const F4 pos = to_point(trs_world_translation(l.local));  // Point3::from(light_node.trs.get_translation())
-    d.position[0] = pos.x; d.position[1] = pos.y; d.position[2] = pos.z; d.position[3] = pos.w;
-    const F4 dir = -rotate(vec3(1.0f, 0.0f, 0.0f), l.local.rotation);  // DirectionalLight::get_direction  directional.rs:47-51
-    d.direction[0] = dir.x; d.direction[1] = dir.y; d.direction[2] = dir.z;
-    d.trs_translation[0] = l.local.translation.x; d.trs_translation[1] = l.local.translation.y; d.trs_translation[2] = l.local.translation.z;
-    d.trs_rotation[0] = l.local.rotation.x; d.trs_rotation[1] = l.local.rotation.y; d.trs_rotation[2] = l.local.rotation.z; d.trs_rotation[3] = l.local.rotation.w;
-    d.trs_scale[0] = l.local.scale.x; d.trs_scale[1] = l.local.scale.y; d.trs_scale[2] = l.local.scale.z;
-    if (l.kind == RAYCA_LIGHT_QUAD) {
-      const F4 n = normalized(cross(l.ab, l.ac));
-      d.normal[0] = n.x; d.normal[1] = n.y; d.normal[2] = n.z;
-      d.area = quad_area(l.ab, l.ac);
-    }
-  }
+  for (size_t i = 0; i < lights.size(); ++i) lights[i] = dev_light(h.lights[i]);
   DevScene& dv = s->dev;
   // binary nodes: what the host laid out is copied, the runs of device-built BLASes are written in place by the device
   // from the trees it still holds (gpu_emit_tree, bvh_build.hip) -- the finished tree never travels to the host and back
@@ -2040,6 +2059,104 @@ int32_t rayca_hip_scene_info(const RaycaScene* s, RaycaSceneInfo* out) {
   out->device_bytes = s->device_bytes + (formats_ready(s) ? s->formats_bytes : 0u);
   out->build_ms = s->build_ms;
   out->runtime_init_ms = s->runtime_init_ms;
+  return RAYCA_OK;
+}
+
+// What SceneDrawInfo::new reads again per draw (scene.rs:88-115) and leaves the BVH alone: the camera, the light table, the
+// material table.  Everything is checked and computed first, into temporaries; a refused edit changes nothing.
+//
+// Lock order.  A frame context's mutex is taken for one context of one scene by the render calls, trace_rays, the thread that
+// sets context 0 up and scene_destroy_now; for ONE context index across several scenes, in address order, by multi_issue
+// (lock_contexts); and here for all eight contexts of ONE scene, in index order.  Every thread thus takes context mutexes in
+// ascending (context index, scene address) order, so no cycle of waits can form.  multi_mu is taken before any context mutex
+// (as multi_issue does), and no thread holds two of those.
+int32_t rayca_hip_scene_update(RaycaScene* s, const RaycaSceneDesc* desc) {
+  if (!s || !desc) return fail(RAYCA_ERR_BAD_ARG, "null scene or descriptor");
+  const RaycaSceneDesc& d = *desc;
+  if (d.abi_version != RAYCA_ABI_VERSION) return fail(RAYCA_ERR_BAD_ARG, "abi version mismatch");
+  const RaycaSceneDesc& was = s->counts;
+  if (d.node_count != was.node_count || d.mesh_count != was.mesh_count || d.primitive_count != was.primitive_count ||
+      d.vertex_count != was.vertex_count || d.index_byte_count != was.index_byte_count || d.material_count != was.material_count ||
+      d.texture_count != was.texture_count || d.image_count != was.image_count || d.image_byte_count != was.image_byte_count ||
+      d.camera_count != was.camera_count || d.light_count != was.light_count)
+    return fail(RAYCA_ERR_BAD_ARG, "an update keeps every count of the scene (a different count needs rayca_hip_scene_create)");
+  if ((d.node_count && !d.nodes) || (d.material_count && !d.materials) || (d.camera_count && !d.cameras) || (d.light_count && !d.lights))
+    return fail(RAYCA_ERR_BAD_ARG, "nodes, materials, cameras or lights is null");
+  HostScene& h = s->host;
+  for (uint32_t i = 0; i < d.node_count; ++i) {
+    const RaycaNode &a = d.nodes[i], &b = h.nodes[i];
+    if (a.parent != b.parent || a.model != b.model || a.mesh != b.mesh || a.camera != b.camera || a.light != b.light)
+      return fail(RAYCA_ERR_BAD_ARG, "node " + std::to_string(i) + ": an update may change a node's trs only");
+  }
+  for (uint32_t i = 0; i < d.material_count; ++i) {
+    const RaycaMaterial& m = d.materials[i];
+    for (const uint32_t t : {m.albedo_texture, m.normal_texture, m.metallic_roughness_texture})
+      if (t != RAYCA_NONE && t >= d.texture_count) return fail(RAYCA_ERR_BAD_ARG, "material " + std::to_string(i) + ": texture index out of range");
+  }
+  SceneGraph g;
+  std::string err;
+  if (const int32_t rc = scene_graph_pass(d, g, err); rc != RAYCA_OK) return fail(rc, err);
+  if (g.lights.size() != h.lights.size()) return fail(RAYCA_ERR_BAD_ARG, "light nodes differ from the scene's");
+
+  // ---- would it move geometry?  The BLASes hold world-space triangles: the meshes' and the quad lights' ----
+  auto same = [](const auto& a, const auto& b) { return std::memcmp(&a, &b, sizeof a) == 0; };
+  const std::string rebuild = ": that moves geometry, which needs rayca_hip_scene_create";
+  for (const uint32_t n : g.mesh_nodes)
+    if (!same(g.world_trs[n], h.world_trs[n]))
+      return fail(RAYCA_ERR_UNSUPPORTED, "node " + std::to_string(n) + " carries a mesh and its world transform changed" + rebuild);
+  for (size_t i = 0; i < g.lights.size(); ++i) {
+    const HostLight &a = g.lights[i], &b = h.lights[i];
+    const std::string which = "light " + std::to_string(d.nodes[a.node].light) + " (node " + std::to_string(a.node) + ")";
+    if ((a.kind == RAYCA_LIGHT_QUAD) != (b.kind == RAYCA_LIGHT_QUAD))
+      return fail(RAYCA_ERR_UNSUPPORTED, which + " changes its kind to or from a quad light" + rebuild);
+    if (a.kind != RAYCA_LIGHT_QUAD) continue;
+    if (!same(a.local, b.local) || !same(g.world_trs[a.node], h.world_trs[a.node]))
+      return fail(RAYCA_ERR_UNSUPPORTED, which + " is a quad light and its transform changed" + rebuild);
+    if (!same(a.ab, b.ab) || !same(a.ac, b.ac) || a.material != b.material)
+      return fail(RAYCA_ERR_UNSUPPORTED, which + " is a quad light and its ab, ac or material changed" + rebuild);
+  }
+
+  // ---- the device tables as scene_create would make them; which of them differ ----
+  std::vector<DevMaterial> mats(d.material_count);
+  bool mats_changed = false;
+  for (uint32_t i = 0; i < d.material_count; ++i) {
+    mats[i] = dev_material(d.materials[i]);
+    mats_changed = mats_changed || !same(mats[i], dev_material(h.materials[i]));
+  }
+  std::vector<DevLight> lights(g.lights.size());
+  bool lights_changed = false;
+  for (size_t i = 0; i < lights.size(); ++i) {
+    lights[i] = dev_light(g.lights[i]);
+    lights_changed = lights_changed || !same(lights[i], dev_light(h.lights[i]));
+  }
+
+  // ---- apply ----
+  const bool tables = mats_changed || lights_changed;
+  std::unique_lock<std::mutex> multi_lock(s->multi_mu, std::defer_lock);
+  if (tables) multi_lock.lock();
+  std::unique_lock<std::mutex> ctx_locks[kMaxContexts];
+  for (uint32_t c = 0; c < kMaxContexts; ++c) ctx_locks[c] = std::unique_lock<std::mutex>(s->ctx[c].mu);
+  if (tables) {
+    // the frames in flight read the tables that are about to be overwritten (as scene_destroy_now waits for them): every
+    // frame records its context's ev_done behind its last kernel, and the gathers this scene assembles end with `gathered`
+    HIP_TRY(hipSetDevice(s->device));
+    for (FrameCtx& cx : s->ctx)
+      if (cx.frame_pending && cx.ev_done) HIP_TRY(hipEventSynchronize(cx.ev_done));
+    for (MultiFrame& f : s->multi.frames)
+      if (f.gathered_valid && f.gathered) HIP_TRY(hipEventSynchronize(f.gathered));
+    // in place: `dev` and `dev_full` (and every DevScene a frame takes by value) keep their pointers.  (A HIP error here
+    // leaves the tables half written: the handle is then to be recreated.)
+    StagedCopier staged;
+    if (mats_changed) HIP_TRY(staged.copy(const_cast<DevMaterial*>(s->dev.materials), mats.data(), sizeof(DevMaterial) * mats.size(), nullptr));
+    if (lights_changed) HIP_TRY(staged.copy(const_cast<DevLight*>(s->dev.lights), lights.data(), sizeof(DevLight) * lights.size(), nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  // what render_body and generation_kernels_cover read (the camera travels to the kernels by value, in FrameParams)
+  std::copy(g.local_trs.begin(), g.local_trs.end(), h.local_trs.begin());
+  std::copy(g.world_trs.begin(), g.world_trs.end(), h.world_trs.begin());
+  h.camera_yfov = g.camera_yfov;
+  std::copy(g.lights.begin(), g.lights.end(), h.lights.begin());
+  std::copy(d.materials, d.materials + d.material_count, h.materials.begin());
   return RAYCA_OK;
 }
 

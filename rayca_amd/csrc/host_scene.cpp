@@ -1099,19 +1099,8 @@ void finish_node_formats(HostScene& s, const std::atomic<bool>* cancel) {
   lap("  4-wide nodes, fp16");
 }
 
-int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder, HostScene& s, std::string& err, const BuildHooks& hooks) {
-  // RAYCA_BUILD_TIMING=1: phase times of the host build on stderr
-  static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[rayca build] %-28s %8.1f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
-  if (d.abi_version != RAYCA_ABI_VERSION) { err = "abi version mismatch"; return RAYCA_ERR_BAD_ARG; }
+int32_t scene_graph_pass(const RaycaSceneDesc& d, SceneGraph& s, std::string& err) {
   if (d.node_count && !d.nodes) { err = "nodes is null"; return RAYCA_ERR_BAD_ARG; }
-  if (d.vertex_count && !d.positions) { err = "positions is null"; return RAYCA_ERR_BAD_ARG; }
   const uint32_t N = d.node_count;
 
   // ---- SceneDrawInfo::new: world(i) = world(parent) * local(i)  (scene.rs:213-215,228,242) ----
@@ -1143,16 +1132,15 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
       for (auto it = children[n].rbegin(); it != children[n].rend(); ++it) stack.push_back(*it);
     }
   }
-  std::vector<uint32_t> mesh_nodes, light_nodes;
   for (uint32_t n : order) {
     const RaycaNode& nd = d.nodes[n];
     if (nd.mesh != RAYCA_NONE) {
       if (nd.mesh >= d.mesh_count) { err = "mesh index out of range"; return RAYCA_ERR_BAD_ARG; }
-      mesh_nodes.push_back(n);
+      s.mesh_nodes.push_back(n);
     }
     if (nd.light != RAYCA_NONE) {
       if (nd.light >= d.light_count) { err = "light index out of range"; return RAYCA_ERR_BAD_ARG; }
-      light_nodes.push_back(n);
+      s.light_nodes.push_back(n);
     }
     if (nd.camera != RAYCA_NONE && !s.has_camera) {
       if (nd.camera >= d.camera_count) { err = "camera index out of range"; return RAYCA_ERR_BAD_ARG; }
@@ -1161,7 +1149,7 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
       s.camera_yfov = d.cameras[nd.camera].yfov_radians;
     }
   }
-  for (uint32_t n : light_nodes) {
+  for (uint32_t n : s.light_nodes) {
     const RaycaLight& l = d.lights[d.nodes[n].light];
     HostLight hl;
     hl.kind = l.kind;
@@ -1175,6 +1163,34 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
     hl.local = s.local_trs[n];
     s.lights.push_back(hl);
   }
+  return RAYCA_OK;
+}
+
+int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder, HostScene& s, std::string& err, const BuildHooks& hooks) {
+  // RAYCA_BUILD_TIMING=1: phase times of the host build on stderr
+  static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
+  auto t_prev = std::chrono::steady_clock::now();
+  auto lap = [&](const char* what) {
+    if (!timing) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[rayca build] %-28s %8.1f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
+    t_prev = now;
+  };
+  if (d.abi_version != RAYCA_ABI_VERSION) { err = "abi version mismatch"; return RAYCA_ERR_BAD_ARG; }
+  if (d.node_count && !d.nodes) { err = "nodes is null"; return RAYCA_ERR_BAD_ARG; }
+  if (d.vertex_count && !d.positions) { err = "positions is null"; return RAYCA_ERR_BAD_ARG; }
+
+  SceneGraph g;
+  if (const int32_t rc = scene_graph_pass(d, g, err); rc != RAYCA_OK) return rc;
+  s.nodes.assign(d.nodes, d.nodes + d.node_count);
+  s.local_trs = std::move(g.local_trs);
+  s.world_trs = std::move(g.world_trs);
+  s.has_camera = g.has_camera;
+  s.camera_node = g.camera_node;
+  s.camera_yfov = g.camera_yfov;
+  s.lights = std::move(g.lights);
+  const std::vector<uint32_t>& mesh_nodes = g.mesh_nodes;
+  const std::vector<uint32_t>& light_nodes = g.light_nodes;
   s.materials.assign(d.materials, d.materials + d.material_count);
   s.textures.assign(d.textures, d.textures + d.texture_count);
   s.images.assign(d.images, d.images + d.image_count);

@@ -156,7 +156,20 @@ struct DefaultInitAllocator : std::allocator<T> {
   }
 };
 
+// SceneDrawInfo::new's pass over the graph (scene.rs:206-282): node-local and world transforms, the first camera, the
+// lights.  build_host_scene and rayca_hip_scene_update both run it, so that an updated scene holds the bits a new one would.
+struct SceneGraph {
+  std::vector<Trs> local_trs, world_trs;
+  bool has_camera = false;
+  uint32_t camera_node = 0;
+  float camera_yfov = 0.0f;
+  std::vector<HostLight> lights;                   // one per light node, in traversal order
+  std::vector<uint32_t> mesh_nodes, light_nodes;   // traversal order: DFS pre-order, children ascending
+};
+int32_t scene_graph_pass(const RaycaSceneDesc& d, SceneGraph& g, std::string& err);
+
 struct HostScene {
+  std::vector<RaycaNode> nodes;     // the descriptor's node records at creation (what rayca_hip_scene_update compares against)
   std::vector<Trs> local_trs, world_trs;
   bool has_camera = false;
   uint32_t camera_node = 0;

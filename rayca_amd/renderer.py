@@ -76,6 +76,14 @@ class DeviceScene:
         first frames must already be eligible for every format (format calibration tests, benchmarks)."""
         lib.check(self._lib.rayca_hip_scene_finish(self.handle))
 
+    def update(self, desc: abi.SceneDesc) -> None:
+        """rayca_hip_scene_update: the camera, lights and materials of `desc` (the whole descriptor of the edited scene)
+        replace the scene's, without a rebuild.  Frames are then bit-identical to those of DeviceScene(desc).  Raises
+        RaycaError with ERR_UNSUPPORTED if the edit would move geometry (recreate the scene then), ERR_BAD_ARG if a count
+        or a node field other than trs differs; a refused edit changes nothing."""
+        lib.check(self._lib.rayca_hip_scene_update(self.handle, desc.ptr()))
+        self.desc = desc
+
     def primitive_order(self) -> np.ndarray:
         n = self.info()["triangle_count"] + self.info()["sphere_count"]
         out = np.zeros(n, np.uint32)
