@@ -681,9 +681,33 @@ struct Draw {
   virtual void draw(const Scene& scene, Image& image) = 0;
 };
 
+// What one draw() did (rayca_hip_renderer_last_draw): the action, where the host's time went, the totals so far.
+struct DrawInfo {
+  uint32_t action = RAYCA_NONE;   // RAYCA_DRAW_REUSED / _UPDATED / _REBUILT, RAYCA_NONE before the first draw
+  float ms[RAYCA_DRAW_MS_COUNT] = {0, 0, 0, 0};
+  uint64_t counters[RAYCA_DRAW_N_COUNT] = {0, 0, 0, 0};
+};
+
 struct SoftRenderer : Draw {
   Config config;
+  uint32_t builder = RAYCA_BUILDER_SAH;   // of the scenes draw() builds (read at the first draw)
+  uint32_t device = 0;
   SoftRenderer() = default;
+  ~SoftRenderer() override { release(); }
+  SoftRenderer(const SoftRenderer&) = delete;
+  SoftRenderer& operator=(const SoftRenderer&) = delete;
+  SoftRenderer(SoftRenderer&& o) noexcept : config(o.config), builder(o.builder), device(o.device), handle_(o.handle_) { o.handle_ = nullptr; }
+  SoftRenderer& operator=(SoftRenderer&& o) noexcept {
+    if (this != &o) {
+      release();
+      config = o.config;
+      builder = o.builder;
+      device = o.device;
+      handle_ = o.handle_;
+      o.handle_ = nullptr;
+    }
+    return *this;
+  }
   static SoftRenderer new_with_config(Config c) {  // scene.rs:57-61
     SoftRenderer r;
     r.config = c;
@@ -705,12 +729,42 @@ struct SoftRenderer : Draw {
     model.root.children.push_back(l1);
     return model;
   }
-  // Like the reference, every call flattens the scene, builds the acceleration structure and drops it.
-  // The tree is the reference's own (RAYCA_BUILDER_REFERENCE) so that depth ties resolve as they do there.
+  // Every call flattens the scene, as the reference's does; the acceleration structure of the previous call stays resident
+  // in a RaycaRenderer, which compares the descriptors and renders, updates or rebuilds (rayca_hip_renderer_draw).
   void draw(const Scene& scene, Image& image) override {
-    DeviceScene resident(scene, config, RAYCA_BUILDER_REFERENCE);
-    resident.draw(config, image);
+    if (image.color_type != ColorType::RGBA8 && image.color_type != ColorType::RGBA32F) throw Error(RAYCA_ERR_BAD_ARG, "draw needs an RGBA8 or RGBA32F image");
+    if (!handle_) {
+      RaycaBuildOptions o;
+      std::memset(&o, 0, sizeof o);
+      o.builder = builder;
+      o.device = device;
+      check(rayca_hip_renderer_create(&o, &handle_));
+    }
+    const FlatScene flat(scene);
+    const RaycaSceneDesc d = flat.desc();
+    const RaycaConfig c = config.to_abi();
+    const bool bytes = image.color_type == ColorType::RGBA8;
+    check(rayca_hip_renderer_draw(handle_, &d, &c, image.w, image.h, nullptr, bytes ? image.bytes_mut() : nullptr,
+                                  bytes ? nullptr : reinterpret_cast<float*>(image.bytes_mut()), &last_stats, nullptr));
   }
+  // what the last draw() did; before the first: action RAYCA_NONE, zeros
+  DrawInfo last_draw() const {
+    DrawInfo info;
+    if (handle_) check(rayca_hip_renderer_last_draw(handle_, &info.action, info.ms, info.counters));
+    return info;
+  }
+  // the next draw() rebuilds, whatever it is handed
+  void invalidate() {
+    if (handle_) check(rayca_hip_renderer_invalidate(handle_));
+  }
+  RaycaStats last_stats{};
+
+ private:
+  void release() {
+    if (handle_) rayca_hip_renderer_destroy(handle_);
+    handle_ = nullptr;
+  }
+  RaycaRenderer* handle_ = nullptr;
 };
 
 // ---- PNG write-out (Image::dump_png image.rs:160-169): zlib "stored" blocks, CRC-32, Adler-32 --------

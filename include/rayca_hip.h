@@ -37,7 +37,8 @@ extern "C" {
 
 #define RAYCA_ABI_VERSION 2u   /* 2: RaycaRenderOptions.wait_event / record_event, RaycaStats.class_ms / class_launches,
                                   RaycaMultiOptions.context, rayca_hip_render_multi_issue / _wait, rayca_hip_scene_reap.
-                                  Added since, without a new version (no layout changed): rayca_hip_scene_update */
+                                  Added since, without a new version (no layout changed): rayca_hip_scene_update; the resident
+                                  draw: RaycaRenderer, the rayca_hip_renderer_ entries, rayca_hip_scene_desc_compare, RAYCA_DRAW_ */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -474,6 +475,60 @@ int32_t rayca_hip_render(RaycaScene* scene, const RaycaConfig* cfg, uint32_t wid
 int32_t rayca_hip_render_device(RaycaScene* scene, const RaycaConfig* cfg, uint32_t width,
                                 uint32_t height, const RaycaRenderOptions* opts,
                                 void* d_rgba8_out, void* d_rgba32f_out, RaycaStats* stats_out);
+
+/* ---- the resident draw(): a renderer handle that reuses, updates or rebuilds -------------------------------------------
+ * `Draw::draw(&mut self, scene, image)` (draw.rs:7-9) hands over the whole scene on every call and promises nothing about
+ * what changed since the last one.  A RaycaRenderer keeps the scene of its last draw resident, together with an exact host
+ * copy of the descriptor it was made from, compares every new descriptor against that copy and does the least that gives
+ * the frame a new scene would give: */
+enum { RAYCA_DRAW_REUSED = 0,    /* descriptor identical to the resident one: render only             */
+       RAYCA_DRAW_UPDATED = 1,   /* differs only in what rayca_hip_scene_update accepts: update+render */
+       RAYCA_DRAW_REBUILT = 2 }; /* anything else, or no resident scene: create (+ destroy the old)    */
+/* indices of rayca_hip_renderer_last_draw's ms_out (host wall time, milliseconds) */
+enum { RAYCA_DRAW_MS_COMPARE = 0, /* descriptor against the kept copy              */
+       RAYCA_DRAW_MS_UPDATE = 1,  /* rayca_hip_scene_update, 0 unless UPDATED      */
+       RAYCA_DRAW_MS_BUILD = 2,   /* rayca_hip_scene_create, 0 unless REBUILT      */
+       RAYCA_DRAW_MS_RENDER = 3,  /* the render call incl. the copy to the host    */
+       RAYCA_DRAW_MS_COUNT = 4 };
+/* indices of its counters_out */
+enum { RAYCA_DRAW_N_BUILDS = 0, RAYCA_DRAW_N_UPDATES = 1, RAYCA_DRAW_N_REUSES = 2, /* totals since renderer_create */
+       RAYCA_DRAW_N_KEPT_BYTES = 3,  /* host memory the renderer holds for comparisons */
+       RAYCA_DRAW_N_COUNT = 4 };
+
+typedef struct RaycaRenderer RaycaRenderer; /* opaque: owns the resident RaycaScene and the kept copy of its descriptor */
+
+/* Touches no GPU.  `opts` are the build options of every scene the renderer creates; NULL means RAYCA_BUILDER_SAH, device 0,
+ * device builder (NOT the default of rayca_hip_scene_create: SAH scenes are tested bit-identical to REFERENCE ones). */
+int32_t rayca_hip_renderer_create(const RaycaBuildOptions* opts, RaycaRenderer** out);
+/* One draw().  The frame -- RGBA8, RGBA32F, statistics and error code alike -- is that of rayca_hip_scene_create(desc, cfg,
+ * the renderer's build options) + rayca_hip_render(cfg, width, height, opts, ...) + rayca_hip_scene_destroy; every field of
+ * `opts` keeps its meaning.  What it costs depends on `desc` against the descriptor of the previous draw:
+ *   - everything equal (every count, table and array bit for bit, which optional vertex arrays are NULL, cfg->bvh): REUSED;
+ *   - counts, meshes, primitives, vertex arrays, indices, textures, images, node parent / model / mesh / camera / light and
+ *     cfg->bvh equal, and the differences in nodes' trs, cameras, lights and materials pass rayca_hip_scene_update's own
+ *     check for moved geometry: UPDATED (that call, then the kept nodes / cameras / lights / materials are refreshed);
+ *   - anything else, no resident scene yet, or rayca_hip_renderer_invalidate since: REBUILT.  The new scene is created
+ *     first and the old one destroyed after; a failed create leaves the old scene resident and returns the error.  A
+ *     descriptor without a camera is refused (RAYCA_ERR_NO_CAMERA) before anything is built, so that it evicts nothing.
+ * A descriptor that is wrong in any scene (version, a null table with a non-zero count, a material's texture index out of
+ * range, a node index out of range) is RAYCA_ERR_BAD_ARG.  `action_out` (may be NULL) receives RAYCA_DRAW_*, RAYCA_NONE on error.
+ * Calls on one renderer are serialised by a mutex of its own; `desc` is not referenced after the call returns. */
+int32_t rayca_hip_renderer_draw(RaycaRenderer* r, const RaycaSceneDesc* desc, const RaycaConfig* cfg, uint32_t width,
+                                uint32_t height, const RaycaRenderOptions* opts, uint8_t* rgba8_out, float* rgba32f_out,
+                                RaycaStats* stats_out, uint32_t* action_out);
+/* The last draw that returned RAYCA_OK: its action (RAYCA_NONE before the first), ms_out[RAYCA_DRAW_MS_COUNT] (zeros before
+ * the first), and counters_out[RAYCA_DRAW_N_COUNT], which are totals up to now.  Any of the three may be NULL. */
+int32_t rayca_hip_renderer_last_draw(const RaycaRenderer* r, uint32_t* action_out, float* ms_out, uint64_t* counters_out);
+/* the resident handle (for rayca_hip_scene_info, rayca_hip_scene_finish, ...), NULL before the first draw; the renderer owns
+ * it, and the next REBUILT draw destroys it */
+int32_t rayca_hip_renderer_scene(RaycaRenderer* r, RaycaScene** out);
+/* the next draw rebuilds, whatever it is handed */
+int32_t rayca_hip_renderer_invalidate(RaycaRenderer* r);
+/* hands the resident scene to rayca_hip_scene_destroy and releases the kept copy; NULL is RAYCA_OK */
+int32_t rayca_hip_renderer_destroy(RaycaRenderer* r);
+/* GPU-free: what a renderer holding `resident` (created with cfg->bvh = resident_bvh) does when handed `next` with next_bvh */
+int32_t rayca_hip_scene_desc_compare(const RaycaSceneDesc* resident, uint32_t resident_bvh,
+                                     const RaycaSceneDesc* next, uint32_t next_bvh, uint32_t* action_out);
 
 /* ---- several devices, one process ----------------------------------------------------------------------
  * Image rows shard across the devices exactly as RaycaTile shards them across ranks (bands of band_rows rows dealt

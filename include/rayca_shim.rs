@@ -72,6 +72,20 @@ pub const RAYCA_KERNEL_OTHER: u32 = 7;
 pub const RAYCA_KERNEL_CLASSES: u32 = 8;
 pub const RAYCA_GATHER_RCCL: u32 = 0;
 pub const RAYCA_GATHER_PEER_COPY: u32 = 1;
+// rayca_hip_renderer_draw: what a draw did, and the indices of rayca_hip_renderer_last_draw's ms_out / counters_out
+pub const RAYCA_DRAW_REUSED: u32 = 0;
+pub const RAYCA_DRAW_UPDATED: u32 = 1;
+pub const RAYCA_DRAW_REBUILT: u32 = 2;
+pub const RAYCA_DRAW_MS_COMPARE: u32 = 0;
+pub const RAYCA_DRAW_MS_UPDATE: u32 = 1;
+pub const RAYCA_DRAW_MS_BUILD: u32 = 2;
+pub const RAYCA_DRAW_MS_RENDER: u32 = 3;
+pub const RAYCA_DRAW_MS_COUNT: u32 = 4;
+pub const RAYCA_DRAW_N_BUILDS: u32 = 0;
+pub const RAYCA_DRAW_N_UPDATES: u32 = 1;
+pub const RAYCA_DRAW_N_REUSES: u32 = 2;
+pub const RAYCA_DRAW_N_KEPT_BYTES: u32 = 3;
+pub const RAYCA_DRAW_N_COUNT: u32 = 4;
 
 // ---- structs, field for field as in include/rayca_hip.h ---------------------------------------------------------------------
 #[repr(C)]
@@ -307,6 +321,12 @@ pub struct RaycaScene {
     _private: [u8; 0],
 }
 
+/// opaque: owns the resident RaycaScene and the kept copy of its descriptor
+#[repr(C)]
+pub struct RaycaRenderer {
+    _private: [u8; 0],
+}
+
 extern "C" {
     pub fn rayca_hip_version() -> u32;
     pub fn rayca_hip_device_count() -> i32;
@@ -320,6 +340,13 @@ extern "C" {
     pub fn rayca_hip_scene_finish(scene: *mut RaycaScene) -> i32;
     pub fn rayca_hip_scene_update(scene: *mut RaycaScene, desc: *const RaycaSceneDesc) -> i32;
     pub fn rayca_hip_render(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaRenderOptions, rgba8_out: *mut u8, rgba32f_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_renderer_create(opts: *const RaycaBuildOptions, out: *mut *mut RaycaRenderer) -> i32;
+    pub fn rayca_hip_renderer_draw(r: *mut RaycaRenderer, desc: *const RaycaSceneDesc, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaRenderOptions, rgba8_out: *mut u8, rgba32f_out: *mut f32, stats_out: *mut RaycaStats, action_out: *mut u32) -> i32;
+    pub fn rayca_hip_renderer_last_draw(r: *const RaycaRenderer, action_out: *mut u32, ms_out: *mut f32, counters_out: *mut u64) -> i32;
+    pub fn rayca_hip_renderer_scene(r: *mut RaycaRenderer, out: *mut *mut RaycaScene) -> i32;
+    pub fn rayca_hip_renderer_invalidate(r: *mut RaycaRenderer) -> i32;
+    pub fn rayca_hip_renderer_destroy(r: *mut RaycaRenderer) -> i32;
+    pub fn rayca_hip_scene_desc_compare(resident: *const RaycaSceneDesc, resident_bvh: u32, next: *const RaycaSceneDesc, next_bvh: u32, action_out: *mut u32) -> i32;
     pub fn rayca_hip_render_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaRenderOptions, d_rgba8_out: *mut c_void, d_rgba32f_out: *mut c_void, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_render_multi(scenes: *const *mut RaycaScene, count: u32, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaMultiOptions, rgba8_out: *mut c_void, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_render_multi_issue(scenes: *const *mut RaycaScene, count: u32, cfg: *const RaycaConfig, width: u32, height: u32, opts: *const RaycaMultiOptions, rgba8_out: *mut c_void) -> i32;
@@ -714,24 +741,63 @@ impl Drop for DeviceScene {
     }
 }
 
-/// Drop-in for `SoftRenderer`: same field, same trait.
-#[derive(Default)]
+/// What one `draw` did (rayca_hip_renderer_last_draw).
+#[derive(Clone, Copy, Default)]
+pub struct DrawInfo {
+    pub action: u32, // RAYCA_DRAW_REUSED / _UPDATED / _REBUILT; RAYCA_NONE before the first draw
+    pub ms: [f32; RAYCA_DRAW_MS_COUNT as usize],
+    pub counters: [u64; RAYCA_DRAW_N_COUNT as usize],
+}
+
+/// Drop-in for `SoftRenderer`: same field, same trait.  It keeps a RaycaRenderer: the scene of the last `draw` stays
+/// resident, and the library decides per call whether to render it as it is, update it or rebuild it.
 pub struct HipRenderer {
     pub config: Config,
+    handle: *mut RaycaRenderer,
+}
+
+impl Default for HipRenderer {
+    fn default() -> Self {
+        Self::new_with_config(Config::default())
+    }
 }
 
 impl HipRenderer {
     pub fn new_with_config(config: Config) -> Self {
-        Self { config }
+        // (null options: RAYCA_BUILDER_SAH on device 0; touches no GPU)
+        let mut handle: *mut RaycaRenderer = std::ptr::null_mut();
+        check(unsafe { rayca_hip_renderer_create(std::ptr::null(), &mut handle) });
+        Self { config, handle }
+    }
+
+    pub fn last_draw(&self) -> DrawInfo {
+        let mut info = DrawInfo { action: RAYCA_NONE, ..Default::default() };
+        check(unsafe { rayca_hip_renderer_last_draw(self.handle, &mut info.action, info.ms.as_mut_ptr(), info.counters.as_mut_ptr()) });
+        info
+    }
+
+    /// The next `draw` rebuilds, whatever it is handed.
+    pub fn invalidate(&mut self) {
+        check(unsafe { rayca_hip_renderer_invalidate(self.handle) });
     }
 }
 
 impl Draw for HipRenderer {
-    /// Like the reference, every call flattens the scene, builds the acceleration structure and drops it; the tree is the
-    /// reference's own (RAYCA_BUILDER_REFERENCE), so depth ties resolve as they do there.
+    /// Every call flattens the scene, as the reference's does; the library compares the descriptor with the previous
+    /// call's and renders, updates or rebuilds (rayca_hip_renderer_draw).  Same pixels as a rebuild per call.
     fn draw(&mut self, scene: &Scene, image: &mut Image) {
         assert!(image.color_type == ColorType::RGBA8, "draw() writes RGBA8 images (scene.rs:117)");
-        let mut resident = DeviceScene::new(scene, &self.config, RAYCA_BUILDER_REFERENCE, 0);
-        resident.draw(&self.config, image);
+        let flat = FlatScene::from(scene);
+        let cfg = RaycaConfig::from(&self.config);
+        let (w, h) = (image.width(), image.height());
+        check(unsafe {
+            rayca_hip_renderer_draw(self.handle, &flat.desc(), &cfg, w, h, std::ptr::null(), image.bytes_mut().as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        });
+    }
+}
+
+impl Drop for HipRenderer {
+    fn drop(&mut self) {
+        unsafe { rayca_hip_renderer_destroy(self.handle) };
     }
 }

@@ -8,4 +8,4 @@ from .abi import SceneDesc  # noqa: F401
 from .model import (Camera, GgxMaterial, Image, Light, Mesh, Model, Node, PbrMaterial,  # noqa: F401
                     PhongMaterial, Primitive, Scene, Sphere, Texture, TriangleMesh, Trs,
                     create_default_model, flatten, quat_axis_angle)
-from .renderer import Config, DeviceScene, IntegratorStrategy, SamplerStrategy, SoftRenderer  # noqa: F401
+from .renderer import Config, DeviceScene, IntegratorStrategy, Renderer, SamplerStrategy, SoftRenderer  # noqa: F401

@@ -42,6 +42,11 @@ CAMERA_AUTO, CAMERA_GENERATION, CAMERA_REFILL = 0, 1, 2
 KERNEL_GENERATION, KERNEL_FLAT_REFILL, KERNEL_WF_TRACE, KERNEL_QUEUE_REFILL, KERNEL_WF_SHADE, KERNEL_WF_SHADOW, KERNEL_SHADOW_REFILL, KERNEL_OTHER = range(8)
 KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill", "k_wf_shade", "k_wf_shadow", "k_shadow_refill", "other")
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
+# the resident draw (rayca_hip_renderer_draw): what it did, and the indices of rayca_hip_renderer_last_draw's two arrays
+DRAW_REUSED, DRAW_UPDATED, DRAW_REBUILT = 0, 1, 2
+DRAW_NAMES = ("reused", "updated", "rebuilt")
+DRAW_MS_COMPARE, DRAW_MS_UPDATE, DRAW_MS_BUILD, DRAW_MS_RENDER, DRAW_MS_COUNT = range(5)
+DRAW_N_BUILDS, DRAW_N_UPDATES, DRAW_N_REUSES, DRAW_N_KEPT_BYTES, DRAW_N_COUNT = range(5)
 
 
 class RaycaConfig(C.Structure):
@@ -365,6 +370,21 @@ def bind_product_signatures(lib):
     lib.rayca_hip_render.restype = C.c_int32
     lib.rayca_hip_render.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, P(RaycaRenderOptions),
                                      C.c_void_p, C.c_void_p, P(RaycaStats)]
+    lib.rayca_hip_renderer_create.restype = C.c_int32
+    lib.rayca_hip_renderer_create.argtypes = [P(RaycaBuildOptions), P(C.c_void_p)]
+    lib.rayca_hip_renderer_draw.restype = C.c_int32
+    lib.rayca_hip_renderer_draw.argtypes = [C.c_void_p, P(RaycaSceneDesc), P(RaycaConfig), C.c_uint32, C.c_uint32, P(RaycaRenderOptions),
+                                            C.c_void_p, C.c_void_p, P(RaycaStats), P(C.c_uint32)]
+    lib.rayca_hip_renderer_last_draw.restype = C.c_int32
+    lib.rayca_hip_renderer_last_draw.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_float), P(C.c_uint64)]
+    lib.rayca_hip_renderer_scene.restype = C.c_int32
+    lib.rayca_hip_renderer_scene.argtypes = [C.c_void_p, P(C.c_void_p)]
+    lib.rayca_hip_renderer_invalidate.restype = C.c_int32
+    lib.rayca_hip_renderer_invalidate.argtypes = [C.c_void_p]
+    lib.rayca_hip_renderer_destroy.restype = C.c_int32
+    lib.rayca_hip_renderer_destroy.argtypes = [C.c_void_p]
+    lib.rayca_hip_scene_desc_compare.restype = C.c_int32
+    lib.rayca_hip_scene_desc_compare.argtypes = [P(RaycaSceneDesc), C.c_uint32, P(RaycaSceneDesc), C.c_uint32, P(C.c_uint32)]
     lib.rayca_hip_render_device.restype = C.c_int32
     lib.rayca_hip_render_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32,
                                             P(RaycaRenderOptions), C.c_void_p, C.c_void_p, P(RaycaStats)]
@@ -396,4 +416,6 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
+    "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",
+    "rayca_hip_renderer_invalidate", "rayca_hip_renderer_destroy", "rayca_hip_scene_desc_compare",
 ]

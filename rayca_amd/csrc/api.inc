@@ -2100,21 +2100,7 @@ int32_t rayca_hip_scene_update(RaycaScene* s, const RaycaSceneDesc* desc) {
 
   // ---- would it move geometry?  The BLASes hold world-space triangles: the meshes' and the quad lights' ----
   auto same = [](const auto& a, const auto& b) { return std::memcmp(&a, &b, sizeof a) == 0; };
-  const std::string rebuild = ": that moves geometry, which needs rayca_hip_scene_create";
-  for (const uint32_t n : g.mesh_nodes)
-    if (!same(g.world_trs[n], h.world_trs[n]))
-      return fail(RAYCA_ERR_UNSUPPORTED, "node " + std::to_string(n) + " carries a mesh and its world transform changed" + rebuild);
-  for (size_t i = 0; i < g.lights.size(); ++i) {
-    const HostLight &a = g.lights[i], &b = h.lights[i];
-    const std::string which = "light " + std::to_string(d.nodes[a.node].light) + " (node " + std::to_string(a.node) + ")";
-    if ((a.kind == RAYCA_LIGHT_QUAD) != (b.kind == RAYCA_LIGHT_QUAD))
-      return fail(RAYCA_ERR_UNSUPPORTED, which + " changes its kind to or from a quad light" + rebuild);
-    if (a.kind != RAYCA_LIGHT_QUAD) continue;
-    if (!same(a.local, b.local) || !same(g.world_trs[a.node], h.world_trs[a.node]))
-      return fail(RAYCA_ERR_UNSUPPORTED, which + " is a quad light and its transform changed" + rebuild);
-    if (!same(a.ab, b.ab) || !same(a.ac, b.ac) || a.material != b.material)
-      return fail(RAYCA_ERR_UNSUPPORTED, which + " is a quad light and its ab, ac or material changed" + rebuild);
-  }
+  if (const int32_t rc = update_moves_geometry(d, g, h.world_trs, h.lights, err); rc != RAYCA_OK) return fail(rc, err);
 
   // ---- the device tables as scene_create would make them; which of them differ ----
   std::vector<DevMaterial> mats(d.material_count);
@@ -2230,6 +2216,151 @@ int32_t rayca_hip_render(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, 
   if (rgba32f_out && npix) HIP_TRY(hipMemcpyAsync(rgba32f_out, c->out32.ptr, npix * 16, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   lap("copy out");
+  return RAYCA_OK;
+}
+
+}  // extern "C"
+
+// The resident draw(): the layer that decides, per call, between rendering the resident scene as it is, updating it in place
+// and rebuilding it.  The decision is host code (desc_compare, host_scene.cpp): the device holds the flattened world-space
+// scene, not the descriptor, so there is nothing on the device to compare a descriptor with.
+struct RaycaRenderer {
+  std::mutex mu;
+  RaycaBuildOptions opts{};
+  RaycaScene* scene = nullptr;
+  KeptDesc kept;             // the descriptor `scene` was created from (and updated with since)
+  bool invalidated = false;  // rayca_hip_renderer_invalidate: the next draw rebuilds
+  uint32_t last_action = RAYCA_NONE;
+  float last_ms[RAYCA_DRAW_MS_COUNT] = {0, 0, 0, 0};
+  uint64_t builds = 0, updates = 0, reuses = 0;
+};
+
+extern "C" {
+
+int32_t rayca_hip_renderer_create(const RaycaBuildOptions* opts, RaycaRenderer** out) {
+  if (!out) return fail(RAYCA_ERR_BAD_ARG, "null out pointer");
+  *out = nullptr;
+  RaycaBuildOptions o{};
+  o.builder = RAYCA_BUILDER_SAH;
+  if (opts) o = *opts;
+  if (o.builder != RAYCA_BUILDER_REFERENCE && o.builder != RAYCA_BUILDER_SAH) return fail(RAYCA_ERR_BAD_ARG, "unknown builder");
+  RaycaRenderer* r = new RaycaRenderer();
+  r->opts = o;
+  *out = r;
+  return RAYCA_OK;
+}
+
+int32_t rayca_hip_renderer_draw(RaycaRenderer* r, const RaycaSceneDesc* desc, const RaycaConfig* cfg, uint32_t width, uint32_t height,
+                                const RaycaRenderOptions* opts, uint8_t* rgba8_out, float* rgba32f_out, RaycaStats* stats_out, uint32_t* action_out) {
+  if (action_out) *action_out = RAYCA_NONE;
+  if (!r || !desc) return fail(RAYCA_ERR_BAD_ARG, "null renderer or descriptor");
+  std::lock_guard<std::mutex> lock(r->mu);
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t) { return std::chrono::duration<float, std::milli>(clock::now() - t).count(); };
+  const bool use_bvh = cfg ? cfg->bvh != 0 : true;
+  float ms[RAYCA_DRAW_MS_COUNT] = {0, 0, 0, 0};
+  std::string err;
+  uint32_t action = RAYCA_DRAW_REBUILT;
+  SceneGraph graph;   // scene_graph_pass(desc), unless REUSED
+  const auto t_compare = clock::now();
+  if (r->scene && r->kept.valid && !r->invalidated) {
+    if (const int32_t rc = desc_compare(r->kept.view, r->kept.bvh, &r->kept.graph, *desc, use_bvh, action, graph, err); rc != RAYCA_OK) return fail(rc, err);
+  } else {
+    if (const int32_t rc = desc_validate(*desc, err); rc != RAYCA_OK) return fail(rc, err);
+    if (const int32_t rc = scene_graph_pass(*desc, graph, err); rc != RAYCA_OK) return fail(rc, err);
+  }
+  ms[RAYCA_DRAW_MS_COMPARE] = ms_since(t_compare);
+  if (action == RAYCA_DRAW_UPDATED) {
+    const auto t = clock::now();
+    const int32_t rc = rayca_hip_scene_update(r->scene, desc);
+    if (rc == RAYCA_ERR_UNSUPPORTED) action = RAYCA_DRAW_REBUILT;   // (the same check said otherwise a moment ago: cannot happen)
+    else if (rc != RAYCA_OK) return rc;
+    else {
+      r->kept.refresh(*desc, std::move(graph));
+      r->updates++;
+      ms[RAYCA_DRAW_MS_UPDATE] = ms_since(t);
+    }
+  }
+  if (action == RAYCA_DRAW_REBUILT) {
+    // what render would refuse in every frame is refused before anything is built: such a descriptor evicts nothing
+    if (!graph.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
+    const auto t = clock::now();
+    // (the copy for the comparisons to come is made by a thread of its own, under the build)
+    KeptDesc fresh;
+    std::thread copier([&] { fresh.assign(*desc, use_bvh, std::move(graph)); });
+    RaycaScene* made = nullptr;
+    const int32_t rc = rayca_hip_scene_create(desc, cfg, &r->opts, &made);
+    const std::string create_err = g_last_error;
+    copier.join();
+    if (rc != RAYCA_OK) return fail(rc, create_err);   // the old scene stays resident, with its copy
+    if (r->scene) (void)rayca_hip_scene_destroy(r->scene);
+    r->scene = made;
+    r->kept = std::move(fresh);
+    r->invalidated = false;
+    r->builds++;
+    ms[RAYCA_DRAW_MS_BUILD] = ms_since(t);
+  }
+  const auto t_render = clock::now();
+  if (const int32_t rc = rayca_hip_render(r->scene, cfg, width, height, opts, rgba8_out, rgba32f_out, stats_out); rc != RAYCA_OK) return rc;
+  ms[RAYCA_DRAW_MS_RENDER] = ms_since(t_render);
+  if (action == RAYCA_DRAW_REUSED) r->reuses++;
+  r->last_action = action;
+  std::copy(ms, ms + RAYCA_DRAW_MS_COUNT, r->last_ms);
+  if (action_out) *action_out = action;
+  return RAYCA_OK;
+}
+
+int32_t rayca_hip_renderer_last_draw(const RaycaRenderer* cr, uint32_t* action_out, float* ms_out, uint64_t* counters_out) {
+  if (!cr) return fail(RAYCA_ERR_BAD_ARG, "null renderer");
+  RaycaRenderer* r = const_cast<RaycaRenderer*>(cr);   // (its mutex)
+  std::lock_guard<std::mutex> lock(r->mu);
+  if (action_out) *action_out = r->last_action;
+  if (ms_out) std::copy(r->last_ms, r->last_ms + RAYCA_DRAW_MS_COUNT, ms_out);
+  if (counters_out) {
+    counters_out[RAYCA_DRAW_N_BUILDS] = r->builds;
+    counters_out[RAYCA_DRAW_N_UPDATES] = r->updates;
+    counters_out[RAYCA_DRAW_N_REUSES] = r->reuses;
+    counters_out[RAYCA_DRAW_N_KEPT_BYTES] = r->kept.bytes();
+  }
+  return RAYCA_OK;
+}
+
+int32_t rayca_hip_renderer_scene(RaycaRenderer* r, RaycaScene** out) {
+  if (!r || !out) return fail(RAYCA_ERR_BAD_ARG, "null renderer or out pointer");
+  std::lock_guard<std::mutex> lock(r->mu);
+  *out = r->scene;
+  return RAYCA_OK;
+}
+
+int32_t rayca_hip_renderer_invalidate(RaycaRenderer* r) {
+  if (!r) return fail(RAYCA_ERR_BAD_ARG, "null renderer");
+  std::lock_guard<std::mutex> lock(r->mu);
+  r->invalidated = true;
+  return RAYCA_OK;
+}
+
+int32_t rayca_hip_renderer_destroy(RaycaRenderer* r) {
+  if (!r) return RAYCA_OK;
+  RaycaScene* scene = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(r->mu);   // (a draw still running on another thread finishes first)
+    scene = r->scene;
+    r->scene = nullptr;
+  }
+  delete r;
+  return rayca_hip_scene_destroy(scene);
+}
+
+int32_t rayca_hip_scene_desc_compare(const RaycaSceneDesc* resident, uint32_t resident_bvh, const RaycaSceneDesc* next, uint32_t next_bvh,
+                                     uint32_t* action_out) {
+  if (action_out) *action_out = RAYCA_NONE;
+  if (!resident || !next || !action_out) return fail(RAYCA_ERR_BAD_ARG, "null descriptor or out pointer");
+  std::string err;
+  if (const int32_t rc = desc_validate(*resident, err); rc != RAYCA_OK) return fail(rc, "resident: " + err);
+  SceneGraph graph;
+  uint32_t action = RAYCA_DRAW_REBUILT;
+  if (const int32_t rc = desc_compare(*resident, resident_bvh != 0, nullptr, *next, next_bvh != 0, action, graph, err); rc != RAYCA_OK) return fail(rc, err);
+  *action_out = action;
   return RAYCA_OK;
 }
 

@@ -1166,6 +1166,238 @@ int32_t scene_graph_pass(const RaycaSceneDesc& d, SceneGraph& s, std::string& er
   return RAYCA_OK;
 }
 
+int32_t update_moves_geometry(const RaycaSceneDesc& d, const SceneGraph& g, const std::vector<Trs>& world_was,
+                              const std::vector<HostLight>& lights_was, std::string& err) {
+  auto same = [](const auto& a, const auto& b) { return std::memcmp(&a, &b, sizeof a) == 0; };
+  const std::string rebuild = ": that moves geometry, which needs rayca_hip_scene_create";
+  for (const uint32_t n : g.mesh_nodes)
+    if (!same(g.world_trs[n], world_was[n])) {
+      err = "node " + std::to_string(n) + " carries a mesh and its world transform changed" + rebuild;
+      return RAYCA_ERR_UNSUPPORTED;
+    }
+  for (size_t i = 0; i < g.lights.size(); ++i) {
+    const HostLight &a = g.lights[i], &b = lights_was[i];
+    const std::string which = "light " + std::to_string(d.nodes[a.node].light) + " (node " + std::to_string(a.node) + ")";
+    if ((a.kind == RAYCA_LIGHT_QUAD) != (b.kind == RAYCA_LIGHT_QUAD)) {
+      err = which + " changes its kind to or from a quad light" + rebuild;
+      return RAYCA_ERR_UNSUPPORTED;
+    }
+    if (a.kind != RAYCA_LIGHT_QUAD) continue;
+    if (!same(a.local, b.local) || !same(g.world_trs[a.node], world_was[a.node])) {
+      err = which + " is a quad light and its transform changed" + rebuild;
+      return RAYCA_ERR_UNSUPPORTED;
+    }
+    if (!same(a.ab, b.ab) || !same(a.ac, b.ac) || a.material != b.material) {
+      err = which + " is a quad light and its ab, ac or material changed" + rebuild;
+      return RAYCA_ERR_UNSUPPORTED;
+    }
+  }
+  return RAYCA_OK;
+}
+
+int32_t desc_validate(const RaycaSceneDesc& d, std::string& err) {
+  if (d.abi_version != RAYCA_ABI_VERSION) { err = "abi version mismatch"; return RAYCA_ERR_BAD_ARG; }
+  const std::pair<const char*, bool> tables[] = {
+      {"nodes", d.node_count && !d.nodes},           {"meshes", d.mesh_count && !d.meshes},
+      {"primitives", d.primitive_count && !d.primitives}, {"positions", d.vertex_count && !d.positions},
+      {"index_bytes", d.index_byte_count && !d.index_bytes}, {"materials", d.material_count && !d.materials},
+      {"textures", d.texture_count && !d.textures},  {"images", d.image_count && !d.images},
+      {"image_bytes", d.image_byte_count && !d.image_bytes}, {"cameras", d.camera_count && !d.cameras},
+      {"lights", d.light_count && !d.lights}};
+  for (const auto& t : tables)
+    if (t.second) { err = std::string(t.first) + " is null"; return RAYCA_ERR_BAD_ARG; }
+  for (uint32_t i = 0; i < d.material_count; ++i) {
+    const RaycaMaterial& m = d.materials[i];
+    for (const uint32_t t : {m.albedo_texture, m.normal_texture, m.metallic_roughness_texture})
+      if (t != RAYCA_NONE && t >= d.texture_count) { err = "material " + std::to_string(i) + ": texture index out of range"; return RAYCA_ERR_BAD_ARG; }
+  }
+  return RAYCA_OK;
+}
+
+namespace {
+
+constexpr int kAttrWidth[6] = {3, 4, 3, 3, 3, 2};
+inline void attr_pointers(const RaycaSceneDesc& d, const float* (&p)[6]) {
+  p[0] = d.positions; p[1] = d.colors; p[2] = d.normals; p[3] = d.tangents; p[4] = d.bitangents; p[5] = d.uvs;
+}
+
+// The counts of two descriptors (and the two words in front of them)
+bool same_counts(const RaycaSceneDesc& a, const RaycaSceneDesc& b) {
+  return a.abi_version == b.abi_version && a.flags == b.flags && a.node_count == b.node_count && a.mesh_count == b.mesh_count &&
+         a.primitive_count == b.primitive_count && a.vertex_count == b.vertex_count && a.index_byte_count == b.index_byte_count &&
+         a.material_count == b.material_count && a.texture_count == b.texture_count && a.image_count == b.image_count &&
+         a.image_byte_count == b.image_byte_count && a.camera_count == b.camera_count && a.light_count == b.light_count;
+}
+
+template <class T>
+bool same_table(const T* a, const T* b, size_t n) {
+  return n == 0 || std::memcmp(a, b, n * sizeof(T)) == 0;
+}
+
+// memcmp of several pairs of large arrays at once: cut into chunks that the threads take in turn; the first difference
+// found stops everybody at their next chunk
+struct BytePair { const uint8_t *a, *b; size_t bytes; };
+bool same_bytes_parallel(const std::vector<BytePair>& pairs) {
+  constexpr size_t kChunk = size_t(256) << 10;
+  struct Chunk { const uint8_t *a, *b; size_t bytes; };
+  std::vector<Chunk> chunks;
+  size_t total = 0;
+  for (const BytePair& p : pairs)
+    for (size_t at = 0; at < p.bytes; at += kChunk) {
+      chunks.push_back(Chunk{p.a + at, p.b + at, std::min(kChunk, p.bytes - at)});
+      total += chunks.back().bytes;
+    }
+  std::atomic<size_t> next{0};
+  std::atomic<bool> differ{false};
+  auto work = [&] {
+    for (;;) {
+      if (differ.load(std::memory_order_relaxed)) return;
+      const size_t i = next.fetch_add(1, std::memory_order_relaxed);
+      if (i >= chunks.size()) return;
+      if (std::memcmp(chunks[i].a, chunks[i].b, chunks[i].bytes) != 0) differ.store(true, std::memory_order_relaxed);
+    }
+  };
+  // (a thread costs some tens of microseconds to start: one per 1 MiB at most)
+  const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), total >> 20));
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
+  work();
+  for (std::thread& th : pool) th.join();
+  return !differ.load();
+}
+
+}  // namespace
+
+void KeptDesc::assign(const RaycaSceneDesc& d, bool use_bvh, SceneGraph&& g) {
+  valid = false;
+  bvh = use_bvh;
+  nodes.assign(d.nodes, d.nodes + d.node_count);
+  meshes.assign(d.meshes, d.meshes + d.mesh_count);
+  primitives.assign(d.primitives, d.primitives + d.primitive_count);
+  const float* src[6];
+  attr_pointers(d, src);
+  // the large arrays: sized without a fill, then copied piecewise on the host threads (first touch of ~10^7 bytes of fresh
+  // pages on one thread costs more than the copy itself)
+  struct Piece { uint8_t* to; const uint8_t* from; size_t bytes; };
+  std::vector<Piece> pieces;
+  auto take = [&pieces](uint8_t* to, const uint8_t* from, size_t bytes) {
+    constexpr size_t kChunk = size_t(1) << 20;
+    for (size_t at = 0; at < bytes; at += kChunk) pieces.push_back(Piece{to + at, from + at, std::min(kChunk, bytes - at)});
+  };
+  for (int k = 0; k < 6; ++k) {
+    const bool has = src[k] != nullptr && d.vertex_count != 0;
+    attr[k].resize(has ? (size_t)d.vertex_count * kAttrWidth[k] : 0);
+    if (has) take(reinterpret_cast<uint8_t*>(attr[k].data()), reinterpret_cast<const uint8_t*>(src[k]), attr[k].size() * sizeof(float));
+  }
+  index_bytes.resize(d.index_byte_count);
+  take(index_bytes.data(), d.index_bytes, d.index_byte_count);
+  image_bytes.resize(d.image_byte_count);
+  take(image_bytes.data(), d.image_bytes, d.image_byte_count);
+  {
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+      for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < pieces.size();) std::memcpy(pieces[i].to, pieces[i].from, pieces[i].bytes);
+    };
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), pieces.size() / 2));
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (std::thread& th : pool) th.join();
+  }
+  materials.assign(d.materials, d.materials + d.material_count);
+  textures.assign(d.textures, d.textures + d.texture_count);
+  images.assign(d.images, d.images + d.image_count);
+  cameras.assign(d.cameras, d.cameras + d.camera_count);
+  lights.assign(d.lights, d.lights + d.light_count);
+  graph = std::move(g);
+  view = d;
+  view.nodes = nodes.data();
+  view.meshes = meshes.data();
+  view.primitives = primitives.data();
+  const float** dst[6] = {&view.positions, &view.colors, &view.normals, &view.tangents, &view.bitangents, &view.uvs};
+  for (int k = 0; k < 6; ++k) *dst[k] = attr[k].empty() ? nullptr : attr[k].data();
+  view.index_bytes = index_bytes.data();
+  view.materials = materials.data();
+  view.textures = textures.data();
+  view.images = images.data();
+  view.image_bytes = image_bytes.data();
+  view.cameras = cameras.data();
+  view.lights = lights.data();
+  valid = true;
+}
+
+void KeptDesc::refresh(const RaycaSceneDesc& d, SceneGraph&& g) {
+  std::copy(d.nodes, d.nodes + d.node_count, nodes.begin());
+  std::copy(d.cameras, d.cameras + d.camera_count, cameras.begin());
+  std::copy(d.lights, d.lights + d.light_count, lights.begin());
+  std::copy(d.materials, d.materials + d.material_count, materials.begin());
+  graph = std::move(g);
+}
+
+uint64_t KeptDesc::bytes() const {
+  if (!valid) return 0;
+  uint64_t b = sizeof(RaycaNode) * nodes.size() + sizeof(RaycaMesh) * meshes.size() + sizeof(RaycaPrimitive) * primitives.size() +
+               index_bytes.size() + image_bytes.size() + sizeof(RaycaMaterial) * materials.size() + sizeof(RaycaTexture) * textures.size() +
+               sizeof(RaycaImage) * images.size() + sizeof(RaycaCamera) * cameras.size() + sizeof(RaycaLight) * lights.size();
+  for (const auto& a : attr) b += sizeof(float) * a.size();
+  b += sizeof(Trs) * (graph.local_trs.size() + graph.world_trs.size()) + sizeof(HostLight) * graph.lights.size();
+  return b;
+}
+
+int32_t desc_compare(const RaycaSceneDesc& was, bool was_bvh, const SceneGraph* was_graph, const RaycaSceneDesc& next, bool next_bvh,
+                     uint32_t& action, SceneGraph& next_graph, std::string& err) {
+  if (const int32_t rc = desc_validate(next, err); rc != RAYCA_OK) return rc;
+  action = RAYCA_DRAW_REBUILT;
+  // ---- what an update cannot change: the tree kind, the counts, the geometry, the textures, the node topology ----
+  bool fixed_equal = was_bvh == next_bvh && same_counts(was, next);
+  bool edited = false;   // a node's trs, a camera, a light or a material differs
+  if (fixed_equal) {
+    fixed_equal = same_table(was.meshes, next.meshes, next.mesh_count) && same_table(was.primitives, next.primitives, next.primitive_count) &&
+                  same_table(was.textures, next.textures, next.texture_count) && same_table(was.images, next.images, next.image_count);
+  }
+  for (uint32_t i = 0; fixed_equal && i < next.node_count; ++i) {
+    const RaycaNode &a = next.nodes[i], &b = was.nodes[i];
+    fixed_equal = a.parent == b.parent && a.model == b.model && a.mesh == b.mesh && a.camera == b.camera && a.light == b.light;
+    edited = edited || std::memcmp(&a.trs, &b.trs, sizeof a.trs) != 0;
+  }
+  if (fixed_equal) {
+    const float *pa[6], *pb[6];
+    attr_pointers(was, pa);
+    attr_pointers(next, pb);
+    std::vector<BytePair> pairs;
+    for (int k = 0; fixed_equal && k < 6; ++k) {
+      const bool has_a = pa[k] && was.vertex_count, has_b = pb[k] && next.vertex_count;
+      fixed_equal = has_a == has_b;   // (a null array means the default attribute, not "as before")
+      if (has_a && has_b && pa[k] != pb[k])
+        pairs.push_back(BytePair{reinterpret_cast<const uint8_t*>(pa[k]), reinterpret_cast<const uint8_t*>(pb[k]), sizeof(float) * kAttrWidth[k] * (size_t)next.vertex_count});
+    }
+    if (next.index_byte_count && was.index_bytes != next.index_bytes) pairs.push_back(BytePair{was.index_bytes, next.index_bytes, (size_t)next.index_byte_count});
+    if (next.image_byte_count && was.image_bytes != next.image_bytes) pairs.push_back(BytePair{was.image_bytes, next.image_bytes, (size_t)next.image_byte_count});
+    fixed_equal = fixed_equal && same_bytes_parallel(pairs);
+  }
+  if (fixed_equal) {
+    edited = edited || !same_table(was.cameras, next.cameras, next.camera_count) || !same_table(was.lights, next.lights, next.light_count) ||
+             !same_table(was.materials, next.materials, next.material_count);
+    if (!edited) {
+      action = RAYCA_DRAW_REUSED;
+      return RAYCA_OK;
+    }
+  }
+  if (const int32_t rc = scene_graph_pass(next, next_graph, err); rc != RAYCA_OK) return rc;
+  if (!fixed_equal) return RAYCA_OK;   // REBUILT
+  // ---- an edit of what rayca_hip_scene_update re-reads: does it leave the geometry where it is? ----
+  SceneGraph made;
+  if (!was_graph) {
+    if (const int32_t rc = scene_graph_pass(was, made, err); rc != RAYCA_OK) return rc;
+    was_graph = &made;
+  }
+  std::string why;
+  if (next_graph.lights.size() == was_graph->lights.size() &&
+      update_moves_geometry(next, next_graph, was_graph->world_trs, was_graph->lights, why) == RAYCA_OK)
+    action = RAYCA_DRAW_UPDATED;
+  return RAYCA_OK;
+}
+
 int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder, HostScene& s, std::string& err, const BuildHooks& hooks) {
   // RAYCA_BUILD_TIMING=1: phase times of the host build on stderr
   static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;

@@ -168,6 +168,48 @@ struct SceneGraph {
 };
 int32_t scene_graph_pass(const RaycaSceneDesc& d, SceneGraph& g, std::string& err);
 
+// Would handing `d` (graph `g`) to a scene whose world transforms and lights were `world_was` / `lights_was` move geometry?
+// The BLASes hold world-space triangles: the meshes' and the quad lights'.  RAYCA_OK, or RAYCA_ERR_UNSUPPORTED with `err`
+// naming the first offending node or light.  rayca_hip_scene_update refuses an edit on this, and the resident draw
+// (rayca_hip_renderer_draw, rayca_hip_scene_desc_compare) decides between an update and a rebuild on it: the same code.
+int32_t update_moves_geometry(const RaycaSceneDesc& d, const SceneGraph& g, const std::vector<Trs>& world_was,
+                              const std::vector<HostLight>& lights_was, std::string& err);
+
+// What is wrong with a descriptor whatever scene is resident: the version, a table that is null while its count is not, a
+// material's texture index out of range.  GPU-free; RAYCA_OK or RAYCA_ERR_BAD_ARG with `err`.
+int32_t desc_validate(const RaycaSceneDesc& d, std::string& err);
+
+// An exact host copy of everything a RaycaSceneDesc points to (which of the optional vertex arrays were null included) plus
+// the cfg->bvh the scene was created with: what rayca_hip_renderer_draw compares the next descriptor against.  A copy, not a
+// fingerprint: every guarantee of the library is bit-exact, and a hash would make "unchanged" a matter of probability.
+struct KeptDesc {
+  bool valid = false;
+  bool bvh = true;
+  RaycaSceneDesc view{};   // counts as given, pointers into the vectors below (null where the descriptor's were)
+  std::vector<RaycaNode> nodes;
+  std::vector<RaycaMesh> meshes;
+  std::vector<RaycaPrimitive> primitives;
+  std::vector<float, DefaultInitAllocator<float>> attr[6];   // positions, colors, normals, tangents, bitangents, uvs
+  std::vector<uint8_t, DefaultInitAllocator<uint8_t>> index_bytes, image_bytes;
+  std::vector<RaycaMaterial> materials;
+  std::vector<RaycaTexture> textures;
+  std::vector<RaycaImage> images;
+  std::vector<RaycaCamera> cameras;
+  std::vector<RaycaLight> lights;
+  SceneGraph graph;        // scene_graph_pass of `view`: the world transforms and lights the resident scene holds
+  void assign(const RaycaSceneDesc& d, bool use_bvh, SceneGraph&& g);
+  // after an update: only nodes (trs), cameras, lights and materials may have changed
+  void refresh(const RaycaSceneDesc& d, SceneGraph&& g);
+  uint64_t bytes() const;
+};
+
+// What a renderer holding `was` (created with was_bvh; `was_graph` = its scene_graph_pass, or null: made here) does when
+// handed `next`: RAYCA_DRAW_REUSED / _UPDATED / _REBUILT in `action`.  The large arrays are compared in chunks on
+// host_threads() threads with an early out, the small tables in line.  `next_graph` receives scene_graph_pass(next) whenever
+// the outcome is not REUSED.  An error (with `err`) only for a descriptor that is wrong in any scene.
+int32_t desc_compare(const RaycaSceneDesc& was, bool was_bvh, const SceneGraph* was_graph, const RaycaSceneDesc& next, bool next_bvh,
+                     uint32_t& action, SceneGraph& next_graph, std::string& err);
+
 struct HostScene {
   std::vector<RaycaNode> nodes;     // the descriptor's node records at creation (what rayca_hip_scene_update compares against)
   std::vector<Trs> local_trs, world_trs;

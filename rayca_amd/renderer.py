@@ -223,15 +223,87 @@ class MultiFrames:
         lib.check(self._l.rayca_hip_render_multi_wait(handles, len(self.scenes), context))
 
 
+class Renderer:
+    """Owns a RaycaRenderer handle: the resident draw().  `draw(desc, ...)` compares `desc` with the descriptor of the previous
+    call inside the library and renders the resident scene as it is (abi.DRAW_REUSED), updates its camera, lights and
+    materials in place (DRAW_UPDATED) or rebuilds it (DRAW_REBUILT); the frame is the one a new DeviceScene(desc, config,
+    builder=...) renders, bit for bit."""
+
+    def __init__(self, device: int = 0, builder: int = abi.BUILDER_SAH, build_on_host: bool = False, _lib=None):
+        self._lib = _lib or lib.load()
+        opts = abi.RaycaBuildOptions()
+        opts.builder, opts.device, opts.build_on_host = builder, device, int(build_on_host)
+        h = C.c_void_p()
+        lib.check(self._lib.rayca_hip_renderer_create(C.byref(opts), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.rayca_hip_renderer_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def draw(self, desc: abi.SceneDesc, config: Config, width: int, height: int, *, traversal=abi.TRAVERSAL_ORDERED,
+             collect_stats=False, tile=None, want_rgba8=True, want_f32=True, engine=abi.ENGINE_AUTO, context=0,
+             camera_rays=abi.CAMERA_AUTO):
+        """rayca_hip_renderer_draw: host outputs, the render options of DeviceScene.render.  Returns (rgba8 | None,
+        rgba32f | None, stats dict, info dict as `last_draw`)."""
+        rows = height
+        if tile is not None:
+            t = abi.RaycaTile()
+            t.part, t.parts, t.band_rows = tile
+            rows = self._lib.rayca_hip_tile_rows(C.byref(t), height)
+        u8 = np.zeros((rows, width, 4), np.uint8) if want_rgba8 else None
+        f32 = np.zeros((rows, width, 4), np.float32) if want_f32 else None
+        st = abi.RaycaStats()
+        cfg = config.to_abi()
+        o = DeviceScene._opts(traversal, collect_stats, tile, None, engine, context, camera_rays)
+        action = C.c_uint32(abi.NONE)
+        lib.check(self._lib.rayca_hip_renderer_draw(self.handle, desc.ptr(), C.byref(cfg), width, height, C.byref(o),
+                                                    u8.ctypes.data if u8 is not None else None,
+                                                    f32.ctypes.data if f32 is not None else None, C.byref(st), C.byref(action)))
+        return u8, f32, st.as_dict(), self.last_draw()
+
+    def last_draw(self) -> dict:
+        """rayca_hip_renderer_last_draw: {"action": abi.DRAW_* (None before the first draw), "ms": {compare, update, build,
+        render} of that draw (host wall time), "builds" / "updates" / "reuses": totals, "kept_bytes"}."""
+        action = C.c_uint32(abi.NONE)
+        ms = (C.c_float * abi.DRAW_MS_COUNT)()
+        n = (C.c_uint64 * abi.DRAW_N_COUNT)()
+        lib.check(self._lib.rayca_hip_renderer_last_draw(self.handle, C.byref(action), ms, n))
+        return {"action": None if action.value == abi.NONE else action.value,
+                "ms": {"compare": ms[abi.DRAW_MS_COMPARE], "update": ms[abi.DRAW_MS_UPDATE], "build": ms[abi.DRAW_MS_BUILD],
+                       "render": ms[abi.DRAW_MS_RENDER]},
+                "builds": n[abi.DRAW_N_BUILDS], "updates": n[abi.DRAW_N_UPDATES], "reuses": n[abi.DRAW_N_REUSES],
+                "kept_bytes": n[abi.DRAW_N_KEPT_BYTES]}
+
+    @property
+    def scene(self) -> Optional[C.c_void_p]:
+        """The resident RaycaScene handle (None before the first draw).  The renderer owns it: the next rebuilding draw
+        destroys it."""
+        h = C.c_void_p()
+        lib.check(self._lib.rayca_hip_renderer_scene(self.handle, C.byref(h)))
+        return h if h.value else None
+
+    def invalidate(self) -> None:
+        """The next draw rebuilds, whatever it is handed."""
+        lib.check(self._lib.rayca_hip_renderer_invalidate(self.handle))
+
+
 class SoftRenderer:
     """Drop-in for rayca_soft::SoftRenderer (scene.rs:11-14): `draw(scene, image)` renders `scene`
-    with camera_draw_infos[0] into `image` (RGBA8).  Like the reference it rebuilds the BVH on
-    every draw; use DeviceScene directly to amortise the build."""
+    with camera_draw_infos[0] into `image` (RGBA8).  The reference rebuilds the BVH on every draw; this one keeps the
+    scene of the last draw resident (a `Renderer`, made at the first draw) and rebuilds only when the scene's geometry,
+    textures or graph changed -- `last_draw` says what the call did.  Same pixels either way."""
 
-    def __init__(self, config: Optional[Config] = None, device: int = 0):
+    def __init__(self, config: Optional[Config] = None, device: int = 0, builder: int = abi.BUILDER_SAH):
         self.config = config or Config()
         self.device = device
+        self.builder = builder
         self.last_stats = None
+        self.last_draw = None
+        self._renderer = None
 
     @staticmethod
     def new_with_config(config: Config) -> "SoftRenderer":
@@ -244,9 +316,14 @@ class SoftRenderer:
     def draw(self, scene: Scene, image: Image) -> None:
         if image.color_type != abi.COLOR_RGBA8:
             raise ValueError("draw() writes RGBA8 images (scene.rs:117)")
-        ds = DeviceScene(flatten(scene), self.config, self.device)
-        try:
-            u8, _, self.last_stats = ds.render(self.config, image.width, image.height, want_f32=False)
-            image.data[...] = u8
-        finally:
-            ds.close()
+        if self._renderer is None:
+            self._renderer = Renderer(self.device, self.builder)
+        u8, _, self.last_stats, self.last_draw = self._renderer.draw(flatten(scene), self.config, image.width, image.height, want_f32=False)
+        image.data[...] = u8
+
+    def close(self) -> None:
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.close()
+            self._renderer = None
+
+    __del__ = close
