@@ -344,7 +344,7 @@ enum {
   RAYCA_KERNEL_WF_SHADE = 4,      /* k_wf_shade: shading, NEE set-up, bounce sampling (wavefront.inc)                */
   RAYCA_KERNEL_WF_SHADOW = 5,     /* k_wf_shadow: shadow rays + direct sum, one pixel per lane (wavefront.inc)       */
   RAYCA_KERNEL_SHADOW_REFILL = 6, /* k_shadow_refill: the same with lane refill (refill.hip)                         */
-  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays                          */
+  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays  */
   RAYCA_KERNEL_CLASSES = 8
 };
 
@@ -591,6 +591,41 @@ uint32_t rayca_hip_tile_rows(const RaycaTile* tile, uint32_t height);
 int32_t rayca_hip_trace_rays(RaycaScene* scene, const RaycaRenderOptions* opts, uint32_t count,
                              const float* rays, float* t_out, uint32_t* prim_out, float* uv_out,
                              RaycaStats* stats_out);
+
+/* Ray queries on DEVICE memory: closest hit or occlusion for `count` caller-supplied rays, each with a distance bound.
+ * Rays, bounds and results stay on the device and the call is asynchronous on the caller's stream, so a host that makes
+ * its rays on the GPU (visibility between point pairs, depth maps from its own ray generator, picking, AO sampling) never
+ * copies them.
+ *   A hit counts iff t < tmax, strictly.  tmax = +inf or FLT_MAX: unbounded.  tmax NaN or <= 0: miss / not occluded.
+ *   RAYCA_QUERY_CLOSEST   per ray exactly the record rayca_hip_trace_rays returns if that record's t < tmax, else the miss
+ *                         record (t = FLT_MAX, prim = RAYCA_NONE, u = v = 0): same bits, same tie rule.  Any of the three
+ *                         outputs may be NULL, not all.
+ *   RAYCA_QUERY_OCCLUDED  one byte per ray: 1 iff CLOSEST with the same tmax reports a hit.  A ray's search ends at its first
+ *                         hit in front of tmax.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event,
+ * record_event, collect_stats and traversal as for rayca_hip_render_device; RAYCA_TRAVERSAL_EXHAUSTIVE is offered for CLOSEST
+ * only (RAYCA_ERR_UNSUPPORTED for OCCLUDED); tile, engine and camera_rays must be zero.  Calls on one context are serialised
+ * and share its work buffers with that context's frames; queries and frames on different contexts overlap.  With
+ * stats_out the call waits for the result: rays_primary (CLOSEST) or rays_shadow (OCCLUDED) = count, the kernel's time
+ * under RAYCA_KERNEL_OTHER.  count == 0 is RAYCA_OK and launches nothing; nothing outside [0, count) of an output is
+ * written.  RAYCA_ERR_BAD_ARG (before any GPU work): NULL scene / query / rays, unknown kind, non-zero reserved, no output
+ * for the kind, context > 7.  RAYCA_ERR_EMPTY_SCENE as rayca_hip_trace_rays. */
+enum { RAYCA_QUERY_CLOSEST = 0, RAYCA_QUERY_OCCLUDED = 1 };
+struct RaycaQuery {
+  uint32_t kind;       /* RAYCA_QUERY_* */
+  uint32_t count;
+  const void* rays;    /* DEVICE: count x 6 f32 (origin xyz, direction xyz; the direction need not be normalised) */
+  const void* tmax;    /* DEVICE: count f32, or NULL => tmax_all for every ray */
+  float tmax_all;
+  uint32_t reserved;   /* must be zero */
+  void* t_out;         /* CLOSEST, DEVICE: count f32, FLT_MAX on miss */
+  void* prim_out;      /* CLOSEST, DEVICE: count u32, RAYCA_NONE on miss; post-build primitive order */
+  void* uv_out;        /* CLOSEST, DEVICE: count x 2 f32, 0 on miss */
+  void* occluded_out;  /* OCCLUDED, DEVICE: count u8, 1 / 0 */
+};
+typedef struct RaycaQuery RaycaQuery;
+int32_t rayca_hip_query_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaQuery* query,
+                               RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

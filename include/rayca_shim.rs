@@ -70,6 +70,9 @@ pub const RAYCA_KERNEL_WF_SHADOW: u32 = 5;
 pub const RAYCA_KERNEL_SHADOW_REFILL: u32 = 6;
 pub const RAYCA_KERNEL_OTHER: u32 = 7;
 pub const RAYCA_KERNEL_CLASSES: u32 = 8;
+// RaycaQuery.kind
+pub const RAYCA_QUERY_CLOSEST: u32 = 0;
+pub const RAYCA_QUERY_OCCLUDED: u32 = 1;
 pub const RAYCA_GATHER_RCCL: u32 = 0;
 pub const RAYCA_GATHER_PEER_COPY: u32 = 1;
 // rayca_hip_renderer_draw: what a draw did, and the indices of rayca_hip_renderer_last_draw's ms_out / counters_out
@@ -280,6 +283,22 @@ pub struct RaycaMultiOptions {
     pub reserved: u32,
 }
 
+// rayca_hip_query_device: rays, bounds and results in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaQuery {
+    pub kind: u32,
+    pub count: u32,
+    pub rays: *const c_void,
+    pub tmax: *const c_void,
+    pub tmax_all: f32,
+    pub reserved: u32,
+    pub t_out: *mut c_void,
+    pub prim_out: *mut c_void,
+    pub uv_out: *mut c_void,
+    pub occluded_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -354,6 +373,7 @@ extern "C" {
     pub fn rayca_hip_rccl_status() -> i32;
     pub fn rayca_hip_tile_rows(tile: *const RaycaTile, height: u32) -> u32;
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

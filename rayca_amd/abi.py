@@ -42,6 +42,7 @@ CAMERA_AUTO, CAMERA_GENERATION, CAMERA_REFILL = 0, 1, 2
 KERNEL_GENERATION, KERNEL_FLAT_REFILL, KERNEL_WF_TRACE, KERNEL_QUEUE_REFILL, KERNEL_WF_SHADE, KERNEL_WF_SHADOW, KERNEL_SHADOW_REFILL, KERNEL_OTHER = range(8)
 KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill", "k_wf_shade", "k_wf_shadow", "k_shadow_refill", "other")
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
+QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # RaycaQuery.kind
 # the resident draw (rayca_hip_renderer_draw): what it did, and the indices of rayca_hip_renderer_last_draw's two arrays
 DRAW_REUSED, DRAW_UPDATED, DRAW_REBUILT = 0, 1, 2
 DRAW_NAMES = ("reused", "updated", "rebuilt")
@@ -277,6 +278,22 @@ def _array(ctype, items):
     return arr
 
 
+class RaycaQuery(C.Structure):
+    """rayca_hip_query_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("count", C.c_uint32),
+        ("rays", C.c_void_p),
+        ("tmax", C.c_void_p),
+        ("tmax_all", C.c_float),
+        ("reserved", C.c_uint32),
+        ("t_out", C.c_void_p),
+        ("prim_out", C.c_void_p),
+        ("uv_out", C.c_void_p),
+        ("occluded_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -393,6 +410,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_trace_rays.restype = C.c_int32
     lib.rayca_hip_trace_rays.argtypes = [C.c_void_p, P(RaycaRenderOptions), C.c_uint32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, P(RaycaStats)]
+    lib.rayca_hip_query_device.restype = C.c_int32
+    lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -413,7 +432,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_version", "rayca_hip_device_count", "rayca_hip_selftest", "rayca_hip_last_error", "rayca_hip_config_default",
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
-    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays",
+    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

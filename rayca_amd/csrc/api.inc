@@ -484,6 +484,26 @@ TraceKernel trace_kernel(Trav t) {
   }
 }
 
+// rayca_hip_query_device, one ray per lane: the flavours that entry falls back to (see there)
+using QueryKernel = void (*)(DevScene, QueryIo, TraceCounters*, TraceLaunch);
+template <bool SPH, bool STATS, bool OCCLUDED>
+QueryKernel query_kernel(Trav t) {
+  switch (t) {
+    case kTravExact:    return k_query_rays<true, false, SPH, false, true, STATS, OCCLUDED>;
+    case kTravExactAll: return k_query_rays<false, false, SPH, false, true, STATS, false>;     // (exhaustive: closest hits only)
+    case kTravFastAll:  return k_query_rays<false, true, SPH, false, true, STATS, false>;
+    default:            return k_query_rays<true, true, SPH, false, true, STATS, OCCLUDED>;    // binary f32 nodes, with the spill path
+  }
+}
+QueryKernel pick_query_kernel(Trav t, bool sph, bool stats, bool occluded) {
+  if (occluded) {
+    if (sph) return stats ? query_kernel<true, true, true>(t) : query_kernel<true, false, true>(t);
+    return stats ? query_kernel<false, true, true>(t) : query_kernel<false, false, true>(t);
+  }
+  if (sph) return stats ? query_kernel<true, true, false>(t) : query_kernel<true, false, false>(t);
+  return stats ? query_kernel<false, true, false>(t) : query_kernel<false, false, false>(t);
+}
+
 // Which node format a generation traverses.  Measured on MI355X (atrium, 1080p, A/B in one run):
 // coherent camera/shadow rays are VALU-bound and the binary tree wins (0.37 vs 0.43 ms for the primary
 // generation: the 4-wide node tests more boxes and sorts), incoherent bounce rays are latency-bound
@@ -2672,6 +2692,110 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
     stats_out->trace_kernel_ms = stats_out->kernel_ms;
     stats_out->kernel_launches = stats_out->trace_kernel_launches = 1;
   }
+  return RAYCA_OK;
+}
+
+// Ray queries on device memory.  A RAYCA_BUILDER_SAH scene whose node formats are there runs the lane-refill kernel
+// (refill.hip k_query_refill, on the 4-wide fp16 nodes k_queue_refill traverses); a RAYCA_BUILDER_REFERENCE scene, exhaustive
+// traversal and a SAH scene whose formats thread has not finished (RaycaStats.node_format bit 11) run k_query_rays, one ray
+// per lane on the binary f32 nodes.  Same results on every path.  The call owns the context like a frame does: it waits for
+// the context's previous work on the device, clears the work counters on the launch stream, and leaves ev_done behind.
+int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaQuery* qin, RaycaStats* stats_out) {
+  if (!s || !qin) return fail(RAYCA_ERR_BAD_ARG, "null scene or query");
+  const RaycaQuery& rq = *qin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (rq.kind != RAYCA_QUERY_CLOSEST && rq.kind != RAYCA_QUERY_OCCLUDED) return fail(RAYCA_ERR_BAD_ARG, "unknown query kind");
+  if (rq.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaQuery.reserved must be zero");
+  if (!rq.rays) return fail(RAYCA_ERR_BAD_ARG, "null rays");
+  const bool occluded = rq.kind == RAYCA_QUERY_OCCLUDED;
+  if (occluded ? !rq.occluded_out : (!rq.t_out && !rq.prim_out && !rq.uv_out)) return fail(RAYCA_ERR_BAD_ARG, "no output for this kind of query");
+  if (o.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
+  if (o.traversal > RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_BAD_ARG, "unknown traversal");
+  if (o.engine != 0 || o.camera_rays != 0 || o.reserved != 0 || o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0)
+    return fail(RAYCA_ERR_BAD_ARG, "tile, engine and camera_rays do not apply to a query: must be zero");
+  const bool ordered = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
+  if (occluded && !ordered) return fail(RAYCA_ERR_UNSUPPORTED, "an occlusion query ends at its first hit: there is no exhaustive form");
+  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if (rq.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  int32_t rc = ensure_ctx(s, c);
+  if (rc != RAYCA_OK) return rc;
+  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
+  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
+  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  const bool stats = o.collect_stats != 0, timing = stats_out != nullptr, sph = s->host.sphere_count != 0;
+  const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+  const bool all_formats = formats_ready(s);
+  const bool refill = ordered && fast && all_formats;
+  QueryIo q{};
+  q.rays = static_cast<const float*>(rq.rays);
+  q.tmax = static_cast<const float*>(rq.tmax);
+  q.tmax_all = rq.tmax_all;
+  q.count = rq.count;
+  if (occluded) {
+    q.occluded_out = static_cast<uint8_t*>(rq.occluded_out);
+  } else {
+    q.t_out = static_cast<float*>(rq.t_out);
+    q.prim_out = static_cast<uint32_t*>(rq.prim_out);
+    q.uv_out = static_cast<float*>(rq.uv_out);
+  }
+  const uint32_t batches = (rq.count + 63u) / 64u;
+  uint32_t grid = (batches + 3u) / 4u;   // one ray per lane; the persistent grid below replaces it
+  StackPlan sp{};
+  QueryKernel k = nullptr;
+  uint32_t node_format = all_formats ? 0u : 2048u;
+  if (refill) {
+    sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);   // (as the wavefront engine plans k_queue_refill's)
+    const uint32_t in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
+    if ((rc = persistent_grid(s, query_refill_kernel(occluded, sph, stats), sp.lds_bytes, batches, true, in_flight, 0u, grid)) != RAYCA_OK) return rc;
+    node_format |= (RAYCA_WF_BOUNCE_WIDE ? 1u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 4u : 0u);
+  } else {
+    const Trav trav = !ordered ? (fast ? kTravFastAll : kTravExactAll) : (fast ? kTravFastSpill : kTravExact);
+    sp = plan_stack(s->host.max_depth);
+    k = pick_query_kernel(trav, sph, stats, occluded);
+    if (fast && RAYCA_NODE_CH && RAYCA_NODE_CH48 && s->dev.nodes_ch) node_format |= 4096u;
+  }
+  TraceLaunch tl{};
+  if ((rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
+  if (timing || stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+  if (refill) {
+    tl.ticket = 1u;
+    HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
+    c->heads_clean = false;   // the next frame of this context clears them for itself
+  }
+  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  if (refill) launch_query_refill(occluded, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, q, c->heads, c->counters, tl);
+  else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, q, c->counters, tl);
+  HIP_TRY(hipGetLastError());
+  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
+  HIP_TRY(hipEventRecord(c->ev_done, stream));
+  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
+  c->frame_pending = true;
+  if (!timing) {   // (as rayca_hip_render_device: the context's own stream is not the caller's to wait on)
+    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RAYCA_OK;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  TraceCounters tc{};
+  if (stats) HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
+  std::memset(stats_out, 0, sizeof *stats_out);
+  (occluded ? stats_out->rays_shadow : stats_out->rays_primary) = rq.count;
+  stats_out->boxes_tested = tc.boxes;
+  stats_out->triangles_tested = tc.tris;
+  stats_out->wave_box_slots = tc.box_slots;
+  stats_out->wave_triangle_slots = tc.tri_slots;
+  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
+  stats_out->trace_kernel_ms = stats_out->kernel_ms;
+  stats_out->kernel_launches = stats_out->trace_kernel_launches = 1;
+  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
+  stats_out->class_launches[RAYCA_KERNEL_OTHER] = 1;
+  stats_out->node_format = node_format;
   return RAYCA_OK;
 }
 

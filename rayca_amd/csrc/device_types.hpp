@@ -114,6 +114,18 @@ struct QueuedRay {
   uint32_t key;    // RNG key of the path vertex this ray leads to
 };
 
+// caller-supplied rays and their results, all in DEVICE memory (rayca_hip_query_device)
+struct QueryIo {
+  const float* rays;   // count x 6: origin xyz, direction xyz
+  const float* tmax;   // count, or nullptr: tmax_all for every ray
+  float tmax_all;
+  uint32_t count;
+  float* t_out;        // closest hit: any of the three may be nullptr
+  uint32_t* prim_out;
+  float* uv_out;
+  uint8_t* occluded_out;
+};
+
 // per generation, per pixel record used to fold the path back in the reference's evaluation order
 enum : uint32_t { kVertexNone = 0, kVertexLit = 1, kVertexEmissive = 2, kVertexLitNoIndirect = 3 };
 

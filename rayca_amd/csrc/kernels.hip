@@ -12,6 +12,8 @@
 //   k_resolve         folds the per-depth records back in the reference's evaluation order,
 //                     accumulates samples, applies gamma and quantises (scene.rs:146-148).
 //   k_trace_rays      Tlas::intersects for caller-supplied rays (parity/debug entry).
+//   k_query_rays      the same for rays in device memory, with a distance bound and an occlusion form
+//                     (rayca_hip_query_device where the lane-refill kernel of refill.hip cannot run).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -305,6 +307,46 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_trace_rays(De
     prim_out[i] = found ? hit.prim : RAYCA_NONE;
     uv_out[2 * i] = found ? hit.u : 0.0f;
     uv_out[2 * i + 1] = found ? hit.v : 0.0f;
+  }
+  if (STATS) {
+    unsigned long long b = cnt.boxes, t = cnt.tris;
+    for (int off = 32; off > 0; off >>= 1) {
+      b += __shfl_down(b, off);
+      t += __shfl_down(t, off);
+    }
+    if (__lane_id() == 0) {
+      atomicAdd(&counters->boxes, b);
+      atomicAdd(&counters->tris, t);
+    }
+  }
+}
+
+// k_trace_rays' sibling for rayca_hip_query_device where the lane-refill kernel (refill.hip k_query_refill) cannot run: scenes
+// without the reference-leaf filter, exhaustive traversal, and the first calls on a scene whose 4-wide / fp16 nodes are still
+// being made.  One ray per lane, rays, bounds and results in device memory.  CLOSEST traces unbounded and applies the bound
+// to the record (trace()'s t_stop would end the search at the first hit in front of it); OCCLUDED hands trace() the bound as
+// t_stop -- for an unbounded ray the largest float below FLT_MAX, so that the early out is on for it too: a hit at or beyond
+// that value merely lets the search run to its end, and query_found() decides either way.
+template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool OCCLUDED>
+__global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(DevScene sc, QueryIo q, TraceCounters* counters, TraceLaunch tl) {
+  extern __shared__ uint32_t lds_stack[];
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  LaneCounters cnt;
+  if (i < q.count) {
+    bool dead;
+    const float bound = query_bound(q, i, dead);
+    DHit hit;
+    hit.t = INFINITY;
+    hit.prim = RAYCA_NONE;
+    hit.u = hit.v = 0.0f;
+    if (!dead) {
+      const float* r = q.rays + 6ull * i;
+      const DRay ray = make_ray(point3(r[0], r[1], r[2]), vec3(r[3], r[4], r[5]));
+      const float t_stop = !OCCLUDED ? FLT_MAX : (bound < FLT_MAX ? bound : __uint_as_float(0x7F7FFFFEu));
+      trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS>(sc, ray, t_stop, stack, hit, cnt);
+    }
+    query_store<OCCLUDED>(q, i, hit, query_found(hit, bound));
   }
   if (STATS) {
     unsigned long long b = cnt.boxes, t = cnt.tris;

@@ -426,6 +426,119 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
   }
 }
 
+// ---- caller-supplied rays (rayca_hip_query_device) with lane refill --------------------------------------------------------
+// k_queue_refill's scheme for rays the caller keeps in device memory: batches of 64 consecutive rays dealt through the per-XCD
+// work counters, a lane that retires its ray writes its outputs and takes the next one.  Differences: the 24-B rays and the
+// optional per-ray bound are read where they lie; the cull bound starts at the ray's tmax (with trace()'s slack) instead of
+// +inf; OCCLUDED ends a ray's search at its first hit in front of tmax (k_shadow_refill's statement, here also for an
+// unbounded ray) and writes one byte.
+// Exactness.  CLOSEST never ends a search early: tmax only seeds `limit`, and test_leaf keeps limit >= min(best t, tmax) +
+// slack.  If the unbounded winner (t*, reference order) has t* < tmax, no box on its path is culled that the unbounded
+// search would not cull with limit = t* + slack, and every candidate that ties with it has the same t*: the same record.
+// Otherwise every hit the search can find has t >= t* >= tmax and query_found() reports the miss record.  OCCLUDED stops at
+// an accepted hit with t < tmax, which implies t* <= t < tmax; without such a stop the search is CLOSEST's.
+// (Threshold, leave-K) = k_queue_refill's measured pair, not retuned.
+template <bool OCCLUDED, bool SPH, bool STATS>
+__global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_query_refill(DevScene sc, QueryIo q, uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
+  constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_queue_refill)
+  extern __shared__ uint32_t lds_stack[];
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  const uint32_t lane = __lane_id();
+  const uint32_t home = xcc_id();
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  const uint32_t count = q.count, n_batches = (count + 63u) >> 6;
+  WorkCursor wc;
+  LaneCounters cnt;
+  bool has = false;
+  uint32_t cur = kTerminated, item = 0;
+  float t_stop = FLT_MAX;
+  DRay ray{};
+  FastRay fr{};
+  DHit hit{};
+  float limit = INFINITY;
+  uint32_t pool_next = 0, pool_end = 0;
+  bool dry = false;
+  for (;;) {
+    const uint32_t n_active = (uint32_t)__popcll(__ballot(cur != kTerminated));
+    if (n_active <= (dry ? 0u : (uint32_t)RAYCA_QREFILL_THRESHOLD)) {
+      if (has && cur == kTerminated) {  // retire: this ray's outputs (item < count: nothing else is ever written)
+        query_store<OCCLUDED>(q, item, hit, query_found(hit, t_stop));
+        has = false;
+      }
+      if (dry && n_active == 0u) break;  // every lane reaches this: n_active and dry are wave-uniform
+      while (!dry) {
+        const unsigned long long idle = __ballot(!has);
+        if (idle == 0ull) break;
+        if (pool_next == pool_end) {
+          const uint32_t batch = next_batch(heads, n_batches, home, wc, tl.ticket);
+          if (batch == RAYCA_NONE) {
+            dry = true;
+            break;
+          }
+          pool_next = batch * 64u;
+          pool_end = min(pool_next + 64u, count);
+        }
+        const uint32_t avail = pool_end - pool_next;
+        const uint32_t rank = (uint32_t)__popcll(idle & lanes_below);
+        if (!has && rank < avail) {
+          item = pool_next + rank;
+          const float* r = q.rays + 6ull * item;
+          ray = make_ray(point3(r[0], r[1], r[2]), vec3(r[3], r[4], r[5]));
+          bool dead;
+          t_stop = query_bound(q, item, dead);
+          fr = make_fast(sc, ray, HALF);   // prologue of trace(): the root box first (blas.rs:136-139)
+          hit.t = INFINITY;
+          hit.prim = RAYCA_NONE;
+          hit.u = hit.v = 0.0f;
+          limit = t_stop < FLT_MAX ? t_stop + fabsf(t_stop) * 9.765625e-4f + sc.cull_abs : INFINITY;
+          stack.clear();
+          float tmin;
+          if (STATS && !dead) cnt.boxes++;
+          cur = !dead && slab(sc.root_min[0], sc.root_min[1], sc.root_min[2], sc.root_max[0], sc.root_max[1], sc.root_max[2], ray, tmin)
+                    ? (WIDE ? sc.root_ref4 : (!HALF && RAYCA_NODE_CH ? sc.root_ref_ch : sc.root_ref))
+                    : kTerminated;
+          has = true;
+        }
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        pool_next += n_idle < avail ? n_idle : avail;
+      }
+    }
+    for (;;) {  // (RAYCA_REFILL_SCHED 0 of k_flat_refill)
+      const bool searching = !(cur & kLeafFlag) && cur != kTerminated;
+      const uint32_t n = (uint32_t)__popcll(__ballot(searching));
+      if (n == 0u) break;
+      if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
+    }
+    if (cur & kLeafFlag) {
+      test_leaf<true, SPH, STATS>(sc, ray, cur, t_stop, hit, limit, cnt);
+      cur = (OCCLUDED && query_found(hit, t_stop)) ? kTerminated : stack.pop();
+    }
+  }
+  if (STATS) {
+    unsigned long long b = cnt.boxes, t = cnt.tris, sb = cnt.slot_boxes, stt = cnt.slot_tris;
+    for (int off = 32; off > 0; off >>= 1) {
+      b += __shfl_down(b, off);
+      t += __shfl_down(t, off);
+      sb += __shfl_down(sb, off);
+      stt += __shfl_down(stt, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&counters->boxes, b);
+      atomicAdd(&counters->tris, t);
+      atomicAdd(&counters->box_slots, sb);
+      atomicAdd(&counters->tri_slots, stt);
+    }
+  }
+}
+
+using QueryRefillKernel = void (*)(DevScene, QueryIo, uint32_t*, TraceCounters*, TraceLaunch);
+template <bool OCCLUDED>
+QueryRefillKernel pick_query(bool sph, bool stats) {
+  if (sph) return stats ? k_query_refill<OCCLUDED, true, true> : k_query_refill<OCCLUDED, true, false>;
+  return stats ? k_query_refill<OCCLUDED, false, true> : k_query_refill<OCCLUDED, false, false>;
+}
+
 using ShadowRefillKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, uint32_t*, TraceCounters*, TraceLaunch);
 template <bool GEN0>
 ShadowRefillKernel pick_shadow(bool sph, bool stats) {
@@ -465,6 +578,15 @@ const void* queue_refill_kernel(bool sph, bool stats) { return reinterpret_cast<
 void launch_queue_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueuedRay* in_rays,
                          const uint32_t* in_count, float4* hits, uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl) {
   hipLaunchKernelGGL(pick_queue(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, in_rays, in_count, hits, heads, counters, tl);
+}
+
+const void* query_refill_kernel(bool occluded, bool sph, bool stats) {
+  return reinterpret_cast<const void*>(occluded ? pick_query<true>(sph, stats) : pick_query<false>(sph, stats));
+}
+
+void launch_query_refill(bool occluded, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueryIo& q,
+                         uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl) {
+  hipLaunchKernelGGL(occluded ? pick_query<true>(sph, stats) : pick_query<false>(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, q, heads, counters, tl);
 }
 
 const void* shadow_refill_kernel(bool gen0, bool sph, bool stats) {

@@ -19,6 +19,11 @@ const void* queue_refill_kernel(bool sph, bool stats);
 void launch_queue_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueuedRay* in_rays,
                          const uint32_t* in_count, float4* hits, uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl);
 
+// the same for rays the caller keeps in device memory (rayca_hip_query_device): closest hit or occlusion, with a distance bound
+const void* query_refill_kernel(bool occluded, bool sph, bool stats);
+void launch_query_refill(bool occluded, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueryIo& q,
+                         uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl);
+
 // and for the shadow-ray pass of a generation (k_wf_shadow's work)
 struct ShadowRefillArgs {
   float4* sh_ray;

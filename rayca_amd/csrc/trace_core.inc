@@ -562,6 +562,30 @@ __device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t
   return hit.prim != RAYCA_NONE;
 }
 
+// ---- ray queries (rayca_hip_query_device): the bound of a caller's ray and its result ------------
+// A hit counts iff t < tmax, strictly (the comparison trace() makes for t_stop, nee.rs:152-156).  The bound as the
+// traversal carries it: FLT_MAX = unbounded (tmax = +inf or FLT_MAX); `dead`: tmax is NaN or <= 0, nothing can count.
+__device__ __forceinline__ float query_bound(const QueryIo& q, uint32_t i, bool& dead) {
+  const float tm = q.tmax ? q.tmax[i] : q.tmax_all;
+  dead = !(tm > 0.0f);
+  return tm < FLT_MAX ? tm : FLT_MAX;
+}
+__device__ __forceinline__ bool query_found(const DHit& hit, float bound) { return hit.prim != RAYCA_NONE && (bound == FLT_MAX || hit.t < bound); }
+// the record k_trace_rays writes, or the miss record; one byte for the occlusion form
+template <bool OCCLUDED>
+__device__ __forceinline__ void query_store(const QueryIo& q, uint32_t i, const DHit& hit, bool found) {
+  if (OCCLUDED) {
+    q.occluded_out[i] = found ? 1 : 0;
+  } else {
+    if (q.t_out) q.t_out[i] = found ? hit.t : FLT_MAX;
+    if (q.prim_out) q.prim_out[i] = found ? hit.prim : RAYCA_NONE;
+    if (q.uv_out) {
+      q.uv_out[2ull * i] = found ? hit.u : 0.0f;
+      q.uv_out[2ull * i + 1ull] = found ? hit.v : 0.0f;
+    }
+  }
+}
+
 // ---- surface data (HitInfo, rayca-soft/src/hit.rs) ---------------------------------------------
 __device__ __forceinline__ Color load_color(const float* c) { return Color{c[0], c[1], c[2], c[3]}; }
 __device__ __forceinline__ F4 load_vec3(const float* c) { return vec3(c[0], c[1], c[2]); }

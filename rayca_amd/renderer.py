@@ -52,6 +52,7 @@ class DeviceScene:
                  builder: int = abi.BUILDER_REFERENCE, build_on_host: bool = False, _lib=None):
         self._lib = _lib or lib.load()  # _lib: an explicitly loaded build of the library (A/B experiments)
         self.desc = desc
+        self.device = device
         cfg = (config or Config()).to_abi()
         opts = abi.RaycaBuildOptions()
         opts.builder, opts.device, opts.build_on_host = builder, device, int(build_on_host)
@@ -172,6 +173,98 @@ class DeviceScene:
         lib.check(self._lib.rayca_hip_trace_rays(self.handle, C.byref(o), n, rays.ctypes.data, t.ctypes.data,
                                                  prim.ctypes.data, uv.ctypes.data, C.byref(st)))
         return t, prim, uv, st.as_dict()
+
+    def query(self, rays, *, tmax=None, kind="closest", stream=None, context=0, out=None, want_stats=False,
+              traversal=abi.TRAVERSAL_ORDERED, collect_stats=False):
+        """rayca_hip_query_device: closest hits or occlusion for rays that live in device memory, asynchronously.
+
+        rays: torch tensor (N, 6) float32 on this scene's device (origin xyz, direction xyz).  tmax: None (unbounded), a
+        float for every ray, or an (N,) float32 tensor; a hit counts iff t < tmax.  kind "closest" returns (t, prim, uv):
+        float32 (N,) with FLT_MAX on a miss, int32 (N,) holding the u32 primitive slot (abi.NONE, i.e. -1, on a miss) and
+        float32 (N, 2); kind "occluded" returns a uint8 (N,) mask.  `out`: the tensor(s) to write instead of new ones (for
+        "closest" a 3-tuple whose entries may be None).  The kernel is launched on `stream` (a torch.cuda.Stream or a raw
+        handle), by default torch's current stream of the device; nothing is copied except an input that is not contiguous,
+        and nothing is waited for unless statistics are asked for (`want_stats` / `collect_stats`: the stats dict is appended
+        to the result)."""
+        import torch
+        if kind not in ("closest", "occluded"):
+            raise ValueError(f"kind must be 'closest' or 'occluded', not {kind!r}")
+        occluded = kind == "occluded"
+        dev = torch.device("cuda", self.device)
+
+        def checked(x, name, dtype, shape):
+            if not isinstance(x, torch.Tensor):
+                raise TypeError(f"{name}: a torch tensor on {dev} is expected, not {type(x).__name__}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if x.dtype != dtype:
+                raise TypeError(f"{name}: dtype {x.dtype}, expected {dtype}")
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
+            return x
+
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError(f"rays: a torch tensor on {dev} is expected, not {type(rays).__name__}")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError(f"rays: shape {tuple(rays.shape)}, expected (N, 6)")
+        n = rays.shape[0]
+        if n > 0xFFFFFFFF:
+            raise ValueError("rays: more than 2**32 - 1 rays")
+        checked(rays, "rays", torch.float32, (n, 6))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        if not handle:
+            # the legacy default stream: the library runs a call without a stream on the context's own (non-blocking) stream
+            # and waits for it, so what torch still has queued for the inputs must have finished first
+            torch.cuda.default_stream(dev).synchronize()
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        rays = contiguous(rays)
+        q = abi.RaycaQuery()
+        q.kind, q.count, q.rays = (abi.QUERY_OCCLUDED if occluded else abi.QUERY_CLOSEST), n, rays.data_ptr()
+        if tmax is None:
+            q.tmax_all = float("inf")
+        elif isinstance(tmax, torch.Tensor):
+            tmax = contiguous(checked(tmax, "tmax", torch.float32, (n,)))
+            q.tmax = tmax.data_ptr()
+        else:
+            q.tmax_all = float(tmax)
+
+        def output(x, name, dtype, shape):
+            if x is None:
+                return torch.empty(shape, dtype=dtype, device=dev)
+            if not checked(x, name, dtype, shape).is_contiguous():
+                raise ValueError(f"{name}: an output must be contiguous")
+            return x
+
+        if occluded:
+            result = (output(out, "out", torch.uint8, (n,)),)
+            q.occluded_out = result[0].data_ptr()
+        else:
+            o_t, o_prim, o_uv = out if out is not None else (None, None, None)
+            result = (output(o_t, "out[0] (t)", torch.float32, (n,)), output(o_prim, "out[1] (prim)", torch.int32, (n,)),
+                      output(o_uv, "out[2] (uv)", torch.float32, (n, 2)))
+            q.t_out, q.prim_out, q.uv_out = (x.data_ptr() for x in result)
+        st = abi.RaycaStats() if (want_stats or collect_stats) else None
+        o = self._opts(traversal, collect_stats, None, handle or None, context=context)
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            lib.check(self._lib.rayca_hip_query_device(self.handle, C.byref(o), C.byref(q), C.byref(st) if st is not None else None))
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        for x in temporaries:   # (a contiguous copy made here is read by a kernel on `stream`: the allocator must know)
+            x.record_stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=dev))
+        result = result[0] if occluded else result
+        if st is None:
+            return result
+        return (result, st.as_dict()) if occluded else (*result, st.as_dict())
 
 
 def _multi_args(scenes, config, band_rows, gather, traversal, collect_stats, engine, context):
