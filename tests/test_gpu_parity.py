@@ -243,6 +243,54 @@ def test_albedo_texture_nearest_wrap(gpu):
     assert_close(f32, of32, u8, ou8)
 
 
+@pytest.mark.parametrize("builder", [abi.BUILDER_REFERENCE, abi.BUILDER_SAH], ids=["reference", "sah"])
+def test_create_that_fails_after_the_build_leaves_the_library_usable(gpu, builder):
+    # both are found once the BVH is built and the primitives are on the device: scene_create gives all of that back
+    desc = flatten(_textured_quad_scene())
+    desc._textures[0].image = desc.c.image_count + 6
+    with pytest.raises(RaycaError) as e:
+        DeviceScene(desc, Config(), builder=builder)
+    assert e.value.code == abi.ERR_BAD_ARG and str(e.value).endswith(": texture references a missing image")
+    desc = flatten(_textured_quad_scene())
+    desc._images[0].width = 0
+    with pytest.raises(RaycaError) as e:
+        DeviceScene(desc, Config(), builder=builder)
+    assert e.value.code == abi.ERR_BAD_ARG and str(e.value).endswith(": empty texture image")
+    # and the next scene of the process is built and rendered as ever
+    desc = flatten(_textured_quad_scene())
+    ds, orc = DeviceScene(desc, Config(), builder=builder), ol.OracleScene(desc, Config())
+    _, f32, _ = ds.render(FLAT, 200, 200)
+    _, of32, _ = orc.render(FLAT, 200, 200)
+    assert_exact(f32, of32)
+    cfg = Config(max_depth=1)
+    u8, f32, _ = ds.render(cfg, 200, 200)
+    ou8, of32, _ = orc.render(cfg, 200, 200)
+    assert_close(f32, of32, u8, ou8)
+    ds.close()
+    orc.close()
+
+
+def test_create_that_fails_with_trees_held_on_the_device(gpu):
+    # 20 000 triangles in one BLAS: built on the device, whose tree is still held there when the texture table is refused
+    def soup(bad):
+        scene = scenes.soup_scene(20000, extent=0.03)
+        if bad:
+            scene.models[0].textures.push(Texture(image=0))     # (the model has no image)
+        return flatten(scene)
+    for _ in range(2):
+        with pytest.raises(RaycaError) as e:
+            DeviceScene(soup(True), Config(), builder=abi.BUILDER_SAH)
+        assert e.value.code == abi.ERR_BAD_ARG and str(e.value).endswith(": texture references a missing image")
+    desc = soup(False)
+    ds = DeviceScene(desc, Config(), builder=abi.BUILDER_SAH)
+    orc = ol.OracleScene(desc, Config(), build=ol.BUILD_BINNED)
+    _, f32, _ = ds.render(FLAT, 384, 384)
+    _, of32, _ = orc.render(FLAT, 384, 384)
+    assert_exact(f32, of32)
+    ds.close()
+    orc.close()
+
+
 def _quad_light_room():
     """Phong room lit by an emissive quad light (the SDTF-style setup, light/quad.rs + nee.rs:72-125)."""
     model = Model()
