@@ -351,7 +351,11 @@ enum {
 /* Filled by every render call (all counters are per call, summed over spp and generations). */
 typedef struct RaycaStats {
   uint64_t rays_primary;
-  uint64_t rays_shadow;
+  uint64_t rays_shadow;      /* NEE / light samples EVALUATED (the reference's count).  A sample that cannot contribute (zero
+                              * in r, g, b, finite alpha) is counted here although no shadow ray is traversed for it: such a
+                              * sample tests no box, not even the root's, so boxes_tested may be smaller than the number of
+                              * rays where many samples are skipped and the tree is shallow (RAYCA_NEE_SKIP=0 traces them all;
+                              * so do exhaustive traversal and a scene whose tree is a single leaf) */
   uint64_t rays_bounce;
   uint64_t boxes_tested;     /* only with collect_stats: AABB slab tests (32 B each)            */
   uint64_t triangles_tested; /* only with collect_stats: ray/triangle tests (36 B each)         */

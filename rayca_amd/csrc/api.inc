@@ -189,6 +189,9 @@ struct RaycaScene {
   MultiCtx multi;
   std::mutex multi_mu;
   std::mutex tune_mu;      // guards every read and write of tune[][] (frames of different contexts run on different threads)
+  // RAYCA_NEE_SKIP=0, read when the scene is created, turns off the skipping of NEE samples that cannot contribute
+  // (trace_core.inc nee_irrelevant): for A/B measurements and the tests that compare frames with and without it.  Same bits.
+  bool nee_skip = true;
 };
 
 namespace {
@@ -1076,6 +1079,10 @@ int32_t fill_stats(Frame& f, RaycaStats* out) {
   out->hits_shaded = tc.shaded;
   out->wave_box_slots = tc.box_slots;
   out->wave_triangle_slots = tc.tri_slots;
+  // RAYCA_NEE_SKIP_REPORT: how many of the frame's NEE samples could not contribute on stderr, for frames of the fused engine with collect_stats (only k_generation counts them) --
+  // RaycaStats has no room for it and its layout is pinned
+  static const bool nee_report = getenv("RAYCA_NEE_SKIP_REPORT") != nullptr;
+  if (nee_report && f.plan.mode == kModePath && !f.plan.wavefront && f.plan.stats) fprintf(stderr, "[rayca nee] irrelevant %llu of %llu samples, skip %s\n", tc.nee_irrelevant, tc.shadow, f.fp.nee_skip ? "on" : "off");
   HIP_TRY(hipEventElapsedTime(&out->kernel_ms, c->ev_begin, c->ev_end));
   float tsum = 0.0f;
   for (size_t i = 0; i + 1 < f.log.ev_used; i += 2) {
@@ -1158,6 +1165,10 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   fp.strate_count = cfg.light_stratify ? (uint32_t)sqrtf((float)cfg.light_samples) : 1u;  // config.rs:73-79
   fp.max_depth = cfg.max_depth; fp.russian_roulette = cfg.russian_roulette; fp.seed = cfg.seed; fp.spp = cfg.samples_per_pixel;
   fp.inv_gamma = 1.0f / cfg.gamma;  // color/mod.rs:175-176
+  // Not with exhaustive traversal, which reproduces the reference's test counts: every sample traced.  And not where the tree is a
+  // single leaf: a ray's whole search is then the root box and that leaf -- there is no traversal to save -- and the accounting
+  // "every counted ray has tested the root box" (boxes_tested >= rays, exact for such a scene: tests/test_gpu_engines.py) holds.
+  fp.nee_skip = s->nee_skip && plan.ordered && !(f.dscene->root_ref & kLeafFlag) ? 1u : 0u;
   const float strate = sqrtf((float)cfg.samples_per_pixel);  // scene.rs:125-127
   const float sub_offset = 0.5f / strate, sub_step = 1.0f / strate;
 

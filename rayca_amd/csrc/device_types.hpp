@@ -85,6 +85,7 @@ struct FrameParams {
   float sub_step_x, sub_step_y; // ix*step, iy*step of this sample; the kernel evaluates (x + ix*step) + offset, the reference's
   float sub_offset;             // association (scene.rs:125-137): folding the two terms on the host differs by 1 ulp for spp = 2, 3, 5, 9 ...
   float inv_gamma;
+  uint32_t nee_skip;            // 1: NEE samples that cannot contribute are not traced (trace_core.inc nee_irrelevant); ORDERED traversal only
 };
 
 // per-launch traversal workspace: the node stack lives in LDS up to `lds_entries` entries per lane
@@ -105,6 +106,7 @@ struct TraceLaunch {
 struct TraceCounters {
   unsigned long long boxes, tris, shaded, shadow, bounce, box_slots, tri_slots;
   unsigned long long flags;  // k_general: kFlagUnsupported | kFlagTooDeep
+  unsigned long long nee_irrelevant;  // STATS instantiations of k_generation: NEE samples that meet nee_irrelevant(), skipped or not
 };
 
 // ray queue entry between two generations (32 B)

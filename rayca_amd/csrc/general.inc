@@ -372,6 +372,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_GENERAL_MIN_WAVES) void k_general(Dev
     float t_stop = FLT_MAX;
     NeeSample ns;               // the NEE / light sample the pending shadow ray decides
     ns.x = black(); ns.t_stop = FLT_MAX; ns.quad = 0u;
+    bool ns_skipped = false;    // that sample cannot contribute: no shadow ray was traced for it
     F4 s_omega = vec3(0, 0, 0); // direction of the pending shadow ray where the handler needs it again
     float s_aux = 0.0f;
     Color ret = black();        // result of the child that just returned
@@ -473,10 +474,19 @@ __global__ __launch_bounds__(kBlock, RAYCA_GENERAL_MIN_WAVES) void k_general(Dev
               }
               ns = nee_prepare(sc, fp, g.s, f.li, f.k, f.key, f.dim, tray);
               s_omega = tray.d;
-              t_stop = ns.t_stop;
-              pending = true;
               n_shadow++;
               f.phase = GP_PT_SHADOW;
+              // A sample that cannot contribute (nee_irrelevant, trace_core.inc) goes straight to its handler as "not lit", without a
+              // traversal.  MIS still records it, as black() = (0, 0, 0, 1) where the traced sample would be (+-0, +-0, +-0, a): both
+              // enter the weighted sum as (w * +-0) * alpha, the same bits because a is finite (the rule) -- +-0 for a finite w, NaN
+              // for a NaN one, whatever the alpha.
+              ns_skipped = ORDERED && fp.nee_skip && nee_irrelevant(ns);
+              if (ns_skipped) {
+                again = true;
+              } else {
+                t_stop = ns.t_stop;
+                pending = true;
+              }
             } else if (fp.direct_sampler == RAYCA_SAMPLER_MIS) {  // BrdfSampler::sample_direct  brdf.rs:47-66
               s_omega = surf_random_dir(g, f.key, f.dim);
               if (g.t_todo) todo = true;
@@ -491,9 +501,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_GENERAL_MIN_WAVES) void k_general(Dev
             }
           } break;
           case GP_PT_SHADOW: {
-            bool lit;
-            if (ns.quad) {
-              lit = false;
+            bool lit = false;
+            if (ns_skipped) {
+              // (no shadow ray was traced: `found` and `h` are not this sample's)
+            } else if (ns.quad) {
               if (found) {
                 const uint32_t hm = sc.ext[h.prim].material;
                 lit = hm != RAYCA_NONE && hm < sc.material_count && sc.materials[hm].emissive != 0u;

@@ -148,13 +148,34 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
         }
       }
       if (live && in_shadow) {
-        if (li < nee_lights) {
-          if (PARK) cx = unpark_ctx(ctx_slot);  // (its own LDS slot: no barrier; the compiler orders a lane's LDS accesses)
+        // the next sample that has to be traced.  A sample that cannot contribute (nee_irrelevant, trace_core.inc) is booked as
+        // "not lit" -- the sum stays as it is, the same bits as adding black() -- and the lane prepares the one after it
+        // instead of entering trace() for it; ORDERED only: the exhaustive form reproduces the reference's test counts
+        bool pending = false;
+        while (li < nee_lights) {
+          // (its own LDS slot: no barrier; the compiler orders a lane's LDS accesses.  Fetched per trip: a context that stayed in
+          // registers over the loop's back edge doubled the kernel's spills)
+          if (PARK) cx = unpark_ctx(ctx_slot);
           const NeeSample ns = nee_prepare(sc, fp, cx, li, k, key, dim, ray);
+          const bool irrelevant = ORDERED && nee_irrelevant(ns);
+          if (STATS) {  // booked at once by one lane: a counter of its own would be one more register the trace loop carries
+            const unsigned long long m = __ballot(irrelevant);
+            if (m != 0ull && lane == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&counters->nee_irrelevant, (unsigned long long)__popcll(m));
+          }
+          if (irrelevant && fp.nee_skip) {
+            if (++k == fp.light_samples) {
+              k = 0;
+              ++li;
+            }
+            continue;
+          }
           if (PARK) ctx_slot[5 * kBlock] = as_f4(ns.x);
           else ns_x = ns.x;
           t_stop = ns.t_stop;
-        } else {
+          pending = true;
+          break;
+        }
+        if (!pending) {
           tail = true;
           live = false;
         }

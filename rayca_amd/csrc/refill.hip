@@ -315,11 +315,20 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
   float limit = INFINITY;
   uint32_t pool_next = 0, pool_end = 0;
   bool dry = false;
-  // the j-th shadow ray of pixel p: prologue of trace() with the any-hit bound
+  // the next shadow ray of pixel p that has to be traced, from the j-th on: prologue of trace() with the any-hit bound.  A sample
+  // that k_wf_shade marked as unable to contribute is "not lit" without a traversal, which leaves the sum as it is
+  // (nee_irrelevant, trace_core.inc).  After the pixel's last sample the sum is written and the lane is free for the next item.
   auto start_ray = [&]() {
+    while (j < wb.nls && (__float_as_uint(wb.sh_ray[2 * ((size_t)j * pb.npix + p) + 1].w) & kShadowSkip)) ++j;
+    if (j == wb.nls) {
+      pb.direct[(size_t)depth * pb.npix + p] = as_f4(direct);
+      has = false;
+      cur = kTerminated;
+      return;
+    }
     const size_t e = (size_t)j * pb.npix + p;
     const float4 a = wb.sh_ray[2 * e], b = wb.sh_ray[2 * e + 1];
-    quad = __float_as_uint(b.w);
+    quad = __float_as_uint(b.w) & kShadowQuad;
     t_stop = a.w;
     ray = make_ray(point3(a.x, a.y, a.z), vec3(b.x, b.y, b.z));
     fr = make_fast(sc, ray, HALF);
@@ -349,12 +358,8 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
         }
         const size_t e = (size_t)j * pb.npix + p;
         direct = direct + (lit ? as_color(wb.sh_x[e]) : black());
-        if (++j == wb.nls) {
-          pb.direct[(size_t)depth * pb.npix + p] = as_f4(direct);
-          has = false;
-        } else {
-          start_ray();
-        }
+        ++j;
+        start_ray();   // (or, after the last sample, the pixel's sum)
       }
       // (every lane reaches this: both operands are wave-uniform.  A lane that still holds a pixel -- its next ray started by
       // the retire above, or ended at the root box at once -- keeps the wave going; it retires on a later trip)

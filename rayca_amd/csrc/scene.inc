@@ -542,6 +542,7 @@ int32_t rayca_hip_scene_create(const RaycaSceneDesc* desc, const RaycaConfig* cf
   b.s = b.pu.s = s;
   b.pu.device = device;
   s->device = device;
+  if (const char* e = getenv("RAYCA_NEE_SKIP")) s->nee_skip = atoi(e) != 0;
   s->counts.node_count = desc->node_count;
   s->counts.mesh_count = desc->mesh_count;
   s->counts.primitive_count = desc->primitive_count;

@@ -992,6 +992,25 @@ __device__ __forceinline__ NeeSample nee_prepare(const DevScene& sc, const Frame
   return ns;
 }
 
+// An NEE sample whose shadow ray need not be traced: its candidate contribution is zero in r, g and b (the surface faces away
+// from the light: n_dot_omega clamps to 0; a zero BRDF; a light of intensity 0) and its alpha is
+// finite.  The outcome of the traversal then cannot change a bit of the pixel:
+//   - every consumer adds the sample with operator+(Color a, Color b) = (a.rgb + b.rgb * b.a, a.a), and "not lit" adds black() =
+//     (0, 0, 0, 1): the terms are +-0 * finite = +-0 against +0 * 1 = +0, and alpha stays a.a either way;
+//   - the sum the sample joins starts at +0 per channel, and a float sum that starts at +0 never becomes -0 under round to nearest
+//     (x + y is -0 only if both are), so it is either +0, where +0 + (+-0) = +0, or non-zero or NaN, where adding +-0 returns it;
+//   - hence sum + x and sum + black() are the same bits, whatever `lit` would have been -- for a quad light too, whose `lit`
+//     depends on the closest hit's material and equally does not matter.
+// (A quad light seen from its back is NOT such a case: d_omega = dot(L.normal, omega) / r^2 is not clamped, the contribution is
+// negative, not zero, and the sample is traced.)
+// A NaN or an infinity anywhere in x fails one of the four comparisons (0 * inf would be NaN): that sample is traced as before.
+// Booking the sample as "not lit" therefore equals tracing it; rays_shadow still counts it (the reference's count of samples).
+__device__ __forceinline__ bool nee_irrelevant(const NeeSample& ns) {
+  return ns.x.r == 0.0f && ns.x.g == 0.0f && ns.x.b == 0.0f && fabsf(ns.x.a) < INFINITY;
+}
+// the shadow-ray record of the wavefront engine (WfBuffers::sh_ray) carries the sample's kind and this mark in one word
+constexpr uint32_t kShadowQuad = 1u, kShadowSkip = 2u;
+
 // ---- shared by the wavefront engine's kernels (wavefront.inc) and their lane-refill forms (refill.hip) ------------------
 struct WfBuffers {
   float4* hits;     // [item]: t, prim, u, v of the generation's rays (item = packed pixel for generation 0, queue slot after)

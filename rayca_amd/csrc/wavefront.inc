@@ -116,9 +116,16 @@ __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_shadow(DevSce
   Color direct = black();
   uint32_t j = 0;
   while (live) {
+    // the pixel's next sample that has to be traced: one that k_wf_shade marked as unable to contribute is "not lit" without
+    // a traversal, which leaves the sum as it is (nee_irrelevant, trace_core.inc)
+    while (j < wb.nls && (__float_as_uint(wb.sh_ray[2 * ((size_t)j * pb.npix + p) + 1].w) & kShadowSkip)) ++j;
+    if (j == wb.nls) {
+      pb.direct[(size_t)depth * pb.npix + p] = as_f4(direct);
+      break;
+    }
     const size_t e = (size_t)j * pb.npix + p;
     const float4 a = wb.sh_ray[2 * e], b = wb.sh_ray[2 * e + 1];
-    const uint32_t quad = __float_as_uint(b.w);
+    const uint32_t quad = __float_as_uint(b.w) & kShadowQuad;
     const float t_stop = a.w;
     DHit hit;
     const bool found = trace<true, FAST, SPH, FAST && RAYCA_WF_SHADOW_WIDE, SPILL, STATS, FAST && RAYCA_WF_SHADOW_HALF, RAYCA_LEAVE_K_WF_SHADOW>(sc, make_ray(point3(a.x, a.y, a.z), vec3(b.x, b.y, b.z)), t_stop, stack, hit, cnt);
@@ -224,7 +231,8 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FramePara
             const NeeSample ns = nee_prepare(sc, fp, cx, li, k, key, dim, sray);
             const size_t e = (size_t)jj * pb.npix + p;
             wb.sh_ray[2 * e] = make_float4(sray.o.x, sray.o.y, sray.o.z, ns.t_stop);
-            wb.sh_ray[2 * e + 1] = make_float4(sray.d.x, sray.d.y, sray.d.z, __uint_as_float(ns.quad));
+            const uint32_t mark = (fp.nee_skip && nee_irrelevant(ns)) ? kShadowSkip : 0u;  // the shadow kernels do not traverse it
+            wb.sh_ray[2 * e + 1] = make_float4(sray.d.x, sray.d.y, sray.d.z, __uint_as_float(ns.quad | mark));
             wb.sh_x[e] = as_f4(ns.x);
             n_shadow++;
           }
