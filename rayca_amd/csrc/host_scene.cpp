@@ -1763,8 +1763,10 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
     if (builder == RAYCA_BUILDER_SAH) {
       // This tree's boxes only have to be conservative (the reference-leaf filter decides candidacy):
       // pad them by 2^-16 of their magnitude plus 2^-20 of the scene diagonal, two orders of magnitude
-      // above the rounding of the slab and triangle arithmetic, so that a triangle the ray hits is
-      // never lost because an enclosing box rounds the other way.
+      // above the rounding of the slab and triangle arithmetic for a ray that starts within four scene
+      // diagonals of the origin, so that a triangle such a ray hits is never lost because an enclosing
+      // box rounds the other way.  The padding cannot know a ray's origin: rays from farther away carry
+      // a slack of their own through the steering tests (trace_core.inc, RAYCA_RAY_SLACK).
       const F4 ext = as_vec(tn[0].bounds.b - tn[0].bounds.a);
       const float diag = sqrtf(ext.x * ext.x + ext.y * ext.y + ext.z * ext.z);
       db.pad_rel = 1.52587890625e-05f;

@@ -94,7 +94,8 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
     while (live) {
       DHit hit;
       constexpr int kLeaveK = !ORDERED ? 0 : (MODE == kModeFlat ? RAYCA_LEAVE_K_CAMERA : (GEN0 ? RAYCA_LEAVE_K_PATH0 : RAYCA_LEAVE_K_BOUNCE));
-      const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, kLeaveK>(sc, ray, t_stop, stack, hit, cnt);
+      constexpr int kSlackForm = MODE == kModeFlat ? kSlackAlways : (GEN0 ? kSlackPerWave : kSlackNever);
+      const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, kLeaveK, kSlackForm>(sc, ray, t_stop, stack, hit, cnt);
       if (!in_shadow) {
         if (!found) {
           if (FUSED) direct = black() + black();  // unwrap_or(BLACK), color += it
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_trace_rays(De
     const float* r = rays + 6ull * i;
     const DRay ray = make_ray(point3(r[0], r[1], r[2]), vec3(r[3], r[4], r[5]));
     DHit hit;
-    const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS>(sc, ray, FLT_MAX, stack, hit, cnt);
+    const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, false, 0, kSlackAlways>(sc, ray, FLT_MAX, stack, hit, cnt);
     t_out[i] = found ? hit.t : FLT_MAX;
     prim_out[i] = found ? hit.prim : RAYCA_NONE;
     uv_out[2 * i] = found ? hit.u : 0.0f;
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
       const float* r = q.rays + 6ull * i;
       const DRay ray = make_ray(point3(r[0], r[1], r[2]), vec3(r[3], r[4], r[5]));
       const float t_stop = !OCCLUDED ? FLT_MAX : (bound < FLT_MAX ? bound : __uint_as_float(0x7F7FFFFEu));
-      trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS>(sc, ray, t_stop, stack, hit, cnt);
+      trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, false, 0, kSlackAlways>(sc, ray, t_stop, stack, hit, cnt);
     }
     query_store<OCCLUDED>(q, i, hit, query_found(hit, bound));
   }

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_REFILL_WAVES) void k_flat_refill(DevS
     if (n_search * (uint32_t)RAYCA_REFILL_NODE_W >= n_leaf * (uint32_t)RAYCA_REFILL_LEAF_W && n_search != 0u) {
       if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
     } else if (at_leaf) {
-      test_leaf<true, SPH, STATS>(sc, ray, cur, FLT_MAX, hit, limit, cnt);
+      test_leaf<true, SPH, STATS>(sc, ray, fr, cur, FLT_MAX, hit, limit, cnt);
       cur = stack.pop();
     }
 #else
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_REFILL_WAVES) void k_flat_refill(DevS
       if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
     }
     if (cur & kLeafFlag) {
-      test_leaf<true, SPH, STATS>(sc, ray, cur, FLT_MAX, hit, limit, cnt);
+      test_leaf<true, SPH, STATS>(sc, ray, fr, cur, FLT_MAX, hit, limit, cnt);
       cur = stack.pop();
     }
 #endif
@@ -196,6 +196,8 @@ __global__ __launch_bounds__(kBlock, RAYCA_REFILL_WAVES) void k_flat_refill(DevS
 #ifndef RAYCA_QREFILL_WAVES
 #define RAYCA_QREFILL_WAVES RAYCA_REFILL_WAVES
 #endif
+// (This kernel and k_shadow_refill trace bounce and shadow rays only: their origins lie on the scene's surfaces, where the padding
+// of the steering boxes covers the rounding of c -- trace_core.inc ray_needs_slack -- so their node steps carry no slack.)
 template <bool SPH, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_queue_refill(DevScene sc, const QueuedRay* in_rays, const uint32_t* in_count, float4* hits,
                                                                               uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
@@ -262,10 +264,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_queue_refill(De
       const uint32_t n = (uint32_t)__popcll(__ballot(searching));
       if (n == 0u) break;
       if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
-      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF, false>(sc, ray, fr, limit, cur, stack, cnt);
     }
     if (cur & kLeafFlag) {
-      test_leaf<true, SPH, STATS>(sc, ray, cur, FLT_MAX, hit, limit, cnt);
+      test_leaf<true, SPH, STATS, false>(sc, ray, fr, cur, FLT_MAX, hit, limit, cnt);
       cur = stack.pop();
     }
   }
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
     hit.t = INFINITY;
     hit.prim = RAYCA_NONE;
     hit.u = hit.v = 0.0f;
-    limit = t_stop < FLT_MAX ? t_stop + fabsf(t_stop) * 9.765625e-4f + sc.cull_abs : INFINITY;
+    limit = t_stop < FLT_MAX ? cull_limit<false>(sc, fr, t_stop) : INFINITY;
     stack.clear();
     float tmin;
     if (STATS) cnt.boxes++;
@@ -407,10 +409,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
       const uint32_t n = (uint32_t)__popcll(__ballot(searching));
       if (n == 0u) break;
       if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
-      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF, false>(sc, ray, fr, limit, cur, stack, cnt);
     }
     if (cur & kLeafFlag) {
-      test_leaf<true, SPH, STATS>(sc, ray, cur, t_stop, hit, limit, cnt);
+      test_leaf<true, SPH, STATS, false>(sc, ray, fr, cur, t_stop, hit, limit, cnt);
       cur = (t_stop < FLT_MAX && hit.t < t_stop) ? kTerminated : stack.pop();   // any hit in front of the light ends the search (trace())
     }
   }
@@ -495,7 +497,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_query_refill(De
           hit.t = INFINITY;
           hit.prim = RAYCA_NONE;
           hit.u = hit.v = 0.0f;
-          limit = t_stop < FLT_MAX ? t_stop + fabsf(t_stop) * 9.765625e-4f + sc.cull_abs : INFINITY;
+          limit = t_stop < FLT_MAX ? cull_limit<true>(sc, fr, t_stop) : INFINITY;
           stack.clear();
           float tmin;
           if (STATS && !dead) cnt.boxes++;
@@ -516,7 +518,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_query_refill(De
       if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
     }
     if (cur & kLeafFlag) {
-      test_leaf<true, SPH, STATS>(sc, ray, cur, t_stop, hit, limit, cnt);
+      test_leaf<true, SPH, STATS>(sc, ray, fr, cur, t_stop, hit, limit, cnt);
       cur = (OCCLUDED && query_found(hit, t_stop)) ? kTerminated : stack.pop();
     }
   }

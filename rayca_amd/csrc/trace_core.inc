@@ -46,10 +46,45 @@ __device__ __forceinline__ bool slab(float ax, float ay, float az, float bx, flo
 // Conservative box test for trees whose boxes are padded (RAYCA_BUILDER_SAH): t = b*rd - o*rd with one
 // FMA per plane.  Not the reference's rounding -- it does not have to be: in that mode a triangle is a
 // candidate iff the reference's own leaf box passes `slab` (reference_candidate), this test only steers
-// the search and the padding of the boxes dominates its rounding error.
+// the search.  It must accept every box whose reference box passes `slab`.  Two error terms stand against that:
+//   * per plane, 2^-23 |b rd|: the padding of the boxes (2^-16 |b| + 2^-20 diagonal, host_scene.cpp) dominates it;
+//   * per ray and axis, 2^-23 |o rd|: c = -(o*rd) is rounded once (2^-24 |c|), the FMA's result lies near c when the
+//     origin is far (another 2^-24 |c|), and the reference's own (b - o) * rd carries as much.  The padding is fixed at
+//     build time and knows nothing of o: it covers this term while |o| <= 4 scene diagonals on every axis (2^-20 diagonal |rd|
+//     >= 2 x 2^-23 |o rd|, whatever the direction: ray_needs_slack) and not beyond.  RAYCA_RAY_SLACK: the tests compare
+//     tmax + slack, slack = 2^-21 max |c|, four times the sum; the cull bound of ORDERED searches gets it too (cull_limit).
+// Every m, c and slack the tests see is finite, so that no plane distance is a NaN (inf - inf, where the reference has +-inf)
+// and a point box -- the unused slots of the 4-wide nodes -- fails as it did without the slack.  fix_axis sees to it:
+//   * m or c overflows for a finite origin (a denormal or tiny direction component): on such an axis the ray does not move,
+//     and the reference accepts a box only if o lies strictly between its planes.  Restated as m = +-M, c = (centre - o) M with
+//     M = min(2^100, 2^120 / |centre - o|): planes on either side of o read -+M x distance (at least M x padding >= 2^104 x
+//     2^-16 |o| or 2^100 x padding: beyond every t of the other axes), planes on one side of it read the same sign;
+//   * the origin itself is NaN or infinite on the axis: the reference's triangle test then yields a NaN or infinite depth, which
+//     never becomes a record (tests/test_ray_edges_cpu.py asserts the miss) -- m = 0, c = -FLT_MAX puts every box
+//     far behind the ray, so every box fails and the search ends at the root.
+#ifndef RAYCA_RAY_SLACK
+#define RAYCA_RAY_SLACK 1
+#endif
 struct FastRay {
   float mx, my, mz, cx, cy, cz;  // plane distance t = coordinate * m + c
+#if RAYCA_RAY_SLACK
+  float slack;                   // what the rounding of c can move a plane distance by (in units of t), times four
+  bool fixed;                    // an axis went through fix_axis
+#endif
 };
+__device__ __forceinline__ bool fix_axis(float& m, float& c, float o, float centre, float inv_scale) {
+  if (fabsf(c) <= FLT_MAX && fabsf(m) <= FLT_MAX) return false;
+  const float d = centre - o;
+  if (!(fabsf(d) <= FLT_MAX)) {   // NaN or infinite origin
+    m = 0.0f;
+    c = -FLT_MAX;
+    return true;
+  }
+  const float big = copysignf(fminf(1.2676506002282294e30f, 1.329227995784916e36f / fabsf(d)), m);   // min(2^100, 2^120 / |d|)
+  m = big * inv_scale;
+  c = d * big;
+  return true;
+}
 // f32 boxes: t = b*rd - o*rd.  fp16 boxes hold (x - centre) * scale: t = h * (rd / scale) + (centre - o) * rd.
 __device__ __forceinline__ FastRay make_fast(const DevScene& sc, const DRay& r, bool half) {
   FastRay f;
@@ -60,12 +95,54 @@ __device__ __forceinline__ FastRay make_fast(const DevScene& sc, const DRay& r, 
     f.mx = r.rd.x; f.my = r.rd.y; f.mz = r.rd.z;
     f.cx = -(r.o.x * r.rd.x); f.cy = -(r.o.y * r.rd.y); f.cz = -(r.o.z * r.rd.z);
   }
+#if RAYCA_RAY_SLACK
+  f.fixed = fix_axis(f.mx, f.cx, r.o.x, half ? sc.half_center[0] : 0.0f, half ? sc.half_inv_scale : 1.0f);
+  f.fixed |= fix_axis(f.my, f.cy, r.o.y, half ? sc.half_center[1] : 0.0f, half ? sc.half_inv_scale : 1.0f);
+  f.fixed |= fix_axis(f.mz, f.cz, r.o.z, half ? sc.half_center[2] : 0.0f, half ? sc.half_inv_scale : 1.0f);
+  f.slack = fmaxf(fmaxf(fabsf(f.cx), fabsf(f.cy)), fabsf(f.cz)) * 4.76837158203125e-07f;   // 2^-21 max |c|
+#endif
   return f;
+}
+// Where the slack is needed.  Per axis the padding of a box is worth at least 2^-20 diagonal |rd| in t, the rounding of c
+// 2^-23 |o rd|: with |o| <= 4 diagonals on every axis (and a finite c) the padding covers it twice over, whatever the
+// direction.  Shadow and bounce rays start on the scene's surfaces and camera rays usually near them, so trace() takes the
+// form with the slack only if a ray of the wave needs it (one wave-uniform branch per ray, nothing in the node loop of the other
+// form: the slack as a seventh value per ray -- kept in a register, recomputed from c in every step, or as the wave's maximum in
+// an SGPR -- cost the path kernels, which sit at their register limits, 13 to 22 %; profiles/r04_ab_slack.log).  The kernels
+// that take the caller's or the camera's rays alone (k_query_refill, k_flat_refill, Flat frames) always carry it: trace()'s SLACK_FORM.
+__device__ __forceinline__ bool ray_needs_slack(const DevScene& sc, const DRay& r, const FastRay& f) {
+#if RAYCA_RAY_SLACK
+  const float radius = sc.cull_abs * 4096.0f;   // cull_abs = 2^-10 diagonal
+  return !(fabsf(r.o.x) <= radius && fabsf(r.o.y) <= radius && fabsf(r.o.z) <= radius) || f.fixed;
+#else
+  return false;
+#endif
+}
+// what a box test reports for tmin / tmax.  (Slack, m and c are finite: a NaN here comes from the NaN planes of an unused
+// fp16 slot, and fails.)
+template <bool SLACK>
+__device__ __forceinline__ bool slab_verdict(float tmin, float tmax, const FastRay& f) {
+#if RAYCA_RAY_SLACK
+  if (SLACK) {
+    const float tp = tmax + f.slack;
+    return tp >= tmin && tp > 0.0f;
+  }
+#endif
+  return tmax >= tmin && tmax > 0.0f;
+}
+// the cull bound of an ORDERED search whose best (or allowed) depth is b: see trace()
+template <bool SLACK>
+__device__ __forceinline__ float cull_limit(const DevScene& sc, const FastRay& f, float b) {
+#if RAYCA_RAY_SLACK
+  if (SLACK) return b + fabsf(b) * 9.765625e-4f + sc.cull_abs + f.slack;
+#endif
+  return b + fabsf(b) * 9.765625e-4f + sc.cull_abs;
 }
 // fp16 -> f32 is exact and free: fmaf((float)half, a, b) is one v_fma_mix_f32
 typedef _Float16 rc_h2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float lo16(uint32_t w) { return (float)__builtin_bit_cast(rc_h2, w).x; }
 __device__ __forceinline__ float hi16(uint32_t w) { return (float)__builtin_bit_cast(rc_h2, w).y; }
+template <bool SLACK>
 __device__ __forceinline__ bool slab_fast(float ax, float ay, float az, float bx, float by, float bz, const FastRay& f, float& tmin_out) {
   const float t1x = __fmaf_rn(ax, f.mx, f.cx), t2x = __fmaf_rn(bx, f.mx, f.cx);
   const float t1y = __fmaf_rn(ay, f.my, f.cy), t2y = __fmaf_rn(by, f.my, f.cy);
@@ -73,14 +150,14 @@ __device__ __forceinline__ bool slab_fast(float ax, float ay, float az, float bx
   const float tmax = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
   const float tmin = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
   tmin_out = tmin;
-  return tmax >= tmin && tmax > 0.0f;
+  return slab_verdict<SLACK>(tmin, tmax, f);
 }
 // RAYCA_NODE_CH (round 3): the steering boxes of the binary f32 nodes as centre c and half extent h (DevScene::nodes_ch, made on
 // the device from the min / max nodes: k_make_ch_nodes).  t of the centre plane = c*m + k; the near and far planes lie h*|m| before
 // and behind it: three v_fma_f32 per axis (|m| is a free source modifier) and no v_min / v_max per axis -- on this chip v_fma issues
 // in ~2.4 cycles, v_min / v_max in 4.1 (profiles/peaks_r03.json): 9 fast + 4 slow instructions per box instead of 6 fast + 10 slow.
-// Conservative like slab_fast (every centre / half box contains its min / max box; the padding of the steering boxes covers the
-// rounding of the evaluation), so the same pixels; measured with binary f32 nodes pinned, four frames in flight: depth-1 frame
+// Conservative like slab_fast (every centre / half box contains its min / max box; the padding of the steering boxes and the
+// ray's slack cover the rounding of the evaluation), so the same pixels; measured with binary f32 nodes pinned, four frames in flight: depth-1 frame
 // 0.3669 -> 0.3607 ms, Flat 0.1888 -> 0.1871 (profiles/r03_ab_ch.log).  -DRAYCA_NODE_CH=0 goes back to min / max planes.
 #ifndef RAYCA_NODE_CH
 #define RAYCA_NODE_CH 1
@@ -120,6 +197,7 @@ constexpr uint32_t kChRefScale = RAYCA_NODE_CH48 ? 48u : 1u;   // an inner refer
 #ifndef RAYCA_WF_SHADOW_HALF
 #define RAYCA_WF_SHADOW_HALF 1
 #endif
+template <bool SLACK>
 __device__ __forceinline__ bool slab_ch(float cx, float cy, float cz, float hx, float hy, float hz, const FastRay& f, float& tmin_out) {
   const float tx = __fmaf_rn(cx, f.mx, f.cx), ty = __fmaf_rn(cy, f.my, f.cy), tz = __fmaf_rn(cz, f.mz, f.cz);
   const float ex = fabsf(f.mx), ey = fabsf(f.my), ez = fabsf(f.mz);
@@ -128,11 +206,12 @@ __device__ __forceinline__ bool slab_ch(float cx, float cy, float cz, float hx, 
   const float tmax = fminf(fminf(fx, fy), fz);
   const float tmin = fmaxf(fmaxf(nx, ny), nz);
   tmin_out = tmin;
-  return tmax >= tmin && tmax > 0.0f;
+  return slab_verdict<SLACK>(tmin, tmax, f);
 }
 // the same arithmetic on decoded fp16 planes (make_fast folds centre and scale into m and c)
+template <bool SLACK>
 __device__ __forceinline__ bool slab_half(float ax, float ay, float az, float bx, float by, float bz, const FastRay& f, float& tmin_out) {
-  return slab_fast(ax, ay, az, bx, by, bz, f, tmin_out);
+  return slab_fast<SLACK>(ax, ay, az, bx, by, bz, f, tmin_out);
 }
 
 // Triangle::intersects  rayca-geometry/src/triangle.rs:84-159 on world-space vertices (identical
@@ -323,8 +402,8 @@ __device__ __forceinline__ NodeStack<SPILL> make_stack(uint32_t* lds_base, const
 }
 
 // leaf: test primitives [first, first+count) -- shared by both node formats
-template <bool ORDERED, bool SPH, bool STATS>
-__device__ __forceinline__ void test_leaf(const DevScene& sc, const DRay& r, uint32_t ref, float t_stop, DHit& hit, float& limit,
+template <bool ORDERED, bool SPH, bool STATS, bool SLACK = true>
+__device__ __forceinline__ void test_leaf(const DevScene& sc, const DRay& r, const FastRay& fr, uint32_t ref, float t_stop, DHit& hit, float& limit,
                                           LaneCounters& cnt) {
   const uint32_t first = ref & kLeafFirstMask;
   const uint32_t count = ((ref >> 25) & 63u) + 1u;
@@ -349,8 +428,7 @@ __device__ __forceinline__ void test_leaf(const DevScene& sc, const DRay& r, uin
         hit.u = u;
         hit.v = v;
         if (ORDERED) {
-          const float b = fminf(t, t_stop);
-          limit = b + fabsf(b) * 9.765625e-4f + sc.cull_abs;
+          limit = cull_limit<SLACK>(sc, fr, fminf(t, t_stop));
         }
       }
     }
@@ -359,7 +437,7 @@ __device__ __forceinline__ void test_leaf(const DevScene& sc, const DRay& r, uin
 
 // One trip through the node loop: test the children of inner node `cur`, push what stays pending, return the
 // next node (inner, leaf or kTerminated).
-template <bool ORDERED, bool FAST, bool WIDE, bool SPILL, bool STATS, bool HALF>
+template <bool ORDERED, bool FAST, bool WIDE, bool SPILL, bool STATS, bool HALF, bool SLACK = true>
 __device__ __forceinline__ uint32_t node_step(const DevScene& sc, const DRay& r, const FastRay& fr, float limit, uint32_t cur, NodeStack<SPILL>& st,
                                               LaneCounters& cnt) {
   if (STATS && cnt.books()) cnt.slot_boxes += WIDE ? 256ull : 128ull;
@@ -377,7 +455,7 @@ __device__ __forceinline__ uint32_t node_step(const DevScene& sc, const DRay& r,
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         float tc;
-        bool h = slab_half(ax[c], ay[c], az[c], bx[c], by[c], bz[c], fr, tc);
+        bool h = slab_half<SLACK>(ax[c], ay[c], az[c], bx[c], by[c], bz[c], fr, tc);
         if (ORDERED) h = h && tc <= limit;
         key[c] = h ? (ORDERED ? tc : (float)c) : INFINITY;
       }
@@ -391,7 +469,7 @@ __device__ __forceinline__ uint32_t node_step(const DevScene& sc, const DRay& r,
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float tc;
-      bool h = FAST ? slab_fast(ax[c], ay[c], az[c], bx[c], by[c], bz[c], fr, tc) : slab(ax[c], ay[c], az[c], bx[c], by[c], bz[c], r, tc);
+      bool h = FAST ? slab_fast<SLACK>(ax[c], ay[c], az[c], bx[c], by[c], bz[c], fr, tc) : slab(ax[c], ay[c], az[c], bx[c], by[c], bz[c], r, tc);
       if (ORDERED) h = h && tc <= limit;
       // sort key: entry distance (ORDERED) or the child's index (reference order); misses sort last
       key[c] = h ? (ORDERED ? tc : (float)c) : INFINITY;
@@ -428,8 +506,8 @@ key[i] = ka; key[j] = kb; ref[i] = ra; ref[j] = rb; \
     if (FAST && HALF) {
       const uint4* nh = sc.nodes_h + 2ull * cur;
       const uint4 a = nh[0], b = nh[1];
-      hl = slab_half(lo16(a.x), hi16(a.x), lo16(a.y), hi16(a.y), lo16(a.z), hi16(a.z), fr, tl);
-      hr = slab_half(lo16(a.w), hi16(a.w), lo16(b.x), hi16(b.x), lo16(b.y), hi16(b.y), fr, tr);
+      hl = slab_half<SLACK>(lo16(a.x), hi16(a.x), lo16(a.y), hi16(a.y), lo16(a.z), hi16(a.z), fr, tl);
+      hr = slab_half<SLACK>(lo16(a.w), hi16(a.w), lo16(b.x), hi16(b.x), lo16(b.y), hi16(b.y), fr, tr);
       lref = b.z;
       rref = b.w;
     } else {
@@ -439,19 +517,19 @@ key[i] = ka; key[j] = kb; ref[i] = ra; ref[j] = rb; \
         // offset: no address arithmetic at all, where a 48-B stride cost a quarter-rate 32- or 64-bit multiply per step)
         const float4* np = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sc.nodes_ch) + cur);
         const float4 q0 = np[0], q1 = np[1], q2 = np[2];
-        hl = slab_ch(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
-        hr = slab_ch(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
+        hl = slab_ch<SLACK>(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
+        hr = slab_ch<SLACK>(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
         lref = __builtin_amdgcn_perm(__float_as_uint(q1.x), __float_as_uint(q0.w), 0x05040100u);   // low halves of (hy : hx)
         rref = __builtin_amdgcn_perm(__float_as_uint(q2.z), __float_as_uint(q2.y), 0x05040100u);
       } else {
         const float4* np = (FAST && RAYCA_NODE_CH ? sc.nodes_ch : sc.nodes) + 4ull * cur;
         const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
         if (FAST && RAYCA_NODE_CH) {
-          hl = slab_ch(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
-          hr = slab_ch(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
+          hl = slab_ch<SLACK>(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
+          hr = slab_ch<SLACK>(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
         } else if (FAST) {
-          hl = slab_fast(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
-          hr = slab_fast(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
+          hl = slab_fast<SLACK>(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
+          hr = slab_fast<SLACK>(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
         } else {
           hl = slab(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, r, tl);
           hr = slab(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, r, tr);
@@ -484,8 +562,9 @@ key[i] = ka; key[j] = kb; ref[i] = ra; ref[j] = rb; \
 //   ORDERED    front-to-back descent, subtrees whose entry distance exceeds the current best are
 //              skipped.  The winner is the (t, reference order) lexicographic minimum, which is what
 //              the reference's strict-< DFS returns (blas.rs:151,161,169).  The skip test carries a
-//              slack (relative 2^-10 plus sc.cull_abs) because a triangle's t and its box's slab
-//              entry are computed by different expressions and may disagree in the last bits.
+//              slack (relative 2^-10 plus sc.cull_abs, plus the ray's own slack: cull_limit) because a
+//              triangle's t and its box's slab entry are computed by different expressions and may
+//              disagree in the last bits -- or, with a far origin, in all the bits c's rounding leaves.
 //   !ORDERED   visits every leaf the reference visits (no culling), children in the reference's order.
 //   FAST       conservative FMA slabs (only with the reference-leaf filter, see slab_fast).
 //   WIDE       4-wide nodes: one 128-B fetch tests four boxes and skips every other level of the
@@ -514,9 +593,8 @@ key[i] = ka; key[j] = kb; ref[i] = ra; ref[j] = rb; \
 #ifndef RAYCA_LEAVE_K_BOUNCE
 #define RAYCA_LEAVE_K_BOUNCE 8    // bounce generations, shadow rays of the wavefront engine, the stack machine
 #endif
-template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF = false, int LEAVE_K = 0>
-__device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t_stop, NodeStack<SPILL>& st, DHit& hit, LaneCounters& cnt) {
-  const FastRay fr = make_fast(sc, r, HALF);
+template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF, int LEAVE_K, bool SLACK>
+__device__ __forceinline__ bool trace_search(const DevScene& sc, const DRay& r, const FastRay& fr, float t_stop, NodeStack<SPILL>& st, DHit& hit, LaneCounters& cnt) {
   hit.t = INFINITY;
   hit.prim = RAYCA_NONE;
   hit.u = hit.v = 0.0f;
@@ -527,7 +605,7 @@ __device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t
   st.clear();
   const bool any_hit = ORDERED && t_stop < FLT_MAX;
   float limit = INFINITY;  // cull bound (ORDERED only)
-  if (any_hit) limit = t_stop + fabsf(t_stop) * 9.765625e-4f + sc.cull_abs;
+  if (any_hit) limit = cull_limit<SLACK>(sc, fr, t_stop);
   if constexpr (LEAVE_K > 0) {
   // Early leave: the node phase ends as soon as fewer than LEAVE_K lanes of the wave are still searching and at
   // least one lane holds a leaf; the lanes that have not found theirs yet keep their inner node and go on in the next round.
@@ -539,10 +617,10 @@ __device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t
       const uint32_t n = (uint32_t)__popcll(__ballot(searching));
       if (n == 0u) break;
       if (n < (uint32_t)LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
-      if (searching) cur = node_step<ORDERED, FAST, WIDE, SPILL, STATS, HALF>(sc, r, fr, limit, cur, st, cnt);
+      if (searching) cur = node_step<ORDERED, FAST, WIDE, SPILL, STATS, HALF, SLACK>(sc, r, fr, limit, cur, st, cnt);
     }
     if ((cur & kLeafFlag) && cur != kTerminated) {
-      test_leaf<ORDERED, SPH, STATS>(sc, r, cur, t_stop, hit, limit, cnt);
+      test_leaf<ORDERED, SPH, STATS, SLACK>(sc, r, fr, cur, t_stop, hit, limit, cnt);
       cur = (any_hit && hit.t < t_stop) ? kTerminated : st.pop();
     }
     if (__ballot(cur != kTerminated) == 0ull) break;
@@ -550,16 +628,35 @@ __device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t
   } else {
   while (cur != kTerminated) {
     while (!(cur & kLeafFlag) && cur != kTerminated) {
-      cur = node_step<ORDERED, FAST, WIDE, SPILL, STATS, HALF>(sc, r, fr, limit, cur, st, cnt);
+      cur = node_step<ORDERED, FAST, WIDE, SPILL, STATS, HALF, SLACK>(sc, r, fr, limit, cur, st, cnt);
     }
     if (cur != kTerminated) {  // a leaf
-      test_leaf<ORDERED, SPH, STATS>(sc, r, cur, t_stop, hit, limit, cnt);
+      test_leaf<ORDERED, SPH, STATS, SLACK>(sc, r, fr, cur, t_stop, hit, limit, cnt);
       if (any_hit && hit.t < t_stop) break;
       cur = st.pop();
     }
   }
   }
   return hit.prim != RAYCA_NONE;
+}
+
+// SLACK_FORM: which form of the steering tests the search takes (see ray_needs_slack).  kSlackPerWave: decided per wave, for
+// kernels whose loop traces a camera ray and then its shadow rays (both forms are instantiated: the registers of the kernel are
+// those of the larger one); kSlackAlways: camera rays alone (Flat frames, generation 0 of the wavefront engine -- measured
+// neutral there); kSlackNever: bounce and shadow rays, whose origins lie on the scene's surfaces.
+constexpr int kSlackPerWave = 0, kSlackAlways = 1, kSlackNever = 2;
+template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF = false, int LEAVE_K = 0, int SLACK_FORM = kSlackPerWave>
+__device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t_stop, NodeStack<SPILL>& st, DHit& hit, LaneCounters& cnt) {
+  const FastRay fr = make_fast(sc, r, HALF);
+  if constexpr (!FAST || !RAYCA_RAY_SLACK || SLACK_FORM == kSlackNever) {
+    return trace_search<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, LEAVE_K, false>(sc, r, fr, t_stop, st, hit, cnt);
+  } else if constexpr (SLACK_FORM == kSlackAlways) {
+    return trace_search<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, LEAVE_K, true>(sc, r, fr, t_stop, st, hit, cnt);
+  } else {
+    if (__ballot(ray_needs_slack(sc, r, fr)) != 0ull)   // (wave-uniform)
+      return trace_search<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, LEAVE_K, true>(sc, r, fr, t_stop, st, hit, cnt);
+    return trace_search<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, LEAVE_K, false>(sc, r, fr, t_stop, st, hit, cnt);
+  }
 }
 
 // ---- ray queries (rayca_hip_query_device): the bound of a caller's ray and its result ------------

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_trace(DevScen
   }
   if (live) {
     DHit hit;
-    trace<true, FAST, SPH, FAST && (GEN0 ? RAYCA_WF_PRIMARY_WIDE : RAYCA_WF_BOUNCE_WIDE), SPILL, STATS, FAST && (GEN0 ? RAYCA_WF_PRIMARY_HALF : RAYCA_WF_BOUNCE_HALF), GEN0 ? RAYCA_LEAVE_K_WF_CAMERA : RAYCA_LEAVE_K_BOUNCE>(sc, ray, FLT_MAX, stack, hit, cnt);
+    trace<true, FAST, SPH, FAST && (GEN0 ? RAYCA_WF_PRIMARY_WIDE : RAYCA_WF_BOUNCE_WIDE), SPILL, STATS, FAST && (GEN0 ? RAYCA_WF_PRIMARY_HALF : RAYCA_WF_BOUNCE_HALF), GEN0 ? RAYCA_LEAVE_K_WF_CAMERA : RAYCA_LEAVE_K_BOUNCE, GEN0 ? kSlackAlways : kSlackNever>(sc, ray, FLT_MAX, stack, hit, cnt);
     wb.hits[out_index] = make_float4(hit.t, __uint_as_float(hit.prim), hit.u, hit.v);
   }
   if (STATS) {
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_shadow(DevSce
     const uint32_t quad = __float_as_uint(b.w) & kShadowQuad;
     const float t_stop = a.w;
     DHit hit;
-    const bool found = trace<true, FAST, SPH, FAST && RAYCA_WF_SHADOW_WIDE, SPILL, STATS, FAST && RAYCA_WF_SHADOW_HALF, RAYCA_LEAVE_K_WF_SHADOW>(sc, make_ray(point3(a.x, a.y, a.z), vec3(b.x, b.y, b.z)), t_stop, stack, hit, cnt);
+    const bool found = trace<true, FAST, SPH, FAST && RAYCA_WF_SHADOW_WIDE, SPILL, STATS, FAST && RAYCA_WF_SHADOW_HALF, RAYCA_LEAVE_K_WF_SHADOW, kSlackNever>(sc, make_ray(point3(a.x, a.y, a.z), vec3(b.x, b.y, b.z)), t_stop, stack, hit, cnt);
     bool lit;
     if (quad) {
       lit = false;
