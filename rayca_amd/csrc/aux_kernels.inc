@@ -25,9 +25,10 @@ __global__ void k_gather_prims(const uint32_t* __restrict__ order, const float* 
 // to nearest, the half extent takes the centre's rounding error and is rounded up.  RAYCA_NODE_CH48 (trace_core.inc): 48-B records,
 // the child references in the low halves of the x and y half extents, which are rounded up to 8 mantissa bits first.
 struct ChNode48 { float q[12]; };
-__device__ __forceinline__ float ch_carry(float h, uint32_t ref16) {
+__device__ __forceinline__ float ch_carry(float h, uint32_t ref16, bool one_more = false) {
   uint32_t b = __float_as_uint(h);                        // h >= 0
   b = (b + 0xFFFFu) & 0xFFFF0000u;                        // up to a multiple of 2^16 ulps
+  if (one_more) b += 0x10000u;
   if (b > 0x7F7F0000u) b = 0x7F7F0000u;                   // (never an infinity: with a reference below it that would be a NaN)
   return __uint_as_float(b | ref16);
 }
@@ -37,6 +38,13 @@ __global__ void k_make_ch_nodes(const DevNode* __restrict__ nodes, void* __restr
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   DevNode d = nodes[i];
+  // A link of the chain that splits a leaf above 64 primitives: two identical boxes, 64 primitives on the left, the rest of the
+  // chain on the right.  Its stack need (one entry) holds only while the left child is entered first, that is while the left box
+  // is entered no later than the right one -- and below, the references make the two x and y half extents differ.  The left
+  // ones get one step of 2^16 ulps more, so that they are the larger ones whatever the references are (a front-to-back
+  // search that entered the right child first kept one leaf pending per link and ran past its stack).
+  bool chain_link = (d.left & kLeafFlag) && ((d.left >> 25) & 63u) == 63u && !(d.right & kLeafFlag) && d.right != kNoChild;
+  for (int k = 0; k < 6; ++k) chain_link = chain_link && __float_as_uint(d.q[k]) == __float_as_uint(d.q[6 + k]);
   for (int b = 0; b < 2; ++b) {
     float* q = d.q + 6 * b;
     for (int a = 0; a < 3; ++a) {
@@ -54,8 +62,8 @@ __global__ void k_make_ch_nodes(const DevNode* __restrict__ nodes, void* __restr
   ChNode48 o;
   for (int k = 0; k < 12; ++k) o.q[k] = d.q[k];
   const uint32_t l = ch_ref(d.left), r = ch_ref(d.right);
-  o.q[3] = ch_carry(d.q[3], l & 0xFFFFu);
-  o.q[4] = ch_carry(d.q[4], l >> 16);
+  o.q[3] = ch_carry(d.q[3], l & 0xFFFFu, chain_link);
+  o.q[4] = ch_carry(d.q[4], l >> 16, chain_link);
   o.q[9] = ch_carry(d.q[9], r & 0xFFFFu);
   o.q[10] = ch_carry(d.q[10], r >> 16);
   static_cast<ChNode48*>(out)[i] = o;

@@ -167,7 +167,8 @@ __device__ __forceinline__ bool slab_fast(float ax, float ay, float az, float bx
 // child references live in the low 16 bits of the x and y half extents of their child's box: a half extent keeps 8 mantissa bits
 // (rounded up before the reference is put below them, so the box only grows, by < 2^-6 = 1.6 % of ITS OWN size -- the centre / half form is
 // what makes that cheap: the error scales with the box, not with the coordinates), is used by the slab test as it is, and the
-// reference comes back with one v_perm_b32.
+// reference comes back with one v_perm_b32.  (The left box of a link of a big leaf's chain grows by one step more, so that it stays
+// the one entered first: k_make_ch_nodes.)
 // Measured, four frames in flight, same bits (profiles/r03_ab_ch.log): atrium depth-1 frame 0.3604 -> 0.3345 ms (-7.2 %), Flat
 // 0.1741 -> 0.1627 (-6.5 %).  The wavefront kernels' incoherent rays stay on 4-wide fp16 nodes (one 16-B load per child box; this
 // record is 1.5): with this record under them the 5-deep 1080p frame goes 3.93 -> 4.19 (bounce) -> 4.41 ms (+ shadow).
