@@ -38,7 +38,9 @@ extern "C" {
 #define RAYCA_ABI_VERSION 2u   /* 2: RaycaRenderOptions.wait_event / record_event, RaycaStats.class_ms / class_launches,
                                   RaycaMultiOptions.context, rayca_hip_render_multi_issue / _wait, rayca_hip_scene_reap.
                                   Added since, without a new version (no layout changed): rayca_hip_scene_update; the resident
-                                  draw: RaycaRenderer, the rayca_hip_renderer_ entries, rayca_hip_scene_desc_compare, RAYCA_DRAW_ */
+                                  draw: RaycaRenderer, the rayca_hip_renderer_ entries, rayca_hip_scene_desc_compare, RAYCA_DRAW_;
+                                  rayca_hip_query_device; the surface queries: RaycaSurfaceQuery, rayca_hip_surface_device,
+                                  rayca_hip_camera_rays_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -344,7 +346,7 @@ enum {
   RAYCA_KERNEL_WF_SHADE = 4,      /* k_wf_shade: shading, NEE set-up, bounce sampling (wavefront.inc)                */
   RAYCA_KERNEL_WF_SHADOW = 5,     /* k_wf_shadow: shadow rays + direct sum, one pixel per lane (wavefront.inc)       */
   RAYCA_KERNEL_SHADOW_REFILL = 6, /* k_shadow_refill: the same with lane refill (refill.hip)                         */
-  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays  */
+  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays, k_surface */
   RAYCA_KERNEL_CLASSES = 8
 };
 
@@ -630,6 +632,64 @@ struct RaycaQuery {
 typedef struct RaycaQuery RaycaQuery;
 int32_t rayca_hip_query_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaQuery* query,
                                RaycaStats* stats_out);
+
+/* Surface records for hit records, on DEVICE memory: what is AT a hit, where rayca_hip_query_device says where the hit is.  Per
+ * record (the ray, t, prim, u, v exactly as RAYCA_QUERY_CLOSEST writes them) the values a render kernel has in hand at the same
+ * hit, bit for bit -- one function computes both:
+ *   point     Hit.point: o + d * t (triangle.rs:122); a sphere's is its model-space hit taken back to the world (sphere.rs:155-163)
+ *   normal    the shading normal: vertex normals interpolated and normalised (primitive.rs:172-182), the material's normal map
+ *             applied (material/mod.rs:125-139, pbr.rs:104-123); a sphere's normal (primitive.rs:183-190)
+ *   color     get_color(): geometry colour x Material::get_color (primitive.rs:142-148, material/mod.rs:107-113) -- what Flat shows
+ *   diffuse   get_diffuse() (primitive.rs:150-155);  specular  get_specular() (material/mod.rs:141-151)
+ *   rough     get_roughness() (material/mod.rs:173-185) and the material's shininess
+ *   material  the primitive's material index, RAYCA_NONE for Material::DEFAULT
+ *   flags     bits 0-1: RAYCA_MATERIAL_* of that material, bit 2: it is emissive (material/phong.rs:54-56), bit 3: the primitive
+ *             is a sphere, bit 31: the record is a hit
+ * Sphere::intersects builds its Hit from the inverse-transformed ray (sphere.rs:138,157-159); `point` and `normal` of a sphere are
+ * derived from that model-space hit the way the render kernels derive them, so `point` is o + d * t only up to the rounding of the
+ * trip through model space.
+ * A record whose prim is RAYCA_NONE, or not below the scene's primitive count, is a miss and reads nothing of the scene: zeros in
+ * every float output, RAYCA_NONE in material_out, 0 in flags_out.  Any output may be NULL, not all; when only color, material and
+ * flags are asked for, nothing behind get_color() is evaluated (as for a Flat frame).  `rays` is required when point_out or
+ * normal_out is asked for, else it may be NULL.  Nothing outside [0, count) of an output is written; count == 0 is RAYCA_OK and
+ * launches nothing (the pointers of an empty batch are not looked at; opts and reserved are checked as always).  Outputs need only their elements' 4-byte alignment (16-byte aligned colour outputs are written 16 bytes a lane).
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_query_device; every other field must be zero.  Calls on one context are serialised with that context's frames and
+ * queries on the device, calls on different contexts overlap; records issued after a rayca_hip_scene_update see the new
+ * materials.  With stats_out the call waits: the kernel's time under RAYCA_KERNEL_OTHER, kernel_launches = 1.
+ * RAYCA_ERR_BAD_ARG (before any GPU work): NULL scene / query, non-zero reserved, NULL t / prim / uv, NULL rays with point_out or
+ * normal_out, no output, context > 7, a non-zero field of opts that does not apply.  RAYCA_ERR_EMPTY_SCENE as the query. */
+struct RaycaSurfaceQuery {
+  uint32_t count;
+  uint32_t reserved;      /* must be zero */
+  const void* rays;       /* DEVICE: count x 6 f32, the rays the hit records belong to */
+  const void* t;          /* DEVICE: count f32 */
+  const void* prim;       /* DEVICE: count u32, post-build primitive order */
+  const void* uv;         /* DEVICE: count x 2 f32 */
+  void* point_out;        /* DEVICE: count x 3 f32 */
+  void* normal_out;       /* DEVICE: count x 3 f32 */
+  void* color_out;        /* DEVICE: count x 4 f32 */
+  void* diffuse_out;      /* DEVICE: count x 4 f32 */
+  void* specular_out;     /* DEVICE: count x 4 f32 */
+  void* rough_out;        /* DEVICE: count x 2 f32 (roughness, shininess) */
+  void* material_out;     /* DEVICE: count u32 */
+  void* flags_out;        /* DEVICE: count u32 */
+};
+typedef struct RaycaSurfaceQuery RaycaSurfaceQuery;
+int32_t rayca_hip_surface_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaSurfaceQuery* query,
+                                 RaycaStats* stats_out);
+
+/* The camera rays a frame traces (scene.rs:117-141 + trs.rs:275-284 + ray.rs:74-91), to DEVICE memory: for camera_draw_infos[0]
+ * the ray of sub-sample `sample` (< cfg->samples_per_pixel, else RAYCA_ERR_BAD_ARG) of every pixel, 6 f32 each (origin xyz,
+ * direction xyz -- the layout rayca_hip_query_device reads), the bits the render kernels trace for the same width, height and
+ * cfg->samples_per_pixel: the sub-pixel position is (x + ix * step) + offset in the reference's association (scene.rs:125-137).
+ * Rows are packed as opts->tile says (all zero => the whole frame): rayca_hip_tile_rows(tile, height) x width rays are written.
+ * Of cfg only samples_per_pixel is read.  opts (may be NULL): tile, stream (NULL => the context's own stream, and the call waits
+ * for it), context, wait_event, record_event; traversal, collect_stats, engine and camera_rays must be zero.  Ordered on its
+ * context like a frame.  RAYCA_ERR_NO_CAMERA and RAYCA_ERR_BAD_ARG (empty image, tile.part >= tile.parts, context > 7) as for a
+ * render call. */
+int32_t rayca_hip_camera_rays_device(RaycaScene* scene, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample,
+                                     const RaycaRenderOptions* opts, void* d_rays_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

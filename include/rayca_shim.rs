@@ -299,6 +299,26 @@ pub struct RaycaQuery {
     pub occluded_out: *mut c_void,
 }
 
+// rayca_hip_surface_device: hit records in, surface records out, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaSurfaceQuery {
+    pub count: u32,
+    pub reserved: u32,
+    pub rays: *const c_void,
+    pub t: *const c_void,
+    pub prim: *const c_void,
+    pub uv: *const c_void,
+    pub point_out: *mut c_void,
+    pub normal_out: *mut c_void,
+    pub color_out: *mut c_void,
+    pub diffuse_out: *mut c_void,
+    pub specular_out: *mut c_void,
+    pub rough_out: *mut c_void,
+    pub material_out: *mut c_void,
+    pub flags_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -374,6 +394,8 @@ extern "C" {
     pub fn rayca_hip_tile_rows(tile: *const RaycaTile, height: u32) -> u32;
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

@@ -294,6 +294,30 @@ class RaycaQuery(C.Structure):
     ]
 
 
+class RaycaSurfaceQuery(C.Structure):
+    """rayca_hip_surface_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("rays", C.c_void_p),
+        ("t", C.c_void_p),
+        ("prim", C.c_void_p),
+        ("uv", C.c_void_p),
+        ("point_out", C.c_void_p),
+        ("normal_out", C.c_void_p),
+        ("color_out", C.c_void_p),
+        ("diffuse_out", C.c_void_p),
+        ("specular_out", C.c_void_p),
+        ("rough_out", C.c_void_p),
+        ("material_out", C.c_void_p),
+        ("flags_out", C.c_void_p),
+    ]
+
+
+# RaycaSurfaceQuery.flags_out
+SURFACE_KIND_MASK, SURFACE_EMISSIVE, SURFACE_SPHERE, SURFACE_HIT = 3, 4, 8, 0x80000000
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -412,6 +436,10 @@ def bind_product_signatures(lib):
                                          C.c_void_p, C.c_void_p, P(RaycaStats)]
     lib.rayca_hip_query_device.restype = C.c_int32
     lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
+    lib.rayca_hip_surface_device.restype = C.c_int32
+    lib.rayca_hip_surface_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceQuery), P(RaycaStats)]
+    lib.rayca_hip_camera_rays_device.restype = C.c_int32
+    lib.rayca_hip_camera_rays_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(RaycaRenderOptions), C.c_void_p]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -433,6 +461,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

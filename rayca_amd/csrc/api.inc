@@ -1101,6 +1101,39 @@ int32_t fill_stats(Frame& f, RaycaStats* out) {
   return RAYCA_OK;
 }
 
+// What camera_ray() and the pixel <-> packed-row mapping of the kernels read from FrameParams, for every call that makes a
+// frame's camera rays (render_body, rayca_hip_camera_rays_device).  The two halves of one set-up: per frame the tile, the
+// image geometry and the camera -- RAYCA_ERR_BAD_ARG for a tile that names no part; fp.rows == 0 means "nothing to do" --
+// and per sample the sub-pixel terms.  The caller has checked that the scene has a camera.
+int32_t camera_frame_params(const RaycaScene* s, uint32_t width, uint32_t height, const RaycaTile& tile_in, FrameParams& fp) {
+  RaycaTile tile = tile_in;
+  if (tile.parts == 0) { tile.parts = 1; tile.part = 0; }
+  if (tile.part >= tile.parts) return fail(RAYCA_ERR_BAD_ARG, "tile.part >= tile.parts");
+  if (tile.band_rows == 0) tile.band_rows = 1;
+  const uint32_t rows = tile_rows(tile, height);
+  fp.width = width; fp.height = height; fp.rows = rows;
+  fp.part = tile.part; fp.parts = tile.parts; fp.band = tile.band_rows;
+  fp.tiles_x = (width + kTileW - 1u) / kTileW;
+  fp.tile_count = fp.tiles_x * ((rows + kTileH - 1u) / kTileH);
+  const float fw = (float)width, fh = (float)height;
+  fp.inv_width = 1.0f / fw;   // scene.rs:106-107
+  fp.inv_height = 1.0f / fh;
+  fp.aspect = fw / fh;        // scene.rs:114
+  fp.angle = tanf(s->host.camera_yfov * 0.5f);  // Camera::get_angle  camera.rs:74-76
+  fp.camera = s->host.world_trs[s->host.camera_node];
+  return RAYCA_OK;
+}
+void camera_sample_params(uint32_t spp, uint32_t sample, FrameParams& fp) {
+  const float strate = sqrtf((float)spp);  // scene.rs:125-127
+  const float sub_offset = 0.5f / strate, sub_step = 1.0f / strate;
+  const uint32_t sc_i = (uint32_t)strate;
+  const float ix = (float)(sample % sc_i), iy = (float)(sample / sc_i);  // scene.rs:130-131
+  fp.sample = sample;
+  fp.sub_step_x = ix * sub_step;
+  fp.sub_step_y = iy * sub_step;
+  fp.sub_offset = sub_offset;
+}
+
 // One frame.  The caller holds the frame context's mutex (render_impl and rayca_hip_render take it): everything a
 // context owns -- work buffers, events, its stream, the staging buffers of rayca_hip_render -- is touched under it.
 int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, uint32_t height, const RaycaRenderOptions* opts_in,
@@ -1119,11 +1152,8 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   int32_t rc = validate_config(s, cfg, opts.engine, plan);
   if (rc != RAYCA_OK) return rc;
   if (opts.camera_rays > RAYCA_CAMERA_REFILL) return fail(RAYCA_ERR_BAD_ARG, "unknown camera_rays choice");
-  RaycaTile tile = opts.tile;
-  if (tile.parts == 0) { tile.parts = 1; tile.part = 0; }
-  if (tile.part >= tile.parts) return fail(RAYCA_ERR_BAD_ARG, "tile.part >= tile.parts");
-  if (tile.band_rows == 0) tile.band_rows = 1;
-  const uint32_t rows = tile_rows(tile, height);
+  if ((rc = camera_frame_params(s, width, height, opts.tile, f.fp)) != RAYCA_OK) return rc;
+  const uint32_t rows = f.fp.rows;
   if (rows == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
@@ -1149,17 +1179,7 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   f.rgba8 = static_cast<uint8_t*>(d_rgba8);
   f.rgba32f = static_cast<float4*>(d_rgba32f);
 
-  FrameParams& fp = f.fp;
-  fp.width = width; fp.height = height; fp.rows = rows;
-  fp.part = tile.part; fp.parts = tile.parts; fp.band = tile.band_rows;
-  fp.tiles_x = (width + kTileW - 1u) / kTileW;
-  fp.tile_count = fp.tiles_x * ((rows + kTileH - 1u) / kTileH);
-  const float fw = (float)width, fh = (float)height;
-  fp.inv_width = 1.0f / fw;   // scene.rs:106-107
-  fp.inv_height = 1.0f / fh;
-  fp.aspect = fw / fh;        // scene.rs:114
-  fp.angle = tanf(s->host.camera_yfov * 0.5f);  // Camera::get_angle  camera.rs:74-76
-  fp.camera = s->host.world_trs[s->host.camera_node];
+  FrameParams& fp = f.fp;   // (the frame's geometry and camera are in it: camera_frame_params above)
   fp.integrator = cfg.integrator; fp.direct_sampler = cfg.direct_sampler; fp.indirect_sampler = cfg.indirect_sampler;
   fp.light_samples = cfg.light_samples; fp.light_stratify = cfg.light_stratify;
   fp.strate_count = cfg.light_stratify ? (uint32_t)sqrtf((float)cfg.light_samples) : 1u;  // config.rs:73-79
@@ -1169,8 +1189,6 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   // single leaf: a ray's whole search is then the root box and that leaf -- there is no traversal to save -- and the accounting
   // "every counted ray has tested the root box" (boxes_tested >= rays, exact for such a scene: tests/test_gpu_engines.py) holds.
   fp.nee_skip = s->nee_skip && plan.ordered && !(f.dscene->root_ref & kLeafFlag) ? 1u : 0u;
-  const float strate = sqrtf((float)cfg.samples_per_pixel);  // scene.rs:125-127
-  const float sub_offset = 0.5f / strate, sub_step = 1.0f / strate;
 
   // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
   // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
@@ -1199,12 +1217,7 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
   uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
   for (uint32_t sample = 0; sample < cfg.samples_per_pixel; ++sample) {
-    fp.sample = sample;
-    const uint32_t sc_i = (uint32_t)strate;
-    const float ix = (float)(sample % sc_i), iy = (float)(sample / sc_i);  // scene.rs:130-131
-    fp.sub_step_x = ix * sub_step;
-    fp.sub_step_y = iy * sub_step;
-    fp.sub_offset = sub_offset;
+    camera_sample_params(cfg.samples_per_pixel, sample, fp);
     if (!fused && depths > 1) HIP_TRY(hipMemsetAsync(pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
     if (general && (rc = stack_machine(f)) != RAYCA_OK) return rc;
     for (uint32_t g = 0; !general && g < depths; ++g) {
@@ -2004,6 +2017,119 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
   stats_out->class_launches[RAYCA_KERNEL_OTHER] = 1;
   stats_out->node_format = node_format;
+  return RAYCA_OK;
+}
+
+namespace {
+// what rayca_hip_surface_device and rayca_hip_camera_rays_device accept of RaycaRenderOptions: stream, context and the two events
+int32_t post_pass_options(const RaycaRenderOptions& o, const char* what) {
+  if (o.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
+  if (o.traversal != 0 || o.collect_stats != 0 || o.engine != 0 || o.camera_rays != 0 || o.reserved != 0)
+    return fail(RAYCA_ERR_BAD_ARG, std::string("traversal, collect_stats, engine and camera_rays do not apply to ") + what + ": must be zero");
+  return RAYCA_OK;
+}
+}  // namespace
+
+// Surface records for hit records (surface.inc k_surface): no traversal, one launch.  The call owns the context as a query
+// does -- behind the context's previous work on the device, ev_done behind its kernel -- so that a rayca_hip_scene_update of
+// materials, which waits for every context's ev_done, never overwrites a table this kernel is still reading.
+int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSurfaceQuery* qin, RaycaStats* stats_out) {
+  if (!s || !qin) return fail(RAYCA_ERR_BAD_ARG, "null scene or query");
+  const RaycaSurfaceQuery& sq = *qin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (sq.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceQuery.reserved must be zero");
+  // (an empty batch has no arrays: its pointers are not looked at, everything else is checked as for any batch)
+  const bool some = sq.count != 0;
+  if (some && (!sq.t || !sq.prim || !sq.uv)) return fail(RAYCA_ERR_BAD_ARG, "null hit records (t, prim and uv are all required)");
+  const bool full = sq.point_out || sq.normal_out || sq.diffuse_out || sq.specular_out || sq.rough_out;
+  if (some && !full && !sq.color_out && !sq.material_out && !sq.flags_out) return fail(RAYCA_ERR_BAD_ARG, "no output");
+  if (some && !sq.rays && (sq.point_out || sq.normal_out)) return fail(RAYCA_ERR_BAD_ARG, "null rays: point_out and normal_out need the rays the records belong to");
+  int32_t rc = post_pass_options(o, "a surface call");
+  if (rc != RAYCA_OK) return rc;
+  if (o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "tile does not apply to a surface call: must be zero");
+  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if (sq.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
+  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
+  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
+  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  SurfaceIo io{};
+  io.rays = static_cast<const float*>(sq.rays);
+  io.t = static_cast<const float*>(sq.t);
+  io.prim = static_cast<const uint32_t*>(sq.prim);
+  io.uv = static_cast<const float*>(sq.uv);
+  io.count = sq.count;
+  io.full = full ? 1u : 0u;   // color, material and flags alone: shade_hit stops behind get_color, as for a Flat frame
+  io.point_out = static_cast<float*>(sq.point_out);
+  io.normal_out = static_cast<float*>(sq.normal_out);
+  io.color_out = static_cast<float*>(sq.color_out);
+  io.diffuse_out = static_cast<float*>(sq.diffuse_out);
+  io.specular_out = static_cast<float*>(sq.specular_out);
+  io.rough_out = static_cast<float*>(sq.rough_out);
+  io.material_out = static_cast<uint32_t*>(sq.material_out);
+  io.flags_out = static_cast<uint32_t*>(sq.flags_out);
+  const bool timing = stats_out != nullptr;
+  const uint32_t grid = (uint32_t)(((uint64_t)sq.count + kBlock - 1u) / kBlock);
+  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, stream, formats_ready(s) ? s->dev_full : s->dev, io);
+  HIP_TRY(hipGetLastError());
+  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
+  HIP_TRY(hipEventRecord(c->ev_done, stream));
+  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
+  c->frame_pending = true;
+  if (!timing) {   // (as rayca_hip_query_device: the context's own stream is not the caller's to wait on)
+    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RAYCA_OK;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  std::memset(stats_out, 0, sizeof *stats_out);
+  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
+  stats_out->kernel_launches = 1;
+  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
+  stats_out->class_launches[RAYCA_KERNEL_OTHER] = 1;
+  return RAYCA_OK;
+}
+
+// The camera rays of one sample of a frame (surface.inc k_camera_rays), from the FrameParams a render call would hand its
+// kernels for the same arguments (camera_frame_params, camera_sample_params).
+int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample,
+                                     const RaycaRenderOptions* opts_in, void* d_rays_out) {
+  if (!s || !cfg) return fail(RAYCA_ERR_BAD_ARG, "null scene or config");
+  if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
+  if (cfg->samples_per_pixel == 0 || sample >= cfg->samples_per_pixel) return fail(RAYCA_ERR_BAD_ARG, "sample must be below samples_per_pixel");
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  int32_t rc = post_pass_options(o, "the camera-ray export");
+  if (rc != RAYCA_OK) return rc;
+  if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  FrameParams fp{};
+  if ((rc = camera_frame_params(s, width, height, o.tile, fp)) != RAYCA_OK) return rc;
+  if (fp.rows == 0) return RAYCA_OK;
+  if (!d_rays_out) return fail(RAYCA_ERR_BAD_ARG, "null output");
+  const uint64_t count = (uint64_t)fp.rows * width;
+  if (count > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 rays");
+  fp.spp = cfg->samples_per_pixel;
+  camera_sample_params(cfg->samples_per_pixel, sample, fp);
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
+  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
+  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
+  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((count + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, fp, static_cast<float*>(d_rays_out));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_done, stream));
+  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
+  c->frame_pending = true;
+  if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
   return RAYCA_OK;
 }
 

@@ -14,6 +14,8 @@
 //   k_trace_rays      Tlas::intersects for caller-supplied rays (parity/debug entry).
 //   k_query_rays      the same for rays in device memory, with a distance bound and an occlusion form
 //                     (rayca_hip_query_device where the lane-refill kernel of refill.hip cannot run).
+//   k_surface,        surface records (shade_hit) for hit records, and a frame's camera rays, in device memory
+//   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -385,6 +387,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 
 #include "general.inc"
 #include "wavefront.inc"
+#include "surface.inc"
 
 }  // namespace
 }  // namespace rayca

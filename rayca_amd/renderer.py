@@ -186,23 +186,10 @@ class DeviceScene:
         handle), by default torch's current stream of the device; nothing is copied except an input that is not contiguous,
         and nothing is waited for unless statistics are asked for (`want_stats` / `collect_stats`: the stats dict is appended
         to the result)."""
-        import torch
         if kind not in ("closest", "occluded"):
             raise ValueError(f"kind must be 'closest' or 'occluded', not {kind!r}")
         occluded = kind == "occluded"
-        dev = torch.device("cuda", self.device)
-
-        def checked(x, name, dtype, shape):
-            if not isinstance(x, torch.Tensor):
-                raise TypeError(f"{name}: a torch tensor on {dev} is expected, not {type(x).__name__}")
-            if x.device != dev:
-                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
-            if x.dtype != dtype:
-                raise TypeError(f"{name}: dtype {x.dtype}, expected {dtype}")
-            if tuple(x.shape) != shape:
-                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
-            return x
-
+        torch, dev, handle, checked, record = self._torch_call(stream)
         if not isinstance(rays, torch.Tensor):
             raise TypeError(f"rays: a torch tensor on {dev} is expected, not {type(rays).__name__}")
         if rays.dim() != 2 or rays.shape[1] != 6:
@@ -211,13 +198,6 @@ class DeviceScene:
         if n > 0xFFFFFFFF:
             raise ValueError("rays: more than 2**32 - 1 rays")
         checked(rays, "rays", torch.float32, (n, 6))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        if not handle:
-            # the legacy default stream: the library runs a call without a stream on the context's own (non-blocking) stream
-            # and waits for it, so what torch still has queued for the inputs must have finished first
-            torch.cuda.default_stream(dev).synchronize()
         temporaries = []
 
         def contiguous(x):
@@ -259,12 +239,137 @@ class DeviceScene:
             lib.check(self._lib.rayca_hip_query_device(self.handle, C.byref(o), C.byref(q), C.byref(st) if st is not None else None))
         elif context >= 8:
             raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
-        for x in temporaries:   # (a contiguous copy made here is read by a kernel on `stream`: the allocator must know)
-            x.record_stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=dev))
+        record(temporaries)
         result = result[0] if occluded else result
         if st is None:
             return result
         return (result, st.as_dict()) if occluded else (*result, st.as_dict())
+
+    # ---- surface queries: what is at a hit (rayca_hip_surface_device), and the rays of a frame (rayca_hip_camera_rays_device) ----
+    SURFACE_OUTPUTS = {"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
+                       "specular": ("float32", 4), "rough": ("float32", 2), "material": ("int32", 0), "flags": ("int32", 0)}
+
+    def _torch_call(self, stream):
+        """The device and stream handling of query(), surface() and camera_rays(): (torch, device, stream handle, checked(),
+        record(temporaries))."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def checked(x, name, dtype, shape):
+            if not isinstance(x, torch.Tensor):
+                raise TypeError(f"{name}: a torch tensor on {dev} is expected, not {type(x).__name__}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if x.dtype != dtype:
+                raise TypeError(f"{name}: dtype {x.dtype}, expected {dtype}")
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
+            return x
+
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        if not handle:
+            # the legacy default stream: the library runs a call without a stream on the context's own (non-blocking) stream
+            # and waits for it, so what torch still has queued for the inputs must have finished first
+            torch.cuda.default_stream(dev).synchronize()
+
+        def record(temporaries):   # (a contiguous copy made here is read by a kernel on `stream`: the allocator must know)
+            for x in temporaries:
+                x.record_stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=dev))
+
+        return torch, dev, handle, checked, record
+
+    def camera_rays(self, config: Config, width: int, height: int, *, sample=0, tile=None, stream=None, context=0, out=None):
+        """rayca_hip_camera_rays_device: the camera rays of sub-sample `sample` of a width x height frame of `config` (only its
+        samples_per_pixel matters), as a (rows * width, 6) float32 tensor on the scene's device -- origin xyz, direction xyz,
+        what query() reads; rows = tile_rows(tile, height), the whole frame without a tile.  Stream handling as query()."""
+        torch, dev, handle, checked, _ = self._torch_call(stream)
+        rows = height if tile is None else self.tile_rows(tile, height)
+        shape = (rows * width, 6)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif not checked(out, "out", torch.float32, shape).is_contiguous():
+            raise ValueError("out: an output must be contiguous")
+        cfg = config.to_abi()
+        o = self._opts(0, False, tile, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_camera_rays_device(self.handle, C.byref(cfg), width, height, sample, C.byref(o), out.data_ptr() or None))
+        return out
+
+    def surface(self, rays, t, prim, uv, *, want=("point", "normal", "color", "diffuse", "specular", "rough", "material", "flags"),
+                stream=None, context=0, out=None, want_stats=False):
+        """rayca_hip_surface_device: the surface at hit records, asynchronously, everything in device memory.
+
+        t (N,) float32, prim (N,) int32 holding the u32 slot, uv (N, 2) float32: records as query(kind="closest") returns
+        them; rays (N, 6) float32 the rays they belong to (may be None unless "point" or "normal" is wanted).  Returns a dict
+        with one tensor per name in `want`: point / normal (N, 3), color / diffuse / specular (N, 4), rough (N, 2: roughness,
+        shininess) float32; material / flags (N,) int32 holding the u32 bits (material abi.NONE, i.e. -1, without a material
+        and on a miss; flags: abi.SURFACE_*).  A record whose prim is not a slot of the scene is a miss: zeros.  `out`: a dict
+        of tensors to write instead of new ones.  Stream handling as query(); `want_stats` waits and adds "stats"."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.SURFACE_OUTPUTS]
+        if unknown or not want or len(set(want)) != len(want):
+            raise ValueError(f"want: a non-empty selection without repeats of {tuple(self.SURFACE_OUTPUTS)}, not {want!r}")
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"t: a torch tensor on {dev} is expected, not {type(t).__name__}")
+        if t.dim() != 1:
+            raise ValueError(f"t: shape {tuple(t.shape)}, expected (N,)")
+        n = t.shape[0]
+        if n > 0xFFFFFFFF:
+            raise ValueError("t: more than 2**32 - 1 records")
+        need_rays = "point" in want or "normal" in want
+        if rays is None and need_rays:
+            raise ValueError("rays: needed for 'point' and 'normal'")
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        q = abi.RaycaSurfaceQuery()
+        q.count = n
+        q.t = contiguous(checked(t, "t", torch.float32, (n,))).data_ptr()
+        q.prim = contiguous(checked(prim, "prim", torch.int32, (n,))).data_ptr()
+        q.uv = contiguous(checked(uv, "uv", torch.float32, (n, 2))).data_ptr()
+        if rays is not None:
+            q.rays = contiguous(checked(rays, "rays", torch.float32, (n, 6))).data_ptr()
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in want]
+        if stray:
+            raise ValueError(f"out: {stray} not in want")
+        result = {}
+        for name in want:
+            dtype, width = self.SURFACE_OUTPUTS[name]
+            dtype, shape = getattr(torch, dtype), ((n, width) if width else (n,))
+            x = out.get(name)
+            if x is None:
+                x = torch.empty(shape, dtype=dtype, device=dev)
+            elif not checked(x, f"out[{name!r}]", dtype, shape).is_contiguous():
+                raise ValueError(f"out[{name!r}]: an output must be contiguous")
+            result[name] = x
+            setattr(q, name + "_out", x.data_ptr() or None)
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        # (an empty batch has no device pointers; the native call checks everything else and launches nothing)
+        lib.check(self._lib.rayca_hip_surface_device(self.handle, C.byref(o), C.byref(q), C.byref(st) if st is not None else None))
+        record(temporaries)
+        if st is not None:
+            result["stats"] = st.as_dict()
+        return result
+
+    def gbuffer(self, config: Config, width: int, height: int, *, sample=0,
+                want=("point", "normal", "color", "diffuse", "specular", "rough", "material", "flags"), stream=None, context=0):
+        """The surface under every pixel of a frame: camera_rays -> query(closest) -> surface on one stream, nothing waited for
+        in between.  Returns surface()'s dict plus "t" and "prim", every tensor shaped (height, width, ...)."""
+        rays = self.camera_rays(config, width, height, sample=sample, stream=stream, context=context)
+        t, prim, uv = self.query(rays, stream=stream, context=context)
+        g = self.surface(rays, t, prim, uv, want=want, stream=stream, context=context)
+        g["t"], g["prim"] = t, prim
+        return {k: v.reshape(height, width, *v.shape[1:]) for k, v in g.items()}
 
 
 def _multi_args(scenes, config, band_rows, gather, traversal, collect_stats, engine, context):
