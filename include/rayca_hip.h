@@ -40,7 +40,7 @@ extern "C" {
                                   Added since, without a new version (no layout changed): rayca_hip_scene_update; the resident
                                   draw: RaycaRenderer, the rayca_hip_renderer_ entries, rayca_hip_scene_desc_compare, RAYCA_DRAW_;
                                   rayca_hip_query_device; the surface queries: RaycaSurfaceQuery, rayca_hip_surface_device,
-                                  rayca_hip_camera_rays_device */
+                                  rayca_hip_camera_rays_device; the denoiser: RaycaDenoise, rayca_hip_denoise_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -690,6 +690,53 @@ int32_t rayca_hip_surface_device(RaycaScene* scene, const RaycaRenderOptions* op
  * render call. */
 int32_t rayca_hip_camera_rays_device(RaycaScene* scene, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample,
                                      const RaycaRenderOptions* opts, void* d_rays_out);
+
+/* The edge-avoiding a-trous wavelet denoiser, on a frame and its G-buffer in DEVICE memory: what rayca_hip_render_device wrote to
+ * d_rgba32f_out (rendered with gamma 1) and what rayca_hip_surface_device wrote for the frame's camera rays go in, the filtered
+ * frame comes out as RGBA32F and / or RGBA8, through the gamma and the quantisation of a render call.  No reference counterpart.
+ * The scene handle gives the call its device and its frame context (stream, scratch images, ordering); the scene is not read, and
+ * an empty scene is no error.  Everything is f32, every operation rounds once, in the association written here (no exp, no pow
+ * inside the filter), so that a literal float32 restatement gives the same bits; max() is maxNum (a NaN operand gives the other).
+ *   demodulate   only with albedo and iterations > 0: den = max(albedo, 1e-3f), c = color / den per r, g, b; alpha stays color's
+ *   iteration i  (i = 0 .. iterations - 1, step s = 2^i): for dy = -2..2 (outer), dx = -2..2 (inner), q = (y + dy s, x + dx s)
+ *                inside the image, sum (r, g, b) and wsum from 0:
+ *                  w = k[|dx|] * k[|dy|], k = {0.375, 0.25, 0.0625}                                  (the 5 x 5 B3 spline)
+ *                  sigma_color > 0:  d = c_p - c_q, dc = (d.r d.r + d.g d.g) + d.b d.b, w = w / (1 + dc * (1 / sigma_color^2))
+ *                  normal:  dn = max((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0), squared normal_power_log2 times, w = w * dn
+ *                  point:   e = x_q - x_p, pd = (n_p.x e.x + n_p.y e.y) + n_p.z e.z, w = w / (1 + (pd pd) * (1 / sigma_plane^2))
+ *                  id:      the tap counts only where id_q == id_p
+ *                  a tap whose w is not > 0 (zero, NaN) does not count; else sum += w * c_q, wsum += w
+ *                wsum > 0: c_p' = sum / wsum, else c_p' = c_p (a NaN colour, the zero normal of a miss: the pixel passes through).
+ *                The centre tap goes through the same formula; the colour weight uses the iteration's own input.
+ *   output       remodulate c = c * den if demodulated; gamma != 1: powf(c, 1 / gamma) on r, g, b as a frame's last kernel;
+ *                rgba32f_out, and rgba8_out quantised and packed as a frame's.  iterations == 0 runs this stage alone.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_surface_device; every other field, tile included, must be zero.  Ordered on its context like a frame; asynchronous
+ * unless stats_out is given: then the call waits and reports the time of its launches (iterations + 1, + 1 with albedo) under
+ * RAYCA_KERNEL_OTHER.  The context keeps two scratch images of 16 bytes a pixel.  color, albedo and rgba32f_out must be 16-byte
+ * aligned (they are read and written 16 bytes a pixel), every other image as its elements (4 bytes).
+ * RAYCA_ERR_BAD_ARG (before any GPU work): NULL scene / arguments / color, no output, width or height 0, width x height > 2^32 - 1,
+ * iterations > 8, normal_power_log2 > 10, point without normal, point with sigma_plane not > 0, gamma not > 0, non-zero reserved,
+ * a misaligned image, context > 7, a non-zero field of opts that does not apply.  RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles number
+ * 2^24 or more (one launch cannot cover it). */
+struct RaycaDenoise {
+  uint32_t width, height;        /* the whole frame; tiles do not apply (packed rows are not neighbours) */
+  uint32_t iterations;           /* 0..8; iteration i uses step 2^i.  0: only the output stage (gamma, RGBA8) */
+  uint32_t normal_power_log2;    /* 0..10: the normal weight is max(0, n_p.n_q) squared this many times */
+  float sigma_color;             /* <= 0: no colour term */
+  float sigma_plane;             /* world units; must be > 0 when `point` is given */
+  float gamma;                   /* > 0; applied to the outputs exactly as a render call applies RaycaConfig.gamma; 1.0: none */
+  uint32_t reserved;             /* must be zero */
+  const void* color;             /* DEVICE H x W x 4 f32, required: what rayca_hip_render_device writes to d_rgba32f_out */
+  const void* albedo;            /* DEVICE H x W x 4 f32 or NULL: demodulate before, remodulate after (surface color_out / diffuse_out) */
+  const void* normal;            /* DEVICE H x W x 3 f32 or NULL (surface normal_out) */
+  const void* point;             /* DEVICE H x W x 3 f32 or NULL; needs `normal` (surface point_out) */
+  const void* id;                /* DEVICE H x W u32 or NULL: a tap counts only where id_q == id_p (material_out, prim, flags ...) */
+  void* rgba32f_out;             /* DEVICE H x W x 4 f32 or NULL; may be the same pointer as `color` (any other overlap is undefined) */
+  void* rgba8_out;               /* DEVICE H x W x 4 u8 or NULL; not both outputs NULL */
+};
+typedef struct RaycaDenoise RaycaDenoise;
+int32_t rayca_hip_denoise_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaDenoise* d, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

@@ -319,6 +319,27 @@ pub struct RaycaSurfaceQuery {
     pub flags_out: *mut c_void,
 }
 
+// rayca_hip_denoise_device: the a-trous filter on a frame and its G-buffer, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaDenoise {
+    pub width: u32,
+    pub height: u32,
+    pub iterations: u32,
+    pub normal_power_log2: u32,
+    pub sigma_color: f32,
+    pub sigma_plane: f32,
+    pub gamma: f32,
+    pub reserved: u32,
+    pub color: *const c_void,
+    pub albedo: *const c_void,
+    pub normal: *const c_void,
+    pub point: *const c_void,
+    pub id: *const c_void,
+    pub rgba32f_out: *mut c_void,
+    pub rgba8_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -396,6 +417,7 @@ extern "C" {
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
+    pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

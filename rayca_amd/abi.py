@@ -318,6 +318,27 @@ class RaycaSurfaceQuery(C.Structure):
 SURFACE_KIND_MASK, SURFACE_EMISSIVE, SURFACE_SPHERE, SURFACE_HIT = 3, 4, 8, 0x80000000
 
 
+class RaycaDenoise(C.Structure):
+    """rayca_hip_denoise_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("normal_power_log2", C.c_uint32),
+        ("sigma_color", C.c_float),
+        ("sigma_plane", C.c_float),
+        ("gamma", C.c_float),
+        ("reserved", C.c_uint32),
+        ("color", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("point", C.c_void_p),
+        ("id", C.c_void_p),
+        ("rgba32f_out", C.c_void_p),
+        ("rgba8_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -440,6 +461,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_surface_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceQuery), P(RaycaStats)]
     lib.rayca_hip_camera_rays_device.restype = C.c_int32
     lib.rayca_hip_camera_rays_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(RaycaRenderOptions), C.c_void_p]
+    lib.rayca_hip_denoise_device.restype = C.c_int32
+    lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -461,7 +484,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
-    "rayca_hip_surface_device", "rayca_hip_camera_rays_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

@@ -61,6 +61,7 @@ struct FrameCtx {
   TraceCounters* counters = nullptr;
   unsigned long long* shade_stats = nullptr;  // [64 lines][16]: shaded / shadow / bounce counts of k_wf_shade
   DeviceBuffer path_direct, path_brdf, path_state, accum, queue[2], out8, out32, ray_io, stack_spill, frames, mis_samples, wf_hits, wf_sh_ray, wf_sh_x;
+  DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
                                       // previous frame cleared them): generation 0 needs no memset launch
@@ -2130,6 +2131,130 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
   c->frame_pending = true;
   if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
+  return RAYCA_OK;
+}
+
+namespace {
+// k_atrous for the terms that are present: [colour term][no guide, normal, normal + point][id]
+using AtrousKernel = void (*)(AtrousIo);
+AtrousKernel pick_atrous_kernel(bool color, bool normal, bool point, bool id) {
+#define RAYCA_ATROUS(C, N, P) {k_atrous<C, N, P, false>, k_atrous<C, N, P, true>}
+  static const AtrousKernel table[2][3][2] = {{RAYCA_ATROUS(false, false, false), RAYCA_ATROUS(false, true, false), RAYCA_ATROUS(false, true, true)},
+                                              {RAYCA_ATROUS(true, false, false), RAYCA_ATROUS(true, true, false), RAYCA_ATROUS(true, true, true)}};
+#undef RAYCA_ATROUS
+  return table[color ? 1 : 0][point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
+}
+}  // namespace
+
+// The a-trous denoiser (denoise.inc): [k_denoise_demod] -> k_atrous x iterations -> k_denoise_finish, between the context's two
+// scratch images.  No kernel reads an image it writes -- every iteration goes from one image to another, and the only kernel
+// that writes rgba32f_out reads a scratch image -- which is what lets rgba32f_out be `color` itself.  The scene handle gives
+// the device and the frame context (stream, scratch, ordering against the context's frames and queries); the scene is not read.
+int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaDenoise* din, RaycaStats* stats_out) {
+  if (!s || !din) return fail(RAYCA_ERR_BAD_ARG, "null scene or denoise arguments");
+  const RaycaDenoise& d = *din;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (d.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDenoise.reserved must be zero");
+  if (!d.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!d.rgba32f_out && !d.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output");
+  if (d.width == 0 || d.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
+  const uint64_t count64 = (uint64_t)d.width * d.height;
+  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels");
+  if (d.iterations > 8) return fail(RAYCA_ERR_BAD_ARG, "iterations above 8");
+  if (d.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
+  if (d.point && !d.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
+  if (d.point && !(d.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
+  if (!(d.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(d.color, 16) || misaligned(d.albedo, 16) || misaligned(d.rgba32f_out, 16) || misaligned(d.rgba8_out, 4) || misaligned(d.normal, 4) ||
+      misaligned(d.point, 4) || misaligned(d.id, 4))
+    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo and rgba32f_out are read and written 16 bytes a pixel, every other image 4 bytes an element");
+  int32_t rc = post_pass_options(o, "a denoise call");
+  if (rc != RAYCA_OK) return rc;
+  if (o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "tile does not apply to a denoise call (packed rows are not neighbours): must be zero");
+  const uint32_t count = (uint32_t)count64;
+  const uint32_t tiles_x = (uint32_t)(((uint64_t)d.width + kDenoiseTileW - 1u) / kDenoiseTileW);
+  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)d.height + kDenoiseTileH - 1u) / kDenoiseTileH);
+  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
+  const size_t image_bytes = (size_t)count * sizeof(float4);
+  const float4* color = static_cast<const float4*>(d.color);
+  const float4* albedo = d.iterations ? static_cast<const float4*>(d.albedo) : nullptr;   // (no filter: nothing to demodulate for)
+  float4* out32 = static_cast<float4*>(d.rgba32f_out);
+  // the output stage reads `color` itself only when nothing runs in front of it; then an rgba32f_out that is `color` goes
+  // through a scratch image and a copy
+  const bool via_copy = d.iterations == 0 && out32 == color;
+  const uint32_t images = d.iterations == 0 ? (via_copy ? 1u : 0u) : ((albedo || d.iterations > 1) ? 2u : 1u);
+  for (uint32_t i = 0; i < images; ++i) {
+    // an earlier call of this context that has not been waited for may still be filtering in the image to be replaced
+    if (c->denoise[i].bytes < image_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
+    if ((rc = ensure(c->denoise[i], image_bytes)) != RAYCA_OK) return rc;
+  }
+  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
+  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
+  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  float4* const scratch[2] = {static_cast<float4*>(c->denoise[0].ptr), static_cast<float4*>(c->denoise[1].ptr)};
+  const bool timing = stats_out != nullptr;
+  const uint32_t flat_grid = (uint32_t)((count64 + kBlock - 1u) / kBlock);
+  uint32_t launches = 0;
+  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  const float4* src = color;
+  uint32_t next = 0;   // the scratch image the next kernel writes (never the one `src` is)
+  if (albedo) {
+    hipLaunchKernelGGL(k_denoise_demod, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, scratch[next], count);
+    HIP_TRY(hipGetLastError());
+    src = scratch[next];
+    next ^= 1u;
+    ++launches;
+  }
+  if (d.iterations) {
+    AtrousIo io{};
+    io.normal = static_cast<const float*>(d.normal);
+    io.point = static_cast<const float*>(d.point);
+    io.id = static_cast<const uint32_t*>(d.id);
+    io.width = d.width;
+    io.height = d.height;
+    io.tiles_x = tiles_x;
+    io.normal_squarings = d.normal_power_log2;
+    const bool with_color = d.sigma_color > 0.0f;
+    io.kc = with_color ? 1.0f / (d.sigma_color * d.sigma_color) : 0.0f;
+    io.kp = io.point ? 1.0f / (d.sigma_plane * d.sigma_plane) : 0.0f;
+    const auto kernel = pick_atrous_kernel(with_color, io.normal != nullptr, io.point != nullptr, io.id != nullptr);
+    for (uint32_t i = 0; i < d.iterations; ++i) {
+      io.in = src;
+      io.out = scratch[next];
+      io.step = 1u << i;
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
+      HIP_TRY(hipGetLastError());
+      src = scratch[next];
+      next ^= 1u;
+      ++launches;
+    }
+  }
+  const float inv_gamma = 1.0f / d.gamma;   // (as a frame's: color/mod.rs:175-176)
+  hipLaunchKernelGGL(k_denoise_finish, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, inv_gamma, static_cast<uint8_t*>(d.rgba8_out),
+                     via_copy ? scratch[0] : out32, count);
+  HIP_TRY(hipGetLastError());
+  ++launches;
+  if (via_copy) HIP_TRY(hipMemcpyAsync(out32, scratch[0], image_bytes, hipMemcpyDeviceToDevice, stream));
+  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
+  HIP_TRY(hipEventRecord(c->ev_done, stream));
+  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
+  c->frame_pending = true;
+  if (!timing) {   // (as rayca_hip_surface_device: the context's own stream is not the caller's to wait on)
+    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
+    return RAYCA_OK;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  std::memset(stats_out, 0, sizeof *stats_out);
+  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
+  stats_out->kernel_launches = launches;
+  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
+  stats_out->class_launches[RAYCA_KERNEL_OTHER] = launches;
   return RAYCA_OK;
 }
 

@@ -16,6 +16,8 @@
 //                     (rayca_hip_query_device where the lane-refill kernel of refill.hip cannot run).
 //   k_surface,        surface records (shade_hit) for hit records, and a frame's camera rays, in device memory
 //   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
+//   k_atrous,         the edge-avoiding a-trous denoiser on a frame and its G-buffer in device memory
+//   k_denoise_*       (denoise.inc: rayca_hip_denoise_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -388,6 +390,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "general.inc"
 #include "wavefront.inc"
 #include "surface.inc"
+#include "denoise.inc"
 
 }  // namespace
 }  // namespace rayca

@@ -371,6 +371,93 @@ class DeviceScene:
         g["t"], g["prim"] = t, prim
         return {k: v.reshape(height, width, *v.shape[1:]) for k, v in g.items()}
 
+    # ---- the denoiser: an edge-avoiding a-trous filter on a frame and its G-buffer (rayca_hip_denoise_device) ----
+    def denoise(self, color, *, albedo=None, normal=None, point=None, id=None, iterations=5, sigma_color=4.0, sigma_plane=None,
+                normal_power_log2=7, gamma=1.0, out=None, rgba8=False, stream=None, context=0, want_stats=False):
+        """rayca_hip_denoise_device: the edge-avoiding a-trous filter, asynchronously, everything in device memory.
+
+        color (H, W, 4) float32: a frame rendered with gamma 1 (render_device's float output).  Guides, each optional, as
+        gbuffer() returns them: albedo (H, W, 4) float32 (the colour is divided by max(albedo, 1e-3) in front of the filter and
+        multiplied with it behind), normal and point (H, W, 3) float32 (point needs normal and a sigma_plane > 0, in world
+        units), id (H, W) int32 (a tap counts only where the ids are equal: material, prim, ...).  iterations 0..8, iteration i
+        with step 2**i; 0 runs the output stage alone.  sigma_color <= 0 switches the colour term off; the normal weight is
+        max(0, n_p . n_q) squared normal_power_log2 times.  `gamma` is applied to the result as a render call applies
+        Config.gamma.  `out`: the (H, W, 4) float32 tensor to write (may be `color` itself), else a new one; rgba8=True adds an
+        (H, W, 4) uint8 tensor (or pass the tensor to write).  Stream handling as query().  Returns the float tensor, or a
+        tuple with the uint8 tensor and the stats dict (`want_stats` waits) behind it when asked for.
+
+        The defaults are starting values: nobody has tuned them on rendered frames."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        h, w = color.shape[:2]
+        if point is not None and sigma_plane is None:
+            raise ValueError("sigma_plane: needed with point")
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        def output(x, name, dtype):
+            if x is None or x is True:
+                return torch.empty((h, w, 4), dtype=dtype, device=dev)
+            if not checked(x, name, dtype, (h, w, 4)).is_contiguous():
+                raise ValueError(f"{name}: an output must be contiguous")
+            return x
+
+        d = abi.RaycaDenoise()
+        d.width, d.height, d.iterations, d.normal_power_log2 = w, h, iterations, normal_power_log2
+        d.sigma_color, d.sigma_plane, d.gamma = sigma_color, (sigma_plane if sigma_plane is not None else 0.0), gamma
+        out = output(out, "out", torch.float32)   # (before a contiguous copy of `color` replaces the name it may share)
+        d.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
+        for name, x, dtype, shape in (("albedo", albedo, torch.float32, (h, w, 4)), ("normal", normal, torch.float32, (h, w, 3)),
+                                      ("point", point, torch.float32, (h, w, 3)), ("id", id, torch.int32, (h, w))):
+            if x is not None:
+                setattr(d, name, contiguous(checked(x, name, dtype, shape)).data_ptr())
+        d.rgba32f_out = out.data_ptr()
+        out8 = None
+        if rgba8 is not None and rgba8 is not False:
+            out8 = output(rgba8, "rgba8", torch.uint8)
+            d.rgba8_out = out8.data_ptr()
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_denoise_device(self.handle, C.byref(o), C.byref(d), C.byref(st) if st is not None else None))
+        record(temporaries)
+        result = (out,) + ((out8,) if out8 is not None else ()) + ((st.as_dict(),) if st is not None else ())
+        return result[0] if len(result) == 1 else result
+
+    DENOISE_GUIDES = {"albedo": "color", "normal": "normal", "point": "point", "id": "material"}   # guide -> surface output
+
+    def render_denoised(self, config: Config, width: int, height: int, *, guides=("albedo", "normal", "point", "id"), stream=None,
+                        context=0, **denoise_kw):
+        """A frame, its G-buffer and the filter on one stream, nothing waited for in between: render_device with gamma forced
+        to 1 into a tensor, gbuffer() for the guides asked for (albedo = the surface's color, id = its material), then
+        denoise(..., gamma=config.gamma) in place.  Returns what denoise() returns; `denoise_kw` are its keywords (with the
+        "point" guide sigma_plane defaults to 0.1 world units -- a starting value like the others)."""
+        import dataclasses
+        torch, dev, handle, _, _ = self._torch_call(stream)
+        guides = tuple(guides)
+        unknown = [g for g in guides if g not in self.DENOISE_GUIDES]
+        if unknown or len(set(guides)) != len(guides):
+            raise ValueError(f"guides: a selection without repeats of {tuple(self.DENOISE_GUIDES)}, not {guides!r}")
+        if "gamma" in denoise_kw or "out" in denoise_kw:
+            raise ValueError("gamma comes from config, and the frame is filtered in place")
+        color = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
+        self.render_device(dataclasses.replace(config, gamma=1.0), width, height, 0, color.data_ptr(), stream=handle or None, context=context)
+        kw = dict(denoise_kw)
+        if guides:
+            g = self.gbuffer(config, width, height, want=tuple(self.DENOISE_GUIDES[k] for k in guides), stream=stream, context=context)
+            kw.update({k: g[self.DENOISE_GUIDES[k]] for k in guides})
+        if "point" in guides and kw.get("sigma_plane") is None:
+            kw["sigma_plane"] = 0.1
+        return self.denoise(color, gamma=config.gamma, out=color, stream=stream, context=context, **kw)
+
 
 def _multi_args(scenes, config, band_rows, gather, traversal, collect_stats, engine, context):
     handles = (C.c_void_p * len(scenes))(*[s.handle for s in scenes])
