@@ -593,7 +593,8 @@ uint32_t rayca_hip_tile_rows(const RaycaTile* tile, uint32_t height);
 /* Debug/parity entry (the analogue of Tlas::intersects, bvh/tlas.rs:271-275): trace `count`
  * caller-supplied rays (origin xyz, dir xyz; 6 floats per ray, HOST memory) and return per ray
  * t (f32::MAX on miss), primitive index in the scene's post-build primitive order (RAYCA_NONE on
- * miss) and the barycentrics u,v.  */
+ * miss) and the barycentrics u,v.  Synchronous, ordered on context 0 like a frame: it starts behind
+ * a frame still in flight there.  */
 int32_t rayca_hip_trace_rays(RaycaScene* scene, const RaycaRenderOptions* opts, uint32_t count,
                              const float* rays, float* t_out, uint32_t* prim_out, float* uv_out,
                              RaycaStats* stats_out);

@@ -750,6 +750,69 @@ int32_t timed_launch(LaunchLog& log, hipStream_t stream, int cls, bool timed, bo
   return RAYCA_OK;
 }
 
+// ---- one pass on a frame context: what a frame, a query and every post pass do around their launches ------------------------
+// The ownership rule.  A pass holds its context's mutex and runs on the caller's stream (opts.stream) or the context's own.
+// It starts behind the context's previous pass ON THE DEVICE -- that one may still be running on another stream and owns the
+// same work buffers -- and behind opts.wait_event; it leaves the context's ev_done (and opts.record_event) behind its last
+// launch.  ev_done is what rayca_hip_scene_update, scene_destroy and every regrowth of a buffer that a pass in flight may
+// use wait for, before they overwrite or free it.  The context's own stream is not the caller's to wait on, so a pass on it
+// is synchronous; so is a pass that reports statistics.
+//   pass_acquire ... [buffers, memsets] ... ev_begin when timing ... launches ... pass_retire ... pass_finish
+// ev_begin is where kernel_ms starts: behind whatever the pass clears or prepares first, so every entry records it itself.
+struct ContextPass {
+  FrameCtx* c;
+  hipStream_t stream;
+  void* record_event;
+  bool timing;       // RaycaStats asked for: ev_begin / ev_end bracket the launches
+  bool own_stream;   // the context's stream, not the caller's
+};
+int32_t pass_acquire(RaycaScene* s, const RaycaRenderOptions& o, bool timing, ContextPass& p) {   // (o.context is in range, its mutex held)
+  FrameCtx* c = &s->ctx[o.context];
+  HIP_TRY(hipSetDevice(s->device));
+  const int32_t rc = ensure_ctx(s, c);
+  if (rc != RAYCA_OK) return rc;
+  p = ContextPass{c, o.stream ? static_cast<hipStream_t>(o.stream) : c->stream, o.record_event, timing, o.stream == nullptr};
+  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(p.stream, c->ev_done, 0));
+  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(p.stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  return RAYCA_OK;
+}
+int32_t pass_retire(const ContextPass& p) {
+  if (p.timing) HIP_TRY(hipEventRecord(p.c->ev_end, p.stream));
+  HIP_TRY(hipEventRecord(p.c->ev_done, p.stream));
+  if (p.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(p.record_event), p.stream));
+  p.c->frame_pending = true;
+  return RAYCA_OK;
+}
+// The synchronisation the rule asks for and, with stats_out (given iff p.timing), the statistics every pass but a frame fills
+// alike: everything zero but the time from ev_begin to pass_retire and its `launches`, under RAYCA_KERNEL_OTHER.
+int32_t pass_finish(const ContextPass& p, uint32_t launches, RaycaStats* stats_out) {
+  if (p.own_stream || stats_out) HIP_TRY(hipStreamSynchronize(p.stream));
+  if (!stats_out) return RAYCA_OK;
+  std::memset(stats_out, 0, sizeof *stats_out);
+  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, p.c->ev_begin, p.c->ev_end));
+  stats_out->kernel_launches = launches;
+  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
+  stats_out->class_launches[RAYCA_KERNEL_OTHER] = launches;
+  return RAYCA_OK;
+}
+
+// What a device pass other than a frame takes of RaycaRenderOptions: stream, context and the two events always, and the
+// groups of fields in `accepts`; every other field must be zero.  `what` names the call in the message.
+enum : uint32_t { kOptTraversal = 1u, kOptCollectStats = 2u, kOptTile = 4u };
+int32_t pass_options(const RaycaRenderOptions& o, const char* what, uint32_t accepts) {
+  if (o.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
+  if ((accepts & kOptTraversal) && o.traversal > RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_BAD_ARG, "unknown traversal");
+  const char* field = nullptr;
+  if (!(accepts & kOptTraversal) && o.traversal != 0) field = "traversal";
+  else if (!(accepts & kOptCollectStats) && o.collect_stats != 0) field = "collect_stats";
+  else if (o.engine != 0) field = "engine";
+  else if (o.camera_rays != 0) field = "camera_rays";
+  else if (o.reserved != 0) field = "reserved";
+  else if (!(accepts & kOptTile) && (o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0)) field = "tile";
+  if (field) return fail(RAYCA_ERR_BAD_ARG, std::string("RaycaRenderOptions.") + field + " does not apply to " + what + ": must be zero");
+  return RAYCA_OK;
+}
+
 // generation class, index of the event pair, the format launched; refill: -1 = a format calibration, 0/1 = a kernel calibration
 struct TuneEvent { int cls; size_t ev; int format; int refill; };
 
@@ -1160,16 +1223,11 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     return RAYCA_OK;
   }
   if (opts.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  FrameCtx* c = f.c = f.log.c = &s->ctx[opts.context];
   f.s = s;
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
-  const hipStream_t stream = f.stream = opts.stream ? static_cast<hipStream_t>(opts.stream) : c->stream;
-  // Calls on one context are serialised on the DEVICE too: the previous frame of this context may still be running
-  // on another stream (asynchronous rayca_hip_render_device calls with different opts->stream) and owns the same
-  // queues, path records and spill area.
-  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
-  if (opts.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(opts.wait_event), 0));
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, opts, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  FrameCtx* c = f.c = f.log.c = pass.c;
+  const hipStream_t stream = f.stream = pass.stream;
   // The wavefront engine's kernels are tied to the 4-wide / fp16 nodes, and so is a pinned format: those wait for the thread
   // that makes them.  Everything else renders on the binary f32 nodes until they are there (node_format bit 2048).
   if ((plan.wavefront || format_forced() > 0) && (rc = formats_wait(s)) != RAYCA_OK) return rc;
@@ -1212,10 +1270,10 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     pb.state = static_cast<uint32_t*>(c->path_state.ptr);
   }
 
-  const bool timing = f.timing = stats_out != nullptr;
+  const bool timing = f.timing = pass.timing;
   const bool general = plan.mode == kModeGeneral;
   if (timing || general) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
-  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
   uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
   for (uint32_t sample = 0; sample < cfg.samples_per_pixel; ++sample) {
     camera_sample_params(cfg.samples_per_pixel, sample, fp);
@@ -1236,10 +1294,7 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
     }
     if (!fused && (rc = resolve(f)) != RAYCA_OK) return rc;
   }
-  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
-  HIP_TRY(hipEventRecord(c->ev_done, stream));
-  if (opts.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opts.record_event), stream));
-  c->frame_pending = true;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
   if (!f.tune_events.empty() && (rc = book_calibration(f)) != RAYCA_OK) return rc;
   if (general && (rc = stack_machine_status(f)) != RAYCA_OK) return rc;
   return timing ? fill_stats(f, stats_out) : RAYCA_OK;
@@ -1870,8 +1925,9 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
   if (count == 0) return RAYCA_OK;
   FrameCtx* c = &s->ctx[0];
   std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));
-  int32_t rc = ensure_ctx(s, c);
+  // a pass on context 0 and its own stream, whatever opts names: behind a frame in flight there, which owns the buffers below
+  ContextPass pass{};
+  int32_t rc = pass_acquire(s, RaycaRenderOptions{}, true, pass);
   if (rc != RAYCA_OK) return rc;
   const bool ordered = !opts || opts->traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
   const bool stats = opts && opts->collect_stats;
@@ -1883,7 +1939,7 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
   float* d_t = reinterpret_cast<float*>(base + in_bytes);
   uint32_t* d_prim = reinterpret_cast<uint32_t*>(base + in_bytes + (size_t)count * 4);
   float* d_uv = reinterpret_cast<float*>(base + in_bytes + (size_t)count * 8);
-  hipStream_t stream = c->stream;
+  const hipStream_t stream = pass.stream;
   HIP_TRY(hipMemcpyAsync(d_rays, rays, in_bytes, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
   if ((rc = formats_wait(s)) != RAYCA_OK) return rc;
@@ -1898,12 +1954,12 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
   HIP_TRY(hipEventRecord(c->ev_begin, stream));
   hipLaunchKernelGGL(k, dim3(tgrid), dim3(kBlock), lds_bytes, stream, s->dev_full, d_rays, count, d_t, d_prim, d_uv, c->counters, tl);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_end, stream));
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;   // (the copies below need no event: the call drains the stream itself)
   HIP_TRY(hipMemcpyAsync(t_out, d_t, (size_t)count * 4, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(prim_out, d_prim, (size_t)count * 4, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(uv_out, d_uv, (size_t)count * 8, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (stats_out) {
+  if ((rc = pass_finish(pass, 1, nullptr)) != RAYCA_OK) return rc;
+  if (stats_out) {   // (its own few fields, none per kernel class)
     TraceCounters tc{};
     HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
     std::memset(stats_out, 0, sizeof *stats_out);
@@ -1920,8 +1976,8 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
 // Ray queries on device memory.  A RAYCA_BUILDER_SAH scene whose node formats are there runs the lane-refill kernel
 // (refill.hip k_query_refill, on the 4-wide fp16 nodes k_queue_refill traverses); a RAYCA_BUILDER_REFERENCE scene, exhaustive
 // traversal and a SAH scene whose formats thread has not finished (RaycaStats.node_format bit 11) run k_query_rays, one ray
-// per lane on the binary f32 nodes.  Same results on every path.  The call owns the context like a frame does: it waits for
-// the context's previous work on the device, clears the work counters on the launch stream, and leaves ev_done behind.
+// per lane on the binary f32 nodes.  Same results on every path.  A pass on its context (ContextPass), which clears the work
+// counters on the launch stream.
 int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaQuery* qin, RaycaStats* stats_out) {
   if (!s || !qin) return fail(RAYCA_ERR_BAD_ARG, "null scene or query");
   const RaycaQuery& rq = *qin;
@@ -1932,10 +1988,8 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   if (!rq.rays) return fail(RAYCA_ERR_BAD_ARG, "null rays");
   const bool occluded = rq.kind == RAYCA_QUERY_OCCLUDED;
   if (occluded ? !rq.occluded_out : (!rq.t_out && !rq.prim_out && !rq.uv_out)) return fail(RAYCA_ERR_BAD_ARG, "no output for this kind of query");
-  if (o.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  if (o.traversal > RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_BAD_ARG, "unknown traversal");
-  if (o.engine != 0 || o.camera_rays != 0 || o.reserved != 0 || o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0)
-    return fail(RAYCA_ERR_BAD_ARG, "tile, engine and camera_rays do not apply to a query: must be zero");
+  int32_t rc = pass_options(o, "a query", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
   const bool ordered = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
   if (occluded && !ordered) return fail(RAYCA_ERR_UNSUPPORTED, "an occlusion query ends at its first hit: there is no exhaustive form");
   if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
@@ -1945,13 +1999,10 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   }
   FrameCtx* c = &s->ctx[o.context];
   std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));
-  int32_t rc = ensure_ctx(s, c);
-  if (rc != RAYCA_OK) return rc;
-  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
-  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
-  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
-  const bool stats = o.collect_stats != 0, timing = stats_out != nullptr, sph = s->host.sphere_count != 0;
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  const hipStream_t stream = pass.stream;
+  const bool stats = o.collect_stats != 0, timing = pass.timing, sph = s->host.sphere_count != 0;
   const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
   const bool all_formats = formats_ready(s);
   const bool refill = ordered && fast && all_formats;
@@ -1991,49 +2042,26 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
     HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
     c->heads_clean = false;   // the next frame of this context clears them for itself
   }
-  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
   if (refill) launch_query_refill(occluded, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, q, c->heads, c->counters, tl);
   else hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, q, c->counters, tl);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
-  HIP_TRY(hipEventRecord(c->ev_done, stream));
-  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
-  c->frame_pending = true;
-  if (!timing) {   // (as rayca_hip_render_device: the context's own stream is not the caller's to wait on)
-    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
-    return RAYCA_OK;
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
+  if ((rc = pass_retire(pass)) != RAYCA_OK || (rc = pass_finish(pass, 1, stats_out)) != RAYCA_OK || !timing) return rc;
   TraceCounters tc{};
   if (stats) HIP_TRY(hipMemcpy(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost));
-  std::memset(stats_out, 0, sizeof *stats_out);
   (occluded ? stats_out->rays_shadow : stats_out->rays_primary) = rq.count;
   stats_out->boxes_tested = tc.boxes;
   stats_out->triangles_tested = tc.tris;
   stats_out->wave_box_slots = tc.box_slots;
   stats_out->wave_triangle_slots = tc.tri_slots;
-  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
   stats_out->trace_kernel_ms = stats_out->kernel_ms;
-  stats_out->kernel_launches = stats_out->trace_kernel_launches = 1;
-  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
-  stats_out->class_launches[RAYCA_KERNEL_OTHER] = 1;
+  stats_out->trace_kernel_launches = 1;
   stats_out->node_format = node_format;
   return RAYCA_OK;
 }
 
-namespace {
-// what rayca_hip_surface_device and rayca_hip_camera_rays_device accept of RaycaRenderOptions: stream, context and the two events
-int32_t post_pass_options(const RaycaRenderOptions& o, const char* what) {
-  if (o.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  if (o.traversal != 0 || o.collect_stats != 0 || o.engine != 0 || o.camera_rays != 0 || o.reserved != 0)
-    return fail(RAYCA_ERR_BAD_ARG, std::string("traversal, collect_stats, engine and camera_rays do not apply to ") + what + ": must be zero");
-  return RAYCA_OK;
-}
-}  // namespace
-
-// Surface records for hit records (surface.inc k_surface): no traversal, one launch.  The call owns the context as a query
-// does -- behind the context's previous work on the device, ev_done behind its kernel -- so that a rayca_hip_scene_update of
-// materials, which waits for every context's ev_done, never overwrites a table this kernel is still reading.
+// Surface records for hit records (surface.inc k_surface): no traversal, one launch.  A pass on its context (ContextPass), so
+// that a rayca_hip_scene_update of materials never overwrites a table this kernel is still reading.
 int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSurfaceQuery* qin, RaycaStats* stats_out) {
   if (!s || !qin) return fail(RAYCA_ERR_BAD_ARG, "null scene or query");
   const RaycaSurfaceQuery& sq = *qin;
@@ -2046,9 +2074,8 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   const bool full = sq.point_out || sq.normal_out || sq.diffuse_out || sq.specular_out || sq.rough_out;
   if (some && !full && !sq.color_out && !sq.material_out && !sq.flags_out) return fail(RAYCA_ERR_BAD_ARG, "no output");
   if (some && !sq.rays && (sq.point_out || sq.normal_out)) return fail(RAYCA_ERR_BAD_ARG, "null rays: point_out and normal_out need the rays the records belong to");
-  int32_t rc = post_pass_options(o, "a surface call");
+  int32_t rc = pass_options(o, "a surface call", 0u);
   if (rc != RAYCA_OK) return rc;
-  if (o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "tile does not apply to a surface call: must be zero");
   if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
   if (sq.count == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
@@ -2056,11 +2083,8 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   }
   FrameCtx* c = &s->ctx[o.context];
   std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
-  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
-  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
-  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
   SurfaceIo io{};
   io.rays = static_cast<const float*>(sq.rays);
   io.t = static_cast<const float*>(sq.t);
@@ -2076,26 +2100,12 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   io.rough_out = static_cast<float*>(sq.rough_out);
   io.material_out = static_cast<uint32_t*>(sq.material_out);
   io.flags_out = static_cast<uint32_t*>(sq.flags_out);
-  const bool timing = stats_out != nullptr;
   const uint32_t grid = (uint32_t)(((uint64_t)sq.count + kBlock - 1u) / kBlock);
-  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, stream, formats_ready(s) ? s->dev_full : s->dev, io);
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
+  hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, pass.stream, formats_ready(s) ? s->dev_full : s->dev, io);
   HIP_TRY(hipGetLastError());
-  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
-  HIP_TRY(hipEventRecord(c->ev_done, stream));
-  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
-  c->frame_pending = true;
-  if (!timing) {   // (as rayca_hip_query_device: the context's own stream is not the caller's to wait on)
-    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
-    return RAYCA_OK;
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  std::memset(stats_out, 0, sizeof *stats_out);
-  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
-  stats_out->kernel_launches = 1;
-  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
-  stats_out->class_launches[RAYCA_KERNEL_OTHER] = 1;
-  return RAYCA_OK;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, 1, stats_out);
 }
 
 // The camera rays of one sample of a frame (surface.inc k_camera_rays), from the FrameParams a render call would hand its
@@ -2107,7 +2117,7 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   if (cfg->samples_per_pixel == 0 || sample >= cfg->samples_per_pixel) return fail(RAYCA_ERR_BAD_ARG, "sample must be below samples_per_pixel");
   RaycaRenderOptions o{};
   if (opts_in) o = *opts_in;
-  int32_t rc = post_pass_options(o, "the camera-ray export");
+  int32_t rc = pass_options(o, "the camera-ray export", kOptTile);
   if (rc != RAYCA_OK) return rc;
   if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
   FrameCtx* c = &s->ctx[o.context];
@@ -2120,18 +2130,12 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   if (count > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 rays");
   fp.spp = cfg->samples_per_pixel;
   camera_sample_params(cfg->samples_per_pixel, sample, fp);
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
-  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
-  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
-  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
-  hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((count + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, fp, static_cast<float*>(d_rays_out));
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, false, pass)) != RAYCA_OK) return rc;
+  hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((count + kBlock - 1u) / kBlock)), dim3(kBlock), 0, pass.stream, fp, static_cast<float*>(d_rays_out));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_done, stream));
-  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
-  c->frame_pending = true;
-  if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
-  return RAYCA_OK;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, 1, nullptr);
 }
 
 namespace {
@@ -2170,17 +2174,15 @@ int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   if (misaligned(d.color, 16) || misaligned(d.albedo, 16) || misaligned(d.rgba32f_out, 16) || misaligned(d.rgba8_out, 4) || misaligned(d.normal, 4) ||
       misaligned(d.point, 4) || misaligned(d.id, 4))
     return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo and rgba32f_out are read and written 16 bytes a pixel, every other image 4 bytes an element");
-  int32_t rc = post_pass_options(o, "a denoise call");
+  int32_t rc = pass_options(o, "a denoise call, which filters a whole frame (a tile's packed rows are not neighbours)", 0u);
   if (rc != RAYCA_OK) return rc;
-  if (o.tile.part != 0 || o.tile.parts != 0 || o.tile.band_rows != 0 || o.tile.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "tile does not apply to a denoise call (packed rows are not neighbours): must be zero");
   const uint32_t count = (uint32_t)count64;
   const uint32_t tiles_x = (uint32_t)(((uint64_t)d.width + kDenoiseTileW - 1u) / kDenoiseTileW);
   const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)d.height + kDenoiseTileH - 1u) / kDenoiseTileH);
   if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
   FrameCtx* c = &s->ctx[o.context];
   std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));
-  if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
+  HIP_TRY(hipSetDevice(s->device));   // (for the scratch images, which have to be there before the pass queues its waits)
   const size_t image_bytes = (size_t)count * sizeof(float4);
   const float4* color = static_cast<const float4*>(d.color);
   const float4* albedo = d.iterations ? static_cast<const float4*>(d.albedo) : nullptr;   // (no filter: nothing to demodulate for)
@@ -2194,14 +2196,13 @@ int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_i
     if (c->denoise[i].bytes < image_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
     if ((rc = ensure(c->denoise[i], image_bytes)) != RAYCA_OK) return rc;
   }
-  const hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
-  if (c->frame_pending) HIP_TRY(hipStreamWaitEvent(stream, c->ev_done, 0));
-  if (o.wait_event) HIP_TRY(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(o.wait_event), 0));
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  const hipStream_t stream = pass.stream;
   float4* const scratch[2] = {static_cast<float4*>(c->denoise[0].ptr), static_cast<float4*>(c->denoise[1].ptr)};
-  const bool timing = stats_out != nullptr;
   const uint32_t flat_grid = (uint32_t)((count64 + kBlock - 1u) / kBlock);
   uint32_t launches = 0;
-  if (timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
   const float4* src = color;
   uint32_t next = 0;   // the scratch image the next kernel writes (never the one `src` is)
   if (albedo) {
@@ -2241,21 +2242,8 @@ int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   HIP_TRY(hipGetLastError());
   ++launches;
   if (via_copy) HIP_TRY(hipMemcpyAsync(out32, scratch[0], image_bytes, hipMemcpyDeviceToDevice, stream));
-  if (timing) HIP_TRY(hipEventRecord(c->ev_end, stream));
-  HIP_TRY(hipEventRecord(c->ev_done, stream));
-  if (o.record_event) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.record_event), stream));
-  c->frame_pending = true;
-  if (!timing) {   // (as rayca_hip_surface_device: the context's own stream is not the caller's to wait on)
-    if (!o.stream) HIP_TRY(hipStreamSynchronize(stream));
-    return RAYCA_OK;
-  }
-  HIP_TRY(hipStreamSynchronize(stream));
-  std::memset(stats_out, 0, sizeof *stats_out);
-  HIP_TRY(hipEventElapsedTime(&stats_out->kernel_ms, c->ev_begin, c->ev_end));
-  stats_out->kernel_launches = launches;
-  stats_out->class_ms[RAYCA_KERNEL_OTHER] = stats_out->kernel_ms;
-  stats_out->class_launches[RAYCA_KERNEL_OTHER] = launches;
-  return RAYCA_OK;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, launches, stats_out);
 }
 
 }  // extern "C"
