@@ -40,7 +40,9 @@ extern "C" {
                                   Added since, without a new version (no layout changed): rayca_hip_scene_update; the resident
                                   draw: RaycaRenderer, the rayca_hip_renderer_ entries, rayca_hip_scene_desc_compare, RAYCA_DRAW_;
                                   rayca_hip_query_device; the surface queries: RaycaSurfaceQuery, rayca_hip_surface_device,
-                                  rayca_hip_camera_rays_device; the denoiser: RaycaDenoise, rayca_hip_denoise_device */
+                                  rayca_hip_camera_rays_device; the denoiser: RaycaDenoise, rayca_hip_denoise_device;
+                                  temporal accumulation: RaycaCameraPose, rayca_hip_scene_camera, RaycaAccumulate,
+                                  rayca_hip_accumulate_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -738,6 +740,99 @@ struct RaycaDenoise {
 };
 typedef struct RaycaDenoise RaycaDenoise;
 int32_t rayca_hip_denoise_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaDenoise* d, RaycaStats* stats_out);
+
+/* The camera a frame of the scene uses (camera_draw_infos[0]), in the form a reprojection needs it.  Host only: no GPU work, no
+ * frame context.  A camera ray is origin + s * R * S * (xx, yy, -1) (scene.rs:125-141, trs.rs:275-284), with R and S the rotation
+ * and the scale of the camera node's world transform; for a world point x with v = x - origin that gives
+ *   xx = (right . v) / -(back . v),  yy = (up . v) / -(back . v)
+ * without a quaternion inverse, for a non-uniform camera scale too.  `rotate` is the reference's (vec3.rs:148-159), evaluated on
+ * the host; every division is per component.  After a rayca_hip_scene_update the call returns the new camera.
+ * RAYCA_ERR_BAD_ARG: a NULL argument.  RAYCA_ERR_NO_CAMERA: the scene has none. */
+struct RaycaCameraPose {
+  float origin[3];  float angle;      /* the origin of the frame's camera rays: the translation of the camera node's world transform;
+                                         tanf(yfov * 0.5f), the bits a frame uses */
+  float right[3];   float reserved0;  /* rotate((1,0,0), rotation) / scale.x; reserved: 0 */
+  float up[3];      float reserved1;  /* rotate((0,1,0), rotation) / scale.y */
+  float back[3];    float reserved2;  /* rotate((0,0,1), rotation) / scale.z */
+};
+typedef struct RaycaCameraPose RaycaCameraPose;
+int32_t rayca_hip_scene_camera(const RaycaScene* scene, RaycaCameraPose* out);
+
+/* Temporal accumulation with reprojection: one pass, one kernel, on a frame, its G-buffer and a history, all in DEVICE memory.
+ * `color` is what rayca_hip_render_device wrote to d_rgba32f_out (gamma 1); point, normal and id are what rayca_hip_surface_device
+ * wrote for the frame's camera rays (of a one-sample frame: the reprojection assumes points on the rays through pixel centres);
+ * the history is what an earlier call wrote to color_out / length_out / moments_out, with the G-buffer (prev_*) and the camera
+ * (prev_camera) of the frame it belongs to.  No reference counterpart.  The scene handle gives the call its device and its frame
+ * context; the scene is not read, and an empty scene is no error.
+ * Everything is f32, every operation rounds once, in the association written here, so that a literal float32 restatement gives
+ * the same bits; every comparison is written so that a NaN fails it.  For pixel p = (x, y), c = color[p], W = width, H = height:
+ *   sample      finite iff c.k - c.k == 0 for all four channels
+ *   luminance   lum = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b
+ *   history, identity mode (prev_camera == NULL):
+ *               h = hist_color[p], L = hist_length[p], m = hist_moments[p]; present iff a history was given and L > 0
+ *   history, reprojection mode (prev_camera given):
+ *               normal[p] == (0, 0, 0) is a miss (as rayca_hip_surface_device writes one): no history.  Otherwise
+ *               v = point[p] - origin
+ *               cx = (right.x v.x + right.y v.y) + right.z v.z, cy the same with up, cz the same with back
+ *               present only if cz < 0;  nz = 0 - cz
+ *               aspect = (float)W / (float)H
+ *               fx = ((cx / nz) / (angle * aspect) + 1) * 0.5 * W - 0.5      (left to right: five roundings behind the quotient)
+ *               fy = (1 - (cy / nz) / angle) * 0.5 * H - 0.5
+ *               present only if fx >= -1 && fx < W && fy >= -1 && fy < H
+ *               x0 = floor(fx), tx = fx - x0; y0 = floor(fy), ty = fy - y0
+ *               the four taps go j = 0, 1 (outer), i = 0, 1 (inner), q = (y0 + j, x0 + i), b = (i ? tx : 1 - tx) * (j ? ty : 1 - ty)
+ *               a tap counts iff q is inside the image, b > 0, hist_length[q] > 0, prev_id[q] == id[p] (where ids are given),
+ *                 (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_min with n_p = normal[p], n_q = prev_normal[q], and, where
+ *                 prev_point is given, |pd| <= plane_max with e = prev_point[q] - point[p], pd = (n_p.x e.x + n_p.y e.y) + n_p.z e.z
+ *               sums from 0: wsum += b, colour += b * hist_color[q] (four channels), length += b * hist_length[q],
+ *                 moments += b * hist_moments[q]
+ *               present iff wsum > 0; then h, L, m = the sums / wsum
+ *   blend       history present, sample finite:      n = L + 1, with max_history > 0 n = min(n, (float)max_history); a = 1 / n
+ *                                                    out = h + (c - h) * a (four channels), length_out = n
+ *                                                    m1 = m.x + (lum - m.x) * a, m2 = m.y + (lum * lum - m.y) * a
+ *               history present, sample not finite:  out = h, length_out = L, moments = m (a firefly NaN does not enter the film)
+ *               no history, sample finite:           out = c, length_out = 1, moments = (lum, lum * lum)
+ *               no history, sample not finite:       out = c, length_out = 0, moments = 0 (hist_length > 0 is the validity
+ *                                                    channel: the next frame reads nothing from this pixel)
+ *               variance_out = max(m2 - m1 * m1, 0)
+ * max() and min() are maxNum and minNum (a NaN operand gives the other one).  Moments are formed only with moments_out; a
+ * hist_moments without it is not read.  Without a history (first frame) prev_camera changes nothing: no pixel has one.
+ * Aliasing.  In identity mode the pass is pixel-local: color_out may be hist_color or color, length_out may be hist_length,
+ * moments_out may be hist_moments -- a film in place.  In reprojection mode taps read neighbours: an output equal to any hist_ or
+ * prev_ input is RAYCA_ERR_BAD_ARG; color_out == color stays allowed.  Any other overlap is undefined.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_surface_device; every other field, tile included, must be zero (a tile's packed rows are not neighbours).
+ * Ordered on its context like a frame; asynchronous unless stats_out is given: then the call waits and reports the time of its
+ * one launch under RAYCA_KERNEL_OTHER.  No scratch image.  color, hist_color and color_out must be 16-byte aligned (read and
+ * written 16 bytes a pixel), every other image as its elements (4 bytes).
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments, width or height 0, width x
+ * height > 2^32 - 1, non-zero reserved, a required pointer missing or a forbidden one given as the struct lists them, normal_min
+ * or plane_max not > 0 where it applies, a misaligned image, the aliasing rule, context > 7, a non-zero field of opts that does not
+ * apply.  RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles number 2^24 or more. */
+struct RaycaAccumulate {
+  uint32_t width, height;   /* the whole frame */
+  uint32_t max_history;     /* 0: unbounded (a running mean); else the history length is capped here (an exponential tail) */
+  uint32_t reserved;        /* must be zero */
+  float normal_min;         /* reprojection: a tap counts only where n_p . n_q >= normal_min; must be > 0 */
+  float plane_max;          /* reprojection with prev_point: a tap counts only where |n_p . (x_q - x_p)| <= plane_max; must be > 0 then */
+  const RaycaCameraPose* prev_camera;   /* HOST, copied during the call; NULL: identity mapping (the camera did not move) */
+  const void* color;        /* DEVICE H x W x 4 f32, required: this frame, gamma 1 */
+  const void* point;        /* DEVICE H x W x 3 f32  } this frame's G-buffer; required with prev_camera, */
+  const void* normal;       /* DEVICE H x W x 3 f32  } must be NULL without it */
+  const void* id;           /* DEVICE H x W u32 or NULL; with prev_id or not at all */
+  const void* hist_color;   /* DEVICE H x W x 4 f32 } the history: all three or none (none = first frame), */
+  const void* hist_length;  /* DEVICE H x W f32     } hist_moments optional with the other two */
+  const void* hist_moments; /* DEVICE H x W x 2 f32: mean luminance, mean squared luminance */
+  const void* prev_normal;  /* DEVICE H x W x 3 f32: the G-buffer of the frame the history belongs to; required with prev_camera + history */
+  const void* prev_point;   /* DEVICE H x W x 3 f32 or NULL */
+  const void* prev_id;      /* DEVICE H x W u32 or NULL */
+  void* color_out;          /* DEVICE H x W x 4 f32, required */
+  void* length_out;         /* DEVICE H x W f32, required */
+  void* moments_out;        /* DEVICE H x W x 2 f32 or NULL; requires hist_moments whenever there is a history */
+  void* variance_out;       /* DEVICE H x W f32 or NULL; needs moments_out */
+};
+typedef struct RaycaAccumulate RaycaAccumulate;
+int32_t rayca_hip_accumulate_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaAccumulate* a, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

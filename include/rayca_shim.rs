@@ -340,6 +340,47 @@ pub struct RaycaDenoise {
     pub rgba8_out: *mut c_void,
 }
 
+// rayca_hip_scene_camera: the camera of a frame as a reprojection reads it
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct RaycaCameraPose {
+    pub origin: [f32; 3],
+    pub angle: f32,
+    pub right: [f32; 3],
+    pub reserved0: f32,
+    pub up: [f32; 3],
+    pub reserved1: f32,
+    pub back: [f32; 3],
+    pub reserved2: f32,
+}
+
+// rayca_hip_accumulate_device: temporal accumulation with reprojection; every pointer but prev_camera (HOST) is DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaAccumulate {
+    pub width: u32,
+    pub height: u32,
+    pub max_history: u32,
+    pub reserved: u32,
+    pub normal_min: f32,
+    pub plane_max: f32,
+    pub prev_camera: *const RaycaCameraPose,
+    pub color: *const c_void,
+    pub point: *const c_void,
+    pub normal: *const c_void,
+    pub id: *const c_void,
+    pub hist_color: *const c_void,
+    pub hist_length: *const c_void,
+    pub hist_moments: *const c_void,
+    pub prev_normal: *const c_void,
+    pub prev_point: *const c_void,
+    pub prev_id: *const c_void,
+    pub color_out: *mut c_void,
+    pub length_out: *mut c_void,
+    pub moments_out: *mut c_void,
+    pub variance_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -418,6 +459,8 @@ extern "C" {
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
+    pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

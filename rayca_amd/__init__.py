@@ -9,3 +9,4 @@ from .model import (Camera, GgxMaterial, Image, Light, Mesh, Model, Node, PbrMat
                     PhongMaterial, Primitive, Scene, Sphere, Texture, TriangleMesh, Trs,
                     create_default_model, flatten, quat_axis_angle)
 from .renderer import Config, DeviceScene, IntegratorStrategy, Renderer, SamplerStrategy, SoftRenderer  # noqa: F401
+from .film import Film  # noqa: F401

@@ -339,6 +339,47 @@ class RaycaDenoise(C.Structure):
     ]
 
 
+class RaycaCameraPose(C.Structure):
+    """rayca_hip_scene_camera: the camera of a frame as a reprojection reads it (xx = right . v / -(back . v), yy = up . v / -(back . v))."""
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("angle", C.c_float),
+        ("right", C.c_float * 3),
+        ("reserved0", C.c_float),
+        ("up", C.c_float * 3),
+        ("reserved1", C.c_float),
+        ("back", C.c_float * 3),
+        ("reserved2", C.c_float),
+    ]
+
+
+class RaycaAccumulate(C.Structure):
+    """rayca_hip_accumulate_device: every pointer but prev_camera (HOST) is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("max_history", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("normal_min", C.c_float),
+        ("plane_max", C.c_float),
+        ("prev_camera", C.POINTER(RaycaCameraPose)),
+        ("color", C.c_void_p),
+        ("point", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("id", C.c_void_p),
+        ("hist_color", C.c_void_p),
+        ("hist_length", C.c_void_p),
+        ("hist_moments", C.c_void_p),
+        ("prev_normal", C.c_void_p),
+        ("prev_point", C.c_void_p),
+        ("prev_id", C.c_void_p),
+        ("color_out", C.c_void_p),
+        ("length_out", C.c_void_p),
+        ("moments_out", C.c_void_p),
+        ("variance_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -463,6 +504,10 @@ def bind_product_signatures(lib):
     lib.rayca_hip_camera_rays_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(RaycaRenderOptions), C.c_void_p]
     lib.rayca_hip_denoise_device.restype = C.c_int32
     lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
+    lib.rayca_hip_scene_camera.restype = C.c_int32
+    lib.rayca_hip_scene_camera.argtypes = [C.c_void_p, P(RaycaCameraPose)]
+    lib.rayca_hip_accumulate_device.restype = C.c_int32
+    lib.rayca_hip_accumulate_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaAccumulate), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -485,6 +530,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_denoise_device",
+    "rayca_hip_scene_camera", "rayca_hip_accumulate_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

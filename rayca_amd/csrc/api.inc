@@ -2246,4 +2246,108 @@ int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   return pass_finish(pass, launches, stats_out);
 }
 
+namespace {
+// k_accumulate for the inputs that are present: identity mode [moments], reprojection [id][prev_point][moments]
+using AccumulateKernel = void (*)(AccumulateIo);
+AccumulateKernel pick_accumulate_kernel(bool reproject, bool id, bool plane, bool moments) {
+  if (!reproject) return moments ? k_accumulate<false, false, false, true> : k_accumulate<false, false, false, false>;
+#define RAYCA_ACCUMULATE(I, P) {k_accumulate<true, I, P, false>, k_accumulate<true, I, P, true>}
+  static const AccumulateKernel table[2][2][2] = {{RAYCA_ACCUMULATE(false, false), RAYCA_ACCUMULATE(false, true)},
+                                                  {RAYCA_ACCUMULATE(true, false), RAYCA_ACCUMULATE(true, true)}};
+#undef RAYCA_ACCUMULATE
+  return table[id ? 1 : 0][plane ? 1 : 0][moments ? 1 : 0];
+}
+}  // namespace
+
+// Temporal accumulation (temporal.inc): one launch of k_accumulate, no scratch image.  Identity mode (no prev_camera) is
+// pixel-local, so an output may be the history it continues; in reprojection mode the taps read neighbours, and an output that
+// is one of the images they read is refused.  The scene handle gives the device and the frame context; the scene is not read.
+int32_t rayca_hip_accumulate_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaAccumulate* ain, RaycaStats* stats_out) {
+  if (!s || !ain) return fail(RAYCA_ERR_BAD_ARG, "null scene or accumulate arguments");
+  const RaycaAccumulate& a = *ain;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (a.width == 0 || a.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaAccumulate.width, height)");
+  const uint64_t count64 = (uint64_t)a.width * a.height;
+  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaAccumulate.width x height)");
+  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaAccumulate.reserved must be zero");
+  if (!a.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!a.color_out) return fail(RAYCA_ERR_BAD_ARG, "null color_out");
+  if (!a.length_out) return fail(RAYCA_ERR_BAD_ARG, "null length_out");
+  const bool reproject = a.prev_camera != nullptr;
+  if (reproject && (!a.point || !a.normal)) return fail(RAYCA_ERR_BAD_ARG, "point and normal are required with prev_camera");
+  if (!reproject && (a.point || a.normal)) return fail(RAYCA_ERR_BAD_ARG, "point and normal must be NULL without prev_camera");
+  if ((a.id != nullptr) != (a.prev_id != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "id and prev_id: both or neither");
+  if ((a.hist_color != nullptr) != (a.hist_length != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "hist_color and hist_length: both or neither");
+  const bool history = a.hist_color != nullptr;
+  if (a.hist_moments && !history) return fail(RAYCA_ERR_BAD_ARG, "hist_moments needs hist_color and hist_length");
+  if (reproject && history && !a.prev_normal) return fail(RAYCA_ERR_BAD_ARG, "prev_normal is required with prev_camera and a history");
+  if (a.moments_out && history && !a.hist_moments) return fail(RAYCA_ERR_BAD_ARG, "moments_out needs hist_moments where there is a history");
+  if (a.variance_out && !a.moments_out) return fail(RAYCA_ERR_BAD_ARG, "variance_out needs moments_out");
+  if (reproject && !(a.normal_min > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "normal_min must be > 0 with prev_camera");
+  if (reproject && a.prev_point && !(a.plane_max > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "plane_max must be > 0 when prev_point is given");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(a.color, 16) || misaligned(a.hist_color, 16) || misaligned(a.color_out, 16))
+    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, hist_color and color_out are read and written 16 bytes a pixel");
+  for (const void* ptr : {a.point, a.normal, a.id, a.hist_length, a.hist_moments, a.prev_normal, a.prev_point, a.prev_id,
+                          (const void*)a.length_out, (const void*)a.moments_out, (const void*)a.variance_out})
+    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, hist_color and color_out is read and written 4 bytes an element");
+  if (reproject)
+    for (const void* out : {(const void*)a.color_out, (const void*)a.length_out, (const void*)a.moments_out, (const void*)a.variance_out})
+      for (const void* in : {a.hist_color, a.hist_length, a.hist_moments, a.prev_normal, a.prev_point, a.prev_id})
+        if (out && out == in) return fail(RAYCA_ERR_BAD_ARG, "aliasing: with prev_camera the taps read neighbours, so no output may be a hist_ or prev_ input");
+  int32_t rc = pass_options(o, "an accumulate call, which reads a whole frame (a tile's packed rows are not neighbours)", 0u);
+  if (rc != RAYCA_OK) return rc;
+  const uint32_t tiles_x = (uint32_t)(((uint64_t)a.width + kDenoiseTileW - 1u) / kDenoiseTileW);
+  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)a.height + kDenoiseTileH - 1u) / kDenoiseTileH);
+  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
+  AccumulateIo io{};
+  io.color = static_cast<const float4*>(a.color);
+  io.hist_color = static_cast<const float4*>(a.hist_color);
+  io.hist_length = static_cast<const float*>(a.hist_length);
+  io.color_out = static_cast<float4*>(a.color_out);
+  io.length_out = static_cast<float*>(a.length_out);
+  const bool moments = a.moments_out != nullptr;
+  if (moments) {
+    io.hist_moments = static_cast<const float*>(a.hist_moments);
+    io.moments_out = static_cast<float*>(a.moments_out);
+    io.variance_out = static_cast<float*>(a.variance_out);
+  }
+  io.width = a.width;
+  io.height = a.height;
+  io.tiles_x = tiles_x;
+  io.cap = (float)a.max_history;
+  // without a history no pixel has one, whatever the camera did: the identity kernel with a null history writes the first frame
+  const bool taps = reproject && history;
+  if (taps) {
+    const RaycaCameraPose& cam = *a.prev_camera;   // (HOST memory, copied here)
+    io.point = static_cast<const float*>(a.point);
+    io.normal = static_cast<const float*>(a.normal);
+    io.prev_normal = static_cast<const float*>(a.prev_normal);
+    io.prev_point = static_cast<const float*>(a.prev_point);
+    io.id = static_cast<const uint32_t*>(a.id);
+    io.prev_id = static_cast<const uint32_t*>(a.prev_id);
+    io.normal_min = a.normal_min;
+    io.plane_max = a.plane_max;
+    io.fw = (float)a.width;
+    io.fh = (float)a.height;
+    io.angle = cam.angle;
+    io.angle_aspect = cam.angle * (io.fw / io.fh);   // (aspect as camera_frame_params forms it)
+    io.ox = cam.origin[0]; io.oy = cam.origin[1]; io.oz = cam.origin[2];
+    io.rx = cam.right[0]; io.ry = cam.right[1]; io.rz = cam.right[2];
+    io.ux = cam.up[0]; io.uy = cam.up[1]; io.uz = cam.up[2];
+    io.bx = cam.back[0]; io.by = cam.back[1]; io.bz = cam.back[2];
+  }
+  const auto kernel = pick_accumulate_kernel(taps, taps && io.id != nullptr, taps && io.prev_point != nullptr, moments);
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
+  HIP_TRY(hipGetLastError());
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, 1, stats_out);
+}
+
 }  // extern "C"

@@ -18,6 +18,8 @@
 //   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
 //   k_atrous,         the edge-avoiding a-trous denoiser on a frame and its G-buffer in device memory
 //   k_denoise_*       (denoise.inc: rayca_hip_denoise_device).
+//   k_accumulate      temporal accumulation of a frame into a history, with reprojection through the previous camera
+//                     (temporal.inc: rayca_hip_accumulate_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -391,6 +393,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "wavefront.inc"
 #include "surface.inc"
 #include "denoise.inc"
+#include "temporal.inc"
 
 }  // namespace
 }  // namespace rayca

@@ -726,6 +726,26 @@ int32_t rayca_hip_scene_info(const RaycaScene* s, RaycaSceneInfo* out) {
   return RAYCA_OK;
 }
 
+// The camera of a frame in the form a reprojection reads it (rayca_hip_accumulate_device): the origin as camera_ray forms it
+// from the camera node's world transform, and the rows of (R S)^-1 = S^-1 R^T -- rotate(e_k, rotation) / scale.k -- so that for
+// a point x on the ray through (xx, yy, -1), right . (x - origin) = s xx, up . = s yy, back . = -s.  Host only.
+int32_t rayca_hip_scene_camera(const RaycaScene* s, RaycaCameraPose* out) {
+  if (!s || !out) return fail(RAYCA_ERR_BAD_ARG, "null scene or camera pose");
+  if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
+  const Trs& t = s->host.world_trs[s->host.camera_node];
+  std::memset(out, 0, sizeof *out);
+  F4 origin = point_rotate(point_scale(point3(0.0f, 0.0f, 0.0f), t.scale), t.rotation);   // (camera_ray: Ray::scale, ::rotate, ::translate)
+  origin.w = 1.0f;
+  origin = origin + t.translation;
+  out->origin[0] = origin.x; out->origin[1] = origin.y; out->origin[2] = origin.z;
+  out->angle = tanf(s->host.camera_yfov * 0.5f);   // (camera_frame_params)
+  const F4 r = rotate(vec3(1.0f, 0.0f, 0.0f), t.rotation), u = rotate(vec3(0.0f, 1.0f, 0.0f), t.rotation), b = rotate(vec3(0.0f, 0.0f, 1.0f), t.rotation);
+  out->right[0] = r.x / t.scale.x; out->right[1] = r.y / t.scale.x; out->right[2] = r.z / t.scale.x;
+  out->up[0] = u.x / t.scale.y; out->up[1] = u.y / t.scale.y; out->up[2] = u.z / t.scale.y;
+  out->back[0] = b.x / t.scale.z; out->back[1] = b.y / t.scale.z; out->back[2] = b.z / t.scale.z;
+  return RAYCA_OK;
+}
+
 // What SceneDrawInfo::new reads again per draw (scene.rs:88-115) and leaves the BVH alone: the camera, the light table, the
 // material table.  Everything is checked and computed first, into temporaries; a refused edit changes nothing.
 //

@@ -1,0 +1,142 @@
+"""A film on device memory: frames of a resident scene accumulated over time (DeviceScene.accumulate), through camera moves.
+
+`Film.add` renders one frame and folds it into the history: pixel by pixel while the camera stands still, through the
+reprojection of rayca_hip_accumulate_device once it has moved (DeviceScene.update).  Everything stays in device memory and
+on one stream; nothing is waited for."""
+from __future__ import annotations
+
+import dataclasses
+
+from .renderer import Config, DeviceScene
+
+GUIDES = ("point", "normal", "material")   # the G-buffer a frame leaves for the next one: surface outputs (id = the material)
+
+
+class Film:
+    """Film(scene, width, height): the history of a width x height view of `scene` (a DeviceScene).
+
+    max_history 0 is a running mean, else the history length is capped there (an exponential tail, which forgets what a
+    moved light or material left).  normal_min and plane_max are the reprojection's thresholds (DeviceScene.accumulate);
+    moments=True keeps the luminance moments, and with them `variance`.  A film's calls belong on one stream and one
+    frame context: its buffers are reused from frame to frame, and that order is all that keeps them apart."""
+
+    def __init__(self, scene: DeviceScene, width: int, height: int, *, max_history=0, normal_min=0.9, plane_max=0.1, moments=True):
+        self.scene, self.width, self.height = scene, width, height
+        self.max_history, self.normal_min, self.plane_max, self.with_moments = max_history, normal_min, plane_max, bool(moments)
+        self._buffers = None
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the history: the next add() is a first frame.  (The buffers are kept.)"""
+        self.frames_added = 0
+        self._pose = None      # bytes of the camera pose the history and its G-buffer belong to
+        self._prev_pose = None # ... and the pose itself
+        self._gamma = 1.0
+        self._hist = 0         # which of the two history sets holds the film
+        self._gbuf = 0         # which of the two G-buffers belongs to it
+
+    def _allocate(self):
+        import torch
+        dev = torch.device("cuda", self.scene.device)
+        h, w, n = self.height, self.width, self.height * self.width
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        def history():
+            s = {"color": f32(h, w, 4), "length": f32(h, w)}
+            if self.with_moments:
+                s["moments"], s["variance"] = f32(h, w, 2), f32(h, w)
+            return s
+
+        def gbuffer():
+            return {"point": f32(n, 3), "normal": f32(n, 3), "material": torch.empty((n,), dtype=torch.int32, device=dev)}
+
+        self._buffers = {"frame": f32(h, w, 4), "rays": f32(n, 6), "t": f32(n), "prim": torch.empty((n,), dtype=torch.int32, device=dev),
+                         "uv": f32(n, 2), "hist": (history(), history()), "gbuf": (gbuffer(), gbuffer())}
+
+    def _gbuffer(self, which, stream, context):
+        """camera rays -> closest hits -> surface, into the film's own tensors (what DeviceScene.gbuffer does into new ones)"""
+        b, s = self._buffers, self.scene
+        one = Config(samples_per_pixel=1)   # (the reprojection assumes points on the rays through pixel centres)
+        s.camera_rays(one, self.width, self.height, stream=stream, context=context, out=b["rays"])
+        s.query(b["rays"], stream=stream, context=context, out=(b["t"], b["prim"], b["uv"]))
+        s.surface(b["rays"], b["t"], b["prim"], b["uv"], want=GUIDES, stream=stream, context=context, out=b["gbuf"][which])
+
+    def _shaped(self, g):
+        h, w = self.height, self.width
+        return {"point": g["point"].view(h, w, 3), "normal": g["normal"].view(h, w, 3), "id": g["material"].view(h, w)}
+
+    def add(self, config: Config, stream=None, context=0):
+        """One more frame of `config`, rendered with gamma 1 and seed (config.seed + frames_added) mod 2^32, into the film.
+        The first frame starts the history; a frame whose camera pose has the bytes of the previous one's continues it pixel by
+        pixel; any other goes through the reprojection with the previous frame's G-buffer.  The two history sets and the two
+        G-buffers change roles from frame to frame, so nothing is waited for.  Returns the film's colour (H, W, 4), which the
+        next add() but one overwrites."""
+        if self._buffers is None:
+            self._allocate()
+        b, s = self._buffers, self.scene
+        handle = s._torch_call(stream)[2]
+        self._gamma = config.gamma
+        cfg = dataclasses.replace(config, gamma=1.0, seed=(config.seed + self.frames_added) % 2 ** 32)
+        s.render_device(cfg, self.width, self.height, 0, b["frame"].data_ptr(), stream=handle or None, context=context)
+        pose = s.camera_pose()
+        pose_bytes = bytes(pose)
+        src, dst = b["hist"][self._hist], b["hist"][self._hist ^ 1]
+        kw = dict(max_history=self.max_history, moments=self.with_moments, variance=self.with_moments, out=dst, stream=stream, context=context)
+        if self.frames_added == 0:
+            self._gbuffer(self._gbuf, stream, context)
+            s.accumulate(b["frame"], **kw)
+        elif pose_bytes == self._pose:
+            s.accumulate(b["frame"], history={k: v for k, v in src.items() if k != "variance"}, **kw)
+        else:
+            self._gbuffer(self._gbuf ^ 1, stream, context)
+            now, then = self._shaped(b["gbuf"][self._gbuf ^ 1]), self._shaped(b["gbuf"][self._gbuf])
+            s.accumulate(b["frame"], history={k: v for k, v in src.items() if k != "variance"}, prev=then, prev_camera=self._prev_pose,
+                         normal_min=self.normal_min, plane_max=self.plane_max, **now, **kw)
+            self._gbuf ^= 1
+        self._hist ^= 1
+        self._pose, self._prev_pose = pose_bytes, pose
+        self.frames_added += 1
+        return dst["color"]
+
+    def _current(self, name):
+        if not self.frames_added:
+            raise ValueError("the film is empty: add() a frame first")
+        return self._buffers["hist"][self._hist].get(name)
+
+    @property
+    def color(self):
+        """(H, W, 4) float32, gamma 1: the accumulated frame"""
+        return self._current("color")
+
+    @property
+    def length(self):
+        """(H, W) float32: how many samples stand behind each pixel (0: none, its colour is not finite)"""
+        return self._current("length")
+
+    @property
+    def variance(self):
+        """(H, W) float32: the luminance variance over the history (None without moments)"""
+        return self._current("variance")
+
+    def gbuffer(self):
+        """the G-buffer of the last frame whose camera differed from its predecessor's -- the film's view: point, normal (H, W, 3), id (H, W)"""
+        if not self.frames_added:
+            raise ValueError("the film is empty: add() a frame first")
+        return self._shaped(self._buffers["gbuf"][self._gbuf])
+
+    def resolve(self, *, denoise=False, gamma=None, rgba8=False, stream=None, context=0, **denoise_kw):
+        """The film through DeviceScene.denoise: its output stage alone (iterations=0: gamma and the RGBA8 quantisation of a
+        render call), or with denoise=True the a-trous filter in front of it, guided by the film's G-buffer (normal, point, id;
+        sigma_plane defaults to 0.1).  gamma None is the gamma of the config last added.  Returns what denoise() returns: a new
+        float tensor, with rgba8 a tuple with the uint8 tensor behind it."""
+        color = self.color
+        kw = dict(denoise_kw)
+        if denoise:
+            kw = {**self.gbuffer(), **kw}
+            if kw.get("sigma_plane") is None:
+                kw["sigma_plane"] = 0.1
+        else:
+            kw["iterations"] = 0
+        return self.scene.denoise(color, gamma=self._gamma if gamma is None else gamma, rgba8=rgba8, stream=stream, context=context, **kw)

@@ -459,6 +459,91 @@ class DeviceScene:
         return self.denoise(color, gamma=config.gamma, out=color, stream=stream, context=context, **kw)
 
 
+    # ---- temporal accumulation: a frame into a history, with reprojection (rayca_hip_scene_camera, rayca_hip_accumulate_device) ----
+    def camera_pose(self) -> abi.RaycaCameraPose:
+        """rayca_hip_scene_camera: the camera the scene's frames use, as accumulate() takes it for `prev_camera` (origin, tan of
+        half the vertical field of view, and the rows right / up / back of the inverse of the camera's rotation and scale).
+        Host only; after update() the new camera."""
+        pose = abi.RaycaCameraPose()
+        lib.check(self._lib.rayca_hip_scene_camera(self.handle, C.byref(pose)))
+        return pose
+
+    def accumulate(self, color, *, history=None, prev=None, prev_camera=None, point=None, normal=None, id=None, max_history=0,
+                   normal_min=0.9, plane_max=0.1, moments=None, variance=False, out=None, stream=None, context=0, want_stats=False):
+        """rayca_hip_accumulate_device: one frame into a history, asynchronously, everything in device memory.
+
+        color (H, W, 4) float32: a frame rendered with gamma 1.  history: None (the first frame) or a dict as this call
+        returns one -- "color" (H, W, 4), "length" (H, W) float32, optionally "moments" (H, W, 2).  Without `prev_camera` the
+        history is taken pixel by pixel (the camera did not move).  With it (a camera_pose() of the frame the history belongs
+        to) every pixel looks its history up where its surface point was seen then: point and normal (H, W, 3) float32 and
+        optionally id (H, W) int32 are this frame's G-buffer as gbuffer() returns it (of a one-sample config: points on the rays
+        through pixel centres), `prev` a dict with the other frame's "normal" and optionally "point" and "id" (id with id or not
+        at all).  A tap of the bilinear footprint counts only where the ids are equal, the normals' dot product is at least
+        normal_min and, with prev["point"], the tap lies within plane_max world units of this pixel's tangent plane.
+        max_history 0 is a running mean, else the length is capped there.  moments (default: whenever the history allows it)
+        adds "moments" (mean and mean square of the luminance), variance=True "variance" (H, W).  `out`: a dict of tensors to
+        write instead of new ones; without prev_camera they may be the history's own (a film in place), and out["color"] may
+        always be `color`.  Stream handling as query().  Returns a dict: color, length, [moments], [variance], [stats]."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        h, w = color.shape[:2]
+        history, prev, out = dict(history or {}), dict(prev or {}), dict(out or {})
+        for name, d, known in (("history", history, ("color", "length", "moments")), ("prev", prev, ("normal", "point", "id")),
+                               ("out", out, ("color", "length", "moments", "variance"))):
+            stray = [k for k in d if k not in known]
+            if stray:
+                raise ValueError(f"{name}: {stray} not in {known}")
+        if moments is None:
+            moments = variance or not history or "moments" in history
+        if variance and not moments:
+            raise ValueError("variance: needs moments")
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        shapes = {"color": (torch.float32, (h, w, 4)), "length": (torch.float32, (h, w)), "moments": (torch.float32, (h, w, 2)),
+                  "variance": (torch.float32, (h, w)), "point": (torch.float32, (h, w, 3)), "normal": (torch.float32, (h, w, 3)),
+                  "id": (torch.int32, (h, w))}
+        a = abi.RaycaAccumulate()
+        a.width, a.height, a.max_history, a.normal_min, a.plane_max = w, h, max_history, normal_min, plane_max
+        result = {}
+        for name in ("color", "length") + (("moments",) if moments else ()) + (("variance",) if variance else ()):
+            x = out.get(name)   # (before a contiguous copy of an input replaces a tensor it may share)
+            if x is None:
+                x = torch.empty(shapes[name][1], dtype=shapes[name][0], device=dev)
+            elif not checked(x, f"out[{name!r}]", *shapes[name]).is_contiguous():
+                raise ValueError(f"out[{name!r}]: an output must be contiguous")
+            result[name] = x
+            setattr(a, name + "_out", x.data_ptr())
+        a.color = contiguous(checked(color, "color", *shapes["color"])).data_ptr()
+        for name, x in (("point", point), ("normal", normal), ("id", id)):
+            if x is not None:
+                setattr(a, name, contiguous(checked(x, name, *shapes[name])).data_ptr())
+        for name, x in history.items():
+            setattr(a, "hist_" + name, contiguous(checked(x, f"history[{name!r}]", *shapes[name])).data_ptr())
+        for name, x in prev.items():
+            setattr(a, "prev_" + name, contiguous(checked(x, f"prev[{name!r}]", *shapes[name])).data_ptr())
+        if prev_camera is not None:
+            if not isinstance(prev_camera, abi.RaycaCameraPose):
+                raise TypeError(f"prev_camera: a camera_pose() is expected, not {type(prev_camera).__name__}")
+            a.prev_camera = C.pointer(prev_camera)
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_accumulate_device(self.handle, C.byref(o), C.byref(a), C.byref(st) if st is not None else None))
+        record(temporaries)
+        if st is not None:
+            result["stats"] = st.as_dict()
+        return result
+
+
 def _multi_args(scenes, config, band_rows, gather, traversal, collect_stats, engine, context):
     handles = (C.c_void_p * len(scenes))(*[s.handle for s in scenes])
     o = abi.RaycaMultiOptions()
