@@ -42,7 +42,8 @@ extern "C" {
                                   rayca_hip_query_device; the surface queries: RaycaSurfaceQuery, rayca_hip_surface_device,
                                   rayca_hip_camera_rays_device; the denoiser: RaycaDenoise, rayca_hip_denoise_device;
                                   temporal accumulation: RaycaCameraPose, rayca_hip_scene_camera, RaycaAccumulate,
-                                  rayca_hip_accumulate_device */
+                                  rayca_hip_accumulate_device; the variance-guided denoiser: RaycaDenoiseVariance,
+                                  rayca_hip_denoise_variance_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -833,6 +834,78 @@ struct RaycaAccumulate {
 };
 typedef struct RaycaAccumulate RaycaAccumulate;
 int32_t rayca_hip_accumulate_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaAccumulate* a, RaycaStats* stats_out);
+
+/* The variance-guided a-trous denoiser (after the filter stage of SVGF, Schied et al. 2017), on a frame, its luminance variance
+ * and its G-buffer in DEVICE memory: the stage behind rayca_hip_accumulate_device.  `color` is a film's color_out (gamma 1),
+ * `variance` its variance_out, `length` its length_out; the guides are rayca_hip_denoise_device's.  Where that filter steers its
+ * colour term with one global sigma_color, this one scales the luminance term with a local variance estimate, filters the variance
+ * along with the colour, and gives a pixel with a short history a spatial estimate: a converged film is left nearly alone, a fresh
+ * one is filtered hard, and an edge that no guide shows survives where it stands out of the noise.  No reference counterpart.  The
+ * scene handle gives the call its device and its frame context; the scene is not read, and an empty scene is no error.
+ * Everything is f32, every operation rounds once, in the association written here (only +, -, x, / and max: no exp, no sqrt, no
+ * pow inside the filter), so that a literal float32 restatement gives the same bits; max() is maxNum (a NaN operand gives the
+ * other one), and every comparison is written so that a NaN fails it.
+ * lum(c) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b;  k = {0.375, 0.25, 0.0625}, the 5 x 5 B3 spline.
+ *   demodulate   only with albedo: den = max(albedo, 1e-3f), c = color / den per r, g, b; alpha stays color's.  ld = lum(den)
+ *   variance v0  v = max(variance[p], 0)                                                              (a NaN becomes 0)
+ *                albedo:  v = v / (ld * ld)        (exact for a grey albedo, an approximation for any other: the luminance of
+ *                                                   a quotient is not the quotient of the luminances)
+ *                length:  L = length[p], v = v / max(L, 1)        (the variance of the film's mean, not of one sample: what
+ *                                                                  makes the filter back off as the film converges)
+ *                min_history > 0 and L < (float)min_history: v is replaced by a spatial estimate over the demodulated image,
+ *                  for dy = -3..3 (outer), dx = -3..3 (inner), q = (y + dy, x + dx) inside the image, s1, s2, ws from 0:
+ *                  w = 1, then the normal and the point term of an iteration below; l_q = lum(c_q)
+ *                  the tap counts iff w > 0, id_q == id_p (with id) and l_q - l_q == 0
+ *                  s1 += w * l_q, s2 += w * (l_q * l_q), ws += w
+ *                  ws > 0: m1 = s1 / ws, m2 = s2 / ws, v = max(m2 - m1 * m1, 0); else v = 0
+ *   iteration i  (i = 0 .. iterations - 1, step s = 2^i), from a colour image and a variance plane into the other two:
+ *                g_p = (sum G v_q) / (sum G) over dy = -1..1 (outer), dx = -1..1 (inner), q = (y + dy, x + dx) inside the image,
+ *                  both sums from 0, G = 0.25 at the centre, 0.125 at an edge, 0.0625 at a corner
+ *                dnm = sl2 * g_p + variance_floor, sl2 = sigma_luminance * sigma_luminance (formed on the host); l_p = lum(c_p)
+ *                for dy = -2..2 (outer), dx = -2..2 (inner), q = (y + dy s, x + dx s) inside the image, sum, vs, ws from 0:
+ *                  w = k[|dx|] * k[|dy|];  d = l_p - lum(c_q), w = w / (1 + (d * d) / dnm)
+ *                  normal:  dn = max((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0), squared normal_power_log2 times, w = w * dn
+ *                  point:   e = x_q - x_p, pd = (n_p.x e.x + n_p.y e.y) + n_p.z e.z, w = w / (1 + (pd pd) * (1 / sigma_plane^2))
+ *                  the tap counts iff w > 0 and id_q == id_p (with id)
+ *                  sum += w * c_q (r, g, b), vs += (w * w) * v_q (v_q: this iteration's unfiltered input variance), ws += w
+ *                ws > 0: c_p' = sum / ws, v_p' = vs / (ws * ws); else both pass through (a NaN colour, the zero normal of a miss)
+ *   output       the colour as rayca_hip_denoise_device's output stage: remodulate c = c * den if demodulated, gamma, rgba32f_out,
+ *                rgba8_out.  variance_out receives the last variance plane, in the units the filter ran in (demodulated with albedo).
+ * No kernel reads an image it writes, and `variance` is read only for v0: rgba32f_out may be `color`, variance_out may be
+ * `variance`.  Any other overlap is undefined.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_surface_device; every other field, tile included, must be zero.  Ordered on its context like a frame; asynchronous
+ * unless stats_out is given: then the call waits and reports the time of its launches (iterations + 2, + 1 with albedo) under
+ * RAYCA_KERNEL_OTHER.  The context keeps the denoiser's two scratch images and two variance planes of 4 bytes a pixel.  color,
+ * albedo and rgba32f_out must be 16-byte aligned, every other image as its elements (4 bytes).
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments / color / variance, no output, width
+ * or height 0, width x height > 2^32 - 1, iterations 0 or > 8, normal_power_log2 > 10, min_history > 0 without length, point
+ * without normal, point with sigma_plane not > 0, sigma_luminance, variance_floor or gamma not > 0, non-zero reserved, a misaligned
+ * image, context > 7, a non-zero field of opts that does not apply.  RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles number
+ * 2^24 or more. */
+struct RaycaDenoiseVariance {
+  uint32_t width, height;        /* the whole frame */
+  uint32_t iterations;           /* 1..8; iteration i uses step 2^i */
+  uint32_t normal_power_log2;    /* 0..10: the normal weight is max(0, n_p.n_q) squared this many times */
+  uint32_t min_history;          /* a pixel whose length is below it takes the spatial estimate; 0: no spatial fallback */
+  uint32_t reserved;             /* must be zero */
+  float sigma_luminance;         /* > 0: the luminance difference is measured in units of sigma_luminance standard deviations */
+  float sigma_plane;             /* world units; must be > 0 when `point` is given */
+  float variance_floor;          /* > 0: added to the scaled variance, so that a zero variance divides by something */
+  float gamma;                   /* > 0; applied to the colour outputs exactly as a render call applies RaycaConfig.gamma */
+  const void* color;             /* DEVICE H x W x 4 f32, required: the film (color_out of rayca_hip_accumulate_device), gamma 1 */
+  const void* variance;          /* DEVICE H x W f32, required: what variance_out of the accumulation holds */
+  const void* length;            /* DEVICE H x W f32 or NULL (length_out); required when min_history > 0 */
+  const void* albedo;            /* DEVICE H x W x 4 f32 or NULL: demodulate before, remodulate after */
+  const void* normal;            /* DEVICE H x W x 3 f32 or NULL */
+  const void* point;             /* DEVICE H x W x 3 f32 or NULL; needs `normal` */
+  const void* id;                /* DEVICE H x W u32 or NULL: a tap counts only where id_q == id_p */
+  void* rgba32f_out;             /* DEVICE H x W x 4 f32 or NULL; may be the same pointer as `color` */
+  void* rgba8_out;               /* DEVICE H x W x 4 u8 or NULL; not both colour outputs NULL */
+  void* variance_out;            /* DEVICE H x W f32 or NULL; may be the same pointer as `variance` */
+};
+typedef struct RaycaDenoiseVariance RaycaDenoiseVariance;
+int32_t rayca_hip_denoise_variance_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaDenoiseVariance* d, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

@@ -381,6 +381,32 @@ pub struct RaycaAccumulate {
     pub variance_out: *mut c_void,
 }
 
+// rayca_hip_denoise_variance_device: the variance-guided a-trous filter on a film, its variance and its G-buffer, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaDenoiseVariance {
+    pub width: u32,
+    pub height: u32,
+    pub iterations: u32,
+    pub normal_power_log2: u32,
+    pub min_history: u32,
+    pub reserved: u32,
+    pub sigma_luminance: f32,
+    pub sigma_plane: f32,
+    pub variance_floor: f32,
+    pub gamma: f32,
+    pub color: *const c_void,
+    pub variance: *const c_void,
+    pub length: *const c_void,
+    pub albedo: *const c_void,
+    pub normal: *const c_void,
+    pub point: *const c_void,
+    pub id: *const c_void,
+    pub rgba32f_out: *mut c_void,
+    pub rgba8_out: *mut c_void,
+    pub variance_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -461,6 +487,7 @@ extern "C" {
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_denoise_variance_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoiseVariance, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

@@ -62,6 +62,7 @@ struct FrameCtx {
   unsigned long long* shade_stats = nullptr;  // [64 lines][16]: shaded / shadow / bounce counts of k_wf_shade
   DeviceBuffer path_direct, path_brdf, path_state, accum, queue[2], out8, out32, ray_io, stack_spill, frames, mis_samples, wf_hits, wf_sh_ray, wf_sh_x;
   DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
+  DeviceBuffer denoise_var[2];        // rayca_hip_denoise_variance_device: the two variance planes that go with them (4 B a pixel)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
                                       // previous frame cleared them): generation 0 needs no memset launch
@@ -2348,6 +2349,163 @@ int32_t rayca_hip_accumulate_device(RaycaScene* s, const RaycaRenderOptions* opt
   HIP_TRY(hipGetLastError());
   if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
   return pass_finish(pass, 1, stats_out);
+}
+
+namespace {
+// k_variance_init for the inputs that are present: [no length, length, length + spatial estimate]; the spatial estimate's
+// guides [no guide, normal, normal + point][id].  Without the spatial estimate no guide is read.
+using VarianceInitKernel = void (*)(VarianceInitIo);
+VarianceInitKernel pick_variance_init_kernel(bool length, bool spatial, bool normal, bool point, bool id) {
+  if (!spatial) return length ? k_variance_init<true, false, false, false, false> : k_variance_init<false, false, false, false, false>;
+#define RAYCA_VARIANCE_INIT(N, P) {k_variance_init<true, true, N, P, false>, k_variance_init<true, true, N, P, true>}
+  static const VarianceInitKernel table[3][2] = {RAYCA_VARIANCE_INIT(false, false), RAYCA_VARIANCE_INIT(true, false), RAYCA_VARIANCE_INIT(true, true)};
+#undef RAYCA_VARIANCE_INIT
+  return table[point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
+}
+// k_atrous_var for the guides that are present: [no guide, normal, normal + point][id]
+using AtrousVarKernel = void (*)(AtrousVarIo);
+AtrousVarKernel pick_atrous_var_kernel(bool normal, bool point, bool id) {
+#define RAYCA_ATROUS_VAR(N, P) {k_atrous_var<N, P, false>, k_atrous_var<N, P, true>}
+  static const AtrousVarKernel table[3][2] = {RAYCA_ATROUS_VAR(false, false), RAYCA_ATROUS_VAR(true, false), RAYCA_ATROUS_VAR(true, true)};
+#undef RAYCA_ATROUS_VAR
+  return table[point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
+}
+}  // namespace
+
+// The variance-guided a-trous denoiser (denoise_variance.inc): [k_denoise_demod] -> k_variance_init -> k_atrous_var x iterations
+// -> k_denoise_finish, between the context's two scratch images and its two variance planes.  No kernel reads an image it
+// writes: every iteration goes from one image and plane to the others, `variance` is read by k_variance_init alone (into a
+// plane), and the only writers of rgba32f_out and variance_out run behind every reader of `color` and `variance` -- which is what
+// lets rgba32f_out be `color` and variance_out be `variance`.  The scene handle gives the device and the frame context; the
+// scene is not read.
+int32_t rayca_hip_denoise_variance_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaDenoiseVariance* din, RaycaStats* stats_out) {
+  if (!s || !din) return fail(RAYCA_ERR_BAD_ARG, "null scene or denoise arguments");
+  const RaycaDenoiseVariance& d = *din;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (d.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDenoiseVariance.reserved must be zero");
+  if (!d.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!d.variance) return fail(RAYCA_ERR_BAD_ARG, "null variance");
+  if (!d.rgba32f_out && !d.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
+  if (d.width == 0 || d.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaDenoiseVariance.width, height)");
+  const uint64_t count64 = (uint64_t)d.width * d.height;
+  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaDenoiseVariance.width x height)");
+  if (d.iterations == 0 || d.iterations > 8) return fail(RAYCA_ERR_BAD_ARG, "iterations must be 1..8");
+  if (d.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
+  if (d.min_history > 0 && !d.length) return fail(RAYCA_ERR_BAD_ARG, "min_history > 0 needs length: the history length chooses the spatial estimate");
+  if (d.point && !d.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
+  if (d.point && !(d.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
+  if (!(d.sigma_luminance > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_luminance must be > 0");
+  if (!(d.variance_floor > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "variance_floor must be > 0");
+  if (!(d.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(d.color, 16) || misaligned(d.albedo, 16) || misaligned(d.rgba32f_out, 16))
+    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo and rgba32f_out are read and written 16 bytes a pixel");
+  for (const void* ptr : {d.variance, d.length, d.normal, d.point, d.id, (const void*)d.rgba8_out, (const void*)d.variance_out})
+    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, albedo and rgba32f_out is read and written 4 bytes an element");
+  int32_t rc = pass_options(o, "a denoise call, which filters a whole frame (a tile's packed rows are not neighbours)", 0u);
+  if (rc != RAYCA_OK) return rc;
+  const uint32_t count = (uint32_t)count64;
+  const uint32_t tiles_x = (uint32_t)(((uint64_t)d.width + kDenoiseTileW - 1u) / kDenoiseTileW);
+  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)d.height + kDenoiseTileH - 1u) / kDenoiseTileH);
+  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  HIP_TRY(hipSetDevice(s->device));   // (for the scratch images, which have to be there before the pass queues its waits)
+  const size_t image_bytes = (size_t)count * sizeof(float4), plane_bytes = (size_t)count * sizeof(float);
+  const float4* color = static_cast<const float4*>(d.color);
+  const float4* albedo = static_cast<const float4*>(d.albedo);
+  const uint32_t images = (albedo || d.iterations > 1) ? 2u : 1u;
+  // an earlier call of this context that has not been waited for may still be filtering in the buffer to be replaced
+  for (uint32_t i = 0; i < images; ++i) {
+    if (c->denoise[i].bytes < image_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
+    if ((rc = ensure(c->denoise[i], image_bytes)) != RAYCA_OK) return rc;
+  }
+  for (DeviceBuffer& plane : c->denoise_var) {
+    if (plane.bytes < plane_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
+    if ((rc = ensure(plane, plane_bytes)) != RAYCA_OK) return rc;
+  }
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  const hipStream_t stream = pass.stream;
+  float4* const scratch[2] = {static_cast<float4*>(c->denoise[0].ptr), static_cast<float4*>(c->denoise[1].ptr)};
+  float* const planes[2] = {static_cast<float*>(c->denoise_var[0].ptr), static_cast<float*>(c->denoise_var[1].ptr)};
+  const uint32_t flat_grid = (uint32_t)((count64 + kBlock - 1u) / kBlock);
+  uint32_t launches = 0;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  const float4* src = color;
+  uint32_t next = 0;   // the scratch image the next kernel writes (never the one `src` is)
+  if (albedo) {
+    hipLaunchKernelGGL(k_denoise_demod, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, scratch[next], count);
+    HIP_TRY(hipGetLastError());
+    src = scratch[next];
+    next ^= 1u;
+    ++launches;
+  }
+  const float* normal = static_cast<const float*>(d.normal);
+  const float* point = static_cast<const float*>(d.point);
+  const uint32_t* id = static_cast<const uint32_t*>(d.id);
+  const float kp = point ? 1.0f / (d.sigma_plane * d.sigma_plane) : 0.0f;
+  {
+    VarianceInitIo io{};
+    io.color = src;
+    io.albedo = albedo;
+    io.variance = static_cast<const float*>(d.variance);
+    io.length = static_cast<const float*>(d.length);
+    io.var_out = planes[0];
+    io.width = d.width;
+    io.height = d.height;
+    io.tiles_x = tiles_x;
+    const bool spatial = d.min_history > 0;
+    if (spatial) {
+      io.normal = normal;
+      io.point = point;
+      io.id = id;
+      io.normal_squarings = d.normal_power_log2;
+      io.kp = kp;
+      io.min_history = (float)d.min_history;
+    }
+    const auto kernel = pick_variance_init_kernel(io.length != nullptr, spatial, spatial && normal, spatial && point, spatial && id);
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+  }
+  uint32_t plane = 0;   // the variance plane the next iteration reads
+  {
+    AtrousVarIo io{};
+    io.normal = normal;
+    io.point = point;
+    io.id = id;
+    io.width = d.width;
+    io.height = d.height;
+    io.tiles_x = tiles_x;
+    io.normal_squarings = d.normal_power_log2;
+    io.sl2 = d.sigma_luminance * d.sigma_luminance;
+    io.variance_floor = d.variance_floor;
+    io.kp = kp;
+    const auto kernel = pick_atrous_var_kernel(normal != nullptr, point != nullptr, id != nullptr);
+    for (uint32_t i = 0; i < d.iterations; ++i) {
+      io.in = src;
+      io.out = scratch[next];
+      io.var_in = planes[plane];
+      io.var_out = planes[plane ^ 1u];
+      io.step = 1u << i;
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
+      HIP_TRY(hipGetLastError());
+      src = scratch[next];
+      next ^= 1u;
+      plane ^= 1u;
+      ++launches;
+    }
+  }
+  const float inv_gamma = 1.0f / d.gamma;   // (as a frame's: color/mod.rs:175-176)
+  hipLaunchKernelGGL(k_denoise_finish, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, inv_gamma, static_cast<uint8_t*>(d.rgba8_out),
+                     static_cast<float4*>(d.rgba32f_out), count);
+  HIP_TRY(hipGetLastError());
+  ++launches;
+  if (d.variance_out) HIP_TRY(hipMemcpyAsync(d.variance_out, planes[plane], plane_bytes, hipMemcpyDeviceToDevice, stream));
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, launches, stats_out);
 }
 
 }  // extern "C"

@@ -20,6 +20,8 @@
 //   k_denoise_*       (denoise.inc: rayca_hip_denoise_device).
 //   k_accumulate      temporal accumulation of a frame into a history, with reprojection through the previous camera
 //                     (temporal.inc: rayca_hip_accumulate_device).
+//   k_variance_init,  the variance-guided a-trous filter: the film's luminance variance steers the luminance weight and is
+//   k_atrous_var      filtered along with the colour (denoise_variance.inc: rayca_hip_denoise_variance_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -393,6 +395,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "wavefront.inc"
 #include "surface.inc"
 #include "denoise.inc"
+#include "denoise_variance.inc"
 #include "temporal.inc"
 
 }  // namespace

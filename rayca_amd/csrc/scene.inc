@@ -686,7 +686,7 @@ int32_t scene_destroy_now(RaycaScene* s) {
     if (b && !keep_streams) (void)hipStreamDestroy(b);
   for (FrameCtx& cx : s->ctx) {
     FrameCtx* c = &cx;
-    for (DeviceBuffer* b : {&c->path_direct, &c->path_brdf, &c->path_state, &c->accum, &c->queue[0], &c->queue[1], &c->out8, &c->out32, &c->ray_io, &c->stack_spill, &c->frames, &c->mis_samples, &c->wf_hits, &c->wf_sh_ray, &c->wf_sh_x, &c->denoise[0], &c->denoise[1]})
+    for (DeviceBuffer* b : {&c->path_direct, &c->path_brdf, &c->path_state, &c->accum, &c->queue[0], &c->queue[1], &c->out8, &c->out32, &c->ray_io, &c->stack_spill, &c->frames, &c->mis_samples, &c->wf_hits, &c->wf_sh_ray, &c->wf_sh_x, &c->denoise[0], &c->denoise[1], &c->denoise_var[0], &c->denoise_var[1]})
       if (b->ptr) (void)hipFree(b->ptr);
     if (c->heads_alloc) (void)hipFree(c->heads_alloc);
     if (c->counters) (void)hipFree(c->counters);

@@ -130,9 +130,23 @@ class Film:
         """The film through DeviceScene.denoise: its output stage alone (iterations=0: gamma and the RGBA8 quantisation of a
         render call), or with denoise=True the a-trous filter in front of it, guided by the film's G-buffer (normal, point, id;
         sigma_plane defaults to 0.1).  gamma None is the gamma of the config last added.  Returns what denoise() returns: a new
-        float tensor, with rgba8 a tuple with the uint8 tensor behind it."""
+        float tensor, with rgba8 a tuple with the uint8 tensor behind it.
+
+        denoise="variance" is the variance-guided filter instead (DeviceScene.denoise_variance): the film's colour, `variance`
+        and `length` with the same G-buffer, so that the filter backs off where the film has converged.  It needs a film with
+        moments=True; `denoise_kw` are denoise_variance's keywords, and it returns what that returns."""
         color = self.color
         kw = dict(denoise_kw)
+        if isinstance(denoise, str):
+            if denoise != "variance":
+                raise ValueError(f"denoise: False, True or 'variance', not {denoise!r}")
+            if not self.with_moments:
+                raise ValueError("denoise='variance': the film keeps no moments (moments=True), so it has no variance")
+            kw = {**self.gbuffer(), **kw}
+            if kw.get("sigma_plane") is None:
+                kw["sigma_plane"] = 0.1
+            return self.scene.denoise_variance(color, self.variance, length=self.length, gamma=self._gamma if gamma is None else gamma,
+                                               rgba8=rgba8, stream=stream, context=context, **kw)
         if denoise:
             kw = {**self.gbuffer(), **kw}
             if kw.get("sigma_plane") is None:

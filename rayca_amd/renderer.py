@@ -458,6 +458,75 @@ class DeviceScene:
             kw["sigma_plane"] = 0.1
         return self.denoise(color, gamma=config.gamma, out=color, stream=stream, context=context, **kw)
 
+    # ---- the variance-guided filter: the stage behind accumulate() (rayca_hip_denoise_variance_device) ----
+    def denoise_variance(self, color, variance, *, length=None, min_history=4, sigma_luminance=4.0, variance_floor=1e-10, variance_out=False,
+                         albedo=None, normal=None, point=None, id=None, iterations=5, sigma_plane=None, normal_power_log2=7, gamma=1.0,
+                         out=None, rgba8=False, stream=None, context=0, want_stats=False):
+        """rayca_hip_denoise_variance_device: the variance-guided a-trous filter, asynchronously, everything in device memory.
+
+        color (H, W, 4) float32 and variance (H, W) float32: a film and its luminance variance as accumulate(variance=True)
+        returns them; length (H, W) float32 its history length -- with it the variance becomes that of the film's mean, so the
+        filter backs off as the film converges, and a pixel whose length is below min_history takes a spatial variance estimate
+        from its 7 x 7 neighbourhood (min_history 0: never; without `length` min_history is not used).  The luminance weight of a
+        tap is 1 / (1 + d^2 / (sigma_luminance^2 * variance + variance_floor)), the variance being prefiltered 3 x 3; the variance
+        is filtered along with the colour.  Guides, iterations (1..8 here), sigma_plane, normal_power_log2, gamma, out, rgba8 and
+        the stream handling are denoise()'s.  variance_out=True adds the filtered variance as an (H, W) float32 tensor (or pass
+        the tensor to write, which may be `variance` itself); it is in the units the filter ran in, demodulated where there is
+        an albedo.  Returns the float tensor, or a tuple with the uint8 tensor, the variance and the stats dict (`want_stats`
+        waits) behind it, each when asked for.
+
+        The defaults are untuned starting values: nobody has tuned them on rendered frames."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        h, w = color.shape[:2]
+        if point is not None and sigma_plane is None:
+            raise ValueError("sigma_plane: needed with point")
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        def output(x, name, dtype, shape):
+            if x is None or x is True:
+                return torch.empty(shape, dtype=dtype, device=dev)
+            if not checked(x, name, dtype, shape).is_contiguous():
+                raise ValueError(f"{name}: an output must be contiguous")
+            return x
+
+        d = abi.RaycaDenoiseVariance()
+        d.width, d.height, d.iterations, d.normal_power_log2 = w, h, iterations, normal_power_log2
+        d.min_history = min_history if length is not None else 0
+        d.sigma_luminance, d.sigma_plane, d.variance_floor, d.gamma = sigma_luminance, (sigma_plane if sigma_plane is not None else 0.0), variance_floor, gamma
+        # (the outputs before a contiguous copy of an input replaces a name it may share)
+        out = output(out, "out", torch.float32, (h, w, 4))
+        out8 = output(rgba8, "rgba8", torch.uint8, (h, w, 4)) if rgba8 is not None and rgba8 is not False else None
+        var_out = output(variance_out, "variance_out", torch.float32, (h, w)) if variance_out is not None and variance_out is not False else None
+        d.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
+        d.variance = contiguous(checked(variance, "variance", torch.float32, (h, w))).data_ptr()
+        for name, x, dtype, shape in (("length", length, torch.float32, (h, w)), ("albedo", albedo, torch.float32, (h, w, 4)),
+                                      ("normal", normal, torch.float32, (h, w, 3)), ("point", point, torch.float32, (h, w, 3)),
+                                      ("id", id, torch.int32, (h, w))):
+            if x is not None:
+                setattr(d, name, contiguous(checked(x, name, dtype, shape)).data_ptr())
+        d.rgba32f_out = out.data_ptr()
+        if out8 is not None:
+            d.rgba8_out = out8.data_ptr()
+        if var_out is not None:
+            d.variance_out = var_out.data_ptr()
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_denoise_variance_device(self.handle, C.byref(o), C.byref(d), C.byref(st) if st is not None else None))
+        record(temporaries)
+        result = (out,) + ((out8,) if out8 is not None else ()) + ((var_out,) if var_out is not None else ()) + ((st.as_dict(),) if st is not None else ())
+        return result[0] if len(result) == 1 else result
+
 
     # ---- temporal accumulation: a frame into a history, with reprojection (rayca_hip_scene_camera, rayca_hip_accumulate_device) ----
     def camera_pose(self) -> abi.RaycaCameraPose:
