@@ -330,12 +330,12 @@ template <bool ORDERED, bool FAST, bool SPH, bool SPILL, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_GENERAL_MIN_WAVES) void k_general(DevScene sc, FrameParams fp, uint32_t* heads, PathBuffers pb, GFrameStore store,
                                                     TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  const uint32_t tid = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t tid = rc_bid() * kBlock + rc_tid();
   NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, tid);
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
-  WorkCursor wc;
-  LaneCounters cnt;
+  WorkCursor wc{};
+  LaneCounters cnt{};
   uint32_t n_shaded = 0, n_shadow = 0, n_bounce = 0;
   unsigned long long flags = 0ull;
   const uint32_t integ = fp.integrator;

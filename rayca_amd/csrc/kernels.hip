@@ -24,13 +24,16 @@
 //   k_atrous_var      filtered along with the colour (denoise_variance.inc: rayca_hip_denoise_variance_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
+#include "no_pk.hpp"   // RAYCA_NO_PK_F32: no packed f32 arithmetic in the traversal, leaf, shading and BRDF code
+RAYCA_NO_PK_BEGIN
 #include <hip/hip_runtime.h>
-
 #include "device_types.hpp"
+RAYCA_NO_PK_END
 
 namespace rayca {
 namespace {
 
+RAYCA_NO_PK_BEGIN
 #include "trace_core.inc"
 
 // One generation of rays.  Per lane a small state machine around ONE traversal call site:
@@ -43,15 +46,15 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
                                                        PathBuffers pb, uint32_t depth, uint8_t* rgba8, float4* rgba32f,
                                                        TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
   // behind the stack rows: this lane's parked ShadeCtx (path frames only; the host sizes the allocation)
-  float4* const ctx_slot = reinterpret_cast<float4*>(lds_stack + tl.lds_entries * kBlock) + threadIdx.x;
+  float4* const ctx_slot = reinterpret_cast<float4*>(lds_stack + tl.lds_entries * kBlock) + rc_tid();
   constexpr bool PARK = RAYCA_PARK_CTX && MODE == kModePath;
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
-  WorkCursor wc;
+  WorkCursor wc{};
   const uint32_t total = GEN0 ? fp.tile_count : (*in_count + 63u) / 64u;
-  LaneCounters cnt;
+  LaneCounters cnt{};
   uint32_t n_shaded = 0, n_shadow = 0, n_bounce = 0;
   const bool collect_emissive = GEN0 ? true : (fp.direct_sampler == RAYCA_SAMPLER_NONE);
   const uint32_t nee_lights = (MODE == kModePath && fp.direct_sampler == RAYCA_SAMPLER_NEE) ? sc.light_count : 0u;
@@ -284,9 +287,9 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
 // host is what limits an 8-GPU run).
 __global__ __launch_bounds__(kBlock) void k_resolve(FrameParams fp, PathBuffers pb, uint32_t depths, float4* accum, uint8_t* rgba8, float4* rgba32f,
                                                     uint32_t* clear, uint32_t clear_words) {
-  if (clear && blockIdx.x == 0)
-    for (uint32_t i = threadIdx.x; i < clear_words; i += blockDim.x) clear[i] = 0u;
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (clear && rc_bid() == 0)
+    for (uint32_t i = rc_tid(); i < clear_words; i += rc_bdim()) clear[i] = 0u;
+  const uint32_t p = rc_bid() * rc_bdim() + rc_tid();
   if (p >= pb.npix) return;
   bool some = false;
   Color L = black();
@@ -325,9 +328,9 @@ template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_trace_rays(DevScene sc, const float* rays, uint32_t count, float* t_out, uint32_t* prim_out, float* uv_out,
                                                        TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  LaneCounters cnt;
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t i = rc_bid() * rc_bdim() + rc_tid();
+  LaneCounters cnt{};
   if (i < count) {
     const float* r = rays + 6ull * i;
     const DRay ray = make_ray(point3(r[0], r[1], r[2]), vec3(r[3], r[4], r[5]));
@@ -360,9 +363,9 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_trace_rays(De
 template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool OCCLUDED>
 __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(DevScene sc, QueryIo q, TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  LaneCounters cnt;
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t i = rc_bid() * rc_bdim() + rc_tid();
+  LaneCounters cnt{};
   if (i < q.count) {
     bool dead;
     const float bound = query_bound(q, i, dead);
@@ -394,6 +397,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "general.inc"
 #include "wavefront.inc"
 #include "surface.inc"
+RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "denoise.inc"
 #include "denoise_variance.inc"
 #include "temporal.inc"

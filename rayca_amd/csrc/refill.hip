@@ -13,14 +13,17 @@
 //
 // Coherent scenes lose with it (the atrium's camera rays: new rays at the root next to old rays deep in the tree
 // diverge in their node addresses), which is why it is a per-scene choice and not the default.
+#include "no_pk.hpp"   // RAYCA_NO_PK_F32
+RAYCA_NO_PK_BEGIN
 #include <hip/hip_runtime.h>
-
 #include "device_types.hpp"
 #include "refill.hpp"
+RAYCA_NO_PK_END
 
 namespace rayca {
 namespace {
 
+RAYCA_NO_PK_BEGIN
 #include "trace_core.inc"
 
 #ifndef RAYCA_REFILL_THRESHOLD
@@ -46,12 +49,12 @@ template <bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF>
 __global__ __launch_bounds__(kBlock, RAYCA_REFILL_WAVES) void k_flat_refill(DevScene sc, FrameParams fp, uint32_t* heads, uint8_t* rgba8, float4* rgba32f,
                                                                              TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
-  WorkCursor wc;
-  LaneCounters cnt;
+  WorkCursor wc{};
+  LaneCounters cnt{};
   uint32_t n_shaded = 0;
   // lane state: a ray that is still traversing (cur != kTerminated), a finished ray waiting to be retired (has), or nothing
   bool has = false;
@@ -203,13 +206,13 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_queue_refill(De
                                                                               uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
   constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_wf_trace traverses bounce rays)
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   const uint32_t count = *in_count, n_batches = (count + 63u) >> 6;
-  WorkCursor wc;
-  LaneCounters cnt;
+  WorkCursor wc{};
+  LaneCounters cnt{};
   bool has = false;
   uint32_t cur = kTerminated, item = 0;
   DRay ray{};
@@ -300,13 +303,13 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_shadow_refill(D
                                                                                 PathBuffers pb, uint32_t depth, uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
   constexpr bool WIDE = RAYCA_WF_SHADOW_WIDE != 0, SPILL = true, HALF = RAYCA_WF_SHADOW_HALF != 0;   // (as k_wf_shadow traverses them)
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   const uint32_t count = GEN0 ? fp.tile_count * 64u : *in_count, n_batches = (count + 63u) >> 6;
-  WorkCursor wc;
-  LaneCounters cnt;
+  WorkCursor wc{};
+  LaneCounters cnt{};
   bool has = false;          // the lane holds a pixel whose shadow rays are not all done
   uint32_t cur = kTerminated, p = 0, j = 0, quad = 0;
   float t_stop = FLT_MAX;
@@ -449,13 +452,13 @@ template <bool OCCLUDED, bool SPH, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_query_refill(DevScene sc, QueryIo q, uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
   constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_queue_refill)
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
   const unsigned long long lanes_below = (1ull << lane) - 1ull;
   const uint32_t count = q.count, n_batches = (count + 63u) >> 6;
-  WorkCursor wc;
-  LaneCounters cnt;
+  WorkCursor wc{};
+  LaneCounters cnt{};
   bool has = false;
   uint32_t cur = kTerminated, item = 0;
   float t_stop = FLT_MAX;
@@ -571,6 +574,7 @@ RefillKernel pick(const RefillFlavour& f) {
   return f.stats ? pick2<false, true>(f.wide, f.spill, f.half) : pick2<false, false>(f.wide, f.spill, f.half);
 }
 
+RAYCA_NO_PK_END
 }  // namespace
 
 const void* flat_refill_kernel(const RefillFlavour& f) { return reinterpret_cast<const void*>(pick(f)); }

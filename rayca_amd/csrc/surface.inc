@@ -33,13 +33,13 @@ template <int N>
 __device__ __forceinline__ void store_records(float* __restrict__ out, uint64_t first, uint32_t count, const float (&v)[N], float* stage) {
   static_assert(N <= kStageFloats, "stage too small");
   __syncthreads();  // the previous output's reads of `stage`
-  for (int k = 0; k < N; ++k) stage[threadIdx.x * N + k] = v[k];
+  for (int k = 0; k < N; ++k) stage[rc_tid() * N + k] = v[k];
   __syncthreads();
   const uint64_t left = (uint64_t)count - first;  // records of this block and behind it (the caller has first < count)
   const uint32_t valid = (uint32_t)(left < (uint64_t)kBlock ? left : (uint64_t)kBlock) * N;
   float* base = out + first * N;
   for (int k = 0; k < N; ++k) {
-    const uint32_t j = k * kBlock + threadIdx.x;
+    const uint32_t j = k * kBlock + rc_tid();
     if (j < valid) base[j] = stage[j];
   }
 }
@@ -60,9 +60,9 @@ __device__ __forceinline__ void store_color(float* __restrict__ out, uint64_t fi
 template <bool SPH>
 __global__ __launch_bounds__(kBlock) void k_surface(DevScene sc, SurfaceIo io) {
   __shared__ float stage[kBlock * kStageFloats];
-  const uint64_t first = (uint64_t)blockIdx.x * kBlock;
-  const uint32_t i = (uint32_t)first + threadIdx.x;   // (first < count <= 2^32 - 1; i may wrap only where i >= count would hold anyway)
-  const bool in_range = first + threadIdx.x < (uint64_t)io.count;
+  const uint64_t first = (uint64_t)rc_bid() * kBlock;
+  const uint32_t i = (uint32_t)first + rc_tid();   // (first < count <= 2^32 - 1; i may wrap only where i >= count would hold anyway)
+  const bool in_range = first + rc_tid() < (uint64_t)io.count;
   DHit hit;
   hit.t = FLT_MAX;
   hit.prim = RAYCA_NONE;
@@ -124,10 +124,10 @@ __global__ __launch_bounds__(kBlock) void k_surface(DevScene sc, SurfaceIo io) {
 __global__ __launch_bounds__(kBlock) void k_camera_rays(FrameParams fp, float* __restrict__ rays_out) {
   __shared__ float stage[kBlock * kStageFloats];
   const uint32_t count = fp.rows * fp.width;   // (the host refuses frames of 2^32 pixels or more)
-  const uint64_t first = (uint64_t)blockIdx.x * kBlock;
-  const uint32_t i = (uint32_t)first + threadIdx.x;
+  const uint64_t first = (uint64_t)rc_bid() * kBlock;
+  const uint32_t i = (uint32_t)first + rc_tid();
   float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  if (first + threadIdx.x < (uint64_t)count) {
+  if (first + rc_tid() < (uint64_t)count) {
     const uint32_t r = i / fp.width, x = i - r * fp.width;
     const uint32_t y = ((r / fp.band) * fp.parts + fp.part) * fp.band + (r % fp.band);
     const DRay ray = camera_ray(fp, x, y);

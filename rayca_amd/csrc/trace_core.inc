@@ -13,6 +13,15 @@ constexpr int kBlock = 256;
 #define RAYCA_MIN_WAVES 4
 #endif
 
+// Thread and block indices from the compiler's builtins.  threadIdx.x and its kin go through functions of the device library,
+// and a function only inlines into one whose target features contain its own: in the RAYCA_NO_PK_F32 functions (no_pk.hpp)
+// every one of them would stay a call.  For the same reason the structs these functions construct are aggregates (no
+// implicit constructor to call) and every device function of the project is __forceinline__ or declared inside the region.
+__device__ __forceinline__ uint32_t rc_tid() { return __builtin_amdgcn_workitem_id_x(); }
+__device__ __forceinline__ uint32_t rc_bid() { return __builtin_amdgcn_workgroup_id_x(); }
+__device__ __forceinline__ uint32_t rc_bdim() { return __builtin_amdgcn_workgroup_size_x(); }
+__device__ __forceinline__ uint32_t rc_gdim() { return __builtin_amdgcn_grid_size_x() / __builtin_amdgcn_workgroup_size_x(); }
+
 struct DRay {
   F4 o, d, rd;  // origin (w=1), direction (w=0), zero-safe reciprocal
 };
@@ -328,11 +337,11 @@ __device__ __forceinline__ bool reference_candidate(const DevScene& sc, const Tr
   return slab(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, r, tmin);
 }
 
-struct LaneCounters {
-  uint32_t boxes = 0, tris = 0;
+struct LaneCounters {   // (an aggregate: `LaneCounters cnt{};`)
+  uint32_t boxes, tris;
   // STATS only: what the lock-step wave pays -- every trip of the node loop / the leaf loop costs all 64 lanes,
   // booked by the first lane that takes the trip
-  unsigned long long slot_boxes = 0, slot_tris = 0;
+  unsigned long long slot_boxes, slot_tris;
   __device__ __forceinline__ bool books() const { return __lane_id() == (uint32_t)__ffsll((long long)__ballot(1)) - 1u; }
 };
 
@@ -393,7 +402,7 @@ struct NodeStack {
 template <bool SPILL>
 __device__ __forceinline__ NodeStack<SPILL> make_stack(uint32_t* lds_base, const TraceLaunch& tl, uint32_t global_thread) {
   NodeStack<SPILL> st;
-  st.lds = lds_base + threadIdx.x;
+  st.lds = lds_base + rc_tid();
   st.ovf = tl.ovf;
   st.gthread = global_thread;
   st.lds_entries = tl.lds_entries;
@@ -948,9 +957,9 @@ __device__ __forceinline__ uint32_t xcc_id() {
 // when there are fewer batches than resident waves (a rank's share of a frame on eight GPUs): pairs would then
 // leave half the waves without work and double the time of the others.
 constexpr uint32_t kHeadStride = 64;
-struct WorkCursor {
-  uint32_t exhausted = 0;  // partitions found empty so far
-  uint32_t next = 0, end = 0;  // batches of the current ticket still to do
+struct WorkCursor {   // (an aggregate: `WorkCursor wc{};`)
+  uint32_t exhausted;  // partitions found empty so far
+  uint32_t next, end;  // batches of the current ticket still to do
 };
 __device__ __forceinline__ uint32_t next_batch(uint32_t* heads, uint32_t total, uint32_t home, WorkCursor& wc, uint32_t ticket) {
   if (wc.next < wc.end) return wc.next++;

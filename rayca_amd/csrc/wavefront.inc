@@ -48,9 +48,9 @@ template <bool GEN0, bool FAST, bool SPH, bool SPILL, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_trace(DevScene sc, FrameParams fp, const QueuedRay* in_rays, const uint32_t* in_count, WfBuffers wb,
                                                       TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
-  const uint32_t item = xcd_contiguous_block(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
-  LaneCounters cnt;
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t item = xcd_contiguous_block(rc_bid(), rc_gdim()) * kBlock + rc_tid();
+  LaneCounters cnt{};
   bool live;
   uint32_t out_index = 0;
   DRay ray = make_ray(point3(0, 0, 0), vec3(0, 0, 1));
@@ -98,9 +98,9 @@ template <bool GEN0, bool FAST, bool SPH, bool SPILL, bool STATS>
 __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_shadow(DevScene sc, FrameParams fp, const QueuedRay* in_rays, const uint32_t* in_count, WfBuffers wb,
                                                        PathBuffers pb, uint32_t depth, TraceCounters* counters, TraceLaunch tl) {
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, blockIdx.x * kBlock + threadIdx.x);
-  const uint32_t item = xcd_contiguous_block(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
-  LaneCounters cnt;
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t item = xcd_contiguous_block(rc_bid(), rc_gdim()) * kBlock + rc_tid();
+  LaneCounters cnt{};
   uint32_t p = RAYCA_NONE;
   if (GEN0) {
     uint32_t x = 0, r = 0;
@@ -169,7 +169,7 @@ template <int MODE, bool GEN0, bool FUSED, bool SPH>
 __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FrameParams fp, const QueuedRay* in_rays, const uint32_t* in_count, QueuedRay* out_rays,
                                                       uint32_t* out_count, WfBuffers wb, PathBuffers pb, uint32_t depth, uint8_t* rgba8, float4* rgba32f,
                                                       unsigned long long* shade_stats) {
-  const uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x;
+  const uint32_t i = rc_bid() * kShadeBlock + rc_tid();
   const uint32_t n_items = GEN0 ? fp.tile_count * 64u : *in_count;
   bool live = i < n_items;
   uint32_t p = 0, key = 0;
@@ -278,10 +278,10 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FramePara
     __shared__ uint32_t wave_count[kShadeBlock / 64];
     __shared__ uint32_t block_base;
     const unsigned long long mask = __ballot(want_bounce);
-    const uint32_t wave = threadIdx.x >> 6, lane = __lane_id();
+    const uint32_t wave = rc_tid() >> 6, lane = __lane_id();
     if (lane == 0) wave_count[wave] = (uint32_t)__popcll(mask);
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (rc_tid() == 0) {
       uint32_t total = 0;
       for (uint32_t w = 0; w < kShadeBlock / 64; ++w) total += wave_count[w];
       block_base = total ? atomicAdd(out_count, total) : 0u;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FramePara
     b2 += __shfl_down(b2, off);
   }
   if (__lane_id() == 0 && (sh | s2 | b2)) {
-    unsigned long long* line = shade_stats + (size_t)(blockIdx.x & 63u) * 16u;
+    unsigned long long* line = shade_stats + (size_t)(rc_bid() & 63u) * 16u;
     atomicAdd(&line[0], sh);
     if (s2) atomicAdd(&line[1], s2);
     if (b2) atomicAdd(&line[2], b2);
