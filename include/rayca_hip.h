@@ -43,7 +43,8 @@ extern "C" {
                                   rayca_hip_camera_rays_device; the denoiser: RaycaDenoise, rayca_hip_denoise_device;
                                   temporal accumulation: RaycaCameraPose, rayca_hip_scene_camera, RaycaAccumulate,
                                   rayca_hip_accumulate_device; the variance-guided denoiser: RaycaDenoiseVariance,
-                                  rayca_hip_denoise_variance_device */
+                                  rayca_hip_denoise_variance_device; guided upsampling: RaycaUpsample,
+                                  rayca_hip_upsample_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -906,6 +907,80 @@ struct RaycaDenoiseVariance {
 };
 typedef struct RaycaDenoiseVariance RaycaDenoiseVariance;
 int32_t rayca_hip_denoise_variance_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaDenoiseVariance* d, RaycaStats* stats_out);
+
+/* Guided upsampling: a low-resolution frame onto a full-size G-buffer (a joint bilateral upsample), one pass, one kernel, all in
+ * DEVICE memory.  `color` is what rayca_hip_render_device wrote to d_rgba32f_out for the width / scale x height / scale view
+ * (gamma 1), or that frame behind a denoiser or a film; the _low guides are what rayca_hip_surface_device wrote for that view's
+ * camera rays, the full-size guides what it wrote for the width x height view of the same camera.  The G-buffers are those of
+ * sample 0 of a one-sample config (points on the rays through pixel centres), as for the accumulation.  Textures, silhouettes
+ * and normals come from the exact full-size surface data; only the demodulated colour -- the low-frequency irradiance -- is
+ * interpolated.  No reference counterpart.  The scene handle gives the call its device and its frame context; the scene is not
+ * read, and an empty scene is no error.
+ * Everything is f32, every operation rounds once, in the association written here (only +, -, x, /, floor and max), so that a
+ * literal float32 restatement gives the same bits; every comparison is written so that a NaN fails it; max() is maxNum (a NaN
+ * operand gives the other one).  The low image is w = width / scale by h = height / scale, both divisions exact (so that both
+ * views share an aspect ratio whose float quotient has the same bits).  For output pixel p = (x, y), s = (float)scale:
+ *   footprint    fx = ((float)x + 0.5f) / s - 0.5f, fy = ((float)y + 0.5f) / s - 0.5f
+ *                x0 = floor(fx), tx = fx - x0; y0 = floor(fy), ty = fy - y0
+ *                the four taps go j = 0, 1 (outer), i = 0, 1 (inner), q = (y0 + j, x0 + i), b = (i ? tx : 1 - tx) * (j ? ty : 1 - ty)
+ *                a tap exists iff q is inside the low image, b > 0 and color[q] is finite (c.k - c.k == 0 for all four channels)
+ *   demodulate   with albedo: c_q.rgb = color[q].rgb / max(albedo_low[q].rgb, 1e-3f); alpha stays color's.  Else c_q = color[q]
+ *   guided pass  over the taps that exist, sum (four channels) and wsum from 0:
+ *                  w = b
+ *                  normal, n_p == (0, 0, 0) (a miss, as rayca_hip_surface_device writes one): the tap counts only where
+ *                    n_q == (0, 0, 0); the normal and the point term are skipped
+ *                  normal, otherwise:
+ *                    dn = max((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0), squared normal_power_log2 times, w = w * dn
+ *                    point:  e = x_q - x_p, pd = (n_p.x e.x + n_p.y e.y) + n_p.z e.z, w = w / (1 + (pd pd) * (1 / sigma_plane^2))
+ *                            (the reciprocal is formed on the host, as the denoiser's)
+ *                  id:      the tap counts only where id_q == id_p
+ *                  the tap counts iff w > 0; then sum += w * c_q, wsum += w
+ *                wsum > 0: o = sum / wsum
+ *   fallback     wsum not > 0 (no tap agrees with the pixel's surface): the same loop with w = b alone, sumb and bsum from 0;
+ *                bsum > 0: o = sumb / bsum.  Otherwise (no tap exists) o = the demodulated colour of the nearest low pixel,
+ *                (min(y / scale, h - 1), min(x / scale, w - 1)) in integer arithmetic, whatever it holds: a NaN passes through,
+ *                as in the other filters.
+ *   weight_out   wsum of the guided pass: 0 where the fallback was used -- the caller's list of pixels that might deserve a
+ *                traced sample
+ *   output       with albedo: o.rgb = o.rgb * max(albedo[p].rgb, 1e-3f); then the output stage of rayca_hip_denoise_device exactly:
+ *                gamma != 1: powf(c, 1 / gamma) on r, g, b as a frame's last kernel; rgba32f_out, and rgba8_out quantised and
+ *                packed as a frame's.
+ * (x_p, n_p, id_p are point, normal, id at p; x_q, n_q, id_q are point_low, normal_low, id_low at q.  At scale 1 every pixel has
+ * the one tap b = 1: without guides the pass is the output stage alone, but for a -0.0, which the sum from 0 returns as +0.0.)
+ * Aliasing: no output may overlap an input.  The images differ in size and the taps read neighbours, so an output pointer equal
+ * to an input pointer is RAYCA_ERR_BAD_ARG; any other overlap is undefined.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_surface_device; every other field, tile included, must be zero (a tile's packed rows are not neighbours).
+ * Ordered on its context like a frame; asynchronous unless stats_out is given: then the call waits and reports the time of its
+ * one launch under RAYCA_KERNEL_OTHER.  No scratch image.  color, albedo_low, albedo and rgba32f_out must be 16-byte aligned (read
+ * and written 16 bytes a pixel), every other image as its elements (4 bytes).
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments / color, scale 0 or > 8, width or
+ * height not divisible by scale, width or height 0, width x height > 2^32 - 1, one half of a guide pair, point without normal,
+ * point with sigma_plane not > 0, gamma not > 0, normal_power_log2 > 10, no colour output, non-zero reserved, a misaligned image,
+ * the aliasing rule, context > 7, a non-zero field of opts that does not apply.  RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4
+ * pixel tiles number 2^24 or more. */
+struct RaycaUpsample {
+  uint32_t width, height;        /* the output: the whole full-size frame, W x H */
+  uint32_t scale;                /* 1..8; the low image is w = width / scale by h = height / scale, both exact */
+  uint32_t normal_power_log2;    /* 0..10: the normal weight is max(0, n_p.n_q) squared this many times */
+  float sigma_plane;             /* world units; must be > 0 when `point` is given */
+  float gamma;                   /* > 0; applied to the colour outputs exactly as a render call applies RaycaConfig.gamma */
+  uint32_t reserved;             /* must be zero */
+  const void* color;             /* DEVICE h x w x 4 f32, required: the low-resolution frame, gamma 1 */
+  const void* albedo_low;        /* DEVICE h x w x 4 f32 } each guide at both resolutions or at neither */
+  const void* normal_low;        /* DEVICE h x w x 3 f32 } */
+  const void* point_low;         /* DEVICE h x w x 3 f32 } */
+  const void* id_low;            /* DEVICE h x w u32     } */
+  const void* albedo;            /* DEVICE H x W x 4 f32 or NULL: demodulate the taps, remodulate the pixel (surface color_out / diffuse_out) */
+  const void* normal;            /* DEVICE H x W x 3 f32 or NULL (surface normal_out) */
+  const void* point;             /* DEVICE H x W x 3 f32 or NULL; needs `normal` (surface point_out) */
+  const void* id;                /* DEVICE H x W u32 or NULL: a tap counts only where id_q == id_p (material_out, prim, ...) */
+  void* rgba32f_out;             /* DEVICE H x W x 4 f32 or NULL */
+  void* rgba8_out;               /* DEVICE H x W x 4 u8 or NULL; not both colour outputs NULL */
+  void* weight_out;              /* DEVICE H x W f32 or NULL: the guided pass's wsum, 0 where the fallback was used */
+};
+typedef struct RaycaUpsample RaycaUpsample;
+int32_t rayca_hip_upsample_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaUpsample* u, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

@@ -407,6 +407,31 @@ pub struct RaycaDenoiseVariance {
     pub variance_out: *mut c_void,
 }
 
+// rayca_hip_upsample_device: a low-resolution frame onto a full-size G-buffer (joint bilateral upsample), all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaUpsample {
+    pub width: u32,
+    pub height: u32,
+    pub scale: u32,
+    pub normal_power_log2: u32,
+    pub sigma_plane: f32,
+    pub gamma: f32,
+    pub reserved: u32,
+    pub color: *const c_void,
+    pub albedo_low: *const c_void,
+    pub normal_low: *const c_void,
+    pub point_low: *const c_void,
+    pub id_low: *const c_void,
+    pub albedo: *const c_void,
+    pub normal: *const c_void,
+    pub point: *const c_void,
+    pub id: *const c_void,
+    pub rgba32f_out: *mut c_void,
+    pub rgba8_out: *mut c_void,
+    pub weight_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -488,6 +513,7 @@ extern "C" {
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_variance_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoiseVariance, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_upsample_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, u: *const RaycaUpsample, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

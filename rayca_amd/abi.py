@@ -406,6 +406,31 @@ class RaycaDenoiseVariance(C.Structure):
     ]
 
 
+class RaycaUpsample(C.Structure):
+    """rayca_hip_upsample_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("scale", C.c_uint32),
+        ("normal_power_log2", C.c_uint32),
+        ("sigma_plane", C.c_float),
+        ("gamma", C.c_float),
+        ("reserved", C.c_uint32),
+        ("color", C.c_void_p),
+        ("albedo_low", C.c_void_p),
+        ("normal_low", C.c_void_p),
+        ("point_low", C.c_void_p),
+        ("id_low", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("point", C.c_void_p),
+        ("id", C.c_void_p),
+        ("rgba32f_out", C.c_void_p),
+        ("rgba8_out", C.c_void_p),
+        ("weight_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -536,6 +561,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_accumulate_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaAccumulate), P(RaycaStats)]
     lib.rayca_hip_denoise_variance_device.restype = C.c_int32
     lib.rayca_hip_denoise_variance_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoiseVariance), P(RaycaStats)]
+    lib.rayca_hip_upsample_device.restype = C.c_int32
+    lib.rayca_hip_upsample_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaUpsample), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -558,7 +585,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_denoise_device",
-    "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device",
+    "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

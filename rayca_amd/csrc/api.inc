@@ -2508,4 +2508,89 @@ int32_t rayca_hip_denoise_variance_device(RaycaScene* s, const RaycaRenderOption
   return pass_finish(pass, launches, stats_out);
 }
 
+namespace {
+// k_upsample for the guide pairs that are present: [albedo][no guide, normal, normal + point][id]
+using UpsampleKernel = void (*)(UpsampleIo);
+UpsampleKernel pick_upsample_kernel(bool albedo, bool normal, bool point, bool id) {
+#define RAYCA_UPSAMPLE(A, N, P) {k_upsample<A, N, P, false>, k_upsample<A, N, P, true>}
+  static const UpsampleKernel table[2][3][2] = {{RAYCA_UPSAMPLE(false, false, false), RAYCA_UPSAMPLE(false, true, false), RAYCA_UPSAMPLE(false, true, true)},
+                                                {RAYCA_UPSAMPLE(true, false, false), RAYCA_UPSAMPLE(true, true, false), RAYCA_UPSAMPLE(true, true, true)}};
+#undef RAYCA_UPSAMPLE
+  return table[albedo ? 1 : 0][point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
+}
+}  // namespace
+
+// Guided upsampling (upsample.inc): one launch of k_upsample, no scratch image.  Every tap reads the low images and every
+// output is full size, so no output may be an input.  The scene handle gives the device and the frame context; the scene is
+// not read.  Every check stands in front of any GPU work, the options' last.
+int32_t rayca_hip_upsample_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaUpsample* uin, RaycaStats* stats_out) {
+  if (!s || !uin) return fail(RAYCA_ERR_BAD_ARG, "null scene or upsample arguments");
+  const RaycaUpsample& u = *uin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (u.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaUpsample.reserved must be zero");
+  if (u.width == 0 || u.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaUpsample.width, height)");
+  const uint64_t count64 = (uint64_t)u.width * u.height;
+  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaUpsample.width x height)");
+  if (u.scale == 0 || u.scale > 8) return fail(RAYCA_ERR_BAD_ARG, "scale must be 1..8");
+  if (u.width % u.scale != 0 || u.height % u.scale != 0)
+    return fail(RAYCA_ERR_BAD_ARG, "width and height must be divisible by scale: the two views share one aspect ratio, bit for bit");
+  if (u.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
+  if (!u.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!u.rgba32f_out && !u.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
+  if ((u.albedo != nullptr) != (u.albedo_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "albedo and albedo_low: both or neither");
+  if ((u.normal != nullptr) != (u.normal_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "normal and normal_low: both or neither");
+  if ((u.point != nullptr) != (u.point_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "point and point_low: both or neither");
+  if ((u.id != nullptr) != (u.id_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "id and id_low: both or neither");
+  if (u.point && !u.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
+  if (u.point && !(u.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
+  if (!(u.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(u.color, 16) || misaligned(u.albedo_low, 16) || misaligned(u.albedo, 16) || misaligned(u.rgba32f_out, 16))
+    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo_low, albedo and rgba32f_out are read and written 16 bytes a pixel");
+  for (const void* ptr : {u.normal_low, u.point_low, u.id_low, u.normal, u.point, u.id, (const void*)u.rgba8_out, (const void*)u.weight_out})
+    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, albedo_low, albedo and rgba32f_out is read and written 4 bytes an element");
+  for (const void* out : {(const void*)u.rgba32f_out, (const void*)u.rgba8_out, (const void*)u.weight_out})
+    for (const void* in : {u.color, u.albedo_low, u.normal_low, u.point_low, u.id_low, u.albedo, u.normal, u.point, u.id})
+      if (out && out == in) return fail(RAYCA_ERR_BAD_ARG, "aliasing: the taps read neighbours and the images differ in size, so no output may be an input");
+  const uint32_t tiles_x = (uint32_t)(((uint64_t)u.width + kDenoiseTileW - 1u) / kDenoiseTileW);
+  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)u.height + kDenoiseTileH - 1u) / kDenoiseTileH);
+  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
+  int32_t rc = pass_options(o, "an upsample call, which resamples a whole frame (a tile's packed rows are not neighbours)", 0u);
+  if (rc != RAYCA_OK) return rc;
+  UpsampleIo io{};
+  io.color = static_cast<const float4*>(u.color);
+  io.albedo_low = static_cast<const float4*>(u.albedo_low);
+  io.normal_low = static_cast<const float*>(u.normal_low);
+  io.point_low = static_cast<const float*>(u.point_low);
+  io.id_low = static_cast<const uint32_t*>(u.id_low);
+  io.albedo = static_cast<const float4*>(u.albedo);
+  io.normal = static_cast<const float*>(u.normal);
+  io.point = static_cast<const float*>(u.point);
+  io.id = static_cast<const uint32_t*>(u.id);
+  io.rgba32f = static_cast<float4*>(u.rgba32f_out);
+  io.rgba8 = static_cast<uint8_t*>(u.rgba8_out);
+  io.weight = static_cast<float*>(u.weight_out);
+  io.width = u.width;
+  io.height = u.height;
+  io.low_width = u.width / u.scale;
+  io.low_height = u.height / u.scale;
+  io.tiles_x = tiles_x;
+  io.scale = u.scale;
+  io.normal_squarings = u.normal_power_log2;
+  io.s = (float)u.scale;
+  io.kp = io.point ? 1.0f / (u.sigma_plane * u.sigma_plane) : 0.0f;
+  io.inv_gamma = 1.0f / u.gamma;   // (as a frame's: color/mod.rs:175-176)
+  const auto kernel = pick_upsample_kernel(io.albedo != nullptr, io.normal != nullptr, io.point != nullptr, io.id != nullptr);
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
+  HIP_TRY(hipGetLastError());
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, 1, stats_out);
+}
+
 }  // extern "C"

@@ -22,6 +22,8 @@
 //                     (temporal.inc: rayca_hip_accumulate_device).
 //   k_variance_init,  the variance-guided a-trous filter: the film's luminance variance steers the luminance weight and is
 //   k_atrous_var      filtered along with the colour (denoise_variance.inc: rayca_hip_denoise_variance_device).
+//   k_upsample        a low-resolution frame onto a full-size G-buffer: a joint bilateral upsample
+//                     (upsample.inc: rayca_hip_upsample_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include "no_pk.hpp"   // RAYCA_NO_PK_F32: no packed f32 arithmetic in the traversal, leaf, shading and BRDF code
@@ -401,6 +403,7 @@ RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole 
 #include "denoise.inc"
 #include "denoise_variance.inc"
 #include "temporal.inc"
+#include "upsample.inc"
 
 }  // namespace
 }  // namespace rayca

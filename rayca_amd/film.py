@@ -126,7 +126,7 @@ class Film:
             raise ValueError("the film is empty: add() a frame first")
         return self._shaped(self._buffers["gbuf"][self._gbuf])
 
-    def resolve(self, *, denoise=False, gamma=None, rgba8=False, stream=None, context=0, **denoise_kw):
+    def resolve(self, *, denoise=False, gamma=None, rgba8=False, upsample=None, upsample_kw=None, stream=None, context=0, **denoise_kw):
         """The film through DeviceScene.denoise: its output stage alone (iterations=0: gamma and the RGBA8 quantisation of a
         render call), or with denoise=True the a-trous filter in front of it, guided by the film's G-buffer (normal, point, id;
         sigma_plane defaults to 0.1).  gamma None is the gamma of the config last added.  Returns what denoise() returns: a new
@@ -134,7 +134,16 @@ class Film:
 
         denoise="variance" is the variance-guided filter instead (DeviceScene.denoise_variance): the film's colour, `variance`
         and `length` with the same G-buffer, so that the filter backs off where the film has converged.  It needs a film with
-        moments=True; `denoise_kw` are denoise_variance's keywords, and it returns what that returns."""
+        moments=True; `denoise_kw` are denoise_variance's keywords, and it returns what that returns.
+
+        upsample=s (1..8) gives a picture of s times the film's size, the film staying at its own: the resolved or denoised
+        colour, with gamma 1, goes through DeviceScene.upsample against the G-buffers of DeviceScene.upsample_guides for the
+        scene's camera as it stands (the film's current pose), and the gamma and the RGBA8 move to that call.  `upsample_kw`
+        are upsample's keywords and, as `guides`, the selection of guides; it returns what upsample() returns."""
+        if upsample is not None:
+            return self._resolve_upsampled(upsample, dict(upsample_kw or {}), denoise, gamma, rgba8, stream, context, denoise_kw)
+        if upsample_kw:
+            raise ValueError("upsample_kw: only with upsample")
         color = self.color
         kw = dict(denoise_kw)
         if isinstance(denoise, str):
@@ -154,3 +163,18 @@ class Film:
         else:
             kw["iterations"] = 0
         return self.scene.denoise(color, gamma=self._gamma if gamma is None else gamma, rgba8=rgba8, stream=stream, context=context, **kw)
+
+    def _resolve_upsampled(self, scale, ukw, denoise, gamma, rgba8, stream, context, denoise_kw):
+        if "gamma" in ukw or "rgba8" in ukw or "low" in ukw or "high" in ukw:
+            raise ValueError("upsample_kw: gamma and rgba8 are resolve's own, and the guides come from `guides`")
+        if "out" in denoise_kw or "variance_out" in denoise_kw:
+            raise ValueError("upsample: the denoised film is an intermediate, its outputs are not the caller's")
+        color = self.color
+        if denoise:
+            color = self.resolve(denoise=denoise, gamma=1.0, stream=stream, context=context, **denoise_kw)
+        guides = ukw.pop("guides", ("albedo", "normal", "point", "id"))
+        low, high = self.scene.upsample_guides(self.width * scale, self.height * scale, scale, guides=guides, stream=stream, context=context)
+        if "point" in low and ukw.get("sigma_plane") is None:
+            ukw["sigma_plane"] = 0.1
+        return self.scene.upsample(color, scale, low=low, high=high, gamma=self._gamma if gamma is None else gamma, rgba8=rgba8,
+                                   stream=stream, context=context, **ukw)

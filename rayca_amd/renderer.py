@@ -527,6 +527,128 @@ class DeviceScene:
         result = (out,) + ((out8,) if out8 is not None else ()) + ((var_out,) if var_out is not None else ()) + ((st.as_dict(),) if st is not None else ())
         return result[0] if len(result) == 1 else result
 
+    # ---- guided upsampling: a low-resolution frame onto a full-size G-buffer (rayca_hip_upsample_device) ----
+    # guide -> (dtype, channels, the keys of a gbuffer() dict it is taken from, the first one present)
+    UPSAMPLE_GUIDES = {"albedo": ("float32", 4, ("albedo", "color")), "normal": ("float32", 3, ("normal",)),
+                       "point": ("float32", 3, ("point",)), "id": ("int32", 0, ("id", "material"))}
+
+    def upsample(self, color, scale, *, low=None, high=None, sigma_plane=None, normal_power_log2=7, gamma=1.0, out=None, rgba8=False,
+                 weight=False, stream=None, context=0, want_stats=False):
+        """rayca_hip_upsample_device: a joint bilateral upsample, asynchronously, everything in device memory.
+
+        color (h, w, 4) float32: a frame rendered with gamma 1 at 1 / scale of the output's size (scale 1..8); the output is
+        (h * scale, w * scale, 4).  `low` and `high`: dicts as gbuffer() returns them for the low and the full-size view of one
+        camera (of a one-sample config).  The keys used are "albedo" (or "color"), "normal", "point" and "id" (or "material");
+        a guide is used where both dicts hold it, and a guide in one dict alone is an error.  With the albedo the taps are
+        divided by max(albedo, 1e-3) at low resolution and the result is multiplied with the full-size one, so textures come
+        from the full-size surface data; normal, point (needs normal and a sigma_plane > 0, in world units) and id weigh the
+        four taps of the bilinear footprint as denoise() weighs its taps.  A pixel none of whose taps agrees with its surface
+        falls back to plain bilinear; weight=True adds the guided weight sum as an (H, W) float32 tensor, 0 at those pixels
+        (or pass the tensor to write).  `gamma`, `out`, `rgba8`, the stream handling and the return convention are
+        denoise()'s; no output may be an input.  Returns the float tensor, or a tuple with the uint8 tensor, the weight and the
+        stats dict (`want_stats` waits) behind it, each when asked for."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (h, w, 4)")
+        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8:
+            raise ValueError(f"scale: an integer 1..8, not {scale!r}")
+        h, w = color.shape[:2]
+        big_h, big_w = h * scale, w * scale
+        low, high = dict(low or {}), dict(high or {})
+        temporaries = []
+
+        def contiguous(x):
+            if x.is_contiguous():
+                return x
+            x = x.contiguous()
+            temporaries.append(x)
+            return x
+
+        def output(x, name, dtype, shape):
+            if x is None or x is True:
+                return torch.empty(shape, dtype=dtype, device=dev)
+            if not checked(x, name, dtype, shape).is_contiguous():
+                raise ValueError(f"{name}: an output must be contiguous")
+            return x
+
+        u = abi.RaycaUpsample()
+        u.width, u.height, u.scale, u.normal_power_log2 = big_w, big_h, scale, normal_power_log2
+        u.sigma_plane, u.gamma = (sigma_plane if sigma_plane is not None else 0.0), gamma
+        out = output(out, "out", torch.float32, (big_h, big_w, 4))
+        out8 = output(rgba8, "rgba8", torch.uint8, (big_h, big_w, 4)) if rgba8 is not None and rgba8 is not False else None
+        weight_out = output(weight, "weight", torch.float32, (big_h, big_w)) if weight is not None and weight is not False else None
+        u.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
+        for guide, (dtype, channels, keys) in self.UPSAMPLE_GUIDES.items():
+            found = [next((d[k] for k in keys if d.get(k) is not None), None) for d in (low, high)]
+            if (found[0] is None) != (found[1] is None):
+                raise ValueError(f"{guide}: in `low` and in `high`, or in neither")
+            if found[0] is None:
+                continue
+            if guide == "point" and sigma_plane is None:
+                raise ValueError("sigma_plane: needed with point")
+            for x, where, field, (gh, gw) in ((found[0], "low", guide + "_low", (h, w)), (found[1], "high", guide, (big_h, big_w))):
+                shape = (gh, gw, channels) if channels else (gh, gw)
+                setattr(u, field, contiguous(checked(x, f"{where}[{guide!r}]", getattr(torch, dtype), shape)).data_ptr())
+        u.rgba32f_out = out.data_ptr()
+        if out8 is not None:
+            u.rgba8_out = out8.data_ptr()
+        if weight_out is not None:
+            u.weight_out = weight_out.data_ptr()
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_upsample_device(self.handle, C.byref(o), C.byref(u), C.byref(st) if st is not None else None))
+        record(temporaries)
+        result = (out,) + ((out8,) if out8 is not None else ()) + ((weight_out,) if weight_out is not None else ()) + ((st.as_dict(),) if st is not None else ())
+        return result[0] if len(result) == 1 else result
+
+    def upsample_guides(self, width: int, height: int, scale: int, *, guides=("albedo", "normal", "point", "id"), stream=None, context=0):
+        """The two G-buffers upsample() takes, (low, high): gbuffer() of a one-sample config at width / scale x height / scale and
+        at width x height for the guides asked for (albedo = the surface's color, id = its material), on one stream."""
+        guides = tuple(guides)
+        unknown = [g for g in guides if g not in self.DENOISE_GUIDES]
+        if unknown or len(set(guides)) != len(guides):
+            raise ValueError(f"guides: a selection without repeats of {tuple(self.DENOISE_GUIDES)}, not {guides!r}")
+        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8 or width % scale or height % scale:
+            raise ValueError(f"scale: an integer 1..8 that divides width and height, not {scale!r} for {width} x {height}")
+        if not guides:
+            return {}, {}
+        one = Config(samples_per_pixel=1)   # (points on the rays through pixel centres)
+        want = tuple(self.DENOISE_GUIDES[k] for k in guides)
+        return tuple({k: g[self.DENOISE_GUIDES[k]] for k in guides}
+                     for g in (self.gbuffer(one, width // scale, height // scale, want=want, stream=stream, context=context),
+                               self.gbuffer(one, width, height, want=want, stream=stream, context=context)))
+
+    def render_upsampled(self, config: Config, width: int, height: int, scale: int = 2, *, guides=("albedo", "normal", "point", "id"),
+                         denoise=False, stream=None, context=0, **upsample_kw):
+        """A width x height picture whose lighting is traced at width / scale x height / scale, on one stream, nothing waited
+        for in between: render_device of the low view with gamma forced to 1, upsample_guides() for the guides asked for,
+        with `denoise` (True, or a dict of denoise()'s keywords) the a-trous filter on the low frame with its low guides and
+        gamma 1, then upsample(..., gamma=config.gamma).  Returns what upsample() returns; `upsample_kw` are its keywords (with
+        the "point" guide sigma_plane defaults to 0.1 world units -- a starting value like the denoiser's)."""
+        import dataclasses
+        torch, dev, handle, _, _ = self._torch_call(stream)
+        if "gamma" in upsample_kw or "low" in upsample_kw or "high" in upsample_kw:
+            raise ValueError("gamma comes from config, and the guides from `guides`")
+        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8 or width % scale or height % scale:
+            raise ValueError(f"scale: an integer 1..8 that divides width and height, not {scale!r} for {width} x {height}")
+        w, h = width // scale, height // scale
+        color = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        self.render_device(dataclasses.replace(config, gamma=1.0), w, h, 0, color.data_ptr(), stream=handle or None, context=context)
+        low, high = self.upsample_guides(width, height, scale, guides=guides, stream=stream, context=context)
+        kw = dict(upsample_kw)
+        if "point" in low and kw.get("sigma_plane") is None:
+            kw["sigma_plane"] = 0.1
+        if denoise:
+            dkw = dict(denoise) if isinstance(denoise, dict) else {}
+            if "gamma" in dkw or "out" in dkw or "rgba8" in dkw:
+                raise ValueError("denoise: the low frame is filtered in place with gamma 1; gamma and the RGBA8 belong to the upsample")
+            if "point" in low and dkw.get("sigma_plane") is None:
+                dkw["sigma_plane"] = kw["sigma_plane"]
+            self.denoise(color, gamma=1.0, out=color, stream=stream, context=context, **low, **dkw)
+        return self.upsample(color, scale, low=low, high=high, gamma=config.gamma, stream=stream, context=context, **kw)
+
 
     # ---- temporal accumulation: a frame into a history, with reprojection (rayca_hip_scene_camera, rayca_hip_accumulate_device) ----
     def camera_pose(self) -> abi.RaycaCameraPose:
