@@ -134,7 +134,13 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
             in_shadow = true;  // enter the NEE loop (possibly empty)
             if (PARK) {
               park_ctx(ctx_slot, cx);
-              ctx_slot[6 * kBlock] = as_f4(black());
+              // (black(), made here from a zero the compiler cannot hoist: as a loop-invariant float4 it sat in four registers over
+              // the whole batch loop, which the counting instantiations could only afford through scratch: with the pipelined node
+              // loop k_generation<1, true, true, false, true, SPH, false, false, true, HALF> went from 0-2 to 4 spilled VGPRs and
+              // k_generation<1, true, false, false, FAST, *, false, true, true, false> from 0-4 to 2-5 -- tests/kernel_resources.py)
+              float zero = 0.0f;
+              asm volatile("" : "+v"(zero));
+              ctx_slot[6 * kBlock] = make_float4(zero, zero, zero, 1.0f);
             }
           }
         }

@@ -357,8 +357,10 @@ struct NodeStack {
   uint32_t* ovf;       // wave-uniform base of the spill area (a per-lane pointer would be two more registers in every loop)
   uint32_t gthread;    // this lane's column in it
   uint32_t lds_entries, ovf_stride, sp;
-  // the newest entry lives in a register: a pop hands it out at once and fetches its successor from LDS behind
-  // the node load that follows, instead of in front of it (-3 % on 5-deep paths, neutral on camera rays)
+  // the newest entry lives in a register: a pop hands it out at once (-3 % on 5-deep paths, neutral on camera rays).  Its
+  // successor comes from LDS: pop() waits for it on the spot (the compiled form reads into a temporary, waits and moves), the
+  // pipelined node loop of trace_search reads it INTO this register (book / pop_late below), and the wait stands at the next use
+  // of `top`, behind the loads of the node that follows.
   uint32_t top;
   __device__ __forceinline__ void clear() { sp = 0; top = kTerminated; }
   // RAYCA_STACK_AS: the two homes of an entry are addressed in their own address spaces.  Through generic pointers the
@@ -396,6 +398,53 @@ struct NodeStack {
     const uint32_t r = top;
     if (sp == 0) top = kTerminated;
     else top = get(--sp);
+    return r;
+  }
+  // ---- the stack operations of the pipelined node loop (trace_search) ----
+  // One operation of the lanes that take part, as straight-line code: `wr` lanes store `top` as entry `at`, `rd` lanes fetch
+  // entry `at` into `top`; in the other lanes `top` stays (`keep`) or becomes `v` (no lane does both; the callers move sp).
+  // Each is one LDS instruction under one exec mask, and nothing waits for the read here.  The spill area (entries >=
+  // lds_entries) is one block out of line, entered when some lane of the wave stands at or above the boundary at all
+  // (`at` <= sp): it serves the lanes whose entry lies beyond it and takes them out of the two masks.
+  // (Always through the address-space pointers: RAYCA_STACK_AS=0 only concerns put / get, i.e. every loop but the pipelined one.
+  // That `top` is made in place rests on the empty asm below; it costs speed, never a result, if a compiler decides otherwise --
+  // profiles/r06_node_loop_after.txt records the compiled form.)
+  __device__ __forceinline__ void transfer(bool wr, bool rd, uint32_t at, bool keep, uint32_t v, uint32_t& out) {
+    if (SPILL && __ballot(sp >= lds_entries) != 0ull) {
+      const bool deep = at >= lds_entries;
+      GlobalWord* const g = (GlobalWord*)ovf + ((size_t)(at - lds_entries) * ovf_stride + gthread);
+      if (wr && deep) *g = top;
+      if (rd && deep) {
+        v = *g;
+        asm volatile("" : "+v"(v));   // (no instruction: the wait for this load stands here, in the cold block, not where the paths join)
+        keep = false;
+      }
+      wr = wr && !deep;
+      rd = rd && !deep;
+    }
+    if (wr) ((LdsWord*)lds)[at * kBlock] = top;
+    // (no instruction: `out`, what the caller hands on of the old `top`, is made in front of this point and the new `top` behind
+    // it, in the old one's register.  Left to itself the compiler makes the new value beside the old one, which it reads last:
+    // the read below then lands in a second register, and a wait for it and a move back stand in front of the next node's loads)
+    asm volatile("" : "+v"(top), "+v"(out));
+    top = keep ? top : v;
+    if (rd) top = ((const LdsWord*)lds)[at * kBlock];
+  }
+  // the binary step's bookkeeping, `cur` = none ? top : nearer child already made (and the next node's loads issued with it):
+  // both children hit -> `far` becomes the newest entry and the one before it is stored; none -> the successor of the entry
+  // handed out is fetched; one hit -> nothing moves
+  __device__ __forceinline__ void book(bool both, bool none, uint32_t far, uint32_t& cur) {
+    const bool wr = both && top != kTerminated, rd = none && sp != 0u;
+    const uint32_t at = rd ? sp - 1u : sp;
+    transfer(wr, rd, at, !(both || none), both ? far : kTerminated, cur);
+    sp = wr ? sp + 1u : at;
+  }
+  // pop() for the lanes with `take`; the others keep their stack and get kTerminated (an any-hit ray that has found its occluder)
+  __device__ __forceinline__ uint32_t pop_late(bool take) {
+    uint32_t r = take ? top : kTerminated;
+    const bool rd = take && sp != 0u;
+    sp -= rd ? 1u : 0u;
+    transfer(false, rd, sp, !take, kTerminated, r);
     return r;
   }
 };
@@ -634,6 +683,46 @@ __device__ __forceinline__ bool trace_search(const DevScene& sc, const DRay& r, 
       cur = (any_hit && hit.t < t_stop) ? kTerminated : st.pop();
     }
     if (__ballot(cur != kTerminated) == 0ull) break;
+  }
+  } else if constexpr (ORDERED && FAST && !WIDE && !HALF && RAYCA_NODE_CH && RAYCA_NODE_CH48) {
+  // The node loop of the 48-B centre / half records, pipelined: node_step's box tests, then the decision as selects -- next
+  // node = none ? newest stack entry : nearer child -- the next node's three loads issued AT ONCE, and only then the stack's
+  // bookkeeping (NodeStack::book: one LDS write, one LDS read, each under one exec mask), which runs under those loads; the
+  // pop's read lands in `top` itself and is waited for at the next decision, a node's worth of arithmetic later.  The same
+  // decisions on the same operands as node_step (strict `tl <= tr`: left first on a tie): the same nodes and triangles in the
+  // same order.  Measured (atrium depth-1 frame, four in flight; profiles/r06_ab_node_step.log): 0.3020 -> 0.2957 ms.  The
+  // decision as selects WITHOUT the early loads (node_step's if / else-if chain replaced, loads at the loop's top as before)
+  // is 5 % SLOWER than the chain: a coherent wave skips the chain's arms that no lane takes, the selects run on every step.
+  while (cur != kTerminated) {
+    if (!(cur & kLeafFlag)) {
+      const float4* np = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sc.nodes_ch) + cur);
+      float4 q0 = np[0], q1 = np[1], q2 = np[2];
+      bool more;
+      do {
+        if (STATS && cnt.books()) cnt.slot_boxes += 128ull;
+        float tl, tr;
+        bool hl = slab_ch<SLACK>(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, fr, tl);
+        bool hr = slab_ch<SLACK>(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, fr, tr);
+        const uint32_t lref = __builtin_amdgcn_perm(__float_as_uint(q1.x), __float_as_uint(q0.w), 0x05040100u);   // (as in node_step)
+        const uint32_t rref = __builtin_amdgcn_perm(__float_as_uint(q2.z), __float_as_uint(q2.y), 0x05040100u);
+        if (STATS) cnt.boxes += 2;
+        hl = hl && tl <= limit;
+        hr = hr && tr <= limit;
+        const bool left_first = tl <= tr;
+        const bool both = hl && hr, none = !(hl || hr);
+        cur = none ? st.top : ((hl && (left_first || !hr)) ? lref : rref);
+        more = !(cur & kLeafFlag) && cur != kTerminated;
+        if (more) {
+          const float4* nn = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sc.nodes_ch) + cur);
+          q0 = nn[0]; q1 = nn[1]; q2 = nn[2];
+        }
+        st.book(both, none, left_first ? rref : lref, cur);
+      } while (more);
+    }
+    if (cur != kTerminated) {  // a leaf
+      test_leaf<ORDERED, SPH, STATS, SLACK>(sc, r, fr, cur, t_stop, hit, limit, cnt);
+      cur = st.pop_late(!(any_hit && hit.t < t_stop));   // (kTerminated ends the search of an any-hit ray)
+    }
   }
   } else {
   while (cur != kTerminated) {
