@@ -44,7 +44,8 @@ extern "C" {
                                   temporal accumulation: RaycaCameraPose, rayca_hip_scene_camera, RaycaAccumulate,
                                   rayca_hip_accumulate_device; the variance-guided denoiser: RaycaDenoiseVariance,
                                   rayca_hip_denoise_variance_device; guided upsampling: RaycaUpsample,
-                                  rayca_hip_upsample_device */
+                                  rayca_hip_upsample_device; exposure metering and tone mapping: RaycaMeter,
+                                  rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_ */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -981,6 +982,94 @@ struct RaycaUpsample {
 };
 typedef struct RaycaUpsample RaycaUpsample;
 int32_t rayca_hip_upsample_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaUpsample* u, RaycaStats* stats_out);
+
+/* Exposure metering: how bright a frame is, measured in DEVICE memory -- a luminance histogram of a linear frame and, from it, an
+ * exposure record that rayca_hip_tonemap_device reads where it lies.  `color` is a frame with gamma 1 (render_device's float
+ * output, a film, a denoised or upsampled frame).  No reference counterpart.  The scene handle gives the call its device and its
+ * frame context; the scene is not read.
+ * Only +, -, x, /, min, max and integer arithmetic, every f32 operation rounded once in the association written here; every
+ * comparison is written so that a NaN fails it.  Everything behind Y is integer arithmetic, so the order in which the pixels
+ * are counted changes no bit, and a literal restatement (tests/tonemap_literal.py) gives the same words.
+ *   histogram  per pixel (r, g, b, a): Y = (0.2126f r + 0.7152f g) + 0.0722f b
+ *              not finite: r, g, b or Y fails x - x == 0.  black: finite and Y <= 0 (a miss of the scene is black).  Any other
+ *              pixel is counted, in bin clamp((int)(bits(Y) >> 20) - ((127 - 16) << 3), 0, 255): the float's own exponent and its
+ *              top three mantissa bits -- 8 bins an octave over 2^-16 .. 2^16, linear inside an octave; below and above, the
+ *              first and the last bin.
+ *              hist_out[0..255] the bins, [256] counted, [257] black, [258] not finite, [259] 0.  The call overwrites all 260.
+ *   exposure   (with exposure_out) from this call's histogram, in u64 with floor:
+ *              N = counted, a = N * low_permille / 1000, b = N * high_permille / 1000
+ *              over the bins in order, c0 / c1 the running count before / after bin i: k_i = max(0, min(c1, b) - max(c0, a))
+ *              K = sum k_i, T = sum k_i * (2 i + 1), Q = (T << 12) / K          (T << 12 < 2^53)
+ *              L = (1 + (float)(Q & 0xffff) / 65536) * 2^((Q >> 16) - 16)      -- both steps exact: the inverse of the bins'
+ *                                                                                 piecewise-linear logarithm at the trimmed mean
+ *              target = min(max(key / L, min_scale), max_scale)
+ *              p = exposure_prev[0] is usable iff exposure_prev is given, p > 0 and p - p == 0
+ *              K == 0 (nothing counted): L = 0, target = p if usable, else 1
+ *              scale = p + (target - p) * rate if p is usable, else target
+ *              exposure_out = {scale, target, L, 0}
+ *              `rate` is the caller's adaptation factor (for instance 1 - exp(-dt * speed), formed by the caller); 1 jumps.
+ * exposure_prev may be exposure_out (the record is read before it is written); hist_out must differ from every other pointer,
+ * and exposure_out from color: equal pointers are RAYCA_ERR_BAD_ARG, any other overlap is undefined.
+ * opts, ordering, stats_out: as for rayca_hip_upsample_device (every field but stream, context, wait_event and record_event
+ * zero, tile included); launches: the clear, the histogram kernel and, with exposure_out, the one-wave exposure kernel.
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments / color / hist_out, width or
+ * height 0, width x height > 2^32 - 1, not 0 <= low_permille < high_permille <= 1000, key not > 0, min_scale or max_scale not
+ * finite or not 0 < min_scale <= max_scale, rate not in (0, 1], non-zero reserved, a misaligned pointer (color and exposure_out
+ * 16 bytes, hist_out and exposure_prev 4), equal pointers as above, context > 7, a non-zero field of opts that does not apply.
+ * RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles number 2^24 or more (as the passes that would display it). */
+struct RaycaMeter {
+  uint32_t width, height;        /* the whole frame, W x H */
+  uint32_t low_permille;         /* the trimmed mean leaves out this share of the counted pixels at the dark end ... */
+  uint32_t high_permille;        /* ... and everything above this share: 0 <= low < high <= 1000 */
+  float key;                     /* > 0: the luminance the metered one is mapped to (0.18: middle grey) */
+  float min_scale, max_scale;    /* finite, 0 < min_scale <= max_scale: the target is clamped between them */
+  float rate;                    /* in (0, 1]: how far the scale moves from exposure_prev's towards the target */
+  uint32_t reserved;             /* must be zero */
+  const void* color;             /* DEVICE H x W x 4 f32, required, gamma 1 */
+  void* hist_out;                /* DEVICE 260 u32, required; overwritten (the caller never clears it) */
+  void* exposure_out;            /* DEVICE 4 f32 or NULL: {scale, target, L, 0} */
+  const void* exposure_prev;     /* DEVICE 4 f32 or NULL: the previous record; may be exposure_out */
+};
+typedef struct RaycaMeter RaycaMeter;
+int32_t rayca_hip_meter_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaMeter* m, RaycaStats* stats_out);
+
+/* Tone mapping: a linear frame through an exposure scale and a display operator into the output stage, one pixel-local pass in
+ * DEVICE memory.  The scale is word 0 of `exposure` -- normally the record rayca_hip_meter_device wrote, so that nothing returns
+ * to the host -- or, without it, the host's `scale`.  No reference counterpart; the scene is not read.
+ * Arithmetic as above (+, -, x, / only, one rounding each, the association written here).  Per pixel c, s the scale,
+ * x.k = c.k * s for k in r, g, b:
+ *   RAYCA_TONEMAP_LINEAR    o = x
+ *   RAYCA_TONEMAP_REINHARD  (extended, on luminance) Y = (0.2126f x.r + 0.7152f x.g) + 0.0722f x.b; where Y > 0:
+ *                           m = (1 + Y * inv_white2) / (1 + Y), o.k = x.k * m; elsewhere o = x.  inv_white2 = 1 / (white * white),
+ *                           formed on the host as the denoiser forms its reciprocals, 0 when white is 0 (no white point)
+ *   RAYCA_TONEMAP_ACES      (the rational fit) per channel o.k = (x.k * (2.51f * x.k + 0.03f)) / (x.k * (2.43f * x.k + 0.59f) + 0.14f)
+ *                           (the denominator has no real root)
+ * Alpha passes through; a channel that is not finite comes out as the arithmetic has it.  Then the output stage of
+ * rayca_hip_denoise_device exactly: gamma != 1: powf(o, 1 / gamma) on r, g, b; rgba32f_out, and rgba8_out quantised and packed as
+ * a frame's.
+ * rgba32f_out may be `color` (a lane reads its pixel before it writes it).  Every other pair of equal pointers among color,
+ * exposure and the outputs is RAYCA_ERR_BAD_ARG; any other overlap is undefined.
+ * opts, ordering, stats_out: as for rayca_hip_upsample_device; one launch.
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments / color, width or height 0,
+ * width x height > 2^32 - 1, an unknown op, exposure NULL and scale not finite or not > 0, white negative or not finite, white
+ * set with an op other than REINHARD, gamma not > 0, no output, non-zero reserved, a misaligned pointer (color and rgba32f_out 16
+ * bytes, exposure and rgba8_out 4), equal pointers as above, context > 7, a non-zero field of opts that does not apply.
+ * RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles number 2^24 or more. */
+enum { RAYCA_TONEMAP_LINEAR = 0, RAYCA_TONEMAP_REINHARD = 1, RAYCA_TONEMAP_ACES = 2 };
+struct RaycaTonemap {
+  uint32_t width, height;        /* the whole frame, W x H */
+  uint32_t op;                   /* RAYCA_TONEMAP_ */
+  float scale;                   /* used when `exposure` is NULL: finite and > 0 */
+  float white;                   /* REINHARD's white point: 0 = none, else finite and > 0; must be 0 for the other operators */
+  float gamma;                   /* > 0; applied to the colour outputs exactly as a render call applies RaycaConfig.gamma */
+  uint32_t reserved;             /* must be zero */
+  const void* color;             /* DEVICE H x W x 4 f32, required, gamma 1 */
+  const void* exposure;          /* DEVICE 4 f32 or NULL: word 0 is the scale (rayca_hip_meter_device's exposure_out) */
+  void* rgba32f_out;             /* DEVICE H x W x 4 f32 or NULL; may be the same pointer as `color` */
+  void* rgba8_out;               /* DEVICE H x W x 4 u8 or NULL; not both outputs NULL */
+};
+typedef struct RaycaTonemap RaycaTonemap;
+int32_t rayca_hip_tonemap_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaTonemap* t, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

@@ -73,6 +73,10 @@ pub const RAYCA_KERNEL_CLASSES: u32 = 8;
 // RaycaQuery.kind
 pub const RAYCA_QUERY_CLOSEST: u32 = 0;
 pub const RAYCA_QUERY_OCCLUDED: u32 = 1;
+// RaycaTonemap.op
+pub const RAYCA_TONEMAP_LINEAR: u32 = 0;
+pub const RAYCA_TONEMAP_REINHARD: u32 = 1;
+pub const RAYCA_TONEMAP_ACES: u32 = 2;
 pub const RAYCA_GATHER_RCCL: u32 = 0;
 pub const RAYCA_GATHER_PEER_COPY: u32 = 1;
 // rayca_hip_renderer_draw: what a draw did, and the indices of rayca_hip_renderer_last_draw's ms_out / counters_out
@@ -432,6 +436,42 @@ pub struct RaycaUpsample {
     pub weight_out: *mut c_void,
 }
 
+// rayca_hip_meter_device: the luminance histogram of a linear frame and the exposure record made from it, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaMeter {
+    pub width: u32,
+    pub height: u32,
+    pub low_permille: u32,
+    pub high_permille: u32,
+    pub key: f32,
+    pub min_scale: f32,
+    pub max_scale: f32,
+    pub rate: f32,
+    pub reserved: u32,
+    pub color: *const c_void,
+    pub hist_out: *mut c_void,
+    pub exposure_out: *mut c_void,
+    pub exposure_prev: *const c_void,
+}
+
+// rayca_hip_tonemap_device: exposure scale, display operator (RAYCA_TONEMAP_) and the output stage, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaTonemap {
+    pub width: u32,
+    pub height: u32,
+    pub op: u32,
+    pub scale: f32,
+    pub white: f32,
+    pub gamma: f32,
+    pub reserved: u32,
+    pub color: *const c_void,
+    pub exposure: *const c_void,
+    pub rgba32f_out: *mut c_void,
+    pub rgba8_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -514,6 +554,8 @@ extern "C" {
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_variance_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoiseVariance, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_upsample_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, u: *const RaycaUpsample, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_meter_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, m: *const RaycaMeter, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_tonemap_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, t: *const RaycaTonemap, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

@@ -43,6 +43,9 @@ KERNEL_GENERATION, KERNEL_FLAT_REFILL, KERNEL_WF_TRACE, KERNEL_QUEUE_REFILL, KER
 KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill", "k_wf_shade", "k_wf_shadow", "k_shadow_refill", "other")
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # RaycaQuery.kind
+TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
+TONEMAP_NAMES = ("linear", "reinhard", "aces")
+METER_WORDS, METER_COUNTED, METER_BLACK, METER_NOT_FINITE = 260, 256, 257, 258   # hist_out of rayca_hip_meter_device
 # the resident draw (rayca_hip_renderer_draw): what it did, and the indices of rayca_hip_renderer_last_draw's two arrays
 DRAW_REUSED, DRAW_UPDATED, DRAW_REBUILT = 0, 1, 2
 DRAW_NAMES = ("reused", "updated", "rebuilt")
@@ -431,6 +434,42 @@ class RaycaUpsample(C.Structure):
     ]
 
 
+class RaycaMeter(C.Structure):
+    """rayca_hip_meter_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("low_permille", C.c_uint32),
+        ("high_permille", C.c_uint32),
+        ("key", C.c_float),
+        ("min_scale", C.c_float),
+        ("max_scale", C.c_float),
+        ("rate", C.c_float),
+        ("reserved", C.c_uint32),
+        ("color", C.c_void_p),
+        ("hist_out", C.c_void_p),
+        ("exposure_out", C.c_void_p),
+        ("exposure_prev", C.c_void_p),
+    ]
+
+
+class RaycaTonemap(C.Structure):
+    """rayca_hip_tonemap_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("op", C.c_uint32),
+        ("scale", C.c_float),
+        ("white", C.c_float),
+        ("gamma", C.c_float),
+        ("reserved", C.c_uint32),
+        ("color", C.c_void_p),
+        ("exposure", C.c_void_p),
+        ("rgba32f_out", C.c_void_p),
+        ("rgba8_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -563,6 +602,10 @@ def bind_product_signatures(lib):
     lib.rayca_hip_denoise_variance_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoiseVariance), P(RaycaStats)]
     lib.rayca_hip_upsample_device.restype = C.c_int32
     lib.rayca_hip_upsample_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaUpsample), P(RaycaStats)]
+    lib.rayca_hip_meter_device.restype = C.c_int32
+    lib.rayca_hip_meter_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaMeter), P(RaycaStats)]
+    lib.rayca_hip_tonemap_device.restype = C.c_int32
+    lib.rayca_hip_tonemap_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaTonemap), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -586,6 +629,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
+    "rayca_hip_meter_device", "rayca_hip_tonemap_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

@@ -2593,4 +2593,125 @@ int32_t rayca_hip_upsample_device(RaycaScene* s, const RaycaRenderOptions* opts_
   return pass_finish(pass, 1, stats_out);
 }
 
+namespace {
+// what the two display passes check alike: the frame's size and the tile count of the passes that display it
+int32_t display_frame_size(uint32_t width, uint32_t height, const char* type, uint32_t* tiles_x_out, uint64_t* tiles_out) {
+  if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, std::string("empty image (") + type + ".width, height)");
+  if ((uint64_t)width * height > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, std::string("more than 2^32 - 1 pixels (") + type + ".width x height)");
+  *tiles_x_out = (uint32_t)(((uint64_t)width + kDenoiseTileW - 1u) / kDenoiseTileW);
+  *tiles_out = (uint64_t)*tiles_x_out * (((uint64_t)height + kDenoiseTileH - 1u) / kDenoiseTileH);
+  if (*tiles_out * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
+  return RAYCA_OK;
+}
+bool finite_f32(float x) { return x - x == 0.0f; }
+
+// k_tonemap for an operator and the outputs that are present: [op][rgba32f][rgba8]
+using TonemapKernel = void (*)(TonemapIo);
+TonemapKernel pick_tonemap_kernel(uint32_t op, bool f32, bool u8) {
+#define RAYCA_TONEMAP(OP) {{nullptr, k_tonemap<OP, false, true>}, {k_tonemap<OP, true, false>, k_tonemap<OP, true, true>}}
+  static const TonemapKernel table[3][2][2] = {RAYCA_TONEMAP(kTonemapLinear), RAYCA_TONEMAP(kTonemapReinhard), RAYCA_TONEMAP(kTonemapAces)};
+#undef RAYCA_TONEMAP
+  return table[op][f32 ? 1 : 0][u8 ? 1 : 0];
+}
+}  // namespace
+
+// Exposure metering (tonemap.inc): the clear of hist_out, k_meter_hist under a capped grid and, with exposure_out, the one-wave
+// k_exposure, each behind the other on the pass's stream.  The scene handle gives the device and the frame context; the scene
+// is not read.  Every check stands in front of any GPU work, the options' last.
+int32_t rayca_hip_meter_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaMeter* m_in, RaycaStats* stats_out) {
+  if (!s || !m_in) return fail(RAYCA_ERR_BAD_ARG, "null scene or meter arguments");
+  const RaycaMeter& m = *m_in;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (m.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaMeter.reserved must be zero");
+  uint32_t tiles_x = 0;
+  uint64_t tiles = 0;
+  int32_t rc = display_frame_size(m.width, m.height, "RaycaMeter", &tiles_x, &tiles);
+  if (rc != RAYCA_OK) return rc;
+  if (!m.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!m.hist_out) return fail(RAYCA_ERR_BAD_ARG, "null hist_out");
+  if (!(m.low_permille < m.high_permille && m.high_permille <= 1000u)) return fail(RAYCA_ERR_BAD_ARG, "low_permille, high_permille: 0 <= low < high <= 1000");
+  if (!(m.key > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "key must be > 0");
+  if (!(finite_f32(m.min_scale) && m.min_scale > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "min_scale must be finite and > 0");
+  if (!(finite_f32(m.max_scale) && m.max_scale >= m.min_scale)) return fail(RAYCA_ERR_BAD_ARG, "max_scale must be finite and >= min_scale");
+  if (!(m.rate > 0.0f && m.rate <= 1.0f)) return fail(RAYCA_ERR_BAD_ARG, "rate must be in (0, 1]");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(m.color, 16) || misaligned(m.exposure_out, 16)) return fail(RAYCA_ERR_BAD_ARG, "alignment: color and exposure_out are read and written 16 bytes at a time");
+  if (misaligned(m.hist_out, 4) || misaligned(m.exposure_prev, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: hist_out and exposure_prev are read and written 4 bytes an element");
+  if (m.hist_out == m.color || m.hist_out == m.exposure_out || m.hist_out == m.exposure_prev || (m.exposure_out && m.exposure_out == m.color))
+    return fail(RAYCA_ERR_BAD_ARG, "aliasing: hist_out must differ from color, exposure_out and exposure_prev, and exposure_out from color");
+  if ((rc = pass_options(o, "a meter call, which measures a whole frame", 0u)) != RAYCA_OK) return rc;
+  const uint64_t count64 = (uint64_t)m.width * m.height;
+  MeterIo io{static_cast<const float4*>(m.color), static_cast<uint32_t*>(m.hist_out), (uint32_t)count64};
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((count64 + kMeterBlock - 1u) / kMeterBlock, kMeterMaxGrid);
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));   // (in front of the clear: it is part of what the call costs)
+  HIP_TRY(hipMemsetAsync(m.hist_out, 0, kMeterWords * sizeof(uint32_t), pass.stream));
+  uint32_t launches = 1;
+  hipLaunchKernelGGL(k_meter_hist, dim3(grid), dim3(kMeterBlock), 0, pass.stream, io);
+  HIP_TRY(hipGetLastError());
+  ++launches;
+  if (m.exposure_out) {
+    ExposureIo e{io.hist, static_cast<float*>(m.exposure_out), static_cast<const float*>(m.exposure_prev), m.low_permille, m.high_permille,
+                 m.key, m.min_scale, m.max_scale, m.rate};
+    hipLaunchKernelGGL(k_exposure, dim3(1), dim3(64), 0, pass.stream, e);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+  }
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, launches, stats_out);
+}
+
+// Tone mapping (tonemap.inc): one launch of k_tonemap, pixel-local, no scratch image.  Every check stands in front of any GPU
+// work, the options' last.
+int32_t rayca_hip_tonemap_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaTonemap* tin, RaycaStats* stats_out) {
+  if (!s || !tin) return fail(RAYCA_ERR_BAD_ARG, "null scene or tonemap arguments");
+  const RaycaTonemap& t = *tin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (t.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaTonemap.reserved must be zero");
+  uint32_t tiles_x = 0;
+  uint64_t tiles = 0;
+  int32_t rc = display_frame_size(t.width, t.height, "RaycaTonemap", &tiles_x, &tiles);
+  if (rc != RAYCA_OK) return rc;
+  if (!t.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!t.rgba32f_out && !t.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
+  if (t.op > RAYCA_TONEMAP_ACES) return fail(RAYCA_ERR_BAD_ARG, "unknown op");
+  if (!t.exposure && !(finite_f32(t.scale) && t.scale > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "scale must be finite and > 0 when exposure is not given");
+  if (!(finite_f32(t.white) && t.white >= 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "white must be 0 (no white point) or finite and > 0");
+  if (t.white != 0.0f && t.op != RAYCA_TONEMAP_REINHARD) return fail(RAYCA_ERR_BAD_ARG, "white belongs to RAYCA_TONEMAP_REINHARD: must be 0 for the other operators");
+  if (!(t.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
+  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
+  if (misaligned(t.color, 16) || misaligned(t.rgba32f_out, 16)) return fail(RAYCA_ERR_BAD_ARG, "alignment: color and rgba32f_out are read and written 16 bytes a pixel");
+  if (misaligned(t.exposure, 4) || misaligned(t.rgba8_out, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: exposure and rgba8_out are read and written 4 bytes an element");
+  if ((t.rgba8_out && (t.rgba8_out == t.color || t.rgba8_out == t.rgba32f_out || t.rgba8_out == t.exposure)) ||
+      (t.rgba32f_out && t.rgba32f_out == t.exposure) || (t.exposure && t.exposure == t.color))
+    return fail(RAYCA_ERR_BAD_ARG, "aliasing: rgba32f_out may be color; no other two of color, exposure, rgba32f_out and rgba8_out may be equal");
+  if ((rc = pass_options(o, "a tonemap call, which maps a whole frame", 0u)) != RAYCA_OK) return rc;
+  TonemapIo io{};
+  io.color = static_cast<const float4*>(t.color);
+  io.exposure = static_cast<const float*>(t.exposure);
+  io.rgba32f = static_cast<float4*>(t.rgba32f_out);
+  io.rgba8 = static_cast<uint8_t*>(t.rgba8_out);
+  io.width = t.width;
+  io.height = t.height;
+  io.tiles_x = tiles_x;
+  io.scale = t.scale;
+  io.inv_white2 = t.white != 0.0f ? 1.0f / (t.white * t.white) : 0.0f;
+  io.inv_gamma = 1.0f / t.gamma;   // (as a frame's: color/mod.rs:175-176)
+  const auto kernel = pick_tonemap_kernel(t.op, io.rgba32f != nullptr, io.rgba8 != nullptr);
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
+  HIP_TRY(hipGetLastError());
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, 1, stats_out);
+}
+
 }  // extern "C"

@@ -24,6 +24,9 @@
 //   k_atrous_var      filtered along with the colour (denoise_variance.inc: rayca_hip_denoise_variance_device).
 //   k_upsample        a low-resolution frame onto a full-size G-buffer: a joint bilateral upsample
 //                     (upsample.inc: rayca_hip_upsample_device).
+//   k_meter_hist,     exposure metering and tone mapping: a luminance histogram of a linear frame (LDS bins, integer atomics),
+//   k_exposure,       the exposure record made from it by one wave, and the display operator in front of the output stage
+//   k_tonemap         (tonemap.inc: rayca_hip_meter_device, rayca_hip_tonemap_device).
 //
 // No MFMA anywhere: there is no dense contraction in this path.  Built with -ffp-contract=off.
 #include "no_pk.hpp"   // RAYCA_NO_PK_F32: no packed f32 arithmetic in the traversal, leaf, shading and BRDF code
@@ -410,6 +413,7 @@ RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole 
 #include "denoise_variance.inc"
 #include "temporal.inc"
 #include "upsample.inc"
+#include "tonemap.inc"
 
 }  // namespace
 }  // namespace rayca

@@ -7,9 +7,11 @@ from __future__ import annotations
 
 import dataclasses
 
+from . import abi
 from .renderer import Config, DeviceScene
 
 GUIDES = ("point", "normal", "material")   # the G-buffer a frame leaves for the next one: surface outputs (id = the material)
+METER_KEYS = ("low_permille", "high_permille", "key", "min_scale", "max_scale", "rate")   # of tonemap_kw: DeviceScene.meter's, the others are tonemap's
 
 
 class Film:
@@ -24,6 +26,7 @@ class Film:
         self.scene, self.width, self.height = scene, width, height
         self.max_history, self.normal_min, self.plane_max, self.with_moments = max_history, normal_min, plane_max, bool(moments)
         self._buffers = None
+        self._meter = None     # the histogram and the two exposure records of resolve(exposure="auto"), made on first use
         self.reset()
 
     def reset(self) -> None:
@@ -34,6 +37,7 @@ class Film:
         self._gamma = 1.0
         self._hist = 0         # which of the two history sets holds the film
         self._gbuf = 0         # which of the two G-buffers belongs to it
+        self._exposure = None  # which of the two exposure records is the current one (None: nothing metered yet)
 
     def _allocate(self):
         import torch
@@ -126,7 +130,45 @@ class Film:
             raise ValueError("the film is empty: add() a frame first")
         return self._shaped(self._buffers["gbuf"][self._gbuf])
 
-    def resolve(self, *, denoise=False, gamma=None, rgba8=False, upsample=None, upsample_kw=None, stream=None, context=0, **denoise_kw):
+    @property
+    def exposure(self):
+        """(4,) float32 {scale, target, L, 0}: the record of the last resolve(exposure="auto") (DeviceScene.meter), None before the
+        first one and after reset()"""
+        return None if self._exposure is None else self._meter["exposure"][self._exposure]
+
+    def _resolve_tonemapped(self, op, exposure, tkw, denoise, gamma, rgba8, upsample, upsample_kw, stream, context, denoise_kw):
+        if "gamma" in tkw or "rgba8" in tkw or "exposure" in tkw or "scale" in tkw:
+            raise ValueError("tonemap_kw: gamma and rgba8 are resolve's own, and the scale comes from `exposure`")
+        if "out" in denoise_kw or "variance_out" in denoise_kw or "out" in (upsample_kw or {}):
+            raise ValueError("tonemap: the frame in front of it is an intermediate, its outputs are not the caller's (tonemap_kw['out'] is)")
+        if upsample is not None or denoise:
+            color = self.resolve(denoise=denoise, gamma=1.0, upsample=upsample, upsample_kw=upsample_kw, stream=stream, context=context, **denoise_kw)
+            if isinstance(color, tuple):   # (upsample_kw may ask for the weight: the colour comes first)
+                color = color[0]
+        else:
+            color = self.color
+        meter_kw = {k: tkw.pop(k) for k in METER_KEYS if k in tkw}
+        if exposure == "auto":
+            if self._meter is None:
+                import torch
+                dev = torch.device("cuda", self.scene.device)
+                self._meter = {"hist": torch.empty((abi.METER_WORDS,), dtype=torch.int32, device=dev),
+                               "exposure": tuple(torch.empty((4,), dtype=torch.float32, device=dev) for _ in range(2))}
+            prev = self.exposure
+            nxt = 0 if self._exposure is None else self._exposure ^ 1
+            self.scene.meter(color, prev=prev, out=(self._meter["hist"], self._meter["exposure"][nxt]), stream=stream, context=context, **meter_kw)
+            self._exposure = nxt
+            tkw["exposure"] = self.exposure
+        else:
+            if meter_kw:
+                raise ValueError(f"tonemap_kw: {sorted(meter_kw)} belong to exposure='auto'")
+            if isinstance(exposure, str):
+                raise ValueError(f"exposure: a float, None or 'auto', not {exposure!r}")
+            tkw["scale"] = 1.0 if exposure is None else float(exposure)
+        return self.scene.tonemap(color, op, gamma=self._gamma if gamma is None else gamma, rgba8=rgba8, stream=stream, context=context, **tkw)
+
+    def resolve(self, *, denoise=False, gamma=None, rgba8=False, upsample=None, upsample_kw=None, tonemap=None, exposure=None, tonemap_kw=None,
+                stream=None, context=0, **denoise_kw):
         """The film through DeviceScene.denoise: its output stage alone (iterations=0: gamma and the RGBA8 quantisation of a
         render call), or with denoise=True the a-trous filter in front of it, guided by the film's G-buffer (normal, point, id;
         sigma_plane defaults to 0.1).  gamma None is the gamma of the config last added.  Returns what denoise() returns: a new
@@ -139,7 +181,19 @@ class Film:
         upsample=s (1..8) gives a picture of s times the film's size, the film staying at its own: the resolved or denoised
         colour, with gamma 1, goes through DeviceScene.upsample against the G-buffers of DeviceScene.upsample_guides for the
         scene's camera as it stands (the film's current pose), and the gamma and the RGBA8 move to that call.  `upsample_kw`
-        are upsample's keywords and, as `guides`, the selection of guides; it returns what upsample() returns."""
+        are upsample's keywords and, as `guides`, the selection of guides; it returns what upsample() returns.
+
+        tonemap="linear", "reinhard" or "aces" puts DeviceScene.tonemap behind all of that: the resolved, denoised or upsampled
+        colour leaves its pass with gamma 1, and the gamma and the RGBA8 move to the tonemap call.  `exposure` is the scale as a
+        float (None: 1), or "auto": the film meters the colour it is about to map (DeviceScene.meter) and the operator reads the
+        record on the device.  The film keeps two records that change roles from resolve to resolve, the previous one being the
+        next call's `prev`, so that a `rate` below 1 adapts over the resolves; `exposure` (the property) is the current one,
+        reset() forgets it.  `tonemap_kw` are tonemap's keywords (white, out) and, with "auto", meter's (low_permille,
+        high_permille, key, min_scale, max_scale, rate); it returns what tonemap() returns."""
+        if tonemap is not None:
+            return self._resolve_tonemapped(tonemap, exposure, dict(tonemap_kw or {}), denoise, gamma, rgba8, upsample, upsample_kw, stream, context, denoise_kw)
+        if exposure is not None or tonemap_kw:
+            raise ValueError("exposure, tonemap_kw: only with tonemap")
         if upsample is not None:
             return self._resolve_upsampled(upsample, dict(upsample_kw or {}), denoise, gamma, rgba8, stream, context, denoise_kw)
         if upsample_kw:

@@ -649,6 +649,105 @@ class DeviceScene:
             self.denoise(color, gamma=1.0, out=color, stream=stream, context=context, **low, **dkw)
         return self.upsample(color, scale, low=low, high=high, gamma=config.gamma, stream=stream, context=context, **kw)
 
+    # ---- exposure metering and tone mapping: a linear frame to a displayable one (rayca_hip_meter_device, rayca_hip_tonemap_device) ----
+    def meter(self, color, *, low_permille=10, high_permille=990, key=0.18, min_scale=2.0 ** -10, max_scale=2.0 ** 10, rate=1.0, prev=None,
+              out=None, stream=None, context=0, want_stats=False):
+        """rayca_hip_meter_device: how bright a frame is, asynchronously, everything in device memory.
+
+        color (H, W, 4) float32, gamma 1.  Returns (hist, exposure): hist (260,) int32 -- 256 luminance bins (8 an octave over
+        2^-16 .. 2^16), then the counts of the counted, the black and the non-finite pixels, then 0 -- and exposure (4,)
+        float32 {scale, target, L, 0}: L the metered luminance (the mean, in the bins' logarithm, of the counted pixels between
+        the low_permille and the high_permille quantile), target = key / L clamped to [min_scale, max_scale], and scale the step
+        from prev[0] towards the target by `rate` (0 < rate <= 1: the caller's adaptation factor, for instance
+        1 - exp(-dt * speed)); without a usable `prev` (None, or a record whose scale is not positive and finite) the scale is
+        the target.  `prev`: a (4,) float32 tensor as this call returns one.  `out`: (hist, exposure) tensors to write instead
+        of new ones; exposure may be `prev` itself.  tonemap(exposure=) reads the record where it lies.  Stream handling as
+        query(); with `want_stats` (which waits) the stats dict comes third."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        h, w = color.shape[:2]
+        hist, exposure = out if out is not None else (None, None)
+        for x, name, dtype, shape in ((hist, "out[0]", torch.int32, (abi.METER_WORDS,)), (exposure, "out[1]", torch.float32, (4,)),
+                                      (prev, "prev", torch.float32, (4,))):
+            if x is not None and not checked(x, name, dtype, shape).is_contiguous():
+                raise ValueError(f"{name}: must be contiguous")
+        if hist is None:
+            hist = torch.empty((abi.METER_WORDS,), dtype=torch.int32, device=dev)
+        if exposure is None:
+            exposure = torch.empty((4,), dtype=torch.float32, device=dev)
+        temporaries = []
+        checked(color, "color", torch.float32, (h, w, 4))
+        if not color.is_contiguous():
+            color = color.contiguous()
+            temporaries.append(color)
+        m = abi.RaycaMeter()
+        m.width, m.height, m.low_permille, m.high_permille = w, h, low_permille, high_permille
+        m.key, m.min_scale, m.max_scale, m.rate = key, min_scale, max_scale, rate
+        m.color, m.hist_out, m.exposure_out = color.data_ptr(), hist.data_ptr(), exposure.data_ptr()
+        if prev is not None:
+            m.exposure_prev = prev.data_ptr()
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_meter_device(self.handle, C.byref(o), C.byref(m), C.byref(st) if st is not None else None))
+        record(temporaries)
+        return (hist, exposure) + ((st.as_dict(),) if st is not None else ())
+
+    def tonemap(self, color, op="aces", *, exposure=None, scale=1.0, white=0.0, gamma=1.0, rgba8=False, out=None, stream=None, context=0,
+                want_stats=False):
+        """rayca_hip_tonemap_device: exposure, a display operator and the output stage, asynchronously, everything in device
+        memory.
+
+        color (H, W, 4) float32, gamma 1.  op: "linear" (the scale alone), "reinhard" (extended Reinhard on the luminance;
+        `white` > 0 is the luminance that maps to 1, 0 none) or "aces" (the rational fit, per channel), or its abi.TONEMAP_
+        value.  The scale is word 0 of `exposure`, a (4,) float32 tensor as meter() returns it -- read on the device, nothing
+        waited for -- or else the float `scale`.  `gamma`, `out` (may be `color` itself), `rgba8`, the stream handling and the
+        return convention are denoise()'s; out=False with rgba8 writes and returns the uint8 picture alone."""
+        torch, dev, handle, checked, record = self._torch_call(stream)
+        if not isinstance(color, torch.Tensor):
+            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        if isinstance(op, str):
+            if op not in abi.TONEMAP_NAMES:
+                raise ValueError(f"op: one of {abi.TONEMAP_NAMES}, not {op!r}")
+            op = abi.TONEMAP_NAMES.index(op)
+        h, w = color.shape[:2]
+        temporaries = []
+
+        def output(x, name, dtype):
+            if x is None or x is True:
+                return torch.empty((h, w, 4), dtype=dtype, device=dev)
+            if not checked(x, name, dtype, (h, w, 4)).is_contiguous():
+                raise ValueError(f"{name}: an output must be contiguous")
+            return x
+
+        t = abi.RaycaTonemap()
+        t.width, t.height, t.op, t.scale, t.white, t.gamma = w, h, op, scale, white, gamma
+        out = output(out, "out", torch.float32) if out is not False else None   # (before a contiguous copy of `color` replaces the name it may share)
+        checked(color, "color", torch.float32, (h, w, 4))
+        if not color.is_contiguous():
+            color = color.contiguous()
+            temporaries.append(color)
+        t.color = color.data_ptr()
+        if out is not None:
+            t.rgba32f_out = out.data_ptr()
+        if exposure is not None:
+            if not checked(exposure, "exposure", torch.float32, (4,)).is_contiguous():
+                raise ValueError("exposure: must be contiguous")
+            t.exposure = exposure.data_ptr()
+        out8 = None
+        if rgba8 is not None and rgba8 is not False:
+            out8 = output(rgba8, "rgba8", torch.uint8)
+            t.rgba8_out = out8.data_ptr()
+        st = abi.RaycaStats() if want_stats else None
+        o = self._opts(0, False, None, handle or None, context=context)
+        lib.check(self._lib.rayca_hip_tonemap_device(self.handle, C.byref(o), C.byref(t), C.byref(st) if st is not None else None))
+        record(temporaries)
+        result = ((out,) if out is not None else ()) + ((out8,) if out8 is not None else ()) + ((st.as_dict(),) if st is not None else ())
+        return result[0] if len(result) == 1 else result
 
     # ---- temporal accumulation: a frame into a history, with reprojection (rayca_hip_scene_camera, rayca_hip_accumulate_device) ----
     def camera_pose(self) -> abi.RaycaCameraPose:
