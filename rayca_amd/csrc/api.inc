@@ -797,6 +797,29 @@ int32_t pass_finish(const ContextPass& p, uint32_t launches, RaycaStats* stats_o
   return RAYCA_OK;
 }
 
+// One pass whose launches need nothing of the context but its stream, shaped like timed_launch: the context's lock,
+// `prepare(c)` under it (buffers of the context that must exist before the pass queues its waits), pass_acquire, ev_begin when
+// timing, `body(stream, launches)`, pass_retire, pass_finish.  The body enqueues on `stream`, checks hipGetLastError behind
+// each launch and counts what it launched.  (o.context is in range: pass_options has seen `o`.)
+template <typename Prepare, typename Body>
+int32_t run_pass(RaycaScene* s, const RaycaRenderOptions& o, RaycaStats* stats_out, Prepare&& prepare, Body&& body) {
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  int32_t rc = prepare(c);
+  if (rc != RAYCA_OK) return rc;
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
+  uint32_t launches = 0;
+  if ((rc = body(pass.stream, launches)) != RAYCA_OK) return rc;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  return pass_finish(pass, launches, stats_out);
+}
+template <typename Body>
+int32_t run_pass(RaycaScene* s, const RaycaRenderOptions& o, RaycaStats* stats_out, Body&& body) {
+  return run_pass(s, o, stats_out, [](FrameCtx*) -> int32_t { return RAYCA_OK; }, body);
+}
+
 // What a device pass other than a frame takes of RaycaRenderOptions: stream, context and the two events always, and the
 // groups of fields in `accepts`; every other field must be zero.  `what` names the call in the message.
 enum : uint32_t { kOptTraversal = 1u, kOptCollectStats = 2u, kOptTile = 4u };
@@ -2082,10 +2105,6 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
   }
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
   SurfaceIo io{};
   io.rays = static_cast<const float*>(sq.rays);
   io.t = static_cast<const float*>(sq.t);
@@ -2102,11 +2121,12 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   io.material_out = static_cast<uint32_t*>(sq.material_out);
   io.flags_out = static_cast<uint32_t*>(sq.flags_out);
   const uint32_t grid = (uint32_t)(((uint64_t)sq.count + kBlock - 1u) / kBlock);
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
-  hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, pass.stream, formats_ready(s) ? s->dev_full : s->dev, io);
-  HIP_TRY(hipGetLastError());
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, 1, stats_out);
+  return run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, stream, formats_ready(s) ? s->dev_full : s->dev, io);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    return RAYCA_OK;
+  });
 }
 
 // The camera rays of one sample of a frame (surface.inc k_camera_rays), from the FrameParams a render call would hand its
@@ -2139,579 +2159,6 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   return pass_finish(pass, 1, nullptr);
 }
 
-namespace {
-// k_atrous for the terms that are present: [colour term][no guide, normal, normal + point][id]
-using AtrousKernel = void (*)(AtrousIo);
-AtrousKernel pick_atrous_kernel(bool color, bool normal, bool point, bool id) {
-#define RAYCA_ATROUS(C, N, P) {k_atrous<C, N, P, false>, k_atrous<C, N, P, true>}
-  static const AtrousKernel table[2][3][2] = {{RAYCA_ATROUS(false, false, false), RAYCA_ATROUS(false, true, false), RAYCA_ATROUS(false, true, true)},
-                                              {RAYCA_ATROUS(true, false, false), RAYCA_ATROUS(true, true, false), RAYCA_ATROUS(true, true, true)}};
-#undef RAYCA_ATROUS
-  return table[color ? 1 : 0][point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
-}
-}  // namespace
-
-// The a-trous denoiser (denoise.inc): [k_denoise_demod] -> k_atrous x iterations -> k_denoise_finish, between the context's two
-// scratch images.  No kernel reads an image it writes -- every iteration goes from one image to another, and the only kernel
-// that writes rgba32f_out reads a scratch image -- which is what lets rgba32f_out be `color` itself.  The scene handle gives
-// the device and the frame context (stream, scratch, ordering against the context's frames and queries); the scene is not read.
-int32_t rayca_hip_denoise_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaDenoise* din, RaycaStats* stats_out) {
-  if (!s || !din) return fail(RAYCA_ERR_BAD_ARG, "null scene or denoise arguments");
-  const RaycaDenoise& d = *din;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (d.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDenoise.reserved must be zero");
-  if (!d.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!d.rgba32f_out && !d.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output");
-  if (d.width == 0 || d.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
-  const uint64_t count64 = (uint64_t)d.width * d.height;
-  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels");
-  if (d.iterations > 8) return fail(RAYCA_ERR_BAD_ARG, "iterations above 8");
-  if (d.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
-  if (d.point && !d.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
-  if (d.point && !(d.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
-  if (!(d.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(d.color, 16) || misaligned(d.albedo, 16) || misaligned(d.rgba32f_out, 16) || misaligned(d.rgba8_out, 4) || misaligned(d.normal, 4) ||
-      misaligned(d.point, 4) || misaligned(d.id, 4))
-    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo and rgba32f_out are read and written 16 bytes a pixel, every other image 4 bytes an element");
-  int32_t rc = pass_options(o, "a denoise call, which filters a whole frame (a tile's packed rows are not neighbours)", 0u);
-  if (rc != RAYCA_OK) return rc;
-  const uint32_t count = (uint32_t)count64;
-  const uint32_t tiles_x = (uint32_t)(((uint64_t)d.width + kDenoiseTileW - 1u) / kDenoiseTileW);
-  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)d.height + kDenoiseTileH - 1u) / kDenoiseTileH);
-  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));   // (for the scratch images, which have to be there before the pass queues its waits)
-  const size_t image_bytes = (size_t)count * sizeof(float4);
-  const float4* color = static_cast<const float4*>(d.color);
-  const float4* albedo = d.iterations ? static_cast<const float4*>(d.albedo) : nullptr;   // (no filter: nothing to demodulate for)
-  float4* out32 = static_cast<float4*>(d.rgba32f_out);
-  // the output stage reads `color` itself only when nothing runs in front of it; then an rgba32f_out that is `color` goes
-  // through a scratch image and a copy
-  const bool via_copy = d.iterations == 0 && out32 == color;
-  const uint32_t images = d.iterations == 0 ? (via_copy ? 1u : 0u) : ((albedo || d.iterations > 1) ? 2u : 1u);
-  for (uint32_t i = 0; i < images; ++i) {
-    // an earlier call of this context that has not been waited for may still be filtering in the image to be replaced
-    if (c->denoise[i].bytes < image_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
-    if ((rc = ensure(c->denoise[i], image_bytes)) != RAYCA_OK) return rc;
-  }
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  const hipStream_t stream = pass.stream;
-  float4* const scratch[2] = {static_cast<float4*>(c->denoise[0].ptr), static_cast<float4*>(c->denoise[1].ptr)};
-  const uint32_t flat_grid = (uint32_t)((count64 + kBlock - 1u) / kBlock);
-  uint32_t launches = 0;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  const float4* src = color;
-  uint32_t next = 0;   // the scratch image the next kernel writes (never the one `src` is)
-  if (albedo) {
-    hipLaunchKernelGGL(k_denoise_demod, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, scratch[next], count);
-    HIP_TRY(hipGetLastError());
-    src = scratch[next];
-    next ^= 1u;
-    ++launches;
-  }
-  if (d.iterations) {
-    AtrousIo io{};
-    io.normal = static_cast<const float*>(d.normal);
-    io.point = static_cast<const float*>(d.point);
-    io.id = static_cast<const uint32_t*>(d.id);
-    io.width = d.width;
-    io.height = d.height;
-    io.tiles_x = tiles_x;
-    io.normal_squarings = d.normal_power_log2;
-    const bool with_color = d.sigma_color > 0.0f;
-    io.kc = with_color ? 1.0f / (d.sigma_color * d.sigma_color) : 0.0f;
-    io.kp = io.point ? 1.0f / (d.sigma_plane * d.sigma_plane) : 0.0f;
-    const auto kernel = pick_atrous_kernel(with_color, io.normal != nullptr, io.point != nullptr, io.id != nullptr);
-    for (uint32_t i = 0; i < d.iterations; ++i) {
-      io.in = src;
-      io.out = scratch[next];
-      io.step = 1u << i;
-      hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
-      HIP_TRY(hipGetLastError());
-      src = scratch[next];
-      next ^= 1u;
-      ++launches;
-    }
-  }
-  const float inv_gamma = 1.0f / d.gamma;   // (as a frame's: color/mod.rs:175-176)
-  hipLaunchKernelGGL(k_denoise_finish, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, inv_gamma, static_cast<uint8_t*>(d.rgba8_out),
-                     via_copy ? scratch[0] : out32, count);
-  HIP_TRY(hipGetLastError());
-  ++launches;
-  if (via_copy) HIP_TRY(hipMemcpyAsync(out32, scratch[0], image_bytes, hipMemcpyDeviceToDevice, stream));
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, launches, stats_out);
-}
-
-namespace {
-// k_accumulate for the inputs that are present: identity mode [moments], reprojection [id][prev_point][moments]
-using AccumulateKernel = void (*)(AccumulateIo);
-AccumulateKernel pick_accumulate_kernel(bool reproject, bool id, bool plane, bool moments) {
-  if (!reproject) return moments ? k_accumulate<false, false, false, true> : k_accumulate<false, false, false, false>;
-#define RAYCA_ACCUMULATE(I, P) {k_accumulate<true, I, P, false>, k_accumulate<true, I, P, true>}
-  static const AccumulateKernel table[2][2][2] = {{RAYCA_ACCUMULATE(false, false), RAYCA_ACCUMULATE(false, true)},
-                                                  {RAYCA_ACCUMULATE(true, false), RAYCA_ACCUMULATE(true, true)}};
-#undef RAYCA_ACCUMULATE
-  return table[id ? 1 : 0][plane ? 1 : 0][moments ? 1 : 0];
-}
-}  // namespace
-
-// Temporal accumulation (temporal.inc): one launch of k_accumulate, no scratch image.  Identity mode (no prev_camera) is
-// pixel-local, so an output may be the history it continues; in reprojection mode the taps read neighbours, and an output that
-// is one of the images they read is refused.  The scene handle gives the device and the frame context; the scene is not read.
-int32_t rayca_hip_accumulate_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaAccumulate* ain, RaycaStats* stats_out) {
-  if (!s || !ain) return fail(RAYCA_ERR_BAD_ARG, "null scene or accumulate arguments");
-  const RaycaAccumulate& a = *ain;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (a.width == 0 || a.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaAccumulate.width, height)");
-  const uint64_t count64 = (uint64_t)a.width * a.height;
-  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaAccumulate.width x height)");
-  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaAccumulate.reserved must be zero");
-  if (!a.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!a.color_out) return fail(RAYCA_ERR_BAD_ARG, "null color_out");
-  if (!a.length_out) return fail(RAYCA_ERR_BAD_ARG, "null length_out");
-  const bool reproject = a.prev_camera != nullptr;
-  if (reproject && (!a.point || !a.normal)) return fail(RAYCA_ERR_BAD_ARG, "point and normal are required with prev_camera");
-  if (!reproject && (a.point || a.normal)) return fail(RAYCA_ERR_BAD_ARG, "point and normal must be NULL without prev_camera");
-  if ((a.id != nullptr) != (a.prev_id != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "id and prev_id: both or neither");
-  if ((a.hist_color != nullptr) != (a.hist_length != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "hist_color and hist_length: both or neither");
-  const bool history = a.hist_color != nullptr;
-  if (a.hist_moments && !history) return fail(RAYCA_ERR_BAD_ARG, "hist_moments needs hist_color and hist_length");
-  if (reproject && history && !a.prev_normal) return fail(RAYCA_ERR_BAD_ARG, "prev_normal is required with prev_camera and a history");
-  if (a.moments_out && history && !a.hist_moments) return fail(RAYCA_ERR_BAD_ARG, "moments_out needs hist_moments where there is a history");
-  if (a.variance_out && !a.moments_out) return fail(RAYCA_ERR_BAD_ARG, "variance_out needs moments_out");
-  if (reproject && !(a.normal_min > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "normal_min must be > 0 with prev_camera");
-  if (reproject && a.prev_point && !(a.plane_max > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "plane_max must be > 0 when prev_point is given");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(a.color, 16) || misaligned(a.hist_color, 16) || misaligned(a.color_out, 16))
-    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, hist_color and color_out are read and written 16 bytes a pixel");
-  for (const void* ptr : {a.point, a.normal, a.id, a.hist_length, a.hist_moments, a.prev_normal, a.prev_point, a.prev_id,
-                          (const void*)a.length_out, (const void*)a.moments_out, (const void*)a.variance_out})
-    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, hist_color and color_out is read and written 4 bytes an element");
-  if (reproject)
-    for (const void* out : {(const void*)a.color_out, (const void*)a.length_out, (const void*)a.moments_out, (const void*)a.variance_out})
-      for (const void* in : {a.hist_color, a.hist_length, a.hist_moments, a.prev_normal, a.prev_point, a.prev_id})
-        if (out && out == in) return fail(RAYCA_ERR_BAD_ARG, "aliasing: with prev_camera the taps read neighbours, so no output may be a hist_ or prev_ input");
-  int32_t rc = pass_options(o, "an accumulate call, which reads a whole frame (a tile's packed rows are not neighbours)", 0u);
-  if (rc != RAYCA_OK) return rc;
-  const uint32_t tiles_x = (uint32_t)(((uint64_t)a.width + kDenoiseTileW - 1u) / kDenoiseTileW);
-  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)a.height + kDenoiseTileH - 1u) / kDenoiseTileH);
-  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
-  AccumulateIo io{};
-  io.color = static_cast<const float4*>(a.color);
-  io.hist_color = static_cast<const float4*>(a.hist_color);
-  io.hist_length = static_cast<const float*>(a.hist_length);
-  io.color_out = static_cast<float4*>(a.color_out);
-  io.length_out = static_cast<float*>(a.length_out);
-  const bool moments = a.moments_out != nullptr;
-  if (moments) {
-    io.hist_moments = static_cast<const float*>(a.hist_moments);
-    io.moments_out = static_cast<float*>(a.moments_out);
-    io.variance_out = static_cast<float*>(a.variance_out);
-  }
-  io.width = a.width;
-  io.height = a.height;
-  io.tiles_x = tiles_x;
-  io.cap = (float)a.max_history;
-  // without a history no pixel has one, whatever the camera did: the identity kernel with a null history writes the first frame
-  const bool taps = reproject && history;
-  if (taps) {
-    const RaycaCameraPose& cam = *a.prev_camera;   // (HOST memory, copied here)
-    io.point = static_cast<const float*>(a.point);
-    io.normal = static_cast<const float*>(a.normal);
-    io.prev_normal = static_cast<const float*>(a.prev_normal);
-    io.prev_point = static_cast<const float*>(a.prev_point);
-    io.id = static_cast<const uint32_t*>(a.id);
-    io.prev_id = static_cast<const uint32_t*>(a.prev_id);
-    io.normal_min = a.normal_min;
-    io.plane_max = a.plane_max;
-    io.fw = (float)a.width;
-    io.fh = (float)a.height;
-    io.angle = cam.angle;
-    io.angle_aspect = cam.angle * (io.fw / io.fh);   // (aspect as camera_frame_params forms it)
-    io.ox = cam.origin[0]; io.oy = cam.origin[1]; io.oz = cam.origin[2];
-    io.rx = cam.right[0]; io.ry = cam.right[1]; io.rz = cam.right[2];
-    io.ux = cam.up[0]; io.uy = cam.up[1]; io.uz = cam.up[2];
-    io.bx = cam.back[0]; io.by = cam.back[1]; io.bz = cam.back[2];
-  }
-  const auto kernel = pick_accumulate_kernel(taps, taps && io.id != nullptr, taps && io.prev_point != nullptr, moments);
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
-  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
-  HIP_TRY(hipGetLastError());
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, 1, stats_out);
-}
-
-namespace {
-// k_variance_init for the inputs that are present: [no length, length, length + spatial estimate]; the spatial estimate's
-// guides [no guide, normal, normal + point][id].  Without the spatial estimate no guide is read.
-using VarianceInitKernel = void (*)(VarianceInitIo);
-VarianceInitKernel pick_variance_init_kernel(bool length, bool spatial, bool normal, bool point, bool id) {
-  if (!spatial) return length ? k_variance_init<true, false, false, false, false> : k_variance_init<false, false, false, false, false>;
-#define RAYCA_VARIANCE_INIT(N, P) {k_variance_init<true, true, N, P, false>, k_variance_init<true, true, N, P, true>}
-  static const VarianceInitKernel table[3][2] = {RAYCA_VARIANCE_INIT(false, false), RAYCA_VARIANCE_INIT(true, false), RAYCA_VARIANCE_INIT(true, true)};
-#undef RAYCA_VARIANCE_INIT
-  return table[point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
-}
-// k_atrous_var for the guides that are present: [no guide, normal, normal + point][id]
-using AtrousVarKernel = void (*)(AtrousVarIo);
-AtrousVarKernel pick_atrous_var_kernel(bool normal, bool point, bool id) {
-#define RAYCA_ATROUS_VAR(N, P) {k_atrous_var<N, P, false>, k_atrous_var<N, P, true>}
-  static const AtrousVarKernel table[3][2] = {RAYCA_ATROUS_VAR(false, false), RAYCA_ATROUS_VAR(true, false), RAYCA_ATROUS_VAR(true, true)};
-#undef RAYCA_ATROUS_VAR
-  return table[point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
-}
-}  // namespace
-
-// The variance-guided a-trous denoiser (denoise_variance.inc): [k_denoise_demod] -> k_variance_init -> k_atrous_var x iterations
-// -> k_denoise_finish, between the context's two scratch images and its two variance planes.  No kernel reads an image it
-// writes: every iteration goes from one image and plane to the others, `variance` is read by k_variance_init alone (into a
-// plane), and the only writers of rgba32f_out and variance_out run behind every reader of `color` and `variance` -- which is what
-// lets rgba32f_out be `color` and variance_out be `variance`.  The scene handle gives the device and the frame context; the
-// scene is not read.
-int32_t rayca_hip_denoise_variance_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaDenoiseVariance* din, RaycaStats* stats_out) {
-  if (!s || !din) return fail(RAYCA_ERR_BAD_ARG, "null scene or denoise arguments");
-  const RaycaDenoiseVariance& d = *din;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (d.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDenoiseVariance.reserved must be zero");
-  if (!d.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!d.variance) return fail(RAYCA_ERR_BAD_ARG, "null variance");
-  if (!d.rgba32f_out && !d.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
-  if (d.width == 0 || d.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaDenoiseVariance.width, height)");
-  const uint64_t count64 = (uint64_t)d.width * d.height;
-  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaDenoiseVariance.width x height)");
-  if (d.iterations == 0 || d.iterations > 8) return fail(RAYCA_ERR_BAD_ARG, "iterations must be 1..8");
-  if (d.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
-  if (d.min_history > 0 && !d.length) return fail(RAYCA_ERR_BAD_ARG, "min_history > 0 needs length: the history length chooses the spatial estimate");
-  if (d.point && !d.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
-  if (d.point && !(d.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
-  if (!(d.sigma_luminance > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_luminance must be > 0");
-  if (!(d.variance_floor > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "variance_floor must be > 0");
-  if (!(d.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(d.color, 16) || misaligned(d.albedo, 16) || misaligned(d.rgba32f_out, 16))
-    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo and rgba32f_out are read and written 16 bytes a pixel");
-  for (const void* ptr : {d.variance, d.length, d.normal, d.point, d.id, (const void*)d.rgba8_out, (const void*)d.variance_out})
-    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, albedo and rgba32f_out is read and written 4 bytes an element");
-  int32_t rc = pass_options(o, "a denoise call, which filters a whole frame (a tile's packed rows are not neighbours)", 0u);
-  if (rc != RAYCA_OK) return rc;
-  const uint32_t count = (uint32_t)count64;
-  const uint32_t tiles_x = (uint32_t)(((uint64_t)d.width + kDenoiseTileW - 1u) / kDenoiseTileW);
-  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)d.height + kDenoiseTileH - 1u) / kDenoiseTileH);
-  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  HIP_TRY(hipSetDevice(s->device));   // (for the scratch images, which have to be there before the pass queues its waits)
-  const size_t image_bytes = (size_t)count * sizeof(float4), plane_bytes = (size_t)count * sizeof(float);
-  const float4* color = static_cast<const float4*>(d.color);
-  const float4* albedo = static_cast<const float4*>(d.albedo);
-  const uint32_t images = (albedo || d.iterations > 1) ? 2u : 1u;
-  // an earlier call of this context that has not been waited for may still be filtering in the buffer to be replaced
-  for (uint32_t i = 0; i < images; ++i) {
-    if (c->denoise[i].bytes < image_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
-    if ((rc = ensure(c->denoise[i], image_bytes)) != RAYCA_OK) return rc;
-  }
-  for (DeviceBuffer& plane : c->denoise_var) {
-    if (plane.bytes < plane_bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
-    if ((rc = ensure(plane, plane_bytes)) != RAYCA_OK) return rc;
-  }
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  const hipStream_t stream = pass.stream;
-  float4* const scratch[2] = {static_cast<float4*>(c->denoise[0].ptr), static_cast<float4*>(c->denoise[1].ptr)};
-  float* const planes[2] = {static_cast<float*>(c->denoise_var[0].ptr), static_cast<float*>(c->denoise_var[1].ptr)};
-  const uint32_t flat_grid = (uint32_t)((count64 + kBlock - 1u) / kBlock);
-  uint32_t launches = 0;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  const float4* src = color;
-  uint32_t next = 0;   // the scratch image the next kernel writes (never the one `src` is)
-  if (albedo) {
-    hipLaunchKernelGGL(k_denoise_demod, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, scratch[next], count);
-    HIP_TRY(hipGetLastError());
-    src = scratch[next];
-    next ^= 1u;
-    ++launches;
-  }
-  const float* normal = static_cast<const float*>(d.normal);
-  const float* point = static_cast<const float*>(d.point);
-  const uint32_t* id = static_cast<const uint32_t*>(d.id);
-  const float kp = point ? 1.0f / (d.sigma_plane * d.sigma_plane) : 0.0f;
-  {
-    VarianceInitIo io{};
-    io.color = src;
-    io.albedo = albedo;
-    io.variance = static_cast<const float*>(d.variance);
-    io.length = static_cast<const float*>(d.length);
-    io.var_out = planes[0];
-    io.width = d.width;
-    io.height = d.height;
-    io.tiles_x = tiles_x;
-    const bool spatial = d.min_history > 0;
-    if (spatial) {
-      io.normal = normal;
-      io.point = point;
-      io.id = id;
-      io.normal_squarings = d.normal_power_log2;
-      io.kp = kp;
-      io.min_history = (float)d.min_history;
-    }
-    const auto kernel = pick_variance_init_kernel(io.length != nullptr, spatial, spatial && normal, spatial && point, spatial && id);
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
-    HIP_TRY(hipGetLastError());
-    ++launches;
-  }
-  uint32_t plane = 0;   // the variance plane the next iteration reads
-  {
-    AtrousVarIo io{};
-    io.normal = normal;
-    io.point = point;
-    io.id = id;
-    io.width = d.width;
-    io.height = d.height;
-    io.tiles_x = tiles_x;
-    io.normal_squarings = d.normal_power_log2;
-    io.sl2 = d.sigma_luminance * d.sigma_luminance;
-    io.variance_floor = d.variance_floor;
-    io.kp = kp;
-    const auto kernel = pick_atrous_var_kernel(normal != nullptr, point != nullptr, id != nullptr);
-    for (uint32_t i = 0; i < d.iterations; ++i) {
-      io.in = src;
-      io.out = scratch[next];
-      io.var_in = planes[plane];
-      io.var_out = planes[plane ^ 1u];
-      io.step = 1u << i;
-      hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, stream, io);
-      HIP_TRY(hipGetLastError());
-      src = scratch[next];
-      next ^= 1u;
-      plane ^= 1u;
-      ++launches;
-    }
-  }
-  const float inv_gamma = 1.0f / d.gamma;   // (as a frame's: color/mod.rs:175-176)
-  hipLaunchKernelGGL(k_denoise_finish, dim3(flat_grid), dim3(kBlock), 0, stream, src, albedo, inv_gamma, static_cast<uint8_t*>(d.rgba8_out),
-                     static_cast<float4*>(d.rgba32f_out), count);
-  HIP_TRY(hipGetLastError());
-  ++launches;
-  if (d.variance_out) HIP_TRY(hipMemcpyAsync(d.variance_out, planes[plane], plane_bytes, hipMemcpyDeviceToDevice, stream));
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, launches, stats_out);
-}
-
-namespace {
-// k_upsample for the guide pairs that are present: [albedo][no guide, normal, normal + point][id]
-using UpsampleKernel = void (*)(UpsampleIo);
-UpsampleKernel pick_upsample_kernel(bool albedo, bool normal, bool point, bool id) {
-#define RAYCA_UPSAMPLE(A, N, P) {k_upsample<A, N, P, false>, k_upsample<A, N, P, true>}
-  static const UpsampleKernel table[2][3][2] = {{RAYCA_UPSAMPLE(false, false, false), RAYCA_UPSAMPLE(false, true, false), RAYCA_UPSAMPLE(false, true, true)},
-                                                {RAYCA_UPSAMPLE(true, false, false), RAYCA_UPSAMPLE(true, true, false), RAYCA_UPSAMPLE(true, true, true)}};
-#undef RAYCA_UPSAMPLE
-  return table[albedo ? 1 : 0][point ? 2 : (normal ? 1 : 0)][id ? 1 : 0];
-}
-}  // namespace
-
-// Guided upsampling (upsample.inc): one launch of k_upsample, no scratch image.  Every tap reads the low images and every
-// output is full size, so no output may be an input.  The scene handle gives the device and the frame context; the scene is
-// not read.  Every check stands in front of any GPU work, the options' last.
-int32_t rayca_hip_upsample_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaUpsample* uin, RaycaStats* stats_out) {
-  if (!s || !uin) return fail(RAYCA_ERR_BAD_ARG, "null scene or upsample arguments");
-  const RaycaUpsample& u = *uin;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (u.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaUpsample.reserved must be zero");
-  if (u.width == 0 || u.height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image (RaycaUpsample.width, height)");
-  const uint64_t count64 = (uint64_t)u.width * u.height;
-  if (count64 > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 pixels (RaycaUpsample.width x height)");
-  if (u.scale == 0 || u.scale > 8) return fail(RAYCA_ERR_BAD_ARG, "scale must be 1..8");
-  if (u.width % u.scale != 0 || u.height % u.scale != 0)
-    return fail(RAYCA_ERR_BAD_ARG, "width and height must be divisible by scale: the two views share one aspect ratio, bit for bit");
-  if (u.normal_power_log2 > 10) return fail(RAYCA_ERR_BAD_ARG, "normal_power_log2 above 10");
-  if (!u.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!u.rgba32f_out && !u.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
-  if ((u.albedo != nullptr) != (u.albedo_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "albedo and albedo_low: both or neither");
-  if ((u.normal != nullptr) != (u.normal_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "normal and normal_low: both or neither");
-  if ((u.point != nullptr) != (u.point_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "point and point_low: both or neither");
-  if ((u.id != nullptr) != (u.id_low != nullptr)) return fail(RAYCA_ERR_BAD_ARG, "id and id_low: both or neither");
-  if (u.point && !u.normal) return fail(RAYCA_ERR_BAD_ARG, "point needs normal: the plane distance is measured along p's normal");
-  if (u.point && !(u.sigma_plane > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "sigma_plane must be > 0 when point is given");
-  if (!(u.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(u.color, 16) || misaligned(u.albedo_low, 16) || misaligned(u.albedo, 16) || misaligned(u.rgba32f_out, 16))
-    return fail(RAYCA_ERR_BAD_ARG, "alignment: color, albedo_low, albedo and rgba32f_out are read and written 16 bytes a pixel");
-  for (const void* ptr : {u.normal_low, u.point_low, u.id_low, u.normal, u.point, u.id, (const void*)u.rgba8_out, (const void*)u.weight_out})
-    if (misaligned(ptr, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: every image but color, albedo_low, albedo and rgba32f_out is read and written 4 bytes an element");
-  for (const void* out : {(const void*)u.rgba32f_out, (const void*)u.rgba8_out, (const void*)u.weight_out})
-    for (const void* in : {u.color, u.albedo_low, u.normal_low, u.point_low, u.id_low, u.albedo, u.normal, u.point, u.id})
-      if (out && out == in) return fail(RAYCA_ERR_BAD_ARG, "aliasing: the taps read neighbours and the images differ in size, so no output may be an input");
-  const uint32_t tiles_x = (uint32_t)(((uint64_t)u.width + kDenoiseTileW - 1u) / kDenoiseTileW);
-  const uint64_t tiles = (uint64_t)tiles_x * (((uint64_t)u.height + kDenoiseTileH - 1u) / kDenoiseTileH);
-  if (tiles * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
-  int32_t rc = pass_options(o, "an upsample call, which resamples a whole frame (a tile's packed rows are not neighbours)", 0u);
-  if (rc != RAYCA_OK) return rc;
-  UpsampleIo io{};
-  io.color = static_cast<const float4*>(u.color);
-  io.albedo_low = static_cast<const float4*>(u.albedo_low);
-  io.normal_low = static_cast<const float*>(u.normal_low);
-  io.point_low = static_cast<const float*>(u.point_low);
-  io.id_low = static_cast<const uint32_t*>(u.id_low);
-  io.albedo = static_cast<const float4*>(u.albedo);
-  io.normal = static_cast<const float*>(u.normal);
-  io.point = static_cast<const float*>(u.point);
-  io.id = static_cast<const uint32_t*>(u.id);
-  io.rgba32f = static_cast<float4*>(u.rgba32f_out);
-  io.rgba8 = static_cast<uint8_t*>(u.rgba8_out);
-  io.weight = static_cast<float*>(u.weight_out);
-  io.width = u.width;
-  io.height = u.height;
-  io.low_width = u.width / u.scale;
-  io.low_height = u.height / u.scale;
-  io.tiles_x = tiles_x;
-  io.scale = u.scale;
-  io.normal_squarings = u.normal_power_log2;
-  io.s = (float)u.scale;
-  io.kp = io.point ? 1.0f / (u.sigma_plane * u.sigma_plane) : 0.0f;
-  io.inv_gamma = 1.0f / u.gamma;   // (as a frame's: color/mod.rs:175-176)
-  const auto kernel = pick_upsample_kernel(io.albedo != nullptr, io.normal != nullptr, io.point != nullptr, io.id != nullptr);
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
-  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
-  HIP_TRY(hipGetLastError());
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, 1, stats_out);
-}
-
-namespace {
-// what the two display passes check alike: the frame's size and the tile count of the passes that display it
-int32_t display_frame_size(uint32_t width, uint32_t height, const char* type, uint32_t* tiles_x_out, uint64_t* tiles_out) {
-  if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, std::string("empty image (") + type + ".width, height)");
-  if ((uint64_t)width * height > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, std::string("more than 2^32 - 1 pixels (") + type + ".width x height)");
-  *tiles_x_out = (uint32_t)(((uint64_t)width + kDenoiseTileW - 1u) / kDenoiseTileW);
-  *tiles_out = (uint64_t)*tiles_x_out * (((uint64_t)height + kDenoiseTileH - 1u) / kDenoiseTileH);
-  if (*tiles_out * kBlock > 0xFFFFFFFFull) return fail(RAYCA_ERR_UNSUPPORTED, "the frame's 64 x 4 tiles hold more than 2^32 - 1 lanes: one launch cannot cover it");
-  return RAYCA_OK;
-}
-bool finite_f32(float x) { return x - x == 0.0f; }
-
-// k_tonemap for an operator and the outputs that are present: [op][rgba32f][rgba8]
-using TonemapKernel = void (*)(TonemapIo);
-TonemapKernel pick_tonemap_kernel(uint32_t op, bool f32, bool u8) {
-#define RAYCA_TONEMAP(OP) {{nullptr, k_tonemap<OP, false, true>}, {k_tonemap<OP, true, false>, k_tonemap<OP, true, true>}}
-  static const TonemapKernel table[3][2][2] = {RAYCA_TONEMAP(kTonemapLinear), RAYCA_TONEMAP(kTonemapReinhard), RAYCA_TONEMAP(kTonemapAces)};
-#undef RAYCA_TONEMAP
-  return table[op][f32 ? 1 : 0][u8 ? 1 : 0];
-}
-}  // namespace
-
-// Exposure metering (tonemap.inc): the clear of hist_out, k_meter_hist under a capped grid and, with exposure_out, the one-wave
-// k_exposure, each behind the other on the pass's stream.  The scene handle gives the device and the frame context; the scene
-// is not read.  Every check stands in front of any GPU work, the options' last.
-int32_t rayca_hip_meter_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaMeter* m_in, RaycaStats* stats_out) {
-  if (!s || !m_in) return fail(RAYCA_ERR_BAD_ARG, "null scene or meter arguments");
-  const RaycaMeter& m = *m_in;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (m.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaMeter.reserved must be zero");
-  uint32_t tiles_x = 0;
-  uint64_t tiles = 0;
-  int32_t rc = display_frame_size(m.width, m.height, "RaycaMeter", &tiles_x, &tiles);
-  if (rc != RAYCA_OK) return rc;
-  if (!m.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!m.hist_out) return fail(RAYCA_ERR_BAD_ARG, "null hist_out");
-  if (!(m.low_permille < m.high_permille && m.high_permille <= 1000u)) return fail(RAYCA_ERR_BAD_ARG, "low_permille, high_permille: 0 <= low < high <= 1000");
-  if (!(m.key > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "key must be > 0");
-  if (!(finite_f32(m.min_scale) && m.min_scale > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "min_scale must be finite and > 0");
-  if (!(finite_f32(m.max_scale) && m.max_scale >= m.min_scale)) return fail(RAYCA_ERR_BAD_ARG, "max_scale must be finite and >= min_scale");
-  if (!(m.rate > 0.0f && m.rate <= 1.0f)) return fail(RAYCA_ERR_BAD_ARG, "rate must be in (0, 1]");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(m.color, 16) || misaligned(m.exposure_out, 16)) return fail(RAYCA_ERR_BAD_ARG, "alignment: color and exposure_out are read and written 16 bytes at a time");
-  if (misaligned(m.hist_out, 4) || misaligned(m.exposure_prev, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: hist_out and exposure_prev are read and written 4 bytes an element");
-  if (m.hist_out == m.color || m.hist_out == m.exposure_out || m.hist_out == m.exposure_prev || (m.exposure_out && m.exposure_out == m.color))
-    return fail(RAYCA_ERR_BAD_ARG, "aliasing: hist_out must differ from color, exposure_out and exposure_prev, and exposure_out from color");
-  if ((rc = pass_options(o, "a meter call, which measures a whole frame", 0u)) != RAYCA_OK) return rc;
-  const uint64_t count64 = (uint64_t)m.width * m.height;
-  MeterIo io{static_cast<const float4*>(m.color), static_cast<uint32_t*>(m.hist_out), (uint32_t)count64};
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((count64 + kMeterBlock - 1u) / kMeterBlock, kMeterMaxGrid);
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));   // (in front of the clear: it is part of what the call costs)
-  HIP_TRY(hipMemsetAsync(m.hist_out, 0, kMeterWords * sizeof(uint32_t), pass.stream));
-  uint32_t launches = 1;
-  hipLaunchKernelGGL(k_meter_hist, dim3(grid), dim3(kMeterBlock), 0, pass.stream, io);
-  HIP_TRY(hipGetLastError());
-  ++launches;
-  if (m.exposure_out) {
-    ExposureIo e{io.hist, static_cast<float*>(m.exposure_out), static_cast<const float*>(m.exposure_prev), m.low_permille, m.high_permille,
-                 m.key, m.min_scale, m.max_scale, m.rate};
-    hipLaunchKernelGGL(k_exposure, dim3(1), dim3(64), 0, pass.stream, e);
-    HIP_TRY(hipGetLastError());
-    ++launches;
-  }
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, launches, stats_out);
-}
-
-// Tone mapping (tonemap.inc): one launch of k_tonemap, pixel-local, no scratch image.  Every check stands in front of any GPU
-// work, the options' last.
-int32_t rayca_hip_tonemap_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaTonemap* tin, RaycaStats* stats_out) {
-  if (!s || !tin) return fail(RAYCA_ERR_BAD_ARG, "null scene or tonemap arguments");
-  const RaycaTonemap& t = *tin;
-  RaycaRenderOptions o{};
-  if (opts_in) o = *opts_in;
-  if (t.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaTonemap.reserved must be zero");
-  uint32_t tiles_x = 0;
-  uint64_t tiles = 0;
-  int32_t rc = display_frame_size(t.width, t.height, "RaycaTonemap", &tiles_x, &tiles);
-  if (rc != RAYCA_OK) return rc;
-  if (!t.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
-  if (!t.rgba32f_out && !t.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output (rgba32f_out, rgba8_out)");
-  if (t.op > RAYCA_TONEMAP_ACES) return fail(RAYCA_ERR_BAD_ARG, "unknown op");
-  if (!t.exposure && !(finite_f32(t.scale) && t.scale > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "scale must be finite and > 0 when exposure is not given");
-  if (!(finite_f32(t.white) && t.white >= 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "white must be 0 (no white point) or finite and > 0");
-  if (t.white != 0.0f && t.op != RAYCA_TONEMAP_REINHARD) return fail(RAYCA_ERR_BAD_ARG, "white belongs to RAYCA_TONEMAP_REINHARD: must be 0 for the other operators");
-  if (!(t.gamma > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "gamma must be > 0");
-  const auto misaligned = [](const void* ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) != 0u; };
-  if (misaligned(t.color, 16) || misaligned(t.rgba32f_out, 16)) return fail(RAYCA_ERR_BAD_ARG, "alignment: color and rgba32f_out are read and written 16 bytes a pixel");
-  if (misaligned(t.exposure, 4) || misaligned(t.rgba8_out, 4)) return fail(RAYCA_ERR_BAD_ARG, "alignment: exposure and rgba8_out are read and written 4 bytes an element");
-  if ((t.rgba8_out && (t.rgba8_out == t.color || t.rgba8_out == t.rgba32f_out || t.rgba8_out == t.exposure)) ||
-      (t.rgba32f_out && t.rgba32f_out == t.exposure) || (t.exposure && t.exposure == t.color))
-    return fail(RAYCA_ERR_BAD_ARG, "aliasing: rgba32f_out may be color; no other two of color, exposure, rgba32f_out and rgba8_out may be equal");
-  if ((rc = pass_options(o, "a tonemap call, which maps a whole frame", 0u)) != RAYCA_OK) return rc;
-  TonemapIo io{};
-  io.color = static_cast<const float4*>(t.color);
-  io.exposure = static_cast<const float*>(t.exposure);
-  io.rgba32f = static_cast<float4*>(t.rgba32f_out);
-  io.rgba8 = static_cast<uint8_t*>(t.rgba8_out);
-  io.width = t.width;
-  io.height = t.height;
-  io.tiles_x = tiles_x;
-  io.scale = t.scale;
-  io.inv_white2 = t.white != 0.0f ? 1.0f / (t.white * t.white) : 0.0f;
-  io.inv_gamma = 1.0f / t.gamma;   // (as a frame's: color/mod.rs:175-176)
-  const auto kernel = pick_tonemap_kernel(t.op, io.rgba32f != nullptr, io.rgba8 != nullptr);
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
-  hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles), dim3(kBlock), 0, pass.stream, io);
-  HIP_TRY(hipGetLastError());
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, 1, stats_out);
-}
-
 }  // extern "C"
+
+#include "post.inc"

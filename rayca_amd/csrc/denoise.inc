@@ -18,32 +18,20 @@ struct AtrousIo {
   float kc, kp;            // 1 / sigma_color^2, 1 / sigma_plane^2
 };
 
-constexpr int kDenoiseTileW = 64, kDenoiseTileH = kBlock / kDenoiseTileW;   // a wave = 64 consecutive pixels of one row
-
 // One pixel per lane, a 64 x 4 tile per block: the 64 lanes of a wave read one 1-KiB run of float4 colour per tap, and a
 // dilated tap is the same run shifted by dx * step pixels.  The 25 taps go dy = -2..2 (outer), dx = -2..2 (inner) into one
 // running sum; p's own colour and guides stay in registers.  A template flag per term: an absent guide costs nothing.
 template <bool COLOR, bool NORMAL, bool POINT, bool ID>
 __global__ __launch_bounds__(kBlock) void k_atrous(AtrousIo io) {
+  // tile_pixel's lines, written out: through the helper the two bounds tests become one branch and this kernel's SGPR count moves
   const uint32_t ty = blockIdx.x / io.tiles_x, tx = blockIdx.x - ty * io.tiles_x;
-  // (tx * 64 <= width - 1 and ty * 4 <= height - 1, so neither sum passes 2^32 + 63: formed in 64 bits)
   const uint64_t x64 = (uint64_t)tx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
   const uint64_t y64 = (uint64_t)ty * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
   if (x64 >= io.width || y64 >= io.height) return;
   const int64_t x = (int64_t)x64, y = (int64_t)y64, s = (int64_t)io.step;
   const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
   const float4 cp = io.in[p];
-  float npx = 0.0f, npy = 0.0f, npz = 0.0f, ppx = 0.0f, ppy = 0.0f, ppz = 0.0f;
-  uint32_t idp = 0u;
-  if (NORMAL) {
-    const float* n = io.normal + 3ull * p;
-    npx = n[0]; npy = n[1]; npz = n[2];
-  }
-  if (POINT) {
-    const float* q = io.point + 3ull * p;
-    ppx = q[0]; ppy = q[1]; ppz = q[2];
-  }
-  if (ID) idp = io.id[p];
+  const GuideCentre g = guide_centre<NORMAL, POINT, ID>(io.normal, io.point, io.id, p);
   constexpr float k[3] = {0.375f, 0.25f, 0.0625f};
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, wsum = 0.0f;
 #pragma unroll
@@ -62,20 +50,9 @@ __global__ __launch_bounds__(kBlock) void k_atrous(AtrousIo io) {
         const float dc = (dr * dr + dg * dg) + db * db;
         w = w / (1.0f + dc * io.kc);
       }
-      if (NORMAL) {
-        const float* n = io.normal + 3ull * q;
-        float dn = fmaxf((npx * n[0] + npy * n[1]) + npz * n[2], 0.0f);
-        for (uint32_t j = 0; j < io.normal_squarings; ++j) dn = dn * dn;
-        w = w * dn;
-      }
-      if (POINT) {
-        const float* xq = io.point + 3ull * q;
-        const float ex = xq[0] - ppx, ey = xq[1] - ppy, ez = xq[2] - ppz;
-        const float pd = (npx * ex + npy * ey) + npz * ez;
-        w = w / (1.0f + (pd * pd) * io.kp);
-      }
+      w = guide_weight<NORMAL, POINT>(w, g, io.normal, io.point, q, io.normal_squarings, io.kp);
       bool take = w > 0.0f;   // (false for zero and for NaN)
-      if (ID) take = take && io.id[q] == idp;
+      if (ID) take = take && io.id[q] == g.idp;
       if (take) {
         sr = sr + w * cq.x;
         sg = sg + w * cq.y;
@@ -93,31 +70,19 @@ __global__ __launch_bounds__(kBlock) void k_atrous(AtrousIo io) {
   io.out[p] = o;
 }
 
-// den = max(albedo, 1e-3) per channel: what the colour is divided by in front of the filter and multiplied with behind it
-__device__ __forceinline__ float4 denoise_den(float4 a) { return make_float4(fmaxf(a.x, 1e-3f), fmaxf(a.y, 1e-3f), fmaxf(a.z, 1e-3f), 1.0f); }
-
 // colour / den -> out, alpha as it is (pixel-local)
 __global__ __launch_bounds__(kBlock) void k_denoise_demod(const float4* color, const float4* albedo, float4* out, uint32_t count) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= (uint64_t)count) return;
-  const float4 c = color[i], den = denoise_den(albedo[i]);
-  out[i] = make_float4(c.x / den.x, c.y / den.y, c.z / den.z, c.w);
+  out[i] = demodulate(color[i], albedo[i]);
 }
 
 // The output stage (pixel-local): remodulate where `albedo` is given, then gamma and RGBA8 as a render call's last kernel
-// does them -- finalize_pixel with one sample per pixel (x / 1.0f is x).  `in` is never one of the outputs.
+// does them (write_display_pixel).  `in` is never one of the outputs.
 __global__ __launch_bounds__(kBlock) void k_denoise_finish(const float4* in, const float4* albedo, float inv_gamma, uint8_t* rgba8, float4* rgba32f, uint32_t count) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= (uint64_t)count) return;
   float4 c = in[i];
-  if (albedo) {
-    const float4 den = denoise_den(albedo[i]);
-    c.x = c.x * den.x;
-    c.y = c.y * den.y;
-    c.z = c.z * den.z;
-  }
-  FrameParams fp{};
-  fp.spp = 1u;
-  fp.inv_gamma = inv_gamma;
-  finalize_pixel(fp, as_color(c), (uint32_t)i, rgba8, rgba32f);
+  if (albedo) c = remodulate(c, albedo[i]);
+  write_display_pixel(c, inv_gamma, (uint32_t)i, rgba8, rgba32f);
 }

@@ -7,47 +7,6 @@
 // (tests/denoise_variance_literal.py).  Every comparison is written so that a NaN fails it; max is maxNum.  The demodulation and
 // the output stage are denoise.inc's own kernels, launched as they are.
 
-__device__ __forceinline__ float denoise_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// p's own guides, kept in registers over the taps
-struct GuideCentre {
-  float npx, npy, npz, ppx, ppy, ppz;
-  uint32_t idp;
-};
-
-template <bool NORMAL, bool POINT, bool ID>
-__device__ __forceinline__ GuideCentre guide_centre(const float* normal, const float* point, const uint32_t* id, uint32_t p) {
-  GuideCentre g{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u};
-  if (NORMAL) {
-    const float* n = normal + 3ull * p;
-    g.npx = n[0]; g.npy = n[1]; g.npz = n[2];
-  }
-  if (POINT) {
-    const float* q = point + 3ull * p;
-    g.ppx = q[0]; g.ppy = q[1]; g.ppz = q[2];
-  }
-  if (ID) g.idp = id[p];
-  return g;
-}
-
-// The normal and the point term of a tap at q, as k_atrous writes them and in its order: w * dn, then w / (1 + pd^2 kp).
-template <bool NORMAL, bool POINT>
-__device__ __forceinline__ float guide_weight(float w, const GuideCentre& g, const float* normal, const float* point, uint32_t q, uint32_t squarings, float kp) {
-  if (NORMAL) {
-    const float* n = normal + 3ull * q;
-    float dn = fmaxf((g.npx * n[0] + g.npy * n[1]) + g.npz * n[2], 0.0f);
-    for (uint32_t j = 0; j < squarings; ++j) dn = dn * dn;
-    w = w * dn;
-  }
-  if (POINT) {
-    const float* xq = point + 3ull * q;
-    const float ex = xq[0] - g.ppx, ey = xq[1] - g.ppy, ez = xq[2] - g.ppz;
-    const float pd = (g.npx * ex + g.npy * ey) + g.npz * ez;
-    w = w / (1.0f + (pd * pd) * kp);
-  }
-  return w;
-}
-
 // What the initial-variance launch reads and writes; every pointer is DEVICE memory.
 struct VarianceInitIo {
   const float4* color;     // H x W: the image the iterations start from (demodulated where there is an albedo)
@@ -71,16 +30,13 @@ struct VarianceInitIo {
 template <bool LENGTH, bool SPATIAL, bool NORMAL, bool POINT, bool ID>
 __global__ __launch_bounds__(kBlock) void k_variance_init(VarianceInitIo io) {
   static_assert(LENGTH || !SPATIAL, "the spatial estimate is chosen by the history length");
-  const uint32_t ty = blockIdx.x / io.tiles_x, tx = blockIdx.x - ty * io.tiles_x;
-  // (tx * 64 <= width - 1 and ty * 4 <= height - 1, so neither sum passes 2^32 + 63: formed in 64 bits)
-  const uint64_t x64 = (uint64_t)tx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
-  const uint64_t y64 = (uint64_t)ty * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
-  if (x64 >= io.width || y64 >= io.height) return;
-  const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
+  TilePixel t;
+  if (!tile_pixel(io.tiles_x, io.width, io.height, t)) return;
+  const uint32_t p = t.p;
   float v = fmaxf(io.variance[p], 0.0f);   // (a NaN becomes 0)
   if (io.albedo) {
     const float4 den = denoise_den(io.albedo[p]);
-    const float ld = denoise_lum(den.x, den.y, den.z);
+    const float ld = luminance(den.x, den.y, den.z);
     v = v / (ld * ld);
   }
   float len = 0.0f;
@@ -89,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void k_variance_init(VarianceInitIo io) {
     v = v / fmaxf(len, 1.0f);
   }
   if (SPATIAL && len < io.min_history) {   // (false for a NaN length)
-    const int64_t x = (int64_t)x64, y = (int64_t)y64;
+    const int64_t x = (int64_t)t.x64, y = (int64_t)t.y64;
     const GuideCentre g = guide_centre<NORMAL, POINT, ID>(io.normal, io.point, io.id, p);
     float s1 = 0.0f, s2 = 0.0f, ws = 0.0f;
 #pragma unroll 1
@@ -103,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void k_variance_init(VarianceInitIo io) {
         const uint32_t q = (uint32_t)((uint64_t)qy * io.width + (uint64_t)qx);
         const float4 cq = io.color[q];
         const float w = guide_weight<NORMAL, POINT>(1.0f, g, io.normal, io.point, q, io.normal_squarings, io.kp);
-        const float lq = denoise_lum(cq.x, cq.y, cq.z);
+        const float lq = luminance(cq.x, cq.y, cq.z);
         bool take = w > 0.0f && lq - lq == 0.0f;   // (false for zero and NaN weights, and for a luminance that is not finite)
         if (ID) take = take && io.id[q] == g.idp;
         if (take) {
@@ -145,13 +101,10 @@ struct AtrousVarIo {
 // variance of a weighted mean of independent values).  A tap moves 48 B where k_atrous moves 44, the prefilter 9 loads of 4 B.
 template <bool NORMAL, bool POINT, bool ID>
 __global__ __launch_bounds__(kBlock) void k_atrous_var(AtrousVarIo io) {
-  const uint32_t ty = blockIdx.x / io.tiles_x, tx = blockIdx.x - ty * io.tiles_x;
-  // (tx * 64 <= width - 1 and ty * 4 <= height - 1, so neither sum passes 2^32 + 63: formed in 64 bits)
-  const uint64_t x64 = (uint64_t)tx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
-  const uint64_t y64 = (uint64_t)ty * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
-  if (x64 >= io.width || y64 >= io.height) return;
-  const int64_t x = (int64_t)x64, y = (int64_t)y64, s = (int64_t)io.step;
-  const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
+  TilePixel t;
+  if (!tile_pixel(io.tiles_x, io.width, io.height, t)) return;
+  const int64_t x = (int64_t)t.x64, y = (int64_t)t.y64, s = (int64_t)io.step;
+  const uint32_t p = t.p;
   const float4 cp = io.in[p];
   const float vp = io.var_in[p];
   const GuideCentre g = guide_centre<NORMAL, POINT, ID>(io.normal, io.point, io.id, p);
@@ -171,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_atrous_var(AtrousVarIo io) {
     }
   }
   const float dnm = io.sl2 * (gs / gw) + io.variance_floor;
-  const float lp = denoise_lum(cp.x, cp.y, cp.z);
+  const float lp = luminance(cp.x, cp.y, cp.z);
   constexpr float k[3] = {0.375f, 0.25f, 0.0625f};
   float sr = 0.0f, sg = 0.0f, sb = 0.0f, vs = 0.0f, wsum = 0.0f;
 #pragma unroll
@@ -185,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_atrous_var(AtrousVarIo io) {
       const uint32_t q = (uint32_t)((uint64_t)qy * io.width + (uint64_t)qx);
       const float4 cq = io.in[q];
       float w = k[dx < 0 ? -dx : dx] * k[dy < 0 ? -dy : dy];
-      const float d = lp - denoise_lum(cq.x, cq.y, cq.z);
+      const float d = lp - luminance(cq.x, cq.y, cq.z);
       w = w / (1.0f + (d * d) / dnm);
       w = guide_weight<NORMAL, POINT>(w, g, io.normal, io.point, q, io.normal_squarings, io.kp);
       bool take = w > 0.0f;   // (false for zero and for NaN)

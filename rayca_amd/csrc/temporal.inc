@@ -36,15 +36,15 @@ struct AccumulateIo {
 // the history (or the frame) itself.  A template flag per optional input: an absent one costs nothing.
 template <bool REPROJECT, bool ID, bool PLANE, bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k_accumulate(AccumulateIo io) {
+  // tile_pixel's lines, written out: through the helper the two bounds tests become one branch and this kernel's SGPR count moves
   const uint32_t tby = blockIdx.x / io.tiles_x, tbx = blockIdx.x - tby * io.tiles_x;
-  // (tbx * 64 <= width - 1 and tby * 4 <= height - 1, so neither sum passes 2^32 + 63: formed in 64 bits)
   const uint64_t x64 = (uint64_t)tbx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
   const uint64_t y64 = (uint64_t)tby * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
   if (x64 >= io.width || y64 >= io.height) return;
   const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
   const float4 c = io.color[p];
-  const bool finite = (c.x - c.x == 0.0f) && (c.y - c.y == 0.0f) && (c.z - c.z == 0.0f) && (c.w - c.w == 0.0f);
-  const float lum = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+  const bool finite = finite4(c);
+  const float lum = luminance(c.x, c.y, c.z);
 
   bool present = false;
   float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);

@@ -13,9 +13,6 @@ constexpr int kMeterBlock = 1024;          // lanes a block: few, large blocks -
 constexpr uint32_t kMeterMaxGrid = 256;    // blocks: one per CU, 16 waves each; a larger frame strides (the cap was swept: DESIGN 4.13)
 constexpr int kMeterBinBias = (127 - 16) << 3;
 
-// temporal.inc's luminance
-__device__ __forceinline__ float meter_luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
 struct MeterIo {
   const float4* color;   // H x W, gamma 1
   uint32_t* hist;        // kMeterWords, cleared in front of the launch
@@ -41,7 +38,7 @@ __global__ __launch_bounds__(kMeterBlock) void k_meter_hist(MeterIo io) {
     // statement names c.w and keeps it one aligned global_load_dwordx4 a lane.  Checked in the ISA of this kernel (hipcc -S
     // --cuda-device-only, the loads of k_meter_hist): one global_load_dwordx4, no dwordx3; look again after a compiler change.
     asm volatile("" ::"v"(c.w));
-    const float y = meter_luminance(c.x, c.y, c.z);
+    const float y = luminance(c.x, c.y, c.z);
     if (!((c.x - c.x == 0.0f) && (c.y - c.y == 0.0f) && (c.z - c.z == 0.0f) && (y - y == 0.0f))) {
       ++not_finite;
     } else if (y <= 0.0f) {
@@ -139,16 +136,14 @@ __device__ __forceinline__ float tonemap_aces(float x) { return (x * (2.51f * x 
 // color.  The operator and the outputs are template flags: an absent output costs nothing.
 template <int OP, bool F32, bool U8>
 __global__ __launch_bounds__(kBlock) void k_tonemap(TonemapIo io) {
-  const uint32_t tby = blockIdx.x / io.tiles_x, tbx = blockIdx.x - tby * io.tiles_x;
-  const uint64_t x64 = (uint64_t)tbx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
-  const uint64_t y64 = (uint64_t)tby * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
-  if (x64 >= io.width || y64 >= io.height) return;
-  const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
+  TilePixel t;
+  if (!tile_pixel(io.tiles_x, io.width, io.height, t)) return;
+  const uint32_t p = t.p;
   const float s = io.exposure ? io.exposure[0] : io.scale;
   const float4 c = io.color[p];
   float4 o = make_float4(c.x * s, c.y * s, c.z * s, c.w);
   if (OP == kTonemapReinhard) {
-    const float y = meter_luminance(o.x, o.y, o.z);
+    const float y = luminance(o.x, o.y, o.z);
     if (y > 0.0f) {
       const float m = (1.0f + y * io.inv_white2) / (1.0f + y);
       o.x = o.x * m;
@@ -160,9 +155,5 @@ __global__ __launch_bounds__(kBlock) void k_tonemap(TonemapIo io) {
     o.y = tonemap_aces(o.y);
     o.z = tonemap_aces(o.z);
   }
-  // the output stage of k_denoise_finish: finalize_pixel with one sample per pixel (x / 1.0f is x)
-  FrameParams fp{};
-  fp.spp = 1u;
-  fp.inv_gamma = io.inv_gamma;
-  finalize_pixel(fp, as_color(o), p, U8 ? io.rgba8 : nullptr, F32 ? io.rgba32f : nullptr);
+  write_display_pixel(o, io.inv_gamma, p, U8 ? io.rgba8 : nullptr, F32 ? io.rgba32f : nullptr);
 }

@@ -37,31 +37,17 @@ struct UpsampleIo {
 template <bool ALBEDO, bool NORMAL, bool POINT, bool ID>
 __global__ __launch_bounds__(kBlock) void k_upsample(UpsampleIo io) {
   constexpr bool GUIDED = NORMAL || ID;   // (POINT needs NORMAL; the albedo rejects no tap)
-  const uint32_t tby = blockIdx.x / io.tiles_x, tbx = blockIdx.x - tby * io.tiles_x;
-  // (tbx * 64 <= width - 1 and tby * 4 <= height - 1, so neither sum passes 2^32 + 63: formed in 64 bits)
-  const uint64_t x64 = (uint64_t)tbx * kDenoiseTileW + (threadIdx.x & (kDenoiseTileW - 1));
-  const uint64_t y64 = (uint64_t)tby * kDenoiseTileH + (threadIdx.x / kDenoiseTileW);
-  if (x64 >= io.width || y64 >= io.height) return;
-  const uint32_t x = (uint32_t)x64, y = (uint32_t)y64;
-  const uint32_t p = (uint32_t)(y64 * io.width + x64);   // (< width * height)
+  TilePixel t;
+  if (!tile_pixel(io.tiles_x, io.width, io.height, t)) return;
+  const uint32_t x = (uint32_t)t.x64, y = (uint32_t)t.y64;
+  const uint32_t p = t.p;
   const float fx = ((float)x + 0.5f) / io.s - 0.5f, fy = ((float)y + 0.5f) / io.s - 0.5f;
   const float x0f = floorf(fx), y0f = floorf(fy);
   const float tx = fx - x0f, ty = fy - y0f;
   const int64_t x0 = (int64_t)x0f, y0 = (int64_t)y0f;   // (in [-1, 2^32]: exact)
 
-  float npx = 0.0f, npy = 0.0f, npz = 0.0f, ppx = 0.0f, ppy = 0.0f, ppz = 0.0f;
-  uint32_t idp = 0u;
-  bool miss = false;
-  if (NORMAL) {
-    const float* n = io.normal + 3ull * p;
-    npx = n[0]; npy = n[1]; npz = n[2];
-    miss = npx == 0.0f && npy == 0.0f && npz == 0.0f;
-  }
-  if (POINT) {
-    const float* xp = io.point + 3ull * p;
-    ppx = xp[0]; ppy = xp[1]; ppz = xp[2];
-  }
-  if (ID) idp = io.id[p];
+  const GuideCentre g = guide_centre<NORMAL, POINT, ID>(io.normal, io.point, io.id, p);
+  const bool miss = NORMAL && g.npx == 0.0f && g.npy == 0.0f && g.npz == 0.0f;
 
   float wsum = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f;   // the guided pass
   float bsum = 0.0f, br = 0.0f, bg = 0.0f, bb = 0.0f, ba = 0.0f;   // the fallback: w = b alone
@@ -77,13 +63,8 @@ __global__ __launch_bounds__(kBlock) void k_upsample(UpsampleIo io) {
       if (!(b > 0.0f)) continue;
       const uint32_t q = (uint32_t)((uint64_t)qy * io.low_width + (uint64_t)qx);   // (inside the low image: < w * h <= width * height)
       float4 c = io.color[q];
-      if (!((c.x - c.x == 0.0f) && (c.y - c.y == 0.0f) && (c.z - c.z == 0.0f) && (c.w - c.w == 0.0f))) continue;
-      if (ALBEDO) {
-        const float4 den = denoise_den(io.albedo_low[q]);
-        c.x = c.x / den.x;
-        c.y = c.y / den.y;
-        c.z = c.z / den.z;
-      }
+      if (!finite4(c)) continue;
+      if (ALBEDO) c = demodulate(c, io.albedo_low[q]);
       if (GUIDED) {
         bsum = bsum + b;
         br = br + b * c.x;
@@ -94,23 +75,24 @@ __global__ __launch_bounds__(kBlock) void k_upsample(UpsampleIo io) {
       float w = b;
       bool take = true;
       if (NORMAL) {
+        // guide_weight's two terms, written out: the tap's normal is loaded once, in front of the miss rule
         const float* n = io.normal_low + 3ull * q;
         const float nqx = n[0], nqy = n[1], nqz = n[2];
         if (miss) {
           take = nqx == 0.0f && nqy == 0.0f && nqz == 0.0f;   // a miss takes misses only, by b alone
         } else {
-          float dn = fmaxf((npx * nqx + npy * nqy) + npz * nqz, 0.0f);
+          float dn = fmaxf((g.npx * nqx + g.npy * nqy) + g.npz * nqz, 0.0f);
           for (uint32_t k = 0; k < io.normal_squarings; ++k) dn = dn * dn;
           w = w * dn;
           if (POINT) {
             const float* xq = io.point_low + 3ull * q;
-            const float ex = xq[0] - ppx, ey = xq[1] - ppy, ez = xq[2] - ppz;
-            const float pd = (npx * ex + npy * ey) + npz * ez;
+            const float ex = xq[0] - g.ppx, ey = xq[1] - g.ppy, ez = xq[2] - g.ppz;
+            const float pd = (g.npx * ex + g.npy * ey) + g.npz * ez;
             w = w / (1.0f + (pd * pd) * io.kp);
           }
         }
       }
-      if (ID) take = take && io.id_low[q] == idp;
+      if (ID) take = take && io.id_low[q] == g.idp;
       if (take && w > 0.0f) {   // (false for zero and for NaN)
         wsum = wsum + w;
         sr = sr + w * c.x;
@@ -130,23 +112,9 @@ __global__ __launch_bounds__(kBlock) void k_upsample(UpsampleIo io) {
     const uint32_t ny = min(y / io.scale, io.low_height - 1u), nx = min(x / io.scale, io.low_width - 1u);
     const uint32_t q = (uint32_t)((uint64_t)ny * io.low_width + nx);
     o = io.color[q];
-    if (ALBEDO) {
-      const float4 den = denoise_den(io.albedo_low[q]);
-      o.x = o.x / den.x;
-      o.y = o.y / den.y;
-      o.z = o.z / den.z;
-    }
+    if (ALBEDO) o = demodulate(o, io.albedo_low[q]);
   }
   if (io.weight) io.weight[p] = wsum;
-  if (ALBEDO) {
-    const float4 den = denoise_den(io.albedo[p]);
-    o.x = o.x * den.x;
-    o.y = o.y * den.y;
-    o.z = o.z * den.z;
-  }
-  // the output stage of k_denoise_finish: finalize_pixel with one sample per pixel (x / 1.0f is x)
-  FrameParams fp{};
-  fp.spp = 1u;
-  fp.inv_gamma = io.inv_gamma;
-  finalize_pixel(fp, as_color(o), p, io.rgba8, io.rgba32f);
+  if (ALBEDO) o = remodulate(o, io.albedo[p]);
+  write_display_pixel(o, io.inv_gamma, p, io.rgba8, io.rgba32f);
 }

@@ -80,7 +80,7 @@ class Film:
         if self._buffers is None:
             self._allocate()
         b, s = self._buffers, self.scene
-        handle = s._torch_call(stream)[2]
+        handle = s.stream_handle(stream)
         self._gamma = config.gamma
         cfg = dataclasses.replace(config, gamma=1.0, seed=(config.seed + self.frames_added) % 2 ** 32)
         s.render_device(cfg, self.width, self.height, 0, b["frame"].data_ptr(), stream=handle or None, context=context)

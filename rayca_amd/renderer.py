@@ -189,110 +189,61 @@ class DeviceScene:
         if kind not in ("closest", "occluded"):
             raise ValueError(f"kind must be 'closest' or 'occluded', not {kind!r}")
         occluded = kind == "occluded"
-        torch, dev, handle, checked, record = self._torch_call(stream)
+        call = _DeviceCall(self, stream)
+        torch = call.torch
         if not isinstance(rays, torch.Tensor):
-            raise TypeError(f"rays: a torch tensor on {dev} is expected, not {type(rays).__name__}")
+            raise TypeError(f"rays: a torch tensor on {call.dev} is expected, not {type(rays).__name__}")
         if rays.dim() != 2 or rays.shape[1] != 6:
             raise ValueError(f"rays: shape {tuple(rays.shape)}, expected (N, 6)")
         n = rays.shape[0]
         if n > 0xFFFFFFFF:
             raise ValueError("rays: more than 2**32 - 1 rays")
-        checked(rays, "rays", torch.float32, (n, 6))
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
-        rays = contiguous(rays)
         q = abi.RaycaQuery()
-        q.kind, q.count, q.rays = (abi.QUERY_OCCLUDED if occluded else abi.QUERY_CLOSEST), n, rays.data_ptr()
+        q.kind, q.count, q.rays = (abi.QUERY_OCCLUDED if occluded else abi.QUERY_CLOSEST), n, call.input(rays, "rays", torch.float32, (n, 6)).data_ptr()
         if tmax is None:
             q.tmax_all = float("inf")
         elif isinstance(tmax, torch.Tensor):
-            tmax = contiguous(checked(tmax, "tmax", torch.float32, (n,)))
-            q.tmax = tmax.data_ptr()
+            q.tmax = call.input(tmax, "tmax", torch.float32, (n,)).data_ptr()
         else:
             q.tmax_all = float(tmax)
-
-        def output(x, name, dtype, shape):
-            if x is None:
-                return torch.empty(shape, dtype=dtype, device=dev)
-            if not checked(x, name, dtype, shape).is_contiguous():
-                raise ValueError(f"{name}: an output must be contiguous")
-            return x
-
         if occluded:
-            result = (output(out, "out", torch.uint8, (n,)),)
-            q.occluded_out = result[0].data_ptr()
+            result = call.output(out, "out", torch.uint8, (n,))
+            q.occluded_out = result.data_ptr()
         else:
             o_t, o_prim, o_uv = out if out is not None else (None, None, None)
-            result = (output(o_t, "out[0] (t)", torch.float32, (n,)), output(o_prim, "out[1] (prim)", torch.int32, (n,)),
-                      output(o_uv, "out[2] (uv)", torch.float32, (n, 2)))
+            result = (call.output(o_t, "out[0] (t)", torch.float32, (n,)), call.output(o_prim, "out[1] (prim)", torch.int32, (n,)),
+                      call.output(o_uv, "out[2] (uv)", torch.float32, (n, 2)))
             q.t_out, q.prim_out, q.uv_out = (x.data_ptr() for x in result)
-        st = abi.RaycaStats() if (want_stats or collect_stats) else None
-        o = self._opts(traversal, collect_stats, None, handle or None, context=context)
+        stats = None
         if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
-            lib.check(self._lib.rayca_hip_query_device(self.handle, C.byref(o), C.byref(q), C.byref(st) if st is not None else None))
+            stats = call.run(self._lib.rayca_hip_query_device, q, context=context, want_stats=want_stats or collect_stats,
+                             traversal=traversal, collect_stats=collect_stats)
         elif context >= 8:
             raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
-        record(temporaries)
-        result = result[0] if occluded else result
-        if st is None:
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is None:
             return result
-        return (result, st.as_dict()) if occluded else (*result, st.as_dict())
+        return (result, stats) if occluded else (*result, stats)
 
     # ---- surface queries: what is at a hit (rayca_hip_surface_device), and the rays of a frame (rayca_hip_camera_rays_device) ----
     SURFACE_OUTPUTS = {"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
                        "specular": ("float32", 4), "rough": ("float32", 2), "material": ("int32", 0), "flags": ("int32", 0)}
 
-    def _torch_call(self, stream):
-        """The device and stream handling of query(), surface() and camera_rays(): (torch, device, stream handle, checked(),
-        record(temporaries))."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def checked(x, name, dtype, shape):
-            if not isinstance(x, torch.Tensor):
-                raise TypeError(f"{name}: a torch tensor on {dev} is expected, not {type(x).__name__}")
-            if x.device != dev:
-                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
-            if x.dtype != dtype:
-                raise TypeError(f"{name}: dtype {x.dtype}, expected {dtype}")
-            if tuple(x.shape) != shape:
-                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
-            return x
-
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-        if not handle:
-            # the legacy default stream: the library runs a call without a stream on the context's own (non-blocking) stream
-            # and waits for it, so what torch still has queued for the inputs must have finished first
-            torch.cuda.default_stream(dev).synchronize()
-
-        def record(temporaries):   # (a contiguous copy made here is read by a kernel on `stream`: the allocator must know)
-            for x in temporaries:
-                x.record_stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(handle, device=dev))
-
-        return torch, dev, handle, checked, record
+    def stream_handle(self, stream=None) -> int:
+        """The raw handle of `stream` (a torch.cuda.Stream, a raw handle, or None: torch's current stream of the scene's device)
+        as the device calls take it; 0 is the legacy default stream, which is synchronised here (see _DeviceCall)."""
+        return _DeviceCall(self, stream).handle
 
     def camera_rays(self, config: Config, width: int, height: int, *, sample=0, tile=None, stream=None, context=0, out=None):
         """rayca_hip_camera_rays_device: the camera rays of sub-sample `sample` of a width x height frame of `config` (only its
         samples_per_pixel matters), as a (rows * width, 6) float32 tensor on the scene's device -- origin xyz, direction xyz,
         what query() reads; rows = tile_rows(tile, height), the whole frame without a tile.  Stream handling as query()."""
-        torch, dev, handle, checked, _ = self._torch_call(stream)
+        call = _DeviceCall(self, stream)
         rows = height if tile is None else self.tile_rows(tile, height)
-        shape = (rows * width, 6)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=dev)
-        elif not checked(out, "out", torch.float32, shape).is_contiguous():
-            raise ValueError("out: an output must be contiguous")
+        out = call.output(out, "out", call.torch.float32, (rows * width, 6))
         cfg = config.to_abi()
-        o = self._opts(0, False, tile, handle or None, context=context)
+        o = call.options(context, tile=tile)
         lib.check(self._lib.rayca_hip_camera_rays_device(self.handle, C.byref(cfg), width, height, sample, C.byref(o), out.data_ptr() or None))
         return out
 
@@ -306,13 +257,14 @@ class DeviceScene:
         shininess) float32; material / flags (N,) int32 holding the u32 bits (material abi.NONE, i.e. -1, without a material
         and on a miss; flags: abi.SURFACE_*).  A record whose prim is not a slot of the scene is a miss: zeros.  `out`: a dict
         of tensors to write instead of new ones.  Stream handling as query(); `want_stats` waits and adds "stats"."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
+        call = _DeviceCall(self, stream)
+        torch = call.torch
         want = tuple(want)
         unknown = [w for w in want if w not in self.SURFACE_OUTPUTS]
         if unknown or not want or len(set(want)) != len(want):
             raise ValueError(f"want: a non-empty selection without repeats of {tuple(self.SURFACE_OUTPUTS)}, not {want!r}")
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"t: a torch tensor on {dev} is expected, not {type(t).__name__}")
+            raise TypeError(f"t: a torch tensor on {call.dev} is expected, not {type(t).__name__}")
         if t.dim() != 1:
             raise ValueError(f"t: shape {tuple(t.shape)}, expected (N,)")
         n = t.shape[0]
@@ -321,22 +273,13 @@ class DeviceScene:
         need_rays = "point" in want or "normal" in want
         if rays is None and need_rays:
             raise ValueError("rays: needed for 'point' and 'normal'")
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
         q = abi.RaycaSurfaceQuery()
         q.count = n
-        q.t = contiguous(checked(t, "t", torch.float32, (n,))).data_ptr()
-        q.prim = contiguous(checked(prim, "prim", torch.int32, (n,))).data_ptr()
-        q.uv = contiguous(checked(uv, "uv", torch.float32, (n, 2))).data_ptr()
+        q.t = call.input(t, "t", torch.float32, (n,)).data_ptr()
+        q.prim = call.input(prim, "prim", torch.int32, (n,)).data_ptr()
+        q.uv = call.input(uv, "uv", torch.float32, (n, 2)).data_ptr()
         if rays is not None:
-            q.rays = contiguous(checked(rays, "rays", torch.float32, (n, 6))).data_ptr()
+            q.rays = call.input(rays, "rays", torch.float32, (n, 6)).data_ptr()
         out = dict(out) if out is not None else {}
         stray = [k for k in out if k not in want]
         if stray:
@@ -344,21 +287,12 @@ class DeviceScene:
         result = {}
         for name in want:
             dtype, width = self.SURFACE_OUTPUTS[name]
-            dtype, shape = getattr(torch, dtype), ((n, width) if width else (n,))
-            x = out.get(name)
-            if x is None:
-                x = torch.empty(shape, dtype=dtype, device=dev)
-            elif not checked(x, f"out[{name!r}]", dtype, shape).is_contiguous():
-                raise ValueError(f"out[{name!r}]: an output must be contiguous")
-            result[name] = x
-            setattr(q, name + "_out", x.data_ptr() or None)
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), (n, width) if width else (n,))
+            setattr(q, name + "_out", result[name].data_ptr() or None)
         # (an empty batch has no device pointers; the native call checks everything else and launches nothing)
-        lib.check(self._lib.rayca_hip_surface_device(self.handle, C.byref(o), C.byref(q), C.byref(st) if st is not None else None))
-        record(temporaries)
-        if st is not None:
-            result["stats"] = st.as_dict()
+        stats = call.run(self._lib.rayca_hip_surface_device, q, context=context, want_stats=want_stats)
+        if stats is not None:
+            result["stats"] = stats
         return result
 
     def gbuffer(self, config: Config, width: int, height: int, *, sample=0,
@@ -387,52 +321,38 @@ class DeviceScene:
         tuple with the uint8 tensor and the stats dict (`want_stats` waits) behind it when asked for.
 
         The defaults are starting values: nobody has tuned them on rendered frames."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
-        h, w = color.shape[:2]
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
         if point is not None and sigma_plane is None:
             raise ValueError("sigma_plane: needed with point")
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
-        def output(x, name, dtype):
-            if x is None or x is True:
-                return torch.empty((h, w, 4), dtype=dtype, device=dev)
-            if not checked(x, name, dtype, (h, w, 4)).is_contiguous():
-                raise ValueError(f"{name}: an output must be contiguous")
-            return x
-
         d = abi.RaycaDenoise()
         d.width, d.height, d.iterations, d.normal_power_log2 = w, h, iterations, normal_power_log2
         d.sigma_color, d.sigma_plane, d.gamma = sigma_color, (sigma_plane if sigma_plane is not None else 0.0), gamma
-        out = output(out, "out", torch.float32)   # (before a contiguous copy of `color` replaces the name it may share)
-        d.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
-        for name, x, dtype, shape in (("albedo", albedo, torch.float32, (h, w, 4)), ("normal", normal, torch.float32, (h, w, 3)),
-                                      ("point", point, torch.float32, (h, w, 3)), ("id", id, torch.int32, (h, w))):
-            if x is not None:
-                setattr(d, name, contiguous(checked(x, name, dtype, shape)).data_ptr())
-        d.rgba32f_out = out.data_ptr()
-        out8 = None
-        if rgba8 is not None and rgba8 is not False:
-            out8 = output(rgba8, "rgba8", torch.uint8)
-            d.rgba8_out = out8.data_ptr()
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_denoise_device(self.handle, C.byref(o), C.byref(d), C.byref(st) if st is not None else None))
-        record(temporaries)
-        result = (out,) + ((out8,) if out8 is not None else ()) + ((st.as_dict(),) if st is not None else ())
-        return result[0] if len(result) == 1 else result
+        out = call.output(out, "out", torch.float32, (h, w, 4))
+        out8 = call.output(rgba8, "rgba8", torch.uint8, (h, w, 4), optional=True)
+        d.color = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr()
+        call.guides(d, h, w, albedo=albedo, normal=normal, point=point, id=id)
+        d.rgba32f_out, d.rgba8_out = out.data_ptr(), _ptr(out8)
+        stats = call.run(self._lib.rayca_hip_denoise_device, d, context=context, want_stats=want_stats)
+        return _asked_for(out, out8, stats)
 
     DENOISE_GUIDES = {"albedo": "color", "normal": "normal", "point": "point", "id": "material"}   # guide -> surface output
+
+    def _guide_selection(self, guides):
+        guides = tuple(guides)
+        unknown = [g for g in guides if g not in self.DENOISE_GUIDES]
+        if unknown or len(set(guides)) != len(guides):
+            raise ValueError(f"guides: a selection without repeats of {tuple(self.DENOISE_GUIDES)}, not {guides!r}")
+        return guides
+
+    def _render_linear(self, config, width, height, stream, context):
+        """render_device with gamma forced to 1 into a new (height, width, 4) float32 tensor, nothing waited for"""
+        import dataclasses
+        call = _DeviceCall(self, stream)
+        color = call.output(None, "color", call.torch.float32, (height, width, 4))
+        self.render_device(dataclasses.replace(config, gamma=1.0), width, height, 0, color.data_ptr(), stream=call.handle or None, context=context)
+        return color
 
     def render_denoised(self, config: Config, width: int, height: int, *, guides=("albedo", "normal", "point", "id"), stream=None,
                         context=0, **denoise_kw):
@@ -440,16 +360,10 @@ class DeviceScene:
         to 1 into a tensor, gbuffer() for the guides asked for (albedo = the surface's color, id = its material), then
         denoise(..., gamma=config.gamma) in place.  Returns what denoise() returns; `denoise_kw` are its keywords (with the
         "point" guide sigma_plane defaults to 0.1 world units -- a starting value like the others)."""
-        import dataclasses
-        torch, dev, handle, _, _ = self._torch_call(stream)
-        guides = tuple(guides)
-        unknown = [g for g in guides if g not in self.DENOISE_GUIDES]
-        if unknown or len(set(guides)) != len(guides):
-            raise ValueError(f"guides: a selection without repeats of {tuple(self.DENOISE_GUIDES)}, not {guides!r}")
+        guides = self._guide_selection(guides)
         if "gamma" in denoise_kw or "out" in denoise_kw:
             raise ValueError("gamma comes from config, and the frame is filtered in place")
-        color = torch.empty((height, width, 4), dtype=torch.float32, device=dev)
-        self.render_device(dataclasses.replace(config, gamma=1.0), width, height, 0, color.data_ptr(), stream=handle or None, context=context)
+        color = self._render_linear(config, width, height, stream, context)
         kw = dict(denoise_kw)
         if guides:
             g = self.gbuffer(config, width, height, want=tuple(self.DENOISE_GUIDES[k] for k in guides), stream=stream, context=context)
@@ -476,56 +390,26 @@ class DeviceScene:
         waits) behind it, each when asked for.
 
         The defaults are untuned starting values: nobody has tuned them on rendered frames."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
-        h, w = color.shape[:2]
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
         if point is not None and sigma_plane is None:
             raise ValueError("sigma_plane: needed with point")
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
-        def output(x, name, dtype, shape):
-            if x is None or x is True:
-                return torch.empty(shape, dtype=dtype, device=dev)
-            if not checked(x, name, dtype, shape).is_contiguous():
-                raise ValueError(f"{name}: an output must be contiguous")
-            return x
-
         d = abi.RaycaDenoiseVariance()
         d.width, d.height, d.iterations, d.normal_power_log2 = w, h, iterations, normal_power_log2
         d.min_history = min_history if length is not None else 0
         d.sigma_luminance, d.sigma_plane, d.variance_floor, d.gamma = sigma_luminance, (sigma_plane if sigma_plane is not None else 0.0), variance_floor, gamma
-        # (the outputs before a contiguous copy of an input replaces a name it may share)
-        out = output(out, "out", torch.float32, (h, w, 4))
-        out8 = output(rgba8, "rgba8", torch.uint8, (h, w, 4)) if rgba8 is not None and rgba8 is not False else None
-        var_out = output(variance_out, "variance_out", torch.float32, (h, w)) if variance_out is not None and variance_out is not False else None
-        d.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
-        d.variance = contiguous(checked(variance, "variance", torch.float32, (h, w))).data_ptr()
-        for name, x, dtype, shape in (("length", length, torch.float32, (h, w)), ("albedo", albedo, torch.float32, (h, w, 4)),
-                                      ("normal", normal, torch.float32, (h, w, 3)), ("point", point, torch.float32, (h, w, 3)),
-                                      ("id", id, torch.int32, (h, w))):
-            if x is not None:
-                setattr(d, name, contiguous(checked(x, name, dtype, shape)).data_ptr())
-        d.rgba32f_out = out.data_ptr()
-        if out8 is not None:
-            d.rgba8_out = out8.data_ptr()
-        if var_out is not None:
-            d.variance_out = var_out.data_ptr()
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_denoise_variance_device(self.handle, C.byref(o), C.byref(d), C.byref(st) if st is not None else None))
-        record(temporaries)
-        result = (out,) + ((out8,) if out8 is not None else ()) + ((var_out,) if var_out is not None else ()) + ((st.as_dict(),) if st is not None else ())
-        return result[0] if len(result) == 1 else result
+        out = call.output(out, "out", torch.float32, (h, w, 4))
+        out8 = call.output(rgba8, "rgba8", torch.uint8, (h, w, 4), optional=True)
+        var_out = call.output(variance_out, "variance_out", torch.float32, (h, w), optional=True)
+        d.color = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr()
+        d.variance = call.input(variance, "variance", torch.float32, (h, w)).data_ptr()
+        if length is not None:
+            d.length = call.input(length, "length", torch.float32, (h, w)).data_ptr()
+        call.guides(d, h, w, albedo=albedo, normal=normal, point=point, id=id)
+        d.rgba32f_out, d.rgba8_out, d.variance_out = out.data_ptr(), _ptr(out8), _ptr(var_out)
+        stats = call.run(self._lib.rayca_hip_denoise_variance_device, d, context=context, want_stats=want_stats)
+        return _asked_for(out, out8, var_out, stats)
 
     # ---- guided upsampling: a low-resolution frame onto a full-size G-buffer (rayca_hip_upsample_device) ----
     # guide -> (dtype, channels, the keys of a gbuffer() dict it is taken from, the first one present)
@@ -547,39 +431,19 @@ class DeviceScene:
         (or pass the tensor to write).  `gamma`, `out`, `rgba8`, the stream handling and the return convention are
         denoise()'s; no output may be an input.  Returns the float tensor, or a tuple with the uint8 tensor, the weight and the
         stats dict (`want_stats` waits) behind it, each when asked for."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (h, w, 4)")
-        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8:
-            raise ValueError(f"scale: an integer 1..8, not {scale!r}")
-        h, w = color.shape[:2]
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
+        _scale_ok(scale)
         big_h, big_w = h * scale, w * scale
         low, high = dict(low or {}), dict(high or {})
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
-        def output(x, name, dtype, shape):
-            if x is None or x is True:
-                return torch.empty(shape, dtype=dtype, device=dev)
-            if not checked(x, name, dtype, shape).is_contiguous():
-                raise ValueError(f"{name}: an output must be contiguous")
-            return x
-
         u = abi.RaycaUpsample()
         u.width, u.height, u.scale, u.normal_power_log2 = big_w, big_h, scale, normal_power_log2
         u.sigma_plane, u.gamma = (sigma_plane if sigma_plane is not None else 0.0), gamma
-        out = output(out, "out", torch.float32, (big_h, big_w, 4))
-        out8 = output(rgba8, "rgba8", torch.uint8, (big_h, big_w, 4)) if rgba8 is not None and rgba8 is not False else None
-        weight_out = output(weight, "weight", torch.float32, (big_h, big_w)) if weight is not None and weight is not False else None
-        u.color = contiguous(checked(color, "color", torch.float32, (h, w, 4))).data_ptr()
+        out = call.output(out, "out", torch.float32, (big_h, big_w, 4))
+        out8 = call.output(rgba8, "rgba8", torch.uint8, (big_h, big_w, 4), optional=True)
+        weight_out = call.output(weight, "weight", torch.float32, (big_h, big_w), optional=True)
+        u.color = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr()
         for guide, (dtype, channels, keys) in self.UPSAMPLE_GUIDES.items():
             found = [next((d[k] for k in keys if d.get(k) is not None), None) for d in (low, high)]
             if (found[0] is None) != (found[1] is None):
@@ -590,28 +454,16 @@ class DeviceScene:
                 raise ValueError("sigma_plane: needed with point")
             for x, where, field, (gh, gw) in ((found[0], "low", guide + "_low", (h, w)), (found[1], "high", guide, (big_h, big_w))):
                 shape = (gh, gw, channels) if channels else (gh, gw)
-                setattr(u, field, contiguous(checked(x, f"{where}[{guide!r}]", getattr(torch, dtype), shape)).data_ptr())
-        u.rgba32f_out = out.data_ptr()
-        if out8 is not None:
-            u.rgba8_out = out8.data_ptr()
-        if weight_out is not None:
-            u.weight_out = weight_out.data_ptr()
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_upsample_device(self.handle, C.byref(o), C.byref(u), C.byref(st) if st is not None else None))
-        record(temporaries)
-        result = (out,) + ((out8,) if out8 is not None else ()) + ((weight_out,) if weight_out is not None else ()) + ((st.as_dict(),) if st is not None else ())
-        return result[0] if len(result) == 1 else result
+                setattr(u, field, call.input(x, f"{where}[{guide!r}]", getattr(torch, dtype), shape).data_ptr())
+        u.rgba32f_out, u.rgba8_out, u.weight_out = out.data_ptr(), _ptr(out8), _ptr(weight_out)
+        stats = call.run(self._lib.rayca_hip_upsample_device, u, context=context, want_stats=want_stats)
+        return _asked_for(out, out8, weight_out, stats)
 
     def upsample_guides(self, width: int, height: int, scale: int, *, guides=("albedo", "normal", "point", "id"), stream=None, context=0):
         """The two G-buffers upsample() takes, (low, high): gbuffer() of a one-sample config at width / scale x height / scale and
         at width x height for the guides asked for (albedo = the surface's color, id = its material), on one stream."""
-        guides = tuple(guides)
-        unknown = [g for g in guides if g not in self.DENOISE_GUIDES]
-        if unknown or len(set(guides)) != len(guides):
-            raise ValueError(f"guides: a selection without repeats of {tuple(self.DENOISE_GUIDES)}, not {guides!r}")
-        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8 or width % scale or height % scale:
-            raise ValueError(f"scale: an integer 1..8 that divides width and height, not {scale!r} for {width} x {height}")
+        guides = self._guide_selection(guides)
+        _scale_ok(scale, width, height)
         if not guides:
             return {}, {}
         one = Config(samples_per_pixel=1)   # (points on the rays through pixel centres)
@@ -627,15 +479,10 @@ class DeviceScene:
         with `denoise` (True, or a dict of denoise()'s keywords) the a-trous filter on the low frame with its low guides and
         gamma 1, then upsample(..., gamma=config.gamma).  Returns what upsample() returns; `upsample_kw` are its keywords (with
         the "point" guide sigma_plane defaults to 0.1 world units -- a starting value like the denoiser's)."""
-        import dataclasses
-        torch, dev, handle, _, _ = self._torch_call(stream)
         if "gamma" in upsample_kw or "low" in upsample_kw or "high" in upsample_kw:
             raise ValueError("gamma comes from config, and the guides from `guides`")
-        if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8 or width % scale or height % scale:
-            raise ValueError(f"scale: an integer 1..8 that divides width and height, not {scale!r} for {width} x {height}")
-        w, h = width // scale, height // scale
-        color = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
-        self.render_device(dataclasses.replace(config, gamma=1.0), w, h, 0, color.data_ptr(), stream=handle or None, context=context)
+        _scale_ok(scale, width, height)
+        color = self._render_linear(config, width // scale, height // scale, stream, context)
         low, high = self.upsample_guides(width, height, scale, guides=guides, stream=stream, context=context)
         kw = dict(upsample_kw)
         if "point" in low and kw.get("sigma_plane") is None:
@@ -663,37 +510,20 @@ class DeviceScene:
         the target.  `prev`: a (4,) float32 tensor as this call returns one.  `out`: (hist, exposure) tensors to write instead
         of new ones; exposure may be `prev` itself.  tonemap(exposure=) reads the record where it lies.  Stream handling as
         query(); with `want_stats` (which waits) the stats dict comes third."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
-        h, w = color.shape[:2]
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
         hist, exposure = out if out is not None else (None, None)
-        for x, name, dtype, shape in ((hist, "out[0]", torch.int32, (abi.METER_WORDS,)), (exposure, "out[1]", torch.float32, (4,)),
-                                      (prev, "prev", torch.float32, (4,))):
-            if x is not None and not checked(x, name, dtype, shape).is_contiguous():
-                raise ValueError(f"{name}: must be contiguous")
-        if hist is None:
-            hist = torch.empty((abi.METER_WORDS,), dtype=torch.int32, device=dev)
-        if exposure is None:
-            exposure = torch.empty((4,), dtype=torch.float32, device=dev)
-        temporaries = []
-        checked(color, "color", torch.float32, (h, w, 4))
-        if not color.is_contiguous():
-            color = color.contiguous()
-            temporaries.append(color)
+        hist = call.output(hist, "out[0]", torch.int32, (abi.METER_WORDS,))
+        exposure = call.output(exposure, "out[1]", torch.float32, (4,))
         m = abi.RaycaMeter()
         m.width, m.height, m.low_permille, m.high_permille = w, h, low_permille, high_permille
         m.key, m.min_scale, m.max_scale, m.rate = key, min_scale, max_scale, rate
-        m.color, m.hist_out, m.exposure_out = color.data_ptr(), hist.data_ptr(), exposure.data_ptr()
-        if prev is not None:
-            m.exposure_prev = prev.data_ptr()
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_meter_device(self.handle, C.byref(o), C.byref(m), C.byref(st) if st is not None else None))
-        record(temporaries)
-        return (hist, exposure) + ((st.as_dict(),) if st is not None else ())
+        m.color, m.hist_out, m.exposure_out = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr(), hist.data_ptr(), exposure.data_ptr()
+        if prev is not None:   # (not copied: it may be the record this call writes)
+            m.exposure_prev = call.output(prev, "prev", torch.float32, (4,)).data_ptr()
+        stats = call.run(self._lib.rayca_hip_meter_device, m, context=context, want_stats=want_stats)
+        return (hist, exposure) + ((stats,) if stats is not None else ())
 
     def tonemap(self, color, op="aces", *, exposure=None, scale=1.0, white=0.0, gamma=1.0, rgba8=False, out=None, stream=None, context=0,
                 want_stats=False):
@@ -705,49 +535,23 @@ class DeviceScene:
         value.  The scale is word 0 of `exposure`, a (4,) float32 tensor as meter() returns it -- read on the device, nothing
         waited for -- or else the float `scale`.  `gamma`, `out` (may be `color` itself), `rgba8`, the stream handling and the
         return convention are denoise()'s; out=False with rgba8 writes and returns the uint8 picture alone."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
         if isinstance(op, str):
             if op not in abi.TONEMAP_NAMES:
                 raise ValueError(f"op: one of {abi.TONEMAP_NAMES}, not {op!r}")
             op = abi.TONEMAP_NAMES.index(op)
-        h, w = color.shape[:2]
-        temporaries = []
-
-        def output(x, name, dtype):
-            if x is None or x is True:
-                return torch.empty((h, w, 4), dtype=dtype, device=dev)
-            if not checked(x, name, dtype, (h, w, 4)).is_contiguous():
-                raise ValueError(f"{name}: an output must be contiguous")
-            return x
-
         t = abi.RaycaTonemap()
         t.width, t.height, t.op, t.scale, t.white, t.gamma = w, h, op, scale, white, gamma
-        out = output(out, "out", torch.float32) if out is not False else None   # (before a contiguous copy of `color` replaces the name it may share)
-        checked(color, "color", torch.float32, (h, w, 4))
-        if not color.is_contiguous():
-            color = color.contiguous()
-            temporaries.append(color)
-        t.color = color.data_ptr()
-        if out is not None:
-            t.rgba32f_out = out.data_ptr()
-        if exposure is not None:
-            if not checked(exposure, "exposure", torch.float32, (4,)).is_contiguous():
-                raise ValueError("exposure: must be contiguous")
-            t.exposure = exposure.data_ptr()
-        out8 = None
-        if rgba8 is not None and rgba8 is not False:
-            out8 = output(rgba8, "rgba8", torch.uint8)
-            t.rgba8_out = out8.data_ptr()
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_tonemap_device(self.handle, C.byref(o), C.byref(t), C.byref(st) if st is not None else None))
-        record(temporaries)
-        result = ((out,) if out is not None else ()) + ((out8,) if out8 is not None else ()) + ((st.as_dict(),) if st is not None else ())
-        return result[0] if len(result) == 1 else result
+        out = call.output(out, "out", torch.float32, (h, w, 4)) if out is not False else None
+        out8 = call.output(rgba8, "rgba8", torch.uint8, (h, w, 4), optional=True)
+        t.color = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr()
+        if exposure is not None:   # (not copied: read where meter() wrote it)
+            t.exposure = call.output(exposure, "exposure", torch.float32, (4,)).data_ptr()
+        t.rgba32f_out, t.rgba8_out = _ptr(out), _ptr(out8)
+        stats = call.run(self._lib.rayca_hip_tonemap_device, t, context=context, want_stats=want_stats)
+        return _asked_for(out, out8, stats)
 
     # ---- temporal accumulation: a frame into a history, with reprojection (rayca_hip_scene_camera, rayca_hip_accumulate_device) ----
     def camera_pose(self) -> abi.RaycaCameraPose:
@@ -774,12 +578,9 @@ class DeviceScene:
         adds "moments" (mean and mean square of the luminance), variance=True "variance" (H, W).  `out`: a dict of tensors to
         write instead of new ones; without prev_camera they may be the history's own (a film in place), and out["color"] may
         always be `color`.  Stream handling as query().  Returns a dict: color, length, [moments], [variance], [stats]."""
-        torch, dev, handle, checked, record = self._torch_call(stream)
-        if not isinstance(color, torch.Tensor):
-            raise TypeError(f"color: a torch tensor on {dev} is expected, not {type(color).__name__}")
-        if color.dim() != 3 or color.shape[2] != 4:
-            raise ValueError(f"color: shape {tuple(color.shape)}, expected (H, W, 4)")
-        h, w = color.shape[:2]
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
         history, prev, out = dict(history or {}), dict(prev or {}), dict(out or {})
         for name, d, known in (("history", history, ("color", "length", "moments")), ("prev", prev, ("normal", "point", "id")),
                                ("out", out, ("color", "length", "moments", "variance"))):
@@ -790,15 +591,6 @@ class DeviceScene:
             moments = variance or not history or "moments" in history
         if variance and not moments:
             raise ValueError("variance: needs moments")
-        temporaries = []
-
-        def contiguous(x):
-            if x.is_contiguous():
-                return x
-            x = x.contiguous()
-            temporaries.append(x)
-            return x
-
         shapes = {"color": (torch.float32, (h, w, 4)), "length": (torch.float32, (h, w)), "moments": (torch.float32, (h, w, 2)),
                   "variance": (torch.float32, (h, w)), "point": (torch.float32, (h, w, 3)), "normal": (torch.float32, (h, w, 3)),
                   "id": (torch.int32, (h, w))}
@@ -806,32 +598,119 @@ class DeviceScene:
         a.width, a.height, a.max_history, a.normal_min, a.plane_max = w, h, max_history, normal_min, plane_max
         result = {}
         for name in ("color", "length") + (("moments",) if moments else ()) + (("variance",) if variance else ()):
-            x = out.get(name)   # (before a contiguous copy of an input replaces a tensor it may share)
-            if x is None:
-                x = torch.empty(shapes[name][1], dtype=shapes[name][0], device=dev)
-            elif not checked(x, f"out[{name!r}]", *shapes[name]).is_contiguous():
-                raise ValueError(f"out[{name!r}]: an output must be contiguous")
-            result[name] = x
-            setattr(a, name + "_out", x.data_ptr())
-        a.color = contiguous(checked(color, "color", *shapes["color"])).data_ptr()
+            result[name] = call.output(out.get(name), f"out[{name!r}]", *shapes[name])
+            setattr(a, name + "_out", result[name].data_ptr())
+        a.color = call.input(color, "color", *shapes["color"]).data_ptr()
         for name, x in (("point", point), ("normal", normal), ("id", id)):
             if x is not None:
-                setattr(a, name, contiguous(checked(x, name, *shapes[name])).data_ptr())
+                setattr(a, name, call.input(x, name, *shapes[name]).data_ptr())
         for name, x in history.items():
-            setattr(a, "hist_" + name, contiguous(checked(x, f"history[{name!r}]", *shapes[name])).data_ptr())
+            setattr(a, "hist_" + name, call.input(x, f"history[{name!r}]", *shapes[name]).data_ptr())
         for name, x in prev.items():
-            setattr(a, "prev_" + name, contiguous(checked(x, f"prev[{name!r}]", *shapes[name])).data_ptr())
+            setattr(a, "prev_" + name, call.input(x, f"prev[{name!r}]", *shapes[name]).data_ptr())
         if prev_camera is not None:
             if not isinstance(prev_camera, abi.RaycaCameraPose):
                 raise TypeError(f"prev_camera: a camera_pose() is expected, not {type(prev_camera).__name__}")
             a.prev_camera = C.pointer(prev_camera)
-        st = abi.RaycaStats() if want_stats else None
-        o = self._opts(0, False, None, handle or None, context=context)
-        lib.check(self._lib.rayca_hip_accumulate_device(self.handle, C.byref(o), C.byref(a), C.byref(st) if st is not None else None))
-        record(temporaries)
-        if st is not None:
-            result["stats"] = st.as_dict()
+        stats = call.run(self._lib.rayca_hip_accumulate_device, a, context=context, want_stats=want_stats)
+        if stats is not None:
+            result["stats"] = stats
         return result
+
+
+class _DeviceCall:
+    """One call of a device entry point on torch tensors: the device and stream handling that query(), surface(), camera_rays()
+    and the post passes share, and the tensors the call has to keep alive.  `stream`: a torch.cuda.Stream, a raw handle, or
+    None for torch's current stream of the scene's device.
+
+    The ordering rule: resolve every output() before the input() that may share its tensor (out=color, a film in place) --
+    an input that is not contiguous is replaced by a copy, and the output must still be the caller's tensor."""
+
+    def __init__(self, scene, stream):
+        import torch
+        self.torch, self.scene = torch, scene
+        self.dev = torch.device("cuda", scene.device)
+        self.stream = torch.cuda.current_stream(self.dev) if stream is None else stream
+        self.handle = self.stream.cuda_stream if hasattr(self.stream, "cuda_stream") else int(self.stream)
+        if not self.handle:
+            # the legacy default stream: the library runs a call without a stream on the context's own (non-blocking) stream
+            # and waits for it, so what torch still has queued for the inputs must have finished first
+            torch.cuda.default_stream(self.dev).synchronize()
+        self.temporaries = []
+
+    def checked(self, x, name, dtype, shape):
+        if not isinstance(x, self.torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on {self.dev} is expected, not {type(x).__name__}")
+        if x.device != self.dev:
+            raise ValueError(f"{name}: on {x.device}, the scene is on {self.dev}")
+        if x.dtype != dtype:
+            raise TypeError(f"{name}: dtype {x.dtype}, expected {dtype}")
+        if tuple(x.shape) != shape:
+            raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
+        return x
+
+    def image(self, color, name="color"):
+        """(H, W) of an (H, W, 4) tensor; input() checks the rest of it"""
+        if not isinstance(color, self.torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on {self.dev} is expected, not {type(color).__name__}")
+        if color.dim() != 3 or color.shape[2] != 4:
+            raise ValueError(f"{name}: shape {tuple(color.shape)}, expected (H, W, 4)")
+        return color.shape[0], color.shape[1]
+
+    def input(self, x, name, dtype, shape):
+        x = self.checked(x, name, dtype, shape)
+        if not x.is_contiguous():
+            x = x.contiguous()
+            self.temporaries.append(x)
+        return x
+
+    def output(self, x, name, dtype, shape, optional=False):
+        """The tensor to write: `x` itself (checked, contiguous), or a new one for None / True; with `optional`, None / False
+        mean that the output is not asked for."""
+        if optional and (x is None or x is False):
+            return None
+        if x is None or x is True:
+            return self.torch.empty(shape, dtype=dtype, device=self.dev)
+        if not self.checked(x, name, dtype, shape).is_contiguous():
+            raise ValueError(f"{name}: must be contiguous (an output, or an input that is read in place)")
+        return x
+
+    def guides(self, args, h, w, **guides):
+        """the guides that are given, into the fields of `args` that carry their names"""
+        f32, i32 = self.torch.float32, self.torch.int32
+        shapes = {"albedo": (f32, (h, w, 4)), "normal": (f32, (h, w, 3)), "point": (f32, (h, w, 3)), "id": (i32, (h, w))}
+        for name, x in guides.items():
+            if x is not None:
+                setattr(args, name, self.input(x, name, *shapes[name]).data_ptr())
+
+    def options(self, context, traversal=0, collect_stats=False, tile=None):
+        return self.scene._opts(traversal, collect_stats, tile, self.handle or None, context=context)
+
+    def run(self, fn, args, *, context, want_stats=False, **options):
+        """fn(scene, options, args, stats) through lib.check; returns the stats dict (the call has waited) or None"""
+        st = abi.RaycaStats() if want_stats else None
+        o = self.options(context, **options)
+        lib.check(fn(self.scene.handle, C.byref(o), C.byref(args), C.byref(st) if st is not None else None))
+        # (a contiguous copy made here is read by a kernel on the stream: the allocator must know)
+        for x in self.temporaries:
+            x.record_stream(self.stream if hasattr(self.stream, "cuda_stream") else self.torch.cuda.ExternalStream(self.handle, device=self.dev))
+        return st.as_dict() if st is not None else None
+
+
+def _ptr(x):
+    return x.data_ptr() if x is not None else None
+
+
+def _asked_for(*parts):
+    """The return convention of the post passes: what was asked for in the order given -- the float tensor, then the optional
+    tensors and the stats dict -- as a tuple, or alone where it is the only thing."""
+    result = tuple(x for x in parts if x is not None)
+    return result[0] if len(result) == 1 else result
+
+
+def _scale_ok(scale, width=0, height=0):
+    if not isinstance(scale, int) or isinstance(scale, bool) or not 1 <= scale <= 8 or width % scale or height % scale:
+        raise ValueError(f"scale: an integer 1..8 that divides width and height, not {scale!r} for {width} x {height}")
 
 
 def _multi_args(scenes, config, band_rows, gather, traversal, collect_stats, engine, context):

@@ -142,6 +142,17 @@ def test_in_place_equals_out_of_place(ds, iterations):
         assert np.array_equal(bits(want[0]), bits(s["color"])) and np.array_equal(want[1], dl.quantize(s["color"]))
 
 
+def test_strided_inputs_equal_contiguous_ones(ds):
+    """an input that is not contiguous reaches the kernels as a contiguous copy: the contiguous call's bits"""
+    import torch
+    from strided import strided
+    s = frame(65, 5)
+    want = run(ds, s, GUIDES, iterations=2)
+    out, out8 = ds.denoise(strided(dev(s["color"])), rgba8=True, iterations=2, **strided(guide_kw(s, GUIDES, True)))
+    torch.cuda.synchronize()
+    assert_same((out.cpu().numpy(), out8.cpu().numpy()), want, "strided inputs")
+
+
 def test_stream_and_context_do_not_change_the_result(ds):
     import torch
     s = frame(130, 70)

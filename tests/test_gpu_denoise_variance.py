@@ -177,6 +177,18 @@ def test_in_place_equals_out_of_place(ds, iterations):
         assert_same((color.cpu().numpy(), out8.cpu().numpy(), variance.cpu().numpy()), want, f"in place, {iterations} iterations, guides {which}")
 
 
+def test_strided_inputs_equal_contiguous_ones(ds):
+    """an input that is not contiguous reaches the kernels as a contiguous copy: the contiguous call's bits"""
+    import torch
+    from strided import strided
+    s = frame(65, 5)
+    want = run(ds, s, GUIDES, iterations=2)
+    out, out8, var = ds.denoise_variance(strided(dev(s["color"])), strided(dev(s["variance"])), length=strided(dev(s["length"])), rgba8=True,
+                                         variance_out=True, iterations=2, **strided(guide_kw(s, GUIDES, True)))
+    torch.cuda.synchronize()
+    assert_same((out.cpu().numpy(), out8.cpu().numpy(), var.cpu().numpy()), want, "strided inputs")
+
+
 def test_stream_and_context_do_not_change_the_result(ds):
     import torch
     s = frame(130, 70)

@@ -186,6 +186,18 @@ def test_in_place_equals_out_of_place_and_eight_frames_equal_the_literal(ds):
 
 
 # ---- 4: the ways of making one call -----------------------------------------------------------------------------------------
+def test_strided_inputs_equal_contiguous_ones(ds):
+    """an input that is not contiguous reaches the kernel as a contiguous copy: the contiguous call's bits"""
+    import torch
+    from strided import strided
+    a, b, hist = case(65, 5)
+    which = ("normal", "point", "id")
+    want = run(ds, b["color"], variance=True, **arguments(b, a, hist, which, True))
+    got = ds.accumulate(strided(dev(b["color"])), variance=True, **strided(arguments(b, a, hist, which, True)))
+    torch.cuda.synchronize()
+    assert_same(host(got), want, "strided inputs")
+
+
 def test_stream_and_context_do_not_change_the_result(ds):
     import torch
     a, b, hist = case(130, 70)

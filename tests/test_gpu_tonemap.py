@@ -269,6 +269,14 @@ def test_gamma_is_the_denoisers_output_stage(ds, op):
 
 
 # ---- 3: both entries ---------------------------------------------------------------------------------------------------------------
+def test_a_strided_frame_equals_a_contiguous_one(ds):
+    """a frame that is not contiguous reaches the kernels as a contiguous copy: the contiguous calls' words and bits"""
+    from strided import strided
+    c = frame(65, 5)
+    assert_meter(metered(ds, strided(dev(c))), metered(ds, c), "strided frame")
+    assert_picture(mapped(ds, strided(dev(c)), "reinhard", scale=2.0, rgba8=True), mapped(ds, c, "reinhard", scale=2.0, rgba8=True), "strided frame")
+
+
 def test_a_callers_stream_another_context_and_the_statistics(ds):
     import torch
     c = frame(333, 77)

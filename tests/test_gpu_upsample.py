@@ -144,6 +144,18 @@ def test_the_special_values_are_where_the_specification_puts_them(ds):
     assert (weight[~thin & ~near_nan] > 0).all()
 
 
+def test_strided_inputs_equal_contiguous_ones(ds):
+    """an input that is not contiguous reaches the kernel as a contiguous copy: the contiguous call's bits"""
+    import torch
+    from strided import strided
+    low, high = case(65, 5, 2)
+    want = run(ds, low, high, 2, ul.GUIDES)
+    out = ds.upsample(strided(dev(low["color"])), 2, low=strided(dev_guides(low, ul.GUIDES)), high=strided(dev_guides(high, ul.GUIDES)),
+                      sigma_plane=SIGMA_PLANE, rgba8=True, weight=True)
+    torch.cuda.synchronize()
+    assert_same(tuple(x.cpu().numpy() for x in out), want, "strided inputs")
+
+
 def test_a_callers_stream_another_context_and_the_statistics(ds):
     import torch
     low, high = case(31, 19, 2)
