@@ -45,7 +45,8 @@ extern "C" {
                                   rayca_hip_accumulate_device; the variance-guided denoiser: RaycaDenoiseVariance,
                                   rayca_hip_denoise_variance_device; guided upsampling: RaycaUpsample,
                                   rayca_hip_upsample_device; exposure metering and tone mapping: RaycaMeter,
-                                  rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_ */
+                                  rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_;
+                                  radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -696,6 +697,47 @@ int32_t rayca_hip_surface_device(RaycaScene* scene, const RaycaRenderOptions* op
  * render call. */
 int32_t rayca_hip_camera_rays_device(RaycaScene* scene, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample,
                                      const RaycaRenderOptions* opts, void* d_rays_out);
+
+/* Radiance along caller-supplied rays, on DEVICE memory: what light arrives along ray i, where rayca_hip_query_device says where
+ * the ray hits.  out[i] is what the pixel of a one-sample frame of `cfg` receives whose camera ray is rays[i] and whose index
+ * y * width + x is first_index + i: Integrator::trace on the ray (integrator/flat.rs:16-28, pathtracer.rs:68-106), BLACK + colour
+ * (scene.rs:143-145), cfg->gamma and the quantisation of a render call (scene.rs:146-148).  The path of ray i draws its random
+ * numbers from the stream of (cfg->seed, pixel index first_index + i, sample).  Hence, bit for bit:
+ *   a frame   rays = rayca_hip_camera_rays_device(cfg with samples_per_pixel 1, w, h, sample 0), count = w * h, sample = 0,
+ *             first_index = 0: both outputs equal rayca_hip_render_device(cfg, w, h)'s, on either engine, and rays_shadow,
+ *             rays_bounce and (with collect_stats) hits_shaded of RaycaStats equal the frame's; rays_primary = count.
+ *   chunks    any split of a ray set into consecutive calls, each with the first_index of its first ray, writes what one call does.
+ *   Flat      (no random numbers) depends on the ray alone: on a hit r, g, b are 0 + rayca_hip_surface_device's `color` for the
+ *             record rayca_hip_query_device returns for the ray, a miss is a render's miss pixel; a degenerate ray (NaN, zero
+ *             direction) is shaded as whatever the query says of it.
+ * Several samples are several calls with different `sample`, folded by the caller (e.g. rayca_hip_accumulate_device).
+ * Configs: those the generation kernels render -- Flat; Pathtracer with direct sampler NEE or NONE, indirect sampler COSINE or
+ * HEMISPHERE, no Russian roulette, and light_samples == 1 where the path bounces.  Everything else is RAYCA_ERR_UNSUPPORTED with
+ * the field named in rayca_hip_last_error: the per-pixel stack machine has no ray-fed form.  cfg->samples_per_pixel and cfg->bvh
+ * are not read.  No camera is needed.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event and
+ * collect_stats as for rayca_hip_render_device; tile, engine and camera_rays must be zero, RAYCA_TRAVERSAL_EXHAUSTIVE is
+ * RAYCA_ERR_UNSUPPORTED.  The call is ordered on its context like a frame and uses that context's work buffers (ray queues,
+ * per-depth path records: 32 B a ray per queue, 36 B a ray and depth); calls and frames on different contexts overlap.  It is
+ * asynchronous unless stats_out is given; then it waits and fills RaycaStats as a frame of the wavefront engine does, the pass
+ * that queues the rays under RAYCA_KERNEL_OTHER, rows_rendered = 1.  Nothing outside [0, count) of an output is written.
+ * Checked first, from the structs alone and in this order, as RAYCA_ERR_BAD_ARG: NULL scene / cfg / radiance, first_index + count
+ * above 2^32 (or count above 2^31), non-zero reserved, NULL rays, no output, rgba32f_out not 16-byte aligned, unknown integrator or
+ * sampler, light_samples == 0, then opts: context > 7, a non-zero field that does not apply.  Then RAYCA_ERR_UNSUPPORTED for the
+ * traversal and the Config.  count == 0 is then RAYCA_OK and launches nothing.  Then the scene: RAYCA_ERR_EMPTY_SCENE as for a
+ * query, RAYCA_ERR_UNSUPPORTED for a directional light under NEE (nee.rs:178). */
+struct RaycaRadiance {
+  uint32_t count;        /* rays */
+  uint32_t sample;       /* RNG stream of the paths: ray i draws from rng_root(cfg->seed, first_index + i, sample) */
+  uint32_t first_index;  /* the "pixel index" of ray 0; first_index + count <= 2^32 */
+  uint32_t reserved;     /* must be zero */
+  const void* rays;      /* DEVICE: count x 6 f32 (origin xyz, direction xyz; the direction need not be normalised) */
+  void* rgba32f_out;     /* DEVICE: count x 4 f32, or NULL; 16-byte aligned */
+  void* rgba8_out;       /* DEVICE: count x 4 u8, or NULL; not both NULL */
+};
+typedef struct RaycaRadiance RaycaRadiance;
+int32_t rayca_hip_radiance_device(RaycaScene* scene, const RaycaConfig* cfg, const RaycaRenderOptions* opts, const RaycaRadiance* radiance,
+                                  RaycaStats* stats_out);
 
 /* The edge-avoiding a-trous wavelet denoiser, on a frame and its G-buffer in DEVICE memory: what rayca_hip_render_device wrote to
  * d_rgba32f_out (rendered with gamma 1) and what rayca_hip_surface_device wrote for the frame's camera rays go in, the filtered

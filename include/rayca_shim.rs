@@ -323,6 +323,19 @@ pub struct RaycaSurfaceQuery {
     pub flags_out: *mut c_void,
 }
 
+// rayca_hip_radiance_device: radiance along caller-supplied rays, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaRadiance {
+    pub count: u32,
+    pub sample: u32,
+    pub first_index: u32,
+    pub reserved: u32,
+    pub rays: *const c_void,
+    pub rgba32f_out: *mut c_void,
+    pub rgba8_out: *mut c_void,
+}
+
 // rayca_hip_denoise_device: the a-trous filter on a frame and its G-buffer, all in DEVICE memory
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -549,6 +562,7 @@ extern "C" {
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
+    pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;

@@ -317,6 +317,19 @@ class RaycaSurfaceQuery(C.Structure):
     ]
 
 
+class RaycaRadiance(C.Structure):
+    """rayca_hip_radiance_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("sample", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("rays", C.c_void_p),
+        ("rgba32f_out", C.c_void_p),
+        ("rgba8_out", C.c_void_p),
+    ]
+
+
 # RaycaSurfaceQuery.flags_out
 SURFACE_KIND_MASK, SURFACE_EMISSIVE, SURFACE_SPHERE, SURFACE_HIT = 3, 4, 8, 0x80000000
 
@@ -592,6 +605,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_surface_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceQuery), P(RaycaStats)]
     lib.rayca_hip_camera_rays_device.restype = C.c_int32
     lib.rayca_hip_camera_rays_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(RaycaRenderOptions), C.c_void_p]
+    lib.rayca_hip_radiance_device.restype = C.c_int32
+    lib.rayca_hip_radiance_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaRadiance), P(RaycaStats)]
     lib.rayca_hip_denoise_device.restype = C.c_int32
     lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
     lib.rayca_hip_scene_camera.restype = C.c_int32
@@ -627,7 +642,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
-    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_denoise_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",

@@ -597,21 +597,29 @@ bool wavefront_by_default(uint32_t generations) {
 // Can the generation kernels (k_generation + k_resolve) render this Config?  They cover Flat and the
 // Pathtracer with Nee/None direct and Cosine/Hemisphere indirect sampling, one indirect sample per vertex
 // and no roulette; everything else runs on the per-pixel stack machine (k_general).
-bool generation_kernels_cover(const RaycaScene* s, const RaycaConfig& c) {
-  if (c.integrator == RAYCA_INTEGRATOR_FLAT) return true;
-  if (c.integrator != RAYCA_INTEGRATOR_PATHTRACER) return false;
-  if (c.russian_roulette) return false;
-  if (c.direct_sampler != RAYCA_SAMPLER_NONE && c.direct_sampler != RAYCA_SAMPLER_NEE) return false;
+// The two halves of that question: the field of the Config that takes it off the generation kernels (nullptr: none does), which
+// needs no scene, and the one thing the scene adds.
+const char* generation_kernels_gap(const RaycaConfig& c) {
+  if (c.integrator == RAYCA_INTEGRATOR_FLAT) return nullptr;
+  if (c.integrator != RAYCA_INTEGRATOR_PATHTRACER) return "integrator";
+  if (c.russian_roulette) return "russian_roulette";
+  if (c.direct_sampler != RAYCA_SAMPLER_NONE && c.direct_sampler != RAYCA_SAMPLER_NEE) return "direct_sampler";
   const uint32_t limit = c.direct_sampler != RAYCA_SAMPLER_NONE ? (c.max_depth ? c.max_depth - 1u : 0u) : c.max_depth;
   const bool bounces = limit > 0 && c.max_depth > 0;
   if (bounces) {
-    if (c.indirect_sampler != RAYCA_SAMPLER_COSINE && c.indirect_sampler != RAYCA_SAMPLER_HEMISPHERE) return false;
-    if (c.light_samples != 1) return false;
+    if (c.indirect_sampler != RAYCA_SAMPLER_COSINE && c.indirect_sampler != RAYCA_SAMPLER_HEMISPHERE) return "indirect_sampler";
+    if (c.light_samples != 1) return "light_samples";
   }
-  if (c.direct_sampler == RAYCA_SAMPLER_NEE)
+  return nullptr;
+}
+bool nee_meets_directional_light(const RaycaScene* s, const RaycaConfig& c) {
+  if (c.integrator == RAYCA_INTEGRATOR_PATHTRACER && c.direct_sampler == RAYCA_SAMPLER_NEE)
     for (const HostLight& l : s->host.lights)
-      if (l.kind == RAYCA_LIGHT_DIRECTIONAL) return false;  // todo!() in the reference (nee.rs:178): k_general reports it
-  return true;
+      if (l.kind == RAYCA_LIGHT_DIRECTIONAL) return true;  // todo!() in the reference (nee.rs:178): k_general reports it
+  return false;
+}
+bool generation_kernels_cover(const RaycaScene* s, const RaycaConfig& c) {
+  return generation_kernels_gap(c) == nullptr && !nee_meets_directional_light(s, c);
 }
 
 int32_t validate_config(const RaycaScene* s, const RaycaConfig& c, uint32_t engine, LaunchPlan& plan) {
@@ -708,7 +716,13 @@ WfShadowKernel pick_wf_shadow(int flavour, bool sph, bool stats) {
   if (sph) return stats ? wf_shadow_kernel<GEN0, true, true>(flavour) : wf_shadow_kernel<GEN0, true, false>(flavour);
   return stats ? wf_shadow_kernel<GEN0, false, true>(flavour) : wf_shadow_kernel<GEN0, false, false>(flavour);
 }
-WfShadeKernel pick_wf_shade(int mode, bool gen0, bool fused, bool sph) {
+// rays: generation 0 of rayca_hip_radiance_device -- queue-fed, and a path's first vertex (k_wf_shade's RAYS); its Flat form
+// finalises in place
+WfShadeKernel pick_wf_shade(int mode, bool gen0, bool fused, bool sph, bool rays) {
+  if (rays) {
+    if (mode == kModeFlat) return sph ? k_wf_shade<kModeFlat, false, true, true, true> : k_wf_shade<kModeFlat, false, true, false, true>;
+    return sph ? k_wf_shade<kModePath, false, false, true, true> : k_wf_shade<kModePath, false, false, false, true>;
+  }
   if (mode == kModeFlat) {
     if (fused) return sph ? k_wf_shade<kModeFlat, true, true, true> : k_wf_shade<kModeFlat, true, true, false>;
     return sph ? k_wf_shade<kModeFlat, true, false, true> : k_wf_shade<kModeFlat, true, false, false>;
@@ -855,6 +869,7 @@ struct Frame {
   float4* rgba32f;
   uint32_t in_flight;               // frames_in_flight_hint
   bool fused;                       // one generation, one sample: the generation kernel writes the pixel (no k_resolve)
+  bool rays;                        // rayca_hip_radiance_device: generation 0 reads the caller's rays from a queue, not the camera
   bool timing;                      // RaycaStats asked for: every launch timed
   bool all_formats;                 // formats_ready
   uint32_t node_format;             // RaycaStats.node_format
@@ -877,14 +892,15 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   RaycaScene* s = f.s;
   FrameCtx* c = f.c;
   const bool sph = s->host.sphere_count != 0, fast = s->dev.ref_leaf_of != nullptr, stats = f.plan.stats;
+  const bool gen0 = g == 0 && !f.rays;   // camera rays; the caller's rays (rayca_hip_radiance_device) are a queue like any bounce generation's
   if (fast)   // (the formats these kernels are compiled for: RAYCA_WF_*, trace_core.inc)
-    f.node_format |= g == 0 ? ((RAYCA_WF_PRIMARY_WIDE ? 1u : 0u) | (RAYCA_WF_PRIMARY_HALF ? 4u : 0u)) : ((RAYCA_WF_BOUNCE_WIDE ? 2u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 8u : 0u));
+    f.node_format |= gen0 ? ((RAYCA_WF_PRIMARY_WIDE ? 1u : 0u) | (RAYCA_WF_PRIMARY_HALF ? 4u : 0u)) : ((RAYCA_WF_BOUNCE_WIDE ? 2u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 8u : 0u));
   // 16 LDS entries per lane (16 KiB per block) so that the lean kernels' occupancy is set by registers
   // (the wide tree never needs more pending entries than the binary one: one plan serves both)
   const StackPlan sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
   const int flavour = !fast ? 2 : (sp.spill_entries ? 1 : 0);
   const uint32_t npix = f.pb.npix;
-  const uint32_t batches = g == 0 ? f.fp.tile_count : (npix + 63u) / 64u;
+  const uint32_t batches = gen0 ? f.fp.tile_count : (npix + 63u) / 64u;
   const uint32_t grid = (batches + 3u) / 4u;  // one thread per ray, four 8x8 tiles per block
   const uint32_t nls = (f.plan.mode == kModePath && f.cfg.direct_sampler == RAYCA_SAMPLER_NEE) ? (uint32_t)s->host.lights.size() * f.cfg.light_samples : 0u;
   int32_t rc;
@@ -906,21 +922,23 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   static const int shadow_refill_mode = [] { const char* e = getenv("RAYCA_WF_SHADOW_REFILL"); return e ? atoi(e) : 1; }();
   TraceLaunch tl{};
   uint32_t lgrid = grid;
-  bool refill = wf_refill && g != 0 && fast;
-  if (refill && (rc = persistent_grid(s, queue_refill_kernel(sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
+  // (a caller's rays on a SAH scene always: k_queue_refill has a form with the slack rays from anywhere need, k_wf_trace<false> has not)
+  const bool caller_rays = f.rays && g == 0;
+  bool refill = (wf_refill || caller_rays) && !gen0 && fast;
+  if (refill && (rc = persistent_grid(s, queue_refill_kernel(sph, stats, caller_rays), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
   if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
   if (refill) tl.ticket = 1u;
-  WfTraceKernel kt = g == 0 ? pick_wf_trace<true>(flavour, sph, stats) : pick_wf_trace<false>(flavour, sph, stats);
+  WfTraceKernel kt = gen0 ? pick_wf_trace<true>(flavour, sph, stats) : pick_wf_trace<false>(flavour, sph, stats);
   rc = timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_QUEUE_REFILL : RAYCA_KERNEL_WF_TRACE, f.timing, true, [&] {
     if (refill)
-      launch_queue_refill(sph, stats, lgrid, sp.lds_bytes, f.stream, *f.dscene, q.in, q.in_count, wb.hits, c->heads, c->counters, tl);
+      launch_queue_refill(sph, stats, caller_rays, lgrid, sp.lds_bytes, f.stream, *f.dscene, q.in, q.in_count, wb.hits, c->heads, c->counters, tl);
     else
       hipLaunchKernelGGL(kt, dim3(lgrid), dim3(kBlock), sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, wb, c->counters, tl);
     return RAYCA_OK;
   });
   if (rc != RAYCA_OK) return rc;
-  WfShadeKernel ks = pick_wf_shade(f.plan.mode, g == 0, f.fused, sph);
-  const uint32_t shade_grid = ((g == 0 ? f.fp.tile_count * 64u : npix) + kShadeBlock - 1) / kShadeBlock;
+  WfShadeKernel ks = pick_wf_shade(f.plan.mode, gen0, f.fused, sph, caller_rays);
+  const uint32_t shade_grid = ((gen0 ? f.fp.tile_count * 64u : npix) + kShadeBlock - 1) / kShadeBlock;
   rc = timed_launch(f.log, f.stream, RAYCA_KERNEL_WF_SHADE, f.timing, false, [&] {
     hipLaunchKernelGGL(ks, dim3(shade_grid), dim3(kShadeBlock), 0, f.stream, *f.dscene, f.fp, q.in, q.in_count, q.out, q.out_count, wb, f.pb, g,
                        f.rgba8, f.rgba32f, c->shade_stats);
@@ -928,15 +946,15 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   });
   if (rc != RAYCA_OK || !nls) return rc;
   lgrid = grid;
-  refill = wf_refill && fast && (g != 0 ? shadow_refill_mode >= 1 : shadow_refill_mode >= 2);
-  if (refill && (rc = persistent_grid(s, shadow_refill_kernel(g == 0, sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
+  refill = wf_refill && fast && (!gen0 ? shadow_refill_mode >= 1 : shadow_refill_mode >= 2);
+  if (refill && (rc = persistent_grid(s, shadow_refill_kernel(gen0, sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
   if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
   if (refill) tl.ticket = 1u;
-  WfShadowKernel kh = g == 0 ? pick_wf_shadow<true>(flavour, sph, stats) : pick_wf_shadow<false>(flavour, sph, stats);
+  WfShadowKernel kh = gen0 ? pick_wf_shadow<true>(flavour, sph, stats) : pick_wf_shadow<false>(flavour, sph, stats);
   const ShadowRefillArgs sa{wb.sh_ray, wb.sh_x, wb.nls, f.pb.direct, f.pb.state, f.pb.npix};
   return timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_SHADOW_REFILL : RAYCA_KERNEL_WF_SHADOW, f.timing, true, [&] {
     if (refill)
-      launch_shadow_refill(g == 0, sph, stats, lgrid, sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, sa, g, c->heads_b, c->counters, tl);
+      launch_shadow_refill(gen0, sph, stats, lgrid, sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, sa, g, c->heads_b, c->counters, tl);
     else
       hipLaunchKernelGGL(kh, dim3(lgrid), dim3(kBlock), sp.lds_bytes, f.stream, *f.dscene, f.fp, q.in, q.in_count, wb, f.pb, g, c->counters, tl);
     return RAYCA_OK;
@@ -1222,6 +1240,20 @@ void camera_sample_params(uint32_t spp, uint32_t sample, FrameParams& fp) {
   fp.sub_offset = sub_offset;
 }
 
+// What the integrators read from FrameParams: the Config of the frame (f.cfg, f.plan and f.dscene are set).
+void config_frame_params(const Frame& f, FrameParams& fp) {
+  const RaycaConfig& cfg = f.cfg;
+  fp.integrator = cfg.integrator; fp.direct_sampler = cfg.direct_sampler; fp.indirect_sampler = cfg.indirect_sampler;
+  fp.light_samples = cfg.light_samples; fp.light_stratify = cfg.light_stratify;
+  fp.strate_count = cfg.light_stratify ? (uint32_t)sqrtf((float)cfg.light_samples) : 1u;  // config.rs:73-79
+  fp.max_depth = cfg.max_depth; fp.russian_roulette = cfg.russian_roulette; fp.seed = cfg.seed; fp.spp = cfg.samples_per_pixel;
+  fp.inv_gamma = 1.0f / cfg.gamma;  // color/mod.rs:175-176
+  // Not with exhaustive traversal, which reproduces the reference's test counts: every sample traced.  And not where the tree is a
+  // single leaf: a ray's whole search is then the root box and that leaf -- there is no traversal to save -- and the accounting
+  // "every counted ray has tested the root box" (boxes_tested >= rays, exact for such a scene: tests/test_gpu_engines.py) holds.
+  fp.nee_skip = f.s->nee_skip && f.plan.ordered && !(f.dscene->root_ref & kLeafFlag) ? 1u : 0u;
+}
+
 // One frame.  The caller holds the frame context's mutex (render_impl and rayca_hip_render take it): everything a
 // context owns -- work buffers, events, its stream, the staging buffers of rayca_hip_render -- is touched under it.
 int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, uint32_t height, const RaycaRenderOptions* opts_in,
@@ -1263,15 +1295,7 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   f.rgba32f = static_cast<float4*>(d_rgba32f);
 
   FrameParams& fp = f.fp;   // (the frame's geometry and camera are in it: camera_frame_params above)
-  fp.integrator = cfg.integrator; fp.direct_sampler = cfg.direct_sampler; fp.indirect_sampler = cfg.indirect_sampler;
-  fp.light_samples = cfg.light_samples; fp.light_stratify = cfg.light_stratify;
-  fp.strate_count = cfg.light_stratify ? (uint32_t)sqrtf((float)cfg.light_samples) : 1u;  // config.rs:73-79
-  fp.max_depth = cfg.max_depth; fp.russian_roulette = cfg.russian_roulette; fp.seed = cfg.seed; fp.spp = cfg.samples_per_pixel;
-  fp.inv_gamma = 1.0f / cfg.gamma;  // color/mod.rs:175-176
-  // Not with exhaustive traversal, which reproduces the reference's test counts: every sample traced.  And not where the tree is a
-  // single leaf: a ray's whole search is then the root box and that leaf -- there is no traversal to save -- and the accounting
-  // "every counted ray has tested the root box" (boxes_tested >= rays, exact for such a scene: tests/test_gpu_engines.py) holds.
-  fp.nee_skip = s->nee_skip && plan.ordered && !(f.dscene->root_ref & kLeafFlag) ? 1u : 0u;
+  config_frame_params(f, fp);
 
   // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
   // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
@@ -2157,6 +2181,117 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   HIP_TRY(hipGetLastError());
   if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
   return pass_finish(pass, 1, nullptr);
+}
+
+// Radiance along the caller's rays: a one-sample frame of the wavefront engine whose generation 0 reads its rays from a queue
+// that k_enqueue_rays (wavefront.inc) fills -- queue 1, the queue generation 1 writes over once generation 0 has read it -- so
+// every generation runs the queue-fed kernels: closest hits on k_queue_refill (SAH scenes) or k_wf_trace<false>, shading on
+// k_wf_shade<.., RAYS> at depth 0, shadow rays on k_shadow_refill<false> / k_wf_shadow<false>.  "Pixel" i is ray i; k_resolve
+// (one sample: it finalises) or the Flat shade kernel writes out[i].
+int32_t rayca_hip_radiance_device(RaycaScene* s, const RaycaConfig* cfg_in, const RaycaRenderOptions* opts_in, const RaycaRadiance* rin,
+                                  RaycaStats* stats_out) {
+  if (!s || !cfg_in || !rin) return fail(RAYCA_ERR_BAD_ARG, "null scene, config or RaycaRadiance");
+  const RaycaRadiance& rr = *rin;
+  const RaycaConfig& cfg = *cfg_in;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if ((uint64_t)rr.first_index + rr.count > (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.first_index + count exceeds 2^32");
+  if (rr.count > (1u << 31)) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.count exceeds 2^31");
+  if (rr.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.reserved must be zero");
+  if (!rr.rays) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.rays: null rays");
+  if (!rr.rgba32f_out && !rr.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output: RaycaRadiance.rgba32f_out and rgba8_out are both null");
+  if (reinterpret_cast<uintptr_t>(rr.rgba32f_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.rgba32f_out must be 16-byte aligned");
+  if (cfg.integrator > RAYCA_INTEGRATOR_PATHTRACER) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.integrator: unknown integrator");
+  if (cfg.direct_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.direct_sampler: unknown sampler");
+  if (cfg.indirect_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.indirect_sampler: unknown sampler");
+  if (cfg.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.light_samples must be > 0");
+  int32_t rc = pass_options(o, "a radiance query", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  // what the queue-fed generation kernels do not cover (the per-pixel stack machine and the exhaustive instantiations have no
+  // queue-fed form)
+  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: a radiance query has no exhaustive form");
+  if (const char* field = generation_kernels_gap(cfg))
+    return fail(RAYCA_ERR_UNSUPPORTED, std::string("RaycaConfig.") + field + ": a radiance query runs on the generation kernels only (Flat; Pathtracer with NEE or no direct sampler, cosine or hemisphere bounces, no roulette, one light sample where it bounces)");
+  if (rr.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if (nee_meets_directional_light(s, cfg)) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaConfig.direct_sampler: a directional light under NEE is a todo!() of the reference (nee.rs:178)");
+
+  FrameCtx* c = &s->ctx[o.context];
+  std::lock_guard<std::mutex> lock(c->mu);
+  Frame f{};
+  f.s = s;
+  f.cfg = cfg;
+  f.cfg.samples_per_pixel = 1;   // (not read from the caller's: a call is one sample of every ray)
+  f.opts = o;
+  f.rays = true;
+  const bool flat = cfg.integrator == RAYCA_INTEGRATOR_FLAT;
+  f.plan = LaunchPlan{flat ? kModeFlat : kModePath, true, o.collect_stats != 0, true, flat ? 1u : cfg.max_depth};
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  f.c = f.log.c = pass.c;
+  const hipStream_t stream = f.stream = pass.stream;
+  if ((rc = formats_wait(s)) != RAYCA_OK) return rc;   // (the wavefront engine's kernels are tied to the 4-wide / fp16 nodes)
+  f.all_formats = formats_ready(s);
+  f.dscene = f.all_formats ? &s->dev_full : &s->dev;
+  f.in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
+  f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
+  f.rgba8 = static_cast<uint8_t*>(rr.rgba8_out);
+  f.rgba32f = static_cast<float4*>(rr.rgba32f_out);
+  f.timing = pass.timing;
+  f.fused = flat;
+
+  // the "frame" is one row of `count` pixels; none of the camera's terms is read by a queue-fed kernel
+  FrameParams& fp = f.fp;
+  fp.width = rr.count; fp.height = 1; fp.rows = 1;
+  fp.part = 0; fp.parts = 1; fp.band = 1;
+  config_frame_params(f, fp);
+  fp.sample = 0;   // (k_resolve: the one sample of this "frame"; the paths' stream is rr.sample, in the queue's keys)
+
+  const uint32_t npix = rr.count, depths = f.plan.generations;
+  PathBuffers& pb = f.pb;
+  pb.npix = npix;
+  if (!flat) {
+    const uint32_t dalloc = depths ? depths : 1;
+    if ((rc = ensure(c->path_direct, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
+    if ((rc = ensure(c->path_state, (size_t)npix * dalloc * 4)) != RAYCA_OK) return rc;
+    if ((rc = ensure(c->path_brdf, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
+    pb.direct = static_cast<float4*>(c->path_direct.ptr);
+    pb.brdf = static_cast<float4*>(c->path_brdf.ptr);
+    pb.state = static_cast<uint32_t*>(c->path_state.ptr);
+  }
+  if ((rc = ensure(c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+  if (depths > 1 && (rc = ensure(c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+
+  if (f.timing) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
+  if (f.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
+  if (depths > 1) HIP_TRY(hipMemsetAsync(pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
+  for (uint32_t g = 0; g < depths; ++g) {
+    // (the counters: as render_body clears them, generation by generation)
+    if (!(g == 0 && c->heads_clean))
+      HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
+    c->heads_clean = false;
+    const GenQueues q{static_cast<QueuedRay*>(c->queue[(g + 1) & 1].ptr), q_count + ((g + 1) & 1), static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
+    if (g == 0) {
+      rc = timed_launch(f.log, stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
+        hipLaunchKernelGGL(k_enqueue_rays, dim3((npix + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, static_cast<const float*>(rr.rays), npix, rr.first_index,
+                           cfg.seed, rr.sample, q.in, q.in_count);
+        return RAYCA_OK;
+      });
+      if (rc != RAYCA_OK) return rc;
+    } else {
+      HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
+    }
+    if ((rc = wavefront_generation(f, g, q)) != RAYCA_OK) return rc;
+  }
+  if (!flat && (rc = resolve(f)) != RAYCA_OK) return rc;
+  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
+  if (f.timing) return fill_stats(f, stats_out);
+  return pass_finish(pass, f.log.launches, nullptr);
 }
 
 }  // extern "C"

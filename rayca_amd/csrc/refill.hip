@@ -200,8 +200,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_REFILL_WAVES) void k_flat_refill(DevS
 #define RAYCA_QREFILL_WAVES RAYCA_REFILL_WAVES
 #endif
 // (This kernel and k_shadow_refill trace bounce and shadow rays only: their origins lie on the scene's surfaces, where the padding
-// of the steering boxes covers the rounding of c -- trace_core.inc ray_needs_slack -- so their node steps carry no slack.)
-template <bool SPH, bool STATS>
+// of the steering boxes covers the rounding of c -- trace_core.inc ray_needs_slack -- so their node steps carry no slack.
+// SLACK: the queue holds rays a caller has supplied (generation 0 of rayca_hip_radiance_device), whose origins may lie anywhere:
+// node steps and leaf tests with the slack, as k_query_refill takes them.)
+template <bool SPH, bool STATS, bool SLACK = false>
 __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_queue_refill(DevScene sc, const QueuedRay* in_rays, const uint32_t* in_count, float4* hits,
                                                                               uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
   constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_wf_trace traverses bounce rays)
@@ -267,10 +269,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_queue_refill(De
       const uint32_t n = (uint32_t)__popcll(__ballot(searching));
       if (n == 0u) break;
       if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
-      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF, false>(sc, ray, fr, limit, cur, stack, cnt);
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF, SLACK>(sc, ray, fr, limit, cur, stack, cnt);
     }
     if (cur & kLeafFlag) {
-      test_leaf<true, SPH, STATS, false>(sc, ray, fr, cur, FLT_MAX, hit, limit, cnt);
+      test_leaf<true, SPH, STATS, SLACK>(sc, ray, fr, cur, FLT_MAX, hit, limit, cnt);
       cur = stack.pop();
     }
   }
@@ -557,7 +559,11 @@ ShadowRefillKernel pick_shadow(bool sph, bool stats) {
 }
 
 using QueueRefillKernel = void (*)(DevScene, const QueuedRay*, const uint32_t*, float4*, uint32_t*, TraceCounters*, TraceLaunch);
-QueueRefillKernel pick_queue(bool sph, bool stats) {
+QueueRefillKernel pick_queue(bool sph, bool stats, bool slack) {
+  if (slack) {
+    if (sph) return stats ? k_queue_refill<true, true, true> : k_queue_refill<true, false, true>;
+    return stats ? k_queue_refill<false, true, true> : k_queue_refill<false, false, true>;
+  }
   if (sph) return stats ? k_queue_refill<true, true> : k_queue_refill<true, false>;
   return stats ? k_queue_refill<false, true> : k_queue_refill<false, false>;
 }
@@ -584,11 +590,11 @@ void launch_flat_refill(const RefillFlavour& f, uint32_t grid, size_t lds_bytes,
   hipLaunchKernelGGL(pick(f), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, fp, heads, rgba8, rgba32f, counters, tl);
 }
 
-const void* queue_refill_kernel(bool sph, bool stats) { return reinterpret_cast<const void*>(pick_queue(sph, stats)); }
+const void* queue_refill_kernel(bool sph, bool stats, bool slack) { return reinterpret_cast<const void*>(pick_queue(sph, stats, slack)); }
 
-void launch_queue_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueuedRay* in_rays,
+void launch_queue_refill(bool sph, bool stats, bool slack, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueuedRay* in_rays,
                          const uint32_t* in_count, float4* hits, uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl) {
-  hipLaunchKernelGGL(pick_queue(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, in_rays, in_count, hits, heads, counters, tl);
+  hipLaunchKernelGGL(pick_queue(sph, stats, slack), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, in_rays, in_count, hits, heads, counters, tl);
 }
 
 const void* query_refill_kernel(bool occluded, bool sph, bool stats) {

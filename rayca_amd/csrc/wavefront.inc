@@ -164,8 +164,10 @@ __global__ __launch_bounds__(kBlock, RAYCA_WF_MIN_WAVES) void k_wf_shadow(DevSce
 
 // HitInfo + sampling of one generation, one thread per ray.  Same statements as the shading part of
 // k_generation's state machine; the shadow rays are written out instead of traced.
+// RAYS (rayca_hip_radiance_device; !GEN0 only): the queue holds the caller's rays, not bounce rays -- the vertex is a path's first,
+// which collects an emissive hit whatever the direct sampler is (pathtracer.rs:83-87), as GEN0 does for a camera ray.
 constexpr uint32_t kShadeBlock = 256;  // 4 waves share one queue-append atomic (see the end of the kernel); 512 and 1024 were slower
-template <int MODE, bool GEN0, bool FUSED, bool SPH>
+template <int MODE, bool GEN0, bool FUSED, bool SPH, bool RAYS = false>
 __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FrameParams fp, const QueuedRay* in_rays, const uint32_t* in_count, QueuedRay* out_rays,
                                                       uint32_t* out_count, WfBuffers wb, PathBuffers pb, uint32_t depth, uint8_t* rgba8, float4* rgba32f,
                                                       unsigned long long* shade_stats) {
@@ -193,7 +195,8 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FramePara
     }
   }
   const size_t slot = (size_t)depth * pb.npix + p;
-  const bool collect_emissive = GEN0 ? true : (fp.direct_sampler == RAYCA_SAMPLER_NONE);
+  static_assert(!(GEN0 && RAYS), "the caller's rays come through the queue");
+  const bool collect_emissive = (GEN0 || RAYS) ? true : (fp.direct_sampler == RAYCA_SAMPLER_NONE);
   const uint32_t nee_lights = (MODE == kModePath && fp.direct_sampler == RAYCA_SAMPLER_NEE) ? sc.light_count : 0u;
   bool want_bounce = false;
   QueuedRay next{};
@@ -307,4 +310,21 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(DevScene sc, FramePara
     if (s2) atomicAdd(&line[1], s2);
     if (b2) atomicAdd(&line[2], b2);
   }
+}
+
+// rayca_hip_radiance_device: the caller's rays (6 f32 each: origin, direction) as the input queue of generation 0, one thread
+// per ray.  Ray i is "pixel" i of the call's outputs and draws from the stream of pixel index first_index + i; the queue's
+// count is written by the launch's first thread (the launch is in stream order behind whatever cleared the counters).
+__global__ __launch_bounds__(kBlock) void k_enqueue_rays(const float* __restrict__ rays, uint32_t count, uint32_t first_index, uint32_t seed, uint32_t sample,
+                                                         QueuedRay* __restrict__ out_rays, uint32_t* out_count) {
+  const uint32_t i = rc_bid() * kBlock + rc_tid();   // (the host keeps count <= 2^31: no wrap)
+  if (i == 0u) *out_count = count;
+  if (i >= count) return;
+  const float* r = rays + 6ull * i;
+  QueuedRay q;
+  q.ox = r[0]; q.oy = r[1]; q.oz = r[2];
+  q.dx = r[3]; q.dy = r[4]; q.dz = r[5];
+  q.pixel = i;
+  q.key = rng_root(seed, first_index + i, sample);
+  out_rays[i] = q;
 }

@@ -19,8 +19,10 @@ class Film:
 
     max_history 0 is a running mean, else the history length is capped there (an exponential tail, which forgets what a
     moved light or material left).  normal_min and plane_max are the reprojection's thresholds (DeviceScene.accumulate);
-    moments=True keeps the luminance moments, and with them `variance`.  A film's calls belong on one stream and one
-    frame context: its buffers are reused from frame to frame, and that order is all that keeps them apart."""
+    moments=True keeps the luminance moments, and with them `variance`.  add(config, jitter=n) traces each frame through
+    another of the n x n stratified sub-pixel positions instead of the pixel centre, so that the history antialiases
+    geometric edges.  A film's calls belong on one stream and one frame context: its buffers are reused from frame to
+    frame, and that order is all that keeps them apart."""
 
     def __init__(self, scene: DeviceScene, width: int, height: int, *, max_history=0, normal_min=0.9, plane_max=0.1, moments=True):
         self.scene, self.width, self.height = scene, width, height
@@ -71,8 +73,13 @@ class Film:
         h, w = self.height, self.width
         return {"point": g["point"].view(h, w, 3), "normal": g["normal"].view(h, w, 3), "id": g["material"].view(h, w)}
 
-    def add(self, config: Config, stream=None, context=0):
+    def add(self, config: Config, stream=None, context=0, *, jitter=None):
         """One more frame of `config`, rendered with gamma 1 and seed (config.seed + frames_added) mod 2^32, into the film.
+        jitter=n (1..8): the frame's rays go through sub-sample frames_added mod n^2 of the n x n stratified sub-pixel
+        positions of a frame with n^2 samples per pixel (DeviceScene.camera_rays: the reference's own positions, row-major), and
+        the colour comes from DeviceScene.radiance along them, with that sub-sample index as `sample`; n^2 adds on a still camera
+        are then the samples of one n^2-spp frame.  A config radiance() does not offer raises its error.  The G-buffer keeps
+        coming from the rays through the pixel centres, which the reprojection assumes.  jitter=None: the frame of a render call.
         The first frame starts the history; a frame whose camera pose has the bytes of the previous one's continues it pixel by
         pixel; any other goes through the reprojection with the previous frame's G-buffer.  The two history sets and the two
         G-buffers change roles from frame to frame, so nothing is waited for.  Returns the film's colour (H, W, 4), which the
@@ -83,7 +90,17 @@ class Film:
         handle = s.stream_handle(stream)
         self._gamma = config.gamma
         cfg = dataclasses.replace(config, gamma=1.0, seed=(config.seed + self.frames_added) % 2 ** 32)
-        s.render_device(cfg, self.width, self.height, 0, b["frame"].data_ptr(), stream=handle or None, context=context)
+        if jitter is None:
+            s.render_device(cfg, self.width, self.height, 0, b["frame"].data_ptr(), stream=handle or None, context=context)
+        else:
+            if not isinstance(jitter, int) or isinstance(jitter, bool) or not 1 <= jitter <= 8:
+                raise ValueError(f"jitter: None or an integer 1..8, not {jitter!r}")
+            if "jitter_rays" not in b:
+                b["jitter_rays"] = b["rays"].new_empty(b["rays"].shape)
+            sub = self.frames_added % (jitter * jitter)
+            s.camera_rays(Config(samples_per_pixel=jitter * jitter), self.width, self.height, sample=sub, stream=stream, context=context,
+                          out=b["jitter_rays"])
+            s.radiance(b["jitter_rays"], cfg, sample=sub, out=b["frame"].view(-1, 4), stream=stream, context=context)
         pose = s.camera_pose()
         pose_bytes = bytes(pose)
         src, dst = b["hist"][self._hist], b["hist"][self._hist ^ 1]

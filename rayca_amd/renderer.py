@@ -305,6 +305,47 @@ class DeviceScene:
         g["t"], g["prim"] = t, prim
         return {k: v.reshape(height, width, *v.shape[1:]) for k, v in g.items()}
 
+    # ---- radiance along the caller's rays (rayca_hip_radiance_device) ----
+    def radiance(self, rays, config: Config, *, sample=0, first_index=0, rgba8=False, out=None, stream=None, context=0,
+                 want_stats=False, collect_stats=False):
+        """rayca_hip_radiance_device: the light that arrives along rays in device memory, asynchronously.
+
+        rays: torch tensor (N, 6) float32 on this scene's device (origin xyz, direction xyz), any rays: another camera model,
+        probe directions, a frame's own camera_rays().  Row i of the result is the pixel of a one-sample frame of `config` whose
+        camera ray is rays[i] and whose pixel index is first_index + i: the integrator's value, alpha 1, through `config.gamma`;
+        the path draws from the random stream of (config.seed, first_index + i, sample).  Several samples are several calls with
+        different `sample`; consecutive chunks of a ray set, each with the first_index of its first ray, give what one call
+        gives.  Flat, and the Pathtracer configs the generation kernels render, are offered (else RaycaError ERR_UNSUPPORTED
+        naming the field); config.samples_per_pixel is not read.  Returns the (N, 4) float32 tensor (`out`: the tensor to
+        write), with rgba8=True (or the tensor to write) also the (N, 4) uint8 one, and the stats dict behind them when
+        `want_stats` / `collect_stats` ask for it (the call then waits).  Stream handling as query()."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError(f"rays: a torch tensor on {call.dev} is expected, not {type(rays).__name__}")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError(f"rays: shape {tuple(rays.shape)}, expected (N, 6)")
+        n = rays.shape[0]
+        if first_index < 0 or first_index + n > 1 << 32:
+            raise ValueError("first_index + the number of rays exceeds 2**32")
+        out = call.output(out, "out", torch.float32, (n, 4))
+        out8 = call.output(rgba8, "rgba8", torch.uint8, (n, 4), optional=True)
+        r = abi.RaycaRadiance()
+        r.count, r.sample, r.first_index = n, sample, first_index
+        r.rays = call.input(rays, "rays", torch.float32, (n, 6)).data_ptr() or None
+        r.rgba32f_out, r.rgba8_out = out.data_ptr() or None, _ptr(out8) or None
+        cfg = config.to_abi()
+        fn = self._lib.rayca_hip_radiance_device
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(lambda handle, o, args, st: fn(handle, C.byref(cfg), o, args, st), r, context=context,
+                             want_stats=want_stats or collect_stats, collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        return _asked_for(out, out8, stats)
+
     # ---- the denoiser: an edge-avoiding a-trous filter on a frame and its G-buffer (rayca_hip_denoise_device) ----
     def denoise(self, color, *, albedo=None, normal=None, point=None, id=None, iterations=5, sigma_color=4.0, sigma_plane=None,
                 normal_power_log2=7, gamma=1.0, out=None, rgba8=False, stream=None, context=0, want_stats=False):
