@@ -622,6 +622,12 @@ bool generation_kernels_cover(const RaycaScene* s, const RaycaConfig& c) {
   return generation_kernels_gap(c) == nullptr && !nee_meets_directional_light(s, c);
 }
 
+// A scene with nothing in it: what every call that traverses it or reads its tables answers.
+int32_t refuse_empty_scene(const RaycaScene* s) {
+  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  return RAYCA_OK;
+}
+
 int32_t validate_config(const RaycaScene* s, const RaycaConfig& c, uint32_t engine, LaunchPlan& plan) {
   if (c.samples_per_pixel == 0 || c.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "samples_per_pixel and light_samples must be > 0");
   if (c.integrator > RAYCA_INTEGRATOR_PATHTRACER) return fail(RAYCA_ERR_BAD_ARG, "unknown integrator");
@@ -731,7 +737,7 @@ WfShadeKernel pick_wf_shade(int mode, bool gen0, bool fused, bool sph, bool rays
   return sph ? k_wf_shade<kModePath, false, false, true> : k_wf_shade<kModePath, false, false, false>;
 }
 
-// ---- one frame: render_body drives the per-engine launch steps below ------------------------------------------------
+// ---- one frame: the frame driver (frame_run) drives the per-engine launch steps below --------------------------------
 
 // The launches of one frame: how many, and the event pairs around the timed ones (the i-th timed launch, of class
 // ev_class[i], sits between events 2i and 2i + 1 of the context's ev_trace, which are made on first use and kept).
@@ -814,13 +820,15 @@ int32_t pass_finish(const ContextPass& p, uint32_t launches, RaycaStats* stats_o
 // One pass whose launches need nothing of the context but its stream, shaped like timed_launch: the context's lock,
 // `prepare(c)` under it (buffers of the context that must exist before the pass queues its waits), pass_acquire, ev_begin when
 // timing, `body(stream, launches)`, pass_retire, pass_finish.  The body enqueues on `stream`, checks hipGetLastError behind
-// each launch and counts what it launched.  (o.context is in range: pass_options has seen `o`.)
+// each launch and counts what it launched.  (o.context is in range: pass_options has seen `o`.)  A `prepare` that finds nothing to
+// do -- what it reads of the scene it reads under the lock -- returns kPassNothing: the call is RAYCA_OK without a pass.
+constexpr int32_t kPassNothing = 1;   // (errors are negative)
 template <typename Prepare, typename Body>
 int32_t run_pass(RaycaScene* s, const RaycaRenderOptions& o, RaycaStats* stats_out, Prepare&& prepare, Body&& body) {
   FrameCtx* c = &s->ctx[o.context];
   std::lock_guard<std::mutex> lock(c->mu);
   int32_t rc = prepare(c);
-  if (rc != RAYCA_OK) return rc;
+  if (rc != RAYCA_OK) return rc == kPassNothing ? RAYCA_OK : rc;
   ContextPass pass{};
   if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
   if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, pass.stream));
@@ -867,10 +875,10 @@ struct Frame {
   const DevScene* dscene;           // s->dev_full once the other node formats are there, else s->dev
   uint8_t* rgba8;
   float4* rgba32f;
+  const RaycaRadiance* rays;        // rayca_hip_radiance_device: generation 0 reads these rays from a queue, not the camera's (null for a frame)
   uint32_t in_flight;               // frames_in_flight_hint
   bool fused;                       // one generation, one sample: the generation kernel writes the pixel (no k_resolve)
-  bool rays;                        // rayca_hip_radiance_device: generation 0 reads the caller's rays from a queue, not the camera
-  bool timing;                      // RaycaStats asked for: every launch timed
+  bool timing;                     // RaycaStats asked for: every launch timed
   bool all_formats;                 // formats_ready
   uint32_t node_format;             // RaycaStats.node_format
   int frame_format[2] = {-2, -2};   // node format of this frame per generation class (-2 = not asked yet, -1 = default)
@@ -879,7 +887,7 @@ struct Frame {
   LaunchLog log;
 };
 
-// generation g reads queue (g - 1) & 1 and writes queue g & 1; their counters sit behind the 8 padded work counters
+// generation g reads queue (g - 1) & 1 and writes queue g & 1 (frame_run); their counters sit behind the 8 padded work counters
 struct GenQueues {
   QueuedRay* in;
   uint32_t* in_count;
@@ -917,7 +925,7 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   // On a SAH scene the bounce generations' closest hits run on persistent lanes that take the next queue entry when their
   // ray is done (refill.hip k_queue_refill; RAYCA_WF_REFILL=0 keeps one ray per lane, k_wf_trace), and so do the shadow
   // rays (k_shadow_refill; RAYCA_WF_SHADOW_REFILL: 0 never, 1 bounce generations, 2 every generation), on the second
-  // set of work counters.  The work counters are cleared by render_body, every generation.
+  // set of work counters.  The work counters are cleared by frame_run, every generation.
   static const bool wf_refill = [] { const char* e = getenv("RAYCA_WF_REFILL"); return e ? atoi(e) != 0 : true; }();
   static const int shadow_refill_mode = [] { const char* e = getenv("RAYCA_WF_SHADOW_REFILL"); return e ? atoi(e) : 1; }();
   TraceLaunch tl{};
@@ -1254,15 +1262,122 @@ void config_frame_params(const Frame& f, FrameParams& fp) {
   fp.nee_skip = f.s->nee_skip && f.plan.ordered && !(f.dscene->root_ref & kLeafFlag) ? 1u : 0u;
 }
 
-// One frame.  The caller holds the frame context's mutex (render_impl and rayca_hip_render take it): everything a
+// ---- the frame driver: what render_body and rayca_hip_radiance_device run behind their own checks and pass_acquire ---------
+// A frame and a radiance query are the same passes over the same buffers: frame_begin, frame_run, frame_finish.  They differ
+// in three places, all read off f.rays: generation 0's input (nothing for camera rays; queue 1, which one k_enqueue_rays
+// launch fills, for a caller's), queue 1 (a caller's rays need it even at depth 1 and for Flat), and where the Frame gets its
+// shape (the caller sets the geometry of f.fp: the camera and tile, or one row of `count` pixels).
+
+// The Frame of an acquired pass and its path buffers.  The caller has set s, cfg, opts, plan, rays and the geometry of fp.
+int32_t frame_begin(Frame& f, const ContextPass& pass, void* d_rgba8, void* d_rgba32f) {
+  RaycaScene* s = f.s;
+  FrameCtx* c = f.c = f.log.c = pass.c;
+  const LaunchPlan& plan = f.plan;
+  f.stream = pass.stream;
+  f.timing = pass.timing;
+  int32_t rc;
+  // The wavefront engine's kernels are tied to the 4-wide / fp16 nodes, and so is a pinned format: those wait for the thread
+  // that makes them.  Everything else renders on the binary f32 nodes until they are there (node_format bit 2048).
+  if ((plan.wavefront || format_forced() > 0) && (rc = formats_wait(s)) != RAYCA_OK) return rc;
+  f.all_formats = formats_ready(s);
+  f.dscene = f.all_formats ? &s->dev_full : &s->dev;
+  f.in_flight = frames_in_flight_hint(s, f.opts.context, f.opts.stream != nullptr);
+  f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
+  f.rgba8 = static_cast<uint8_t*>(d_rgba8);
+  f.rgba32f = static_cast<float4*>(d_rgba32f);
+  // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
+  // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
+  f.fused = f.cfg.samples_per_pixel == 1 && plan.mode == kModeFlat;
+  config_frame_params(f, f.fp);
+
+  // One record per pixel and depth; the two queues where a path bounces, queue 1 also where generation 0 reads the caller's rays.
+  PathBuffers& pb = f.pb;
+  const uint32_t npix = pb.npix = f.fp.rows * f.fp.width;
+  const size_t records = (size_t)npix * (plan.generations ? plan.generations : 1);
+  const bool path = plan.mode == kModePath, bounces = path && plan.generations > 1;
+  if (!f.fused) {
+    if ((rc = ensure(c->path_direct, records * 16)) != RAYCA_OK) return rc;
+    if ((rc = ensure(c->path_state, records * 4)) != RAYCA_OK) return rc;
+    if (path && (rc = ensure(c->path_brdf, records * 16)) != RAYCA_OK) return rc;
+    if (f.cfg.samples_per_pixel > 1 && (rc = ensure(c->accum, (size_t)npix * 16)) != RAYCA_OK) return rc;
+    pb.direct = static_cast<float4*>(c->path_direct.ptr);
+    pb.brdf = static_cast<float4*>(c->path_brdf.ptr);
+    pb.state = static_cast<uint32_t*>(c->path_state.ptr);
+  }
+  if (bounces && (rc = ensure(c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+  if ((bounces || f.rays) && (rc = ensure(c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+  return RAYCA_OK;
+}
+
+// Every sample and generation of the frame, up to k_resolve.
+int32_t frame_run(Frame& f) {
+  FrameCtx* c = f.c;
+  const hipStream_t stream = f.stream;
+  const LaunchPlan& plan = f.plan;
+  const bool general = plan.mode == kModeGeneral;
+  const uint32_t npix = f.pb.npix, depths = plan.generations, spp = f.cfg.samples_per_pixel;
+  int32_t rc;
+  if (f.timing || general) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
+  if (f.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
+  uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
+  for (uint32_t sample = 0; sample < spp; ++sample) {
+    // (a caller's rays: fp.sample stays 0, the one sample k_resolve finalises; the paths' stream is rays->sample, in the queue's keys)
+    if (!f.rays) camera_sample_params(spp, sample, f.fp);
+    if (!f.fused && depths > 1) HIP_TRY(hipMemsetAsync(f.pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
+    if (general && (rc = stack_machine(f)) != RAYCA_OK) return rc;
+    for (uint32_t g = 0; !general && g < depths; ++g) {
+      // generation 0 clears the work counters and both queue counters in one go (unless k_resolve of the previous frame
+      // left them clean); later generations must keep the input queue's counter.  One memset clears both counter sets (the
+      // second one is only used by the wavefront engine), in whole lines: a size that is not a multiple of the fill
+      // kernel's granule costs a second fill launch, ~5 us.
+      if (!(g == 0 && c->heads_clean))
+        HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
+      c->heads_clean = false;
+      // generation g reads what generation g - 1 wrote; generation 0 the caller's rays in queue 1, which generation 1 writes
+      // over once they are read, or nothing (the camera)
+      const int in = g ? (int)((g - 1) & 1) : (f.rays ? 1 : -1);
+      const GenQueues q{in < 0 ? nullptr : static_cast<QueuedRay*>(c->queue[in].ptr), in < 0 ? nullptr : q_count + in,
+                        static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
+      if (g != 0) HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
+      else if (f.rays) {
+        const RaycaRadiance& rr = *f.rays;
+        rc = timed_launch(f.log, stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
+          hipLaunchKernelGGL(k_enqueue_rays, dim3((npix + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, static_cast<const float*>(rr.rays), npix, rr.first_index,
+                             f.cfg.seed, rr.sample, q.in, q.in_count);
+          return RAYCA_OK;
+        });
+        if (rc != RAYCA_OK) return rc;
+      }
+      if ((rc = plan.wavefront ? wavefront_generation(f, g, q) : fused_generation(f, g, q)) != RAYCA_OK) return rc;
+    }
+    if (!f.fused && (rc = resolve(f)) != RAYCA_OK) return rc;
+  }
+  return RAYCA_OK;
+}
+
+// Behind the last launch: the pass retires, a calibration frame books its times, the stack machine reports its flags, then the
+// statistics -- or the rule of every pass: one on the context's own stream is synchronous.  `caller_drains`: the caller waits
+// for that stream itself (rayca_hip_render behind its copies, the parts of rayca_hip_render_multi behind their exchange).
+int32_t frame_finish(Frame& f, const ContextPass& pass, RaycaStats* stats_out, bool caller_drains) {
+  int32_t rc = pass_retire(pass);
+  if (rc != RAYCA_OK) return rc;
+  if (!f.tune_events.empty() && (rc = book_calibration(f)) != RAYCA_OK) return rc;
+  if (f.plan.mode == kModeGeneral && (rc = stack_machine_status(f)) != RAYCA_OK) return rc;
+  if (f.timing) return fill_stats(f, stats_out);
+  return caller_drains ? RAYCA_OK : pass_finish(pass, f.log.launches, nullptr);
+}
+
+// One frame: the three differences above are the camera's -- f.rays stays null, and camera_frame_params gives the Frame its
+// shape.  The caller holds the frame context's mutex (render_impl and rayca_hip_render take it): everything a
 // context owns -- work buffers, events, its stream, the staging buffers of rayca_hip_render -- is touched under it.
 int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, uint32_t height, const RaycaRenderOptions* opts_in,
-                    void* d_rgba8, void* d_rgba32f, RaycaStats* stats_out) {
+                    void* d_rgba8, void* d_rgba32f, RaycaStats* stats_out, bool caller_drains) {
   if (!s || !cfg_in) return fail(RAYCA_ERR_BAD_ARG, "null scene or config");
   if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
   if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if (const int32_t e = refuse_empty_scene(s); e != RAYCA_OK) return e;
   Frame f{};
+  f.s = s;
   const RaycaConfig& cfg = f.cfg = *cfg_in;
   const RaycaRenderOptions& opts = f.opts;
   if (opts_in) f.opts = *opts_in;
@@ -1273,93 +1388,26 @@ int32_t render_body(RaycaScene* s, const RaycaConfig* cfg_in, uint32_t width, ui
   if (rc != RAYCA_OK) return rc;
   if (opts.camera_rays > RAYCA_CAMERA_REFILL) return fail(RAYCA_ERR_BAD_ARG, "unknown camera_rays choice");
   if ((rc = camera_frame_params(s, width, height, opts.tile, f.fp)) != RAYCA_OK) return rc;
-  const uint32_t rows = f.fp.rows;
-  if (rows == 0) {
+  if (f.fp.rows == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
   }
   if (opts.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  f.s = s;
   ContextPass pass{};
   if ((rc = pass_acquire(s, opts, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  FrameCtx* c = f.c = f.log.c = pass.c;
-  const hipStream_t stream = f.stream = pass.stream;
-  // The wavefront engine's kernels are tied to the 4-wide / fp16 nodes, and so is a pinned format: those wait for the thread
-  // that makes them.  Everything else renders on the binary f32 nodes until they are there (node_format bit 2048).
-  if ((plan.wavefront || format_forced() > 0) && (rc = formats_wait(s)) != RAYCA_OK) return rc;
-  f.all_formats = formats_ready(s);
-  f.dscene = f.all_formats ? &s->dev_full : &s->dev;
-  f.in_flight = frames_in_flight_hint(s, opts.context, opts.stream != nullptr);
-  f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
-  f.rgba8 = static_cast<uint8_t*>(d_rgba8);
-  f.rgba32f = static_cast<float4*>(d_rgba32f);
-
-  FrameParams& fp = f.fp;   // (the frame's geometry and camera are in it: camera_frame_params above)
-  config_frame_params(f, fp);
-
-  // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
-  // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
-  const uint32_t npix = rows * width, depths = plan.generations;
-  const bool fused = f.fused = cfg.samples_per_pixel == 1 && plan.mode == kModeFlat;
-  PathBuffers& pb = f.pb;
-  pb.npix = npix;
-  if (!fused) {
-    const uint32_t dalloc = depths ? depths : 1;
-    if ((rc = ensure(c->path_direct, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
-    if ((rc = ensure(c->path_state, (size_t)npix * dalloc * 4)) != RAYCA_OK) return rc;
-    if (plan.mode == kModePath && (rc = ensure(c->path_brdf, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
-    if (cfg.samples_per_pixel > 1 && (rc = ensure(c->accum, (size_t)npix * 16)) != RAYCA_OK) return rc;
-    if (plan.mode == kModePath && depths > 1) {
-      if ((rc = ensure(c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
-      if ((rc = ensure(c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
-    }
-    pb.direct = static_cast<float4*>(c->path_direct.ptr);
-    pb.brdf = static_cast<float4*>(c->path_brdf.ptr);
-    pb.state = static_cast<uint32_t*>(c->path_state.ptr);
-  }
-
-  const bool timing = f.timing = pass.timing;
-  const bool general = plan.mode == kModeGeneral;
-  if (timing || general) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
-  if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
-  for (uint32_t sample = 0; sample < cfg.samples_per_pixel; ++sample) {
-    camera_sample_params(cfg.samples_per_pixel, sample, fp);
-    if (!fused && depths > 1) HIP_TRY(hipMemsetAsync(pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
-    if (general && (rc = stack_machine(f)) != RAYCA_OK) return rc;
-    for (uint32_t g = 0; !general && g < depths; ++g) {
-      // generation 0 clears the work counters and both queue counters in one go (unless k_resolve of the previous frame
-      // left them clean); later generations must keep the input queue's counter.  One memset clears both counter sets (the
-      // second one is only used by the wavefront engine), in whole lines: a size that is not a multiple of the fill
-      // kernel's granule costs a second fill launch, ~5 us.
-      if (!(g == 0 && c->heads_clean))
-        HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
-      c->heads_clean = false;
-      const GenQueues q{g ? static_cast<QueuedRay*>(c->queue[(g - 1) & 1].ptr) : nullptr, g ? q_count + ((g - 1) & 1) : nullptr,
-                        static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
-      if (g != 0) HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
-      if ((rc = plan.wavefront ? wavefront_generation(f, g, q) : fused_generation(f, g, q)) != RAYCA_OK) return rc;
-    }
-    if (!fused && (rc = resolve(f)) != RAYCA_OK) return rc;
-  }
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  if (!f.tune_events.empty() && (rc = book_calibration(f)) != RAYCA_OK) return rc;
-  if (general && (rc = stack_machine_status(f)) != RAYCA_OK) return rc;
-  return timing ? fill_stats(f, stats_out) : RAYCA_OK;
+  if ((rc = frame_begin(f, pass, d_rgba8, d_rgba32f)) != RAYCA_OK || (rc = frame_run(f)) != RAYCA_OK) return rc;
+  return frame_finish(f, pass, stats_out, caller_drains);
 }
 
 // rayca_hip_render_device: takes the context's mutex around the frame.  With opts->stream == NULL the frame runs on the
-// context's own (non-blocking) stream, which the caller has no handle to wait on: that case is synchronous.
+// context's own (non-blocking) stream, which the caller has no handle to wait on: that case is synchronous (frame_finish).
 int32_t render_impl(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, uint32_t height, const RaycaRenderOptions* opts,
                     void* d_rgba8, void* d_rgba32f, RaycaStats* stats_out) {
   if (!s) return fail(RAYCA_ERR_BAD_ARG, "null scene or config");
   const uint32_t context = opts ? opts->context : 0u;
   if (context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  FrameCtx* c = &s->ctx[context];
-  std::lock_guard<std::mutex> lock(c->mu);
-  const int32_t rc = render_body(s, cfg, width, height, opts, d_rgba8, d_rgba32f, stats_out);
-  if (rc == RAYCA_OK && !(opts && opts->stream) && c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
-  return rc;
+  std::lock_guard<std::mutex> lock(s->ctx[context].mu);
+  return render_body(s, cfg, width, height, opts, d_rgba8, d_rgba32f, stats_out, false);
 }
 
 }  // namespace
@@ -1549,7 +1597,7 @@ int32_t rayca_hip_render(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, 
   if (rgba32f_out && (rc = ensure(c->out32, npix * 16 + 16)) != RAYCA_OK) return rc;
   lap("staging buffers");
   // (no statistics unless asked for: they cost two event records per launch, a stream synchronisation and a read-back)
-  rc = render_body(s, cfg, width, height, &o, rgba8_out ? c->out8.ptr : nullptr, rgba32f_out ? c->out32.ptr : nullptr, stats_out);
+  rc = render_body(s, cfg, width, height, &o, rgba8_out ? c->out8.ptr : nullptr, rgba32f_out ? c->out32.ptr : nullptr, stats_out, true);
   if (rc != RAYCA_OK) return rc;
   lap("render_body (issue)");
   hipStream_t stream = o.stream ? static_cast<hipStream_t>(o.stream) : c->stream;
@@ -1851,7 +1899,7 @@ int32_t multi_issue(RaycaScene* const* scenes, uint32_t count, const RaycaConfig
       part_err[i] = "hipSetDevice failed";
       return;
     }
-    part_rc[i] = render_body(scenes[i], cfg, width, height, &o, rows[i] ? part_dst[i] : nullptr, nullptr, stats_out ? &stats_out[i] : nullptr);
+    part_rc[i] = render_body(scenes[i], cfg, width, height, &o, rows[i] ? part_dst[i] : nullptr, nullptr, stats_out ? &stats_out[i] : nullptr, true);
     if (part_rc[i] != RAYCA_OK) part_err[i] = g_last_error;
     else if (hipEventRecord(f.done[i], scenes[i]->ctx[ctx].stream) != hipSuccess) {
       part_rc[i] = RAYCA_ERR_HIP;
@@ -1969,7 +2017,7 @@ int32_t rayca_hip_render_multi_wait(RaycaScene* const* scenes, uint32_t count, u
 int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint32_t count, const float* rays, float* t_out, uint32_t* prim_out,
                              float* uv_out, RaycaStats* stats_out) {
   if (!s || !rays || !t_out || !prim_out || !uv_out) return fail(RAYCA_ERR_BAD_ARG, "null argument");
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if (const int32_t e = refuse_empty_scene(s); e != RAYCA_OK) return e;
   if (count == 0) return RAYCA_OK;
   FrameCtx* c = &s->ctx[0];
   std::lock_guard<std::mutex> lock(c->mu);
@@ -2040,7 +2088,7 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   if (rc != RAYCA_OK) return rc;
   const bool ordered = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
   if (occluded && !ordered) return fail(RAYCA_ERR_UNSUPPORTED, "an occlusion query ends at its first hit: there is no exhaustive form");
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
   if (rq.count == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
@@ -2124,7 +2172,7 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   if (some && !sq.rays && (sq.point_out || sq.normal_out)) return fail(RAYCA_ERR_BAD_ARG, "null rays: point_out and normal_out need the rays the records belong to");
   int32_t rc = pass_options(o, "a surface call", 0u);
   if (rc != RAYCA_OK) return rc;
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
   if (sq.count == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
@@ -2165,27 +2213,31 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   int32_t rc = pass_options(o, "the camera-ray export", kOptTile);
   if (rc != RAYCA_OK) return rc;
   if (!s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
   FrameParams fp{};
-  if ((rc = camera_frame_params(s, width, height, o.tile, fp)) != RAYCA_OK) return rc;
-  if (fp.rows == 0) return RAYCA_OK;
-  if (!d_rays_out) return fail(RAYCA_ERR_BAD_ARG, "null output");
-  const uint64_t count = (uint64_t)fp.rows * width;
-  if (count > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 rays");
-  fp.spp = cfg->samples_per_pixel;
-  camera_sample_params(cfg->samples_per_pixel, sample, fp);
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, false, pass)) != RAYCA_OK) return rc;
-  hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((count + kBlock - 1u) / kBlock)), dim3(kBlock), 0, pass.stream, fp, static_cast<float*>(d_rays_out));
-  HIP_TRY(hipGetLastError());
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  return pass_finish(pass, 1, nullptr);
+  uint64_t count = 0;
+  return run_pass(s, o, nullptr, [&](FrameCtx*) -> int32_t {   // (the camera is the scene's to move: read under the context's lock)
+    const int32_t prc = camera_frame_params(s, width, height, o.tile, fp);
+    if (prc != RAYCA_OK) return prc;
+    if (fp.rows == 0) return kPassNothing;
+    if (!d_rays_out) return fail(RAYCA_ERR_BAD_ARG, "null output");
+    count = (uint64_t)fp.rows * width;
+    if (count > 0xFFFFFFFFull) return fail(RAYCA_ERR_BAD_ARG, "more than 2^32 - 1 rays");
+    fp.spp = cfg->samples_per_pixel;
+    camera_sample_params(cfg->samples_per_pixel, sample, fp);
+    return RAYCA_OK;
+  }, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)((count + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, fp, static_cast<float*>(d_rays_out));
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    return RAYCA_OK;
+  });
 }
 
-// Radiance along the caller's rays: a one-sample frame of the wavefront engine whose generation 0 reads its rays from a queue
-// that k_enqueue_rays (wavefront.inc) fills -- queue 1, the queue generation 1 writes over once generation 0 has read it -- so
-// every generation runs the queue-fed kernels: closest hits on k_queue_refill (SAH scenes) or k_wf_trace<false>, shading on
+// Radiance along the caller's rays: a one-sample frame of the wavefront engine, run by the frame driver (frame_begin, frame_run,
+// frame_finish) as render_body's is.  What is its own are the driver's three differences, all behind f.rays: generation 0 reads
+// its rays from a queue that k_enqueue_rays (wavefront.inc) fills -- queue 1, the queue generation 1 writes over once generation
+// 0 has read it, and which is therefore there at every depth -- and the Frame's shape is one row of `count` pixels.  So every
+// generation runs the queue-fed kernels: closest hits on k_queue_refill (SAH scenes) or k_wf_trace<false>, shading on
 // k_wf_shade<.., RAYS> at depth 0, shadow rays on k_shadow_refill<false> / k_wf_shadow<false>.  "Pixel" i is ray i; k_resolve
 // (one sample: it finalises) or the Flat shade kernel writes out[i].
 int32_t rayca_hip_radiance_device(RaycaScene* s, const RaycaConfig* cfg_in, const RaycaRenderOptions* opts_in, const RaycaRadiance* rin,
@@ -2217,81 +2269,26 @@ int32_t rayca_hip_radiance_device(RaycaScene* s, const RaycaConfig* cfg_in, cons
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
   }
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
   if (nee_meets_directional_light(s, cfg)) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaConfig.direct_sampler: a directional light under NEE is a todo!() of the reference (nee.rs:178)");
 
-  FrameCtx* c = &s->ctx[o.context];
-  std::lock_guard<std::mutex> lock(c->mu);
+  std::lock_guard<std::mutex> lock(s->ctx[o.context].mu);
   Frame f{};
   f.s = s;
   f.cfg = cfg;
   f.cfg.samples_per_pixel = 1;   // (not read from the caller's: a call is one sample of every ray)
   f.opts = o;
-  f.rays = true;
+  f.rays = rin;
   const bool flat = cfg.integrator == RAYCA_INTEGRATOR_FLAT;
   f.plan = LaunchPlan{flat ? kModeFlat : kModePath, true, o.collect_stats != 0, true, flat ? 1u : cfg.max_depth};
-  ContextPass pass{};
-  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
-  f.c = f.log.c = pass.c;
-  const hipStream_t stream = f.stream = pass.stream;
-  if ((rc = formats_wait(s)) != RAYCA_OK) return rc;   // (the wavefront engine's kernels are tied to the 4-wide / fp16 nodes)
-  f.all_formats = formats_ready(s);
-  f.dscene = f.all_formats ? &s->dev_full : &s->dev;
-  f.in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
-  f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
-  f.rgba8 = static_cast<uint8_t*>(rr.rgba8_out);
-  f.rgba32f = static_cast<float4*>(rr.rgba32f_out);
-  f.timing = pass.timing;
-  f.fused = flat;
-
   // the "frame" is one row of `count` pixels; none of the camera's terms is read by a queue-fed kernel
   FrameParams& fp = f.fp;
   fp.width = rr.count; fp.height = 1; fp.rows = 1;
   fp.part = 0; fp.parts = 1; fp.band = 1;
-  config_frame_params(f, fp);
-  fp.sample = 0;   // (k_resolve: the one sample of this "frame"; the paths' stream is rr.sample, in the queue's keys)
-
-  const uint32_t npix = rr.count, depths = f.plan.generations;
-  PathBuffers& pb = f.pb;
-  pb.npix = npix;
-  if (!flat) {
-    const uint32_t dalloc = depths ? depths : 1;
-    if ((rc = ensure(c->path_direct, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
-    if ((rc = ensure(c->path_state, (size_t)npix * dalloc * 4)) != RAYCA_OK) return rc;
-    if ((rc = ensure(c->path_brdf, (size_t)npix * dalloc * 16)) != RAYCA_OK) return rc;
-    pb.direct = static_cast<float4*>(c->path_direct.ptr);
-    pb.brdf = static_cast<float4*>(c->path_brdf.ptr);
-    pb.state = static_cast<uint32_t*>(c->path_state.ptr);
-  }
-  if ((rc = ensure(c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
-  if (depths > 1 && (rc = ensure(c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
-
-  if (f.timing) HIP_TRY(hipMemsetAsync(c->counters, 0, kCountersBytes, stream));
-  if (f.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
-  uint32_t* q_count = c->heads + 8 * kHeadStride;  // the two queue counters
-  if (depths > 1) HIP_TRY(hipMemsetAsync(pb.state + npix, 0, (size_t)npix * (depths - 1) * 4, stream));
-  for (uint32_t g = 0; g < depths; ++g) {
-    // (the counters: as render_body clears them, generation by generation)
-    if (!(g == 0 && c->heads_clean))
-      HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
-    c->heads_clean = false;
-    const GenQueues q{static_cast<QueuedRay*>(c->queue[(g + 1) & 1].ptr), q_count + ((g + 1) & 1), static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
-    if (g == 0) {
-      rc = timed_launch(f.log, stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
-        hipLaunchKernelGGL(k_enqueue_rays, dim3((npix + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, static_cast<const float*>(rr.rays), npix, rr.first_index,
-                           cfg.seed, rr.sample, q.in, q.in_count);
-        return RAYCA_OK;
-      });
-      if (rc != RAYCA_OK) return rc;
-    } else {
-      HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
-    }
-    if ((rc = wavefront_generation(f, g, q)) != RAYCA_OK) return rc;
-  }
-  if (!flat && (rc = resolve(f)) != RAYCA_OK) return rc;
-  if ((rc = pass_retire(pass)) != RAYCA_OK) return rc;
-  if (f.timing) return fill_stats(f, stats_out);
-  return pass_finish(pass, f.log.launches, nullptr);
+  ContextPass pass{};
+  if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+  if ((rc = frame_begin(f, pass, rr.rgba8_out, rr.rgba32f_out)) != RAYCA_OK || (rc = frame_run(f)) != RAYCA_OK) return rc;
+  return frame_finish(f, pass, stats_out, false);
 }
 
 }  // extern "C"
