@@ -423,319 +423,7 @@ DevLight dev_light(const HostLight& l) {
   return d;
 }
 
-#ifndef RAYCA_WF_LDS_ENTRIES
-#define RAYCA_WF_LDS_ENTRIES 16u
-#endif
-
-struct LaunchPlan {
-  int mode;          // kModeFlat / kModePath / kModeGeneral
-  bool ordered, stats;
-  bool wavefront;    // traversal split from shading (wavefront.inc) instead of the fused k_generation
-  uint32_t generations;
-};
-
-using GenKernel = void (*)(DevScene, FrameParams, uint32_t*, const QueuedRay*, const uint32_t*, QueuedRay*, uint32_t*, PathBuffers, uint32_t,
-                           uint8_t*, float4*, TraceCounters*, TraceLaunch);
-
-// Traversal flavours that are actually instantiated (the full cross product would be 32 per kernel):
-//   kTravFast        ordered, conservative slabs, binary tree, stack entirely in LDS   <- production, generation 0
-//   kTravFastSpill   same with the global spill path (trees whose stack need exceeds the LDS part)
-//   kTravFastWide    ordered, conservative slabs, 4-wide tree, spill                   <- production, bounce generations
-//   kTravExact       ordered, the reference's slab arithmetic, binary, spill           <- RAYCA_BUILDER_REFERENCE
-//   kTravExactAll    exhaustive, exact slabs, binary, spill                             <- visits the reference's leaves
-//   kTravFastAll     exhaustive, conservative slabs, binary, spill                      <- verification of the SAH tree
-//   kTrav*Half       the three production flavours on the fp16 node arrays (DevNodeH / DevNode4H)
-enum Trav { kTravFast, kTravFastSpill, kTravFastWide, kTravExact, kTravExactAll, kTravFastAll, kTravFastHalf, kTravFastSpillHalf, kTravFastWideHalf, kTravCount };
-
-template <int MODE, bool GEN0, bool FUSED, bool SPH, bool STATS>
-GenKernel gen_kernel(Trav t) {
-  switch (t) {  //                  ORDERED FUSED  FAST  SPH  WIDE   SPILL        HALF
-    case kTravFast:          return k_generation<MODE, GEN0, true, FUSED, true, SPH, false, false, STATS, false>;
-    case kTravFastSpill:     return k_generation<MODE, GEN0, true, FUSED, true, SPH, false, true, STATS, false>;
-    case kTravFastWide:      return k_generation<MODE, GEN0, true, FUSED, true, SPH, true, true, STATS, false>;
-    case kTravFastHalf:      return k_generation<MODE, GEN0, true, FUSED, true, SPH, false, false, STATS, true>;
-    case kTravFastSpillHalf: return k_generation<MODE, GEN0, true, FUSED, true, SPH, false, true, STATS, true>;
-    case kTravFastWideHalf:  return k_generation<MODE, GEN0, true, FUSED, true, SPH, true, true, STATS, true>;
-    case kTravExact:         return k_generation<MODE, GEN0, true, FUSED, false, SPH, false, true, STATS, false>;
-    case kTravExactAll:      return k_generation<MODE, GEN0, false, FUSED, false, SPH, false, true, STATS, false>;
-    default:                 return k_generation<MODE, GEN0, false, FUSED, true, SPH, false, true, STATS, false>;
-  }
-}
-template <int MODE, bool GEN0, bool FUSED>
-GenKernel gen_kernel2(Trav t, bool sph, bool stats) {
-  if (stats) return sph ? gen_kernel<MODE, GEN0, FUSED, true, true>(t) : gen_kernel<MODE, GEN0, FUSED, false, true>(t);
-  return sph ? gen_kernel<MODE, GEN0, FUSED, true, false>(t) : gen_kernel<MODE, GEN0, FUSED, false, false>(t);
-}
-// stats: the counting instantiation (RaycaRenderOptions.collect_stats); the counters cost registers in
-// the traversal loop (measured: +15 % frame time on the depth-1 path kernel), so production launches
-// use the instantiation without them
-GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats) {
-  if (mode == kModeFlat) return fused ? gen_kernel2<kModeFlat, true, true>(t, sph, stats) : gen_kernel2<kModeFlat, true, false>(t, sph, stats);
-  return gen0 ? gen_kernel2<kModePath, true, false>(t, sph, stats) : gen_kernel2<kModePath, false, false>(t, sph, stats);
-}
-
-using TraceKernel = void (*)(DevScene, const float*, uint32_t, float*, uint32_t*, float*, TraceCounters*, TraceLaunch);
-template <bool SPH, bool STATS>
-TraceKernel trace_kernel(Trav t) {
-  switch (t) {
-    case kTravFastHalf:      return k_trace_rays<true, true, SPH, false, false, STATS>;  // caller-supplied rays: f32 nodes
-    case kTravFastSpillHalf: return k_trace_rays<true, true, SPH, false, true, STATS>;
-    case kTravFastWideHalf:  return k_trace_rays<true, true, SPH, true, true, STATS>;
-    case kTravFast:      return k_trace_rays<true, true, SPH, false, false, STATS>;
-    case kTravFastSpill: return k_trace_rays<true, true, SPH, false, true, STATS>;
-    case kTravFastWide:  return k_trace_rays<true, true, SPH, true, true, STATS>;
-    case kTravExact:     return k_trace_rays<true, false, SPH, false, true, STATS>;
-    case kTravExactAll:  return k_trace_rays<false, false, SPH, false, true, STATS>;
-    default:             return k_trace_rays<false, true, SPH, false, true, STATS>;
-  }
-}
-
-// rayca_hip_query_device, one ray per lane: the flavours that entry falls back to (see there)
-using QueryKernel = void (*)(DevScene, QueryIo, TraceCounters*, TraceLaunch);
-template <bool SPH, bool STATS, bool OCCLUDED>
-QueryKernel query_kernel(Trav t) {
-  switch (t) {
-    case kTravExact:    return k_query_rays<true, false, SPH, false, true, STATS, OCCLUDED>;
-    case kTravExactAll: return k_query_rays<false, false, SPH, false, true, STATS, false>;     // (exhaustive: closest hits only)
-    case kTravFastAll:  return k_query_rays<false, true, SPH, false, true, STATS, false>;
-    default:            return k_query_rays<true, true, SPH, false, true, STATS, OCCLUDED>;    // binary f32 nodes, with the spill path
-  }
-}
-QueryKernel pick_query_kernel(Trav t, bool sph, bool stats, bool occluded) {
-  if (occluded) {
-    if (sph) return stats ? query_kernel<true, true, true>(t) : query_kernel<true, false, true>(t);
-    return stats ? query_kernel<false, true, true>(t) : query_kernel<false, false, true>(t);
-  }
-  if (sph) return stats ? query_kernel<true, true, false>(t) : query_kernel<true, false, false>(t);
-  return stats ? query_kernel<false, true, false>(t) : query_kernel<false, false, false>(t);
-}
-
-// Which node format a generation traverses.  Measured on MI355X (atrium, 1080p, A/B in one run):
-// coherent camera/shadow rays are VALU-bound and the binary tree wins (0.37 vs 0.43 ms for the primary
-// generation: the 4-wide node tests more boxes and sorts), incoherent bounce rays are latency-bound
-// and the 4-wide tree wins (-9 % on the 4-bounce frame).
-// RAYCA_NODE_FORMAT=0..3 pins the node format of every generation (bit 0 = 4-wide, bit 1 = fp16 boxes) instead of
-// letting the scene time them; RAYCA_WIDE=0/1 is the older spelling for the f32 formats.  For profiling sessions,
-// where counter collection perturbs the timing.
-int format_forced() {
-  static const int forced = [] {
-    if (const char* e = getenv("RAYCA_NODE_FORMAT")) return atoi(e) & 3;
-    if (const char* e = getenv("RAYCA_WIDE")) return atoi(e) ? 1 : 0;
-    return -1;
-  }();
-  return forced;
-}
-int wide_forced() {
-  const int f = format_forced();
-  return f < 0 ? -1 : (f & 1);
-}
-bool use_wide(uint32_t generation) {
-  const int forced = wide_forced();
-  return forced >= 0 ? forced != 0 : generation > 0;
-}
-
-// LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
-// else 24 entries + a global spill area for the rest
-#ifndef RAYCA_MAX_LDS_ENTRIES
-#define RAYCA_MAX_LDS_ENTRIES 24
-#endif
-constexpr uint32_t kMaxLdsEntries = RAYCA_MAX_LDS_ENTRIES;
-struct StackPlan {
-  uint32_t lds_entries, spill_entries;
-  size_t lds_bytes;
-};
-StackPlan plan_stack(uint32_t need, uint32_t max_entries = kMaxLdsEntries) {
-  StackPlan p;
-  const uint32_t want = need + 1u;
-  p.lds_entries = want < max_entries ? ((want + 3u) / 4u) * 4u : max_entries;
-  if (p.lds_entries == 0) p.lds_entries = 4;
-  p.spill_entries = want > p.lds_entries ? want - p.lds_entries : 0u;
-  p.lds_bytes = (size_t)p.lds_entries * kBlock * 4u;
-  return p;
-}
-// A launch's node stack: the LDS part, and the spill area (a column per thread of the grid: entry e of thread t at
-// ovf[e * ovf_stride + t]) when the plan needs one.  The context's one spill area grows to the largest launch.
-int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch& tl) {
-  tl = TraceLaunch{};
-  tl.lds_entries = sp.lds_entries;
-  if (sp.spill_entries) {
-    tl.ovf_stride = grid * kBlock;
-    const int32_t rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
-    if (rc != RAYCA_OK) return rc;
-    tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
-  }
-  return RAYCA_OK;
-}
-
-#ifndef RAYCA_PATH_LDS_ENTRIES
-#define RAYCA_PATH_LDS_ENTRIES 12
-#endif
-uint32_t path_lds_entries() {
-  static const uint32_t n = [] { const char* e = getenv("RAYCA_PATH_LDS_ENTRIES"); return e ? (uint32_t)atoi(e) : (uint32_t)RAYCA_PATH_LDS_ENTRIES; }();
-  return n < 4u ? 4u : (n > kMaxLdsEntries ? kMaxLdsEntries : n);
-}
-
-// flavour for one launch + its stack plan
-struct TravPlan {
-  Trav trav;
-  bool wide, half;
-  StackPlan stack;
-};
-TravPlan plan_traversal(const RaycaScene* s, bool ordered, uint32_t generation, int format_choice = -1, uint32_t max_lds_entries = kMaxLdsEntries);
-
-// RAYCA_ENGINE_AUTO: which of the two generation-by-generation engines.  Measured with two frames in flight at 1080p
-// (tests/gpu_engine_depth_probe.py), fused vs wavefront: atrium depth 1 0.449 vs 0.567 ms, depth 2 1.80 vs 1.88,
-// depth 3 4.06 vs 3.23, depth 4 6.24 vs 4.54, depth 5 8.42 vs 5.86; Cornell 0.186 vs 0.118 ... 2.21 vs 1.27: the lean
-// trace kernels win once incoherent bounce generations dominate.  So: wavefront from three generations up.
-// RAYCA_WAVEFRONT=0/1 overrides.
-bool wavefront_by_default(uint32_t generations) {
-  static const int forced = [] { const char* e = getenv("RAYCA_WAVEFRONT"); return e ? atoi(e) : -1; }();
-  if (forced >= 0) return forced != 0;
-  return generations >= 3u;
-}
-
-// Can the generation kernels (k_generation + k_resolve) render this Config?  They cover Flat and the
-// Pathtracer with Nee/None direct and Cosine/Hemisphere indirect sampling, one indirect sample per vertex
-// and no roulette; everything else runs on the per-pixel stack machine (k_general).
-// The two halves of that question: the field of the Config that takes it off the generation kernels (nullptr: none does), which
-// needs no scene, and the one thing the scene adds.
-const char* generation_kernels_gap(const RaycaConfig& c) {
-  if (c.integrator == RAYCA_INTEGRATOR_FLAT) return nullptr;
-  if (c.integrator != RAYCA_INTEGRATOR_PATHTRACER) return "integrator";
-  if (c.russian_roulette) return "russian_roulette";
-  if (c.direct_sampler != RAYCA_SAMPLER_NONE && c.direct_sampler != RAYCA_SAMPLER_NEE) return "direct_sampler";
-  const uint32_t limit = c.direct_sampler != RAYCA_SAMPLER_NONE ? (c.max_depth ? c.max_depth - 1u : 0u) : c.max_depth;
-  const bool bounces = limit > 0 && c.max_depth > 0;
-  if (bounces) {
-    if (c.indirect_sampler != RAYCA_SAMPLER_COSINE && c.indirect_sampler != RAYCA_SAMPLER_HEMISPHERE) return "indirect_sampler";
-    if (c.light_samples != 1) return "light_samples";
-  }
-  return nullptr;
-}
-bool nee_meets_directional_light(const RaycaScene* s, const RaycaConfig& c) {
-  if (c.integrator == RAYCA_INTEGRATOR_PATHTRACER && c.direct_sampler == RAYCA_SAMPLER_NEE)
-    for (const HostLight& l : s->host.lights)
-      if (l.kind == RAYCA_LIGHT_DIRECTIONAL) return true;  // todo!() in the reference (nee.rs:178): k_general reports it
-  return false;
-}
-bool generation_kernels_cover(const RaycaScene* s, const RaycaConfig& c) {
-  return generation_kernels_gap(c) == nullptr && !nee_meets_directional_light(s, c);
-}
-
-// A scene with nothing in it: what every call that traverses it or reads its tables answers.
-int32_t refuse_empty_scene(const RaycaScene* s) {
-  if (s->host.blas.empty() || s->prim_count == 0) return fail(RAYCA_ERR_EMPTY_SCENE, "empty TLAS (tlas.rs:272)");
-  return RAYCA_OK;
-}
-
-int32_t validate_config(const RaycaScene* s, const RaycaConfig& c, uint32_t engine, LaunchPlan& plan) {
-  if (c.samples_per_pixel == 0 || c.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "samples_per_pixel and light_samples must be > 0");
-  if (c.integrator > RAYCA_INTEGRATOR_PATHTRACER) return fail(RAYCA_ERR_BAD_ARG, "unknown integrator");
-  if (c.direct_sampler > RAYCA_SAMPLER_MIS || c.indirect_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "unknown sampler");
-  if (engine > RAYCA_ENGINE_FUSED) return fail(RAYCA_ERR_BAD_ARG, "unknown engine");
-  const uint32_t generations_if_path = c.integrator == RAYCA_INTEGRATOR_PATHTRACER ? c.max_depth : 1u;
-  plan.wavefront = plan.ordered && (engine == RAYCA_ENGINE_WAVEFRONT || (engine == RAYCA_ENGINE_AUTO && wavefront_by_default(generations_if_path)));
-  if (c.integrator == RAYCA_INTEGRATOR_FLAT) {
-    plan.mode = kModeFlat;
-    plan.generations = 1;
-    return RAYCA_OK;
-  }
-  if (engine == RAYCA_ENGINE_GENERAL || !generation_kernels_cover(s, c)) {
-    if (!plan.ordered) return fail(RAYCA_ERR_UNSUPPORTED, "exhaustive traversal is only offered with the generation kernels");
-    plan.mode = kModeGeneral;
-    plan.generations = 1;
-    return RAYCA_OK;
-  }
-  plan.mode = kModePath;
-  plan.generations = c.max_depth;  // generation g traces depth g; depth >= max_depth returns None
-  return RAYCA_OK;
-}
-
-// VGPRs of a kernel (hipFuncGetAttributes costs microseconds per call: looked up once per kernel)
-int32_t kernel_registers(const void* k, uint32_t& regs) {
-  static std::mutex mu;
-  static std::vector<std::pair<const void*, uint32_t>> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  for (const auto& e : cache)
-    if (e.first == k) { regs = e.second; return RAYCA_OK; }
-  hipFuncAttributes fa{};
-  HIP_TRY(hipFuncGetAttributes(&fa, k));
-  regs = fa.numRegs > 0 ? (uint32_t)fa.numRegs : 128u;
-  cache.emplace_back(k, regs);
-  return RAYCA_OK;
-}
-
-// Grid of a persistent kernel, whose blocks take batches (64 rays or one 8x8 tile) off a work counter until none are
-// left.  Persistent blocks need no co-residency (there are no inter-block waits), so the grid only has to fill every CU:
-// blocks per CU = what registers and LDS admit (one 256-thread block = one wave per SIMD; 512 VGPRs per lane per SIMD,
-// allocated in granules of 8; 160 KiB of LDS per CU), and no more blocks than the batches fill (4 per block).
-// `per_cu_forced` != 0 replaces the blocks per CU (RAYCA_GRID_MULT, for experiments).
-// `capped`: at most 8 blocks per CU, and fewer with frames in flight (the stack machine goes without both).  A frame
-// that takes every block slot of the chip keeps the next frame's blocks out until its own retire; with fewer slots per
-// frame the blocks of two frames are resident side by side and one frame's slow tiles run under the other's work
-// (DESIGN.md, "the frames leave each other room"; tests/gpu_inflight_probe.py with RAYCA_GRID_MULT).
-int32_t persistent_grid(const RaycaScene* s, const void* kernel, size_t lds_bytes, uint32_t batches, bool capped, uint32_t in_flight,
-                        uint32_t per_cu_forced, uint32_t& grid) {
-  uint32_t per_cu = per_cu_forced;
-  if (per_cu == 0) {
-    uint32_t regs = 0;
-    const int32_t rc = kernel_registers(kernel, regs);
-    if (rc != RAYCA_OK) return rc;
-    per_cu = std::min(512u / (((regs + 7u) / 8u) * 8u), lds_bytes ? (uint32_t)((160u * 1024u) / lds_bytes) : 8u);
-    if (capped) {
-      per_cu = std::max(1u, std::min(per_cu, 8u));
-      if (in_flight >= 4u) per_cu = (per_cu + 1u) / 2u;
-      else if (in_flight >= 2u) per_cu = (per_cu * 3u + 3u) / 4u;
-    }
-    per_cu = std::max(1u, per_cu);
-  }
-  const uint32_t need = (batches + 3u) / 4u;
-  grid = std::min((uint32_t)s->cu_count * per_cu, need ? need : 1u);
-  return RAYCA_OK;
-}
-
-// ---- wavefront engine: one generation = k_wf_trace, k_wf_shade, k_wf_shadow (wavefront.inc) -------------------
-using WfTraceKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, TraceCounters*, TraceLaunch);
-using WfShadowKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, TraceCounters*, TraceLaunch);
-using WfShadeKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, QueuedRay*, uint32_t*, WfBuffers, PathBuffers, uint32_t, uint8_t*,
-                               float4*, unsigned long long*);
-// flavour: 0 = conservative slabs, stack in LDS; 1 = conservative slabs, spill; 2 = the reference's slabs, spill
-template <bool GEN0, bool SPH, bool STATS>
-WfTraceKernel wf_trace_kernel(int flavour) {
-  if (flavour == 0) return k_wf_trace<GEN0, true, SPH, false, STATS>;
-  if (flavour == 1) return k_wf_trace<GEN0, true, SPH, true, STATS>;
-  return k_wf_trace<GEN0, false, SPH, true, STATS>;
-}
-template <bool GEN0, bool SPH, bool STATS>
-WfShadowKernel wf_shadow_kernel(int flavour) {
-  if (flavour == 0) return k_wf_shadow<GEN0, true, SPH, false, STATS>;
-  if (flavour == 1) return k_wf_shadow<GEN0, true, SPH, true, STATS>;
-  return k_wf_shadow<GEN0, false, SPH, true, STATS>;
-}
-template <bool GEN0>
-WfTraceKernel pick_wf_trace(int flavour, bool sph, bool stats) {
-  if (sph) return stats ? wf_trace_kernel<GEN0, true, true>(flavour) : wf_trace_kernel<GEN0, true, false>(flavour);
-  return stats ? wf_trace_kernel<GEN0, false, true>(flavour) : wf_trace_kernel<GEN0, false, false>(flavour);
-}
-template <bool GEN0>
-WfShadowKernel pick_wf_shadow(int flavour, bool sph, bool stats) {
-  if (sph) return stats ? wf_shadow_kernel<GEN0, true, true>(flavour) : wf_shadow_kernel<GEN0, true, false>(flavour);
-  return stats ? wf_shadow_kernel<GEN0, false, true>(flavour) : wf_shadow_kernel<GEN0, false, false>(flavour);
-}
-// rays: generation 0 of rayca_hip_radiance_device -- queue-fed, and a path's first vertex (k_wf_shade's RAYS); its Flat form
-// finalises in place
-WfShadeKernel pick_wf_shade(int mode, bool gen0, bool fused, bool sph, bool rays) {
-  if (rays) {
-    if (mode == kModeFlat) return sph ? k_wf_shade<kModeFlat, false, true, true, true> : k_wf_shade<kModeFlat, false, true, false, true>;
-    return sph ? k_wf_shade<kModePath, false, false, true, true> : k_wf_shade<kModePath, false, false, false, true>;
-  }
-  if (mode == kModeFlat) {
-    if (fused) return sph ? k_wf_shade<kModeFlat, true, true, true> : k_wf_shade<kModeFlat, true, true, false>;
-    return sph ? k_wf_shade<kModeFlat, true, false, true> : k_wf_shade<kModeFlat, true, false, false>;
-  }
-  if (gen0) return sph ? k_wf_shade<kModePath, true, false, true> : k_wf_shade<kModePath, true, false, false>;
-  return sph ? k_wf_shade<kModePath, false, false, true> : k_wf_shade<kModePath, false, false, false>;
-}
+#include "select.inc"   // how a launch gets its kernel and its plan
 
 // ---- one frame: the frame driver (frame_run) drives the per-engine launch steps below --------------------------------
 
@@ -906,7 +594,7 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   // 16 LDS entries per lane (16 KiB per block) so that the lean kernels' occupancy is set by registers
   // (the wide tree never needs more pending entries than the binary one: one plan serves both)
   const StackPlan sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
-  const int flavour = !fast ? 2 : (sp.spill_entries ? 1 : 0);
+  const Trav trav = !fast ? kTravExact : (sp.spill_entries ? kTravFastSpill : kTravFast);
   const uint32_t npix = f.pb.npix;
   const uint32_t batches = gen0 ? f.fp.tile_count : (npix + 63u) / 64u;
   const uint32_t grid = (batches + 3u) / 4u;  // one thread per ray, four 8x8 tiles per block
@@ -923,11 +611,11 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
     wb.sh_x = static_cast<float4*>(c->wf_sh_x.ptr);
   }
   // On a SAH scene the bounce generations' closest hits run on persistent lanes that take the next queue entry when their
-  // ray is done (refill.hip k_queue_refill; RAYCA_WF_REFILL=0 keeps one ray per lane, k_wf_trace), and so do the shadow
-  // rays (k_shadow_refill; RAYCA_WF_SHADOW_REFILL: 0 never, 1 bounce generations, 2 every generation), on the second
+  // ray is done (refill.hip k_queue_refill; Knobs.wf_refill off keeps one ray per lane, k_wf_trace), and so do the shadow
+  // rays (k_shadow_refill; Knobs.wf_shadow_refill: 0 never, 1 bounce generations, 2 every generation), on the second
   // set of work counters.  The work counters are cleared by frame_run, every generation.
-  static const bool wf_refill = [] { const char* e = getenv("RAYCA_WF_REFILL"); return e ? atoi(e) != 0 : true; }();
-  static const int shadow_refill_mode = [] { const char* e = getenv("RAYCA_WF_SHADOW_REFILL"); return e ? atoi(e) : 1; }();
+  const bool wf_refill = knobs().wf_refill;
+  const int shadow_refill_mode = knobs().wf_shadow_refill;
   TraceLaunch tl{};
   uint32_t lgrid = grid;
   // (a caller's rays on a SAH scene always: k_queue_refill has a form with the slack rays from anywhere need, k_wf_trace<false> has not)
@@ -936,7 +624,7 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   if (refill && (rc = persistent_grid(s, queue_refill_kernel(sph, stats, caller_rays), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
   if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
   if (refill) tl.ticket = 1u;
-  WfTraceKernel kt = gen0 ? pick_wf_trace<true>(flavour, sph, stats) : pick_wf_trace<false>(flavour, sph, stats);
+  WfTraceKernel kt = pick_wf_trace(gen0, trav, sph, stats);
   rc = timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_QUEUE_REFILL : RAYCA_KERNEL_WF_TRACE, f.timing, true, [&] {
     if (refill)
       launch_queue_refill(sph, stats, caller_rays, lgrid, sp.lds_bytes, f.stream, *f.dscene, q.in, q.in_count, wb.hits, c->heads, c->counters, tl);
@@ -958,7 +646,7 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   if (refill && (rc = persistent_grid(s, shadow_refill_kernel(gen0, sph, stats), sp.lds_bytes, batches, true, f.in_flight, 0u, lgrid)) != RAYCA_OK) return rc;
   if ((rc = bind_stack(c, sp, lgrid, tl)) != RAYCA_OK) return rc;
   if (refill) tl.ticket = 1u;
-  WfShadowKernel kh = gen0 ? pick_wf_shadow<true>(flavour, sph, stats) : pick_wf_shadow<false>(flavour, sph, stats);
+  WfShadowKernel kh = pick_wf_shadow(gen0, trav, sph, stats);
   const ShadowRefillArgs sa{wb.sh_ray, wb.sh_x, wb.nls, f.pb.direct, f.pb.state, f.pb.npix};
   return timed_launch(f.log, f.stream, refill ? RAYCA_KERNEL_SHADOW_REFILL : RAYCA_KERNEL_WF_SHADOW, f.timing, true, [&] {
     if (refill)
@@ -969,25 +657,18 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   });
 }
 
-// What one generation of the fused engine launches: its node format (decided by timing on this scene, RaycaScene::Tune, or
-// forced by RAYCA_NODE_FORMAT / RAYCA_WIDE), and for Flat camera rays k_generation or the lane-refill kernel.
-struct GenChoice {
-  int format;          // -1 = default, else bit 0 = 4-wide nodes, bit 1 = fp16 nodes
-  bool calibrating;    // a node-format calibration launch
-  bool refill;         // k_flat_refill instead of k_generation
-  bool refill_cal;     // a kernel calibration launch
-};
+// What one generation of the fused engine launches (GenChoice, select.inc).
 GenChoice choose_generation(Frame& f, uint32_t g) {
   RaycaScene* s = f.s;
   const LaunchPlan& plan = f.plan;
   RaycaScene::Tune& tu = s->tune[plan.mode == kModePath ? 1 : 0][g == 0 ? 0 : 1];
   GenChoice ch{f.all_formats ? format_forced() : 0, false, false, false};  // (binary f32 until the other formats are there)
   // Flat camera rays on a SAH scene: k_generation, or the lane-refill kernel (refill.hip)?  Decided per scene by timing
-  // eight frames (RAYCA_REFILL=0/1 pins it) -- BEFORE the node format is timed, on 4-wide f32 nodes: the kernels differ
+  // eight frames (Knobs.refill pins it) -- BEFORE the node format is timed, on 4-wide f32 nodes: the kernels differ
   // by far more than the formats do (soup: 6.2 against 11 ms), and the formats rank differently under the two (soup:
   // binary and 4-wide fp16 nodes tie under k_generation, 7.2 against 6.2 ms under lane refill), so the format has to be
   // timed on the kernel that will run it.
-  static const int refill_env = [] { const char* e = getenv("RAYCA_REFILL"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+  const int refill_env = knobs().refill;
   const bool refill_possible = f.fused && plan.mode == kModeFlat && plan.ordered && s->dev.ref_leaf_of != nullptr;
   const int refill_forced = !refill_possible ? 0 : (f.opts.camera_rays == RAYCA_CAMERA_REFILL ? 1 : (f.opts.camera_rays == RAYCA_CAMERA_GENERATION ? 0 : refill_env));
   ch.refill = refill_forced > 0;
@@ -1031,21 +712,21 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   // entries go to the (cold) spill area.
   const bool park = RAYCA_PARK_CTX && f.plan.mode == kModePath;
   const TravPlan tp = plan_traversal(s, f.plan.ordered, g, ch.format, park ? path_lds_entries() : kMaxLdsEntries);
-  f.node_format |= (tp.wide ? (g == 0 ? 1u : 2u) : 0u) | (tp.half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
+  f.node_format |= (traits(tp.trav).wide ? (g == 0 ? 1u : 2u) : 0u) | (traits(tp.trav).half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
                    (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u);
   const StackPlan sp = tp.stack;
   const size_t lds_bytes = sp.lds_bytes + (park ? (size_t)kCtxQuads * 16u * kBlock : 0u);
   const bool sph = s->host.sphere_count != 0;
   GenKernel k = pick_kernel(f.plan.mode, g == 0, f.fused, tp.trav, sph, f.plan.stats);
-  const RefillFlavour rf{sph, tp.wide, tp.wide || sp.spill_entries != 0, f.plan.stats, tp.half};
+  const RefillFlavour rf{tp.trav, sph, f.plan.stats};   // (launched only where choose_generation allows it: one of the kTravFast*)
   const uint32_t batches = g == 0 ? f.fp.tile_count : (f.pb.npix + 63u) / 64u;
-  static const uint32_t grid_mult = [] { const char* e = getenv("RAYCA_GRID_MULT"); return e ? (uint32_t)atoi(e) : 0u; }();
+  const uint32_t grid_mult = knobs().grid_mult;
   uint32_t grid = 0;
   TraceLaunch tl{};
   int32_t rc = persistent_grid(s, ch.refill ? flat_refill_kernel(rf) : reinterpret_cast<const void*>(k), lds_bytes, batches, true, f.in_flight, grid_mult, grid);
   if (rc != RAYCA_OK || (rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
   // work tickets (next_batch): pairs of batches while every wave still gets several, single batches for small frames
-  static const uint32_t ticket_forced = [] { const char* e = getenv("RAYCA_TICKET"); return e ? (uint32_t)atoi(e) : 0u; }();
+  const uint32_t ticket_forced = knobs().ticket;
   tl.ticket = ticket_forced ? ticket_forced : (batches >= 16u * grid ? 2u : 1u);
   size_t ev = 0;
   rc = timed_launch(f.log, f.stream, ch.refill ? RAYCA_KERNEL_FLAT_REFILL : RAYCA_KERNEL_GENERATION, f.timing || ch.calibrating || ch.refill_cal, true, [&] {
@@ -1063,18 +744,11 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
 }
 
 // One launch of the per-pixel stack machine (general.inc) for one sample of the frame.
-using GeneralKernel = void (*)(DevScene, FrameParams, uint32_t*, PathBuffers, GFrameStore, TraceCounters*, TraceLaunch);
-template <bool SPH, bool STATS>
-GeneralKernel general_kernel(bool fast) {
-  return fast ? k_general<true, true, SPH, true, STATS> : k_general<true, false, SPH, true, STATS>;
-}
 int32_t stack_machine(Frame& f) {
   RaycaScene* s = f.s;
   FrameCtx* c = f.c;
   const RaycaConfig& cfg = f.cfg;
-  const bool fast = s->dev.ref_leaf_of != nullptr, sph = s->host.sphere_count != 0, stats = f.plan.stats;
-  GeneralKernel k = sph ? (stats ? general_kernel<true, true>(fast) : general_kernel<true, false>(fast))
-                        : (stats ? general_kernel<false, true>(fast) : general_kernel<false, false>(fast));
+  GeneralKernel k = pick_general_kernel(s->dev.ref_leaf_of != nullptr, s->host.sphere_count != 0, f.plan.stats);
   const StackPlan sp = plan_stack(s->host.max_depth);
   uint32_t grid = 0;
   int32_t rc = persistent_grid(s, reinterpret_cast<const void*>(k), sp.lds_bytes, f.fp.tile_count, false, 1u, 0u, grid);
@@ -1412,25 +1086,6 @@ int32_t render_impl(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, uint3
 
 }  // namespace
 
-namespace {
-TravPlan plan_traversal(const RaycaScene* s, bool ordered, uint32_t generation, int format_choice, uint32_t max_lds_entries) {
-  // format_choice: -1 = default, else bit 0 = 4-wide nodes, bit 1 = fp16 nodes
-  TravPlan tp{};
-  const bool fast = s->dev.ref_leaf_of != nullptr;  // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
-  tp.wide = ordered && fast && formats_ready(s) && (format_choice >= 0 ? (format_choice & 1) != 0 : use_wide(generation));
-  const bool half = ordered && fast && format_choice >= 0 && (format_choice & 2) != 0 && formats_ready(s) && s->dev_full.nodes_h != nullptr;
-  const uint32_t need = tp.wide ? s->host.max_depth4 : s->host.max_depth;
-  tp.stack = plan_stack(need, max_lds_entries);  // (also decides between the kernels with and without the spill path)
-  if (!ordered) tp.trav = fast ? kTravFastAll : kTravExactAll;
-  else if (!fast) tp.trav = kTravExact;
-  else if (tp.wide) tp.trav = half ? kTravFastWideHalf : kTravFastWide;
-  else if (tp.stack.spill_entries) tp.trav = half ? kTravFastSpillHalf : kTravFastSpill;
-  else tp.trav = half ? kTravFastHalf : kTravFast;
-  tp.half = half;
-  return tp;
-}
-}  // namespace
-
 // ---- rayca_hip_render_multi ----------------------------------------------------------------------------------------------
 namespace {
 
@@ -1521,6 +1176,7 @@ int32_t rayca_hip_selftest(void) {
   std::string err;
   int32_t rc = selftest_half_rounding(err);
   if (rc == RAYCA_OK) rc = selftest_device_layouts(err);
+  if (rc == RAYCA_OK) rc = selftest_kernel_selection(err);
   return rc == RAYCA_OK ? RAYCA_OK : fail(rc, err);
 }
 
@@ -2042,8 +1698,7 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
   const TravPlan tp = plan_traversal(s, ordered, 0);
   const StackPlan sp = tp.stack;
   const size_t lds_bytes = sp.lds_bytes;
-  TraceKernel k = s->host.sphere_count ? (stats ? trace_kernel<true, true>(tp.trav) : trace_kernel<true, false>(tp.trav))
-                                       : (stats ? trace_kernel<false, true>(tp.trav) : trace_kernel<false, false>(tp.trav));
+  TraceKernel k = pick_trace_kernel(tp.trav, s->host.sphere_count != 0, stats);
   const uint32_t tgrid = (count + kBlock - 1) / kBlock;
   TraceLaunch tl{};
   if ((rc = bind_stack(c, sp, tgrid, tl)) != RAYCA_OK) return rc;
@@ -2194,7 +1849,7 @@ int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   io.flags_out = static_cast<uint32_t*>(sq.flags_out);
   const uint32_t grid = (uint32_t)(((uint64_t)sq.count + kBlock - 1u) / kBlock);
   return run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
-    hipLaunchKernelGGL(s->host.sphere_count ? k_surface<true> : k_surface<false>, dim3(grid), dim3(kBlock), 0, stream, formats_ready(s) ? s->dev_full : s->dev, io);
+    hipLaunchKernelGGL(pick_surface_kernel(s->host.sphere_count != 0), dim3(grid), dim3(kBlock), 0, stream, formats_ready(s) ? s->dev_full : s->dev, io);
     HIP_TRY(hipGetLastError());
     ++launches;
     return RAYCA_OK;

@@ -544,40 +544,26 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_query_refill(De
   }
 }
 
+// The pickers: flags only, but for k_flat_refill, which reads WIDE, SPILL and HALF of a flavour -- of the six kTravFast* in
+// production; the 4-wide forms always have the spill path, and the other flavours have no form of their own.
 using QueryRefillKernel = void (*)(DevScene, QueryIo, uint32_t*, TraceCounters*, TraceLaunch);
-template <bool OCCLUDED>
-QueryRefillKernel pick_query(bool sph, bool stats) {
-  if (sph) return stats ? k_query_refill<OCCLUDED, true, true> : k_query_refill<OCCLUDED, true, false>;
-  return stats ? k_query_refill<OCCLUDED, false, true> : k_query_refill<OCCLUDED, false, false>;
+QueryRefillKernel pick_query(bool occluded, bool sph, bool stats) {
+  return with_flags([](auto OCCLUDED, auto SPH, auto STATS) -> QueryRefillKernel { return k_query_refill<OCCLUDED, SPH, STATS>; }, occluded, sph, stats);
 }
 
 using ShadowRefillKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, uint32_t*, TraceCounters*, TraceLaunch);
-template <bool GEN0>
-ShadowRefillKernel pick_shadow(bool sph, bool stats) {
-  if (sph) return stats ? k_shadow_refill<GEN0, true, true> : k_shadow_refill<GEN0, true, false>;
-  return stats ? k_shadow_refill<GEN0, false, true> : k_shadow_refill<GEN0, false, false>;
+ShadowRefillKernel pick_shadow(bool gen0, bool sph, bool stats) {
+  return with_flags([](auto GEN0, auto SPH, auto STATS) -> ShadowRefillKernel { return k_shadow_refill<GEN0, SPH, STATS>; }, gen0, sph, stats);
 }
 
 using QueueRefillKernel = void (*)(DevScene, const QueuedRay*, const uint32_t*, float4*, uint32_t*, TraceCounters*, TraceLaunch);
 QueueRefillKernel pick_queue(bool sph, bool stats, bool slack) {
-  if (slack) {
-    if (sph) return stats ? k_queue_refill<true, true, true> : k_queue_refill<true, false, true>;
-    return stats ? k_queue_refill<false, true, true> : k_queue_refill<false, false, true>;
-  }
-  if (sph) return stats ? k_queue_refill<true, true> : k_queue_refill<true, false>;
-  return stats ? k_queue_refill<false, true> : k_queue_refill<false, false>;
+  return with_flags([](auto SPH, auto STATS, auto SLACK) -> QueueRefillKernel { return k_queue_refill<SPH, STATS, SLACK>; }, sph, stats, slack);
 }
 
 using RefillKernel = void (*)(DevScene, FrameParams, uint32_t*, uint8_t*, float4*, TraceCounters*, TraceLaunch);
-template <bool SPH, bool STATS>
-RefillKernel pick2(bool wide, bool spill, bool half) {
-  if (wide) return half ? k_flat_refill<SPH, true, true, STATS, true> : k_flat_refill<SPH, true, true, STATS, false>;  // 4-wide: always with the spill path
-  if (spill) return half ? k_flat_refill<SPH, false, true, STATS, true> : k_flat_refill<SPH, false, true, STATS, false>;
-  return half ? k_flat_refill<SPH, false, false, STATS, true> : k_flat_refill<SPH, false, false, STATS, false>;
-}
 RefillKernel pick(const RefillFlavour& f) {
-  if (f.sph) return f.stats ? pick2<true, true>(f.wide, f.spill, f.half) : pick2<true, false>(f.wide, f.spill, f.half);
-  return f.stats ? pick2<false, true>(f.wide, f.spill, f.half) : pick2<false, false>(f.wide, f.spill, f.half);
+  return with_flavour([](auto T, auto SPH, auto STATS) -> RefillKernel { return k_flat_refill<SPH, T.WIDE, T.SPILL, STATS, T.HALF>; }, f.trav, f.sph, f.stats);
 }
 
 RAYCA_NO_PK_END
@@ -598,16 +584,16 @@ void launch_queue_refill(bool sph, bool stats, bool slack, uint32_t grid, size_t
 }
 
 const void* query_refill_kernel(bool occluded, bool sph, bool stats) {
-  return reinterpret_cast<const void*>(occluded ? pick_query<true>(sph, stats) : pick_query<false>(sph, stats));
+  return reinterpret_cast<const void*>(pick_query(occluded, sph, stats));
 }
 
 void launch_query_refill(bool occluded, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueryIo& q,
                          uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl) {
-  hipLaunchKernelGGL(occluded ? pick_query<true>(sph, stats) : pick_query<false>(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, q, heads, counters, tl);
+  hipLaunchKernelGGL(pick_query(occluded, sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, q, heads, counters, tl);
 }
 
 const void* shadow_refill_kernel(bool gen0, bool sph, bool stats) {
-  return reinterpret_cast<const void*>(gen0 ? pick_shadow<true>(sph, stats) : pick_shadow<false>(sph, stats));
+  return reinterpret_cast<const void*>(pick_shadow(gen0, sph, stats));
 }
 
 void launch_shadow_refill(bool gen0, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const FrameParams& fp,
@@ -621,7 +607,7 @@ void launch_shadow_refill(bool gen0, bool sph, bool stats, uint32_t grid, size_t
   pb.direct = a.direct;
   pb.state = a.state;
   pb.npix = a.npix;
-  hipLaunchKernelGGL(gen0 ? pick_shadow<true>(sph, stats) : pick_shadow<false>(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, fp, in_rays, in_count, wb,
+  hipLaunchKernelGGL(pick_shadow(gen0, sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, fp, in_rays, in_count, wb,
                      pb, depth, heads, counters, tl);
 }
 

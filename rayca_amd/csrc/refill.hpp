@@ -3,11 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.hpp"
+#include "flavour.hpp"
 
 namespace rayca {
 
 struct RefillFlavour {
-  bool sph, wide, spill, stats, half;
+  Trav trav;   // one of the six kTravFast* (k_flat_refill reads its WIDE, SPILL and HALF)
+  bool sph, stats;
 };
 // host stub of the instantiation (for hipFuncGetAttributes) and its launch
 const void* flat_refill_kernel(const RefillFlavour& f);

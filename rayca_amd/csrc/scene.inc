@@ -61,7 +61,7 @@ int32_t warm_device(int device, bool build_on_host) {
   // the three code objects (kernels.hip, refill.hip, bvh_build.hip) are loaded on first use of a kernel of theirs
   hipFuncAttributes fa{};
   HIP_TRY(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_resolve)));
-  HIP_TRY(hipFuncGetAttributes(&fa, flat_refill_kernel(RefillFlavour{false, false, false, false, false})));
+  HIP_TRY(hipFuncGetAttributes(&fa, flat_refill_kernel(RefillFlavour{kTravFast, false, false})));
   HIP_TRY(hipFuncGetAttributes(&fa, gpu_builder_any_kernel()));
   // a process's first stream, first asynchronous copies from pageable memory and first device allocation set up
   // runtime-internal staging (measured: ~150 ms inside the first BVH build of a process, nothing afterwards)

@@ -11,7 +11,7 @@ extern "C" int host_build_probe(const RaycaSceneDesc* d, unsigned builder, int r
     const int32_t rc = rayca::build_host_scene(*d, true, builder, s, err);
     const auto t1 = std::chrono::steady_clock::now();
     if (rc) { fprintf(stderr, "build failed: %s\n", err.c_str()); return rc; }
-    fprintf(stderr, "[probe] build #%d: %.1f ms, %zu nodes, %zu 4-wide\n", r, std::chrono::duration<float, std::milli>(t1 - t0).count(), s.dev_nodes.size(), s.dev_nodes4.size());
+    fprintf(stderr, "[probe] build #%d: %.1f ms, %zu nodes, %zu 4-wide, stack need %u / %u\n", r, std::chrono::duration<float, std::milli>(t1 - t0).count(), s.dev_nodes.size(), s.dev_nodes4.size(), s.max_depth, s.max_depth4);
   }
   return 0;
 }

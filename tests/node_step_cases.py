@@ -357,6 +357,9 @@ def oracle_depth(desc):
 
 
 # ---- frames (need a GPU) ----------------------------------------------------------------------------------------------------
+NODE_FORMATS = {}   # RaycaStats.node_format of the counting frames render_frames made, by their key
+
+
 def render_frames(names=None):
     """{"<scene>/<builder>/<config>/u8|f32|counters": array}: the fused engine's frames of leaf_shade_cases (production
     instantiation) and the six counters of its counting instantiation, RAYCA_BUILDER_SAH and RAYCA_BUILDER_REFERENCE"""
@@ -373,6 +376,7 @@ def render_frames(names=None):
                 key = f"{name}/{bname}/{cname}/"
                 out[key + "u8"], out[key + "f32"] = u8, f32
                 out[key + "counters"] = np.array([int(st[k]) for k in COUNTER_KEYS], np.uint64)
+                NODE_FORMATS[key] = int(st["node_format"])
             ds.close()
     return out
 
@@ -408,3 +412,5 @@ def table_counters():
 if __name__ == "__main__":   # the child process of the spill-boundary test
     np.savez(sys.argv[1], **render_frames(sys.argv[2:] or None))
     print("wrote", sys.argv[1], "RAYCA_PATH_LDS_ENTRIES =", os.environ.get("RAYCA_PATH_LDS_ENTRIES"))
+    # bits 0-3 of RaycaStats.node_format: 4-wide nodes in generation 0 / in bounces, fp16 nodes in generation 0 / in bounces
+    print("node formats of the RAYCA_BUILDER_SAH frames:", sorted({v & 15 for k, v in NODE_FORMATS.items() if "/sah/" in k}))

@@ -58,6 +58,14 @@ def test_engines_agree(gpu, case):
         assert st["wave_triangle_slots"] >= st["triangles_tested"] > 0
 
 
+WF_LDS_ENTRIES = 16   # RAYCA_WF_LDS_ENTRIES (select.inc): the LDS part of the wavefront engine's node stack
+
+
+def wavefront_stack_spills(ds):
+    """does the wavefront engine plan this scene's traversals with spill entries (plan_stack: stack need + 1 > the LDS part)?"""
+    return ds.info()["max_depth"] + 1 > WF_LDS_ENTRIES
+
+
 def test_engines_agree_on_tiles_and_builders(gpu):
     desc = flatten(scenes.cornell_scene())
     cfg = Config(max_depth=2, seed=9)
@@ -78,6 +86,7 @@ def test_engines_agree_on_tiles_and_builders(gpu):
 def test_engines_agree_at_full_size(gpu):
     """The bench frame (atrium 1080p, primary + shadow) and the 4-bounce frame at reduced size."""
     ds = DeviceScene(flatten(scenes.atrium_scene()), Config(), builder=abi.BUILDER_SAH)
+    assert wavefront_stack_spills(ds)   # k_wf_trace / k_wf_shadow on their spill path (kTravFastSpill), counting instantiations
     for cfg, w, h in ((Config(max_depth=1), 1920, 1080), (Config(integrator=I.Flat), 1920, 1080), (Config(seed=2), 640, 360)):
         (u8a, fa, sa), (u8b, fb, sb) = both(ds, cfg, w, h, want_f32=True)
         assert np.array_equal(fa.view(np.uint32), fb.view(np.uint32)), f"max abs diff {np.abs(fa - fb).max():.3e}"
@@ -92,6 +101,7 @@ def test_config4_4k_four_bounce_engines_and_eight_tiles(gpu):
     w, h = 3840, 2160
     cfg = Config(max_depth=5, seed=4)
     ds = DeviceScene(flatten(scenes.atrium_scene()), Config(), builder=abi.BUILDER_SAH)
+    assert wavefront_stack_spills(ds)   # the same on the production instantiations
     whole, _, st = ds.render(cfg, w, h, want_f32=False, engine=abi.ENGINE_WAVEFRONT)
     fused, _, sf = ds.render(cfg, w, h, want_f32=False, engine=abi.ENGINE_FUSED)
     assert np.array_equal(whole, fused)

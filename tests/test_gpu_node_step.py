@@ -14,7 +14,9 @@ runs node_step's if / else-if chain as before and is here as the issue's second 
   rendered by a child process with RAYCA_PATH_LDS_ENTRIES=4 equal this process's frames (default entries) in RGBA8, rgba32f
   and all six counters.  On the four small scenes no camera ray holds more than four entries (walked: the cold block of
   NodeStack::transfer is entered, no entry goes beyond LDS); deep_soup is there so that entries do: its camera rays are walked
-  on the device's tree and must store entries beyond the fourth LDS entry, in both forms of the search.
+  on the device's tree and must store entries beyond the fourth LDS entry, in both forms of the search.  A second child with
+  RAYCA_NODE_FORMAT=2 as well renders the same frames on the binary fp16 nodes (k_generation's kTravFastSpillHalf on deep_soup,
+  kTravFastHalf where the stack fits): the same pixels and ray counts, bit for bit.
 * Counters: the counting instantiations reproduce tests/golden/node_step_counters.json, recorded from the build before the
   change (tests/make_node_step_golden.py): fused, wavefront and reference-builder frames, and the table's ray batch."""
 import json
@@ -37,16 +39,33 @@ def golden():
     return json.load(open(N.GOLDEN))
 
 
-@pytest.fixture(scope="module")
-def spilled_frames(gpu, tmp_path_factory):
-    """the frames of a fresh child process whose LDS stack holds SPILL_ENTRIES entries (the knob is read once per process)"""
+def spill_child(tmp_path_factory, **knobs):
+    """(frames, stdout) of a fresh child process whose LDS stack holds SPILL_ENTRIES entries (the knobs are read once per process)"""
     out = str(tmp_path_factory.mktemp("node_step") / "spill.npz")
-    env = dict(os.environ, RAYCA_PATH_LDS_ENTRIES=str(N.SPILL_ENTRIES))
+    env = dict(os.environ, RAYCA_PATH_LDS_ENTRIES=str(N.SPILL_ENTRIES), **knobs)
     r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "node_step_cases.py"), out],
                        env=env, capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
     assert f"RAYCA_PATH_LDS_ENTRIES = {N.SPILL_ENTRIES}" in r.stdout
-    return dict(np.load(out))
+    return dict(np.load(out)), r.stdout
+
+
+@pytest.fixture(scope="module")
+def spilled_frames(gpu, tmp_path_factory):
+    return spill_child(tmp_path_factory)[0]
+
+
+@pytest.fixture(scope="module")
+def spilled_half_frames(gpu, tmp_path_factory):
+    """the same child with the binary fp16 nodes pinned for every generation: its path frames run k_generation's kTravFastSpillHalf
+    where the stack need exceeds the LDS part (deep_soup: test_the_deep_scene_crosses_the_spill_boundary) and kTravFastHalf elsewhere"""
+    frames, stdout = spill_child(tmp_path_factory, RAYCA_NODE_FORMAT="2")
+    line = [l for l in stdout.splitlines() if l.startswith("node formats of the RAYCA_BUILDER_SAH frames:")]
+    formats = json.loads(line[0].split(":", 1)[1])
+    print("half child:", line[0])
+    # fp16 nodes in generation 0 (4) and in the bounces (8), never the 4-wide tree (1, 2); 0: a frame of the stack machine
+    assert 4 in formats and 12 in formats and set(formats) <= {0, 4, 12}, formats
+    return frames
 
 
 @pytest.mark.parametrize("name", list(N.SPILL_SCENES))
@@ -64,6 +83,25 @@ def test_frames_across_the_spill_boundary(gpu, spilled_frames, name):
         else:
             assert np.array_equal(a, b), f"{k}: {a if a.size == 6 else ''} vs {b if b.size == 6 else ''}"
     assert lit > 0.0
+
+
+@pytest.mark.parametrize("name", list(N.SPILL_SCENES))
+def test_frames_across_the_spill_boundary_on_fp16_nodes(gpu, spilled_half_frames, name):
+    """The fp16 boxes steer the search and never decide a hit (test_gpu_ray_edges.py::test_node_formats holds them to the oracle):
+    the frames are this process's, bit for bit -- which test_gpu_leaf_shade.py and the oracle-checked frames above pin.  The box
+    and triangle counts are the fp16 tree's own and are not compared; the ray counts are."""
+    assert "RAYCA_PATH_LDS_ENTRIES" not in os.environ and "RAYCA_NODE_FORMAT" not in os.environ
+    here = N.render_frames([name])
+    keys = [k for k in spilled_half_frames if k.startswith(name + "/")]
+    assert sorted(keys) == sorted(here) and len(keys) == 2 * len(L.CONFIGS) * 3
+    for k in keys:
+        a, b = here[k], spilled_half_frames[k]
+        if k.endswith("/f32"):
+            assert np.array_equal(Q.bits(a), Q.bits(b)), f"{k}: max abs diff {np.nanmax(np.abs(a - b)):.3e}"
+        elif k.endswith("/u8"):
+            assert np.array_equal(a, b), k
+        else:
+            assert np.array_equal(a[:4], b[:4]), f"{k}: {a} vs {b}"   # rays_primary, rays_shadow, rays_bounce, hits_shaded
 
 
 @pytest.mark.parametrize("name", list(N.SPILL_SCENES))
