@@ -708,14 +708,16 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   FrameCtx* c = f.c;
   const GenChoice ch = choose_generation(f, g);
   // path frames park each lane's ShadeCtx behind the stack rows (kernels.hip, RAYCA_PARK_CTX): 7 KiB per wave.  Their
-  // LDS part of the stack is capped at path_lds_entries() so that four blocks per CU still fit 160 KiB; deeper
+  // LDS part of the stack is capped at path_lds_entries() so that sixteen waves per CU (10 KiB each) still fit 160 KiB; deeper
   // entries go to the (cold) spill area.
   const bool park = RAYCA_PARK_CTX && f.plan.mode == kModePath;
   const TravPlan tp = plan_traversal(s, f.plan.ordered, g, ch.format, park ? path_lds_entries() : kMaxLdsEntries);
   f.node_format |= (traits(tp.trav).wide ? (g == 0 ? 1u : 2u) : 0u) | (traits(tp.trav).half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
                    (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u);
   const StackPlan sp = tp.stack;
-  const size_t lds_bytes = sp.lds_bytes + (park ? (size_t)kCtxQuads * 16u * kBlock : 0u);
+  // (k_generation runs as workgroups of kGenBlock threads, k_flat_refill as 256-thread blocks: rows and quads per thread of the workgroup)
+  const uint32_t block = ch.refill ? (uint32_t)kBlock : (uint32_t)kGenBlock;
+  const size_t lds_bytes = ((size_t)sp.lds_entries * 4u + (park ? (size_t)kCtxQuads * 16u : 0u)) * block;
   const bool sph = s->host.sphere_count != 0;
   GenKernel k = pick_kernel(f.plan.mode, g == 0, f.fused, tp.trav, sph, f.plan.stats);
   const RefillFlavour rf{tp.trav, sph, f.plan.stats};   // (launched only where choose_generation allows it: one of the kTravFast*)
@@ -723,18 +725,17 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   const uint32_t grid_mult = knobs().grid_mult;
   uint32_t grid = 0;
   TraceLaunch tl{};
-  int32_t rc = persistent_grid(s, ch.refill ? flat_refill_kernel(rf) : reinterpret_cast<const void*>(k), lds_bytes, batches, true, f.in_flight, grid_mult, grid);
-  if (rc != RAYCA_OK || (rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
-  // work tickets (next_batch): pairs of batches while every wave still gets several, single batches for small frames
+  int32_t rc = persistent_grid(s, ch.refill ? flat_refill_kernel(rf) : reinterpret_cast<const void*>(k), lds_bytes, batches, true, f.in_flight, grid_mult, grid, block / 64u);
+  if (rc != RAYCA_OK || (rc = bind_stack(c, sp, grid, tl, block)) != RAYCA_OK) return rc;
   const uint32_t ticket_forced = knobs().ticket;
-  tl.ticket = ticket_forced ? ticket_forced : (batches >= 16u * grid ? 2u : 1u);
+  tl.ticket = ticket_forced ? ticket_forced : ticket_policy(batches, grid, block / 64u);
   size_t ev = 0;
   rc = timed_launch(f.log, f.stream, ch.refill ? RAYCA_KERNEL_FLAT_REFILL : RAYCA_KERNEL_GENERATION, f.timing || ch.calibrating || ch.refill_cal, true, [&] {
     if (ch.refill)
       launch_flat_refill(rf, grid, lds_bytes, f.stream, *f.dscene, f.fp, c->heads, f.rgba8, f.rgba32f, c->counters, tl);
     else
-      hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds_bytes, f.stream, *f.dscene, f.fp, c->heads, q.in, q.in_count, q.out, q.out_count, f.pb, g,
-                         f.rgba8, f.rgba32f, c->counters, tl);
+      hipLaunchKernelGGL(k, dim3(grid), dim3(kGenBlock), lds_bytes, f.stream,
+                         GenArgs{*f.dscene, f.fp, c->heads, q.in, q.in_count, q.out, q.out_count, f.pb, g, f.rgba8, f.rgba32f, c->counters, tl});
     return RAYCA_OK;
   }, &ev);
   if (rc != RAYCA_OK) return rc;
@@ -1177,6 +1178,7 @@ int32_t rayca_hip_selftest(void) {
   int32_t rc = selftest_half_rounding(err);
   if (rc == RAYCA_OK) rc = selftest_device_layouts(err);
   if (rc == RAYCA_OK) rc = selftest_kernel_selection(err);
+  if (rc == RAYCA_OK) rc = selftest_grid_policy(err);
   return rc == RAYCA_OK ? RAYCA_OK : fail(rc, err);
 }
 

@@ -47,24 +47,54 @@ RAYCA_NO_PK_BEGIN
 //   primary ray -> shade -> [NEE shadow ray]* -> bounce sample -> done
 // so the traversal loop is instantiated once per kernel and the registers that must survive it are
 // the ray, the hit, the compact ShadeCtx and a few colours.
+// k_generation's arguments as ONE aggregate, so that every field has a known offset in the kernel-argument segment.  Hot fields
+// -- what trace() and NodeStack read of `sc`, `heads`, `depth`, `tl` -- are read from the argument itself and live in SGPRs over
+// the persistent loop.  Cold fields -- the camera and sampling fields of `fp`, the shading tables of `sc`, `pb`, the queues, the
+// counters and the outputs -- are read through GEN_COLD(member) in the block that uses them (cold_arg, trace_core.inc): once per
+// batch, vertex or sample, a scalar load from the (cached) argument segment instead of an SGPR kept, or spilled, over the loop.
+// -DRAYCA_COLD_ARGS=0: every field from the by-value argument, for A/B runs.
+#ifndef RAYCA_COLD_ARGS
+#define RAYCA_COLD_ARGS 1
+#endif
+struct GenArgs {
+  DevScene sc;
+  FrameParams fp;
+  uint32_t* heads;
+  const QueuedRay* in_rays;
+  const uint32_t* in_count;
+  QueuedRay* out_rays;
+  uint32_t* out_count;
+  PathBuffers pb;
+  uint32_t depth;
+  uint8_t* rgba8;
+  float4* rgba32f;
+  TraceCounters* counters;
+  TraceLaunch tl;
+};
+#if RAYCA_COLD_ARGS
+#define GEN_COLD(member) cold_arg<decltype(GenArgs::member)>((uint32_t)offsetof(GenArgs, member))
+#else
+#define GEN_COLD(member) (a.member)
+#endif
 template <int MODE, bool GEN0, bool ORDERED, bool FUSED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF>
-__global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : RAYCA_MIN_WAVES) void k_generation(DevScene sc, FrameParams fp, uint32_t* heads, const QueuedRay* in_rays,
-                                                       const uint32_t* in_count, QueuedRay* out_rays, uint32_t* out_count,
-                                                       PathBuffers pb, uint32_t depth, uint8_t* rgba8, float4* rgba32f,
-                                                       TraceCounters* counters, TraceLaunch tl) {
+__global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : RAYCA_MIN_WAVES) void k_generation(GenArgs a) {
+  const TraceLaunch& tl = a.tl;
+  uint32_t* const heads = a.heads;
+  const uint32_t depth = a.depth;
   extern __shared__ uint32_t lds_stack[];
-  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  // (workgroups of kGenBlock threads: the stride of the stack rows and of the parked context; no barrier, nothing shared between waves)
+  NodeStack<SPILL, kGenBlock> stack = make_stack<SPILL, kGenBlock>(lds_stack, tl, rc_bid() * kGenBlock + rc_tid());
   // behind the stack rows: this lane's parked ShadeCtx (path frames only; the host sizes the allocation)
-  float4* const ctx_slot = reinterpret_cast<float4*>(lds_stack + tl.lds_entries * kBlock) + rc_tid();
+  float4* const ctx_slot = reinterpret_cast<float4*>(lds_stack + tl.lds_entries * kGenBlock) + rc_tid();
   constexpr bool PARK = RAYCA_PARK_CTX && MODE == kModePath;
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
   WorkCursor wc{};
-  const uint32_t total = GEN0 ? fp.tile_count : (*in_count + 63u) / 64u;
+  const uint32_t total = GEN0 ? GEN_COLD(fp).tile_count : (*GEN_COLD(in_count) + 63u) / 64u;
   LaneCounters cnt{};
   uint32_t n_shaded = 0, n_shadow = 0, n_bounce = 0;
-  const bool collect_emissive = GEN0 ? true : (fp.direct_sampler == RAYCA_SAMPLER_NONE);
-  const uint32_t nee_lights = (MODE == kModePath && fp.direct_sampler == RAYCA_SAMPLER_NEE) ? sc.light_count : 0u;
+  const bool collect_emissive = GEN0 ? true : (GEN_COLD(fp).direct_sampler == RAYCA_SAMPLER_NONE);
+  const uint32_t nee_lights = (MODE == kModePath && GEN_COLD(fp).direct_sampler == RAYCA_SAMPLER_NEE) ? GEN_COLD(sc).light_count : 0u;
 
   for (;;) {
     const uint32_t batch = next_batch(heads, total, home, wc, tl.ticket);
@@ -73,6 +103,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
     uint32_t p = 0, key = 0;
     DRay ray;
     if (GEN0) {
+      const FrameParams& fp = GEN_COLD(fp);
       const uint32_t ty = batch / fp.tiles_x, tx = batch - ty * fp.tiles_x;
       const uint32_t x = tx * kTileW + (lane & (kTileW - 1u)), r = ty * kTileH + (lane >> RAYCA_TILE_W_LOG2);
       live = x < fp.width && r < fp.rows;
@@ -84,15 +115,15 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
       }
     } else {
       const uint32_t i = batch * 64u + lane;
-      live = i < *in_count;
+      live = i < *GEN_COLD(in_count);
       if (live) {
-        const QueuedRay q = in_rays[i];
+        const QueuedRay q = GEN_COLD(in_rays)[i];
         ray = make_ray(point3(q.ox, q.oy, q.oz), vec3(q.dx, q.dy, q.dz));
         p = q.pixel;
         key = q.key;
       }
     }
-    const size_t slot = (size_t)depth * pb.npix + p;
+    const size_t slot = (size_t)depth * GEN_COLD(pb).npix + p;
     bool in_shadow = false;
     // shadow rays: the any-hit bound.  A point light's is its distance (a finite square root, never FLT_MAX); FLT_MAX
     // means "closest hit wanted": camera and bounce rays, and the shadow ray of a quad light (NeeSample.quad)
@@ -113,17 +144,18 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
       DHit hit;
       constexpr int kLeaveK = !ORDERED ? 0 : (MODE == kModeFlat ? RAYCA_LEAVE_K_CAMERA : (GEN0 ? RAYCA_LEAVE_K_PATH0 : RAYCA_LEAVE_K_BOUNCE));
       constexpr int kSlackForm = MODE == kModeFlat ? kSlackAlways : (GEN0 ? kSlackPerWave : kSlackNever);
-      const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, kLeaveK, kSlackForm>(sc, ray, t_stop, stack, hit, cnt);
+      const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, kLeaveK, kSlackForm>(a.sc, ray, t_stop, stack, hit, cnt);
       if (!in_shadow) {
         if (!found) {
           if (FUSED) direct = black() + black();  // unwrap_or(BLACK), color += it
-          else pb.state[slot] = kVertexNone;
+          else GEN_COLD(pb).state[slot] = kVertexNone;
           live = false;
         } else {
           n_shaded++;
           Color color;
           bool emissive;
-          shade_hit<SPH>(sc, ray, hit, MODE == kModePath, color, emissive, cx);
+          const PathBuffers& pb = GEN_COLD(pb);
+          shade_hit<SPH>(GEN_COLD(sc), ray, hit, MODE == kModePath, color, emissive, cx);
           if (MODE == kModeFlat) {  // Flat::trace  integrator/flat.rs:16-28
             if (FUSED) direct = black() + color;
             else {
@@ -138,14 +170,14 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
           } else {
             in_shadow = true;  // enter the NEE loop (possibly empty)
             if (PARK) {
-              park_ctx(ctx_slot, cx);
+              park_ctx<kGenBlock>(ctx_slot, cx);
               // (black(), made here from a zero the compiler cannot hoist: as a loop-invariant float4 it sat in four registers over
               // the whole batch loop, which the counting instantiations could only afford through scratch: with the pipelined node
               // loop k_generation<1, true, true, false, true, SPH, false, false, true, HALF> went from 0-2 to 4 spilled VGPRs and
               // k_generation<1, true, false, false, FAST, *, false, true, true, false> from 0-4 to 2-5 -- tests/kernel_resources.py)
               float zero = 0.0f;
               asm volatile("" : "+v"(zero));
-              ctx_slot[6 * kBlock] = make_float4(zero, zero, zero, 1.0f);
+              ctx_slot[6 * kGenBlock] = make_float4(zero, zero, zero, 1.0f);
             }
           }
         }
@@ -155,6 +187,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
         if (t_stop == FLT_MAX) {  // quad light: "lit iff the closest hit is emissive" (nee.rs:103-104)
           lit = false;
           if (found) {
+            const DevScene& sc = GEN_COLD(sc);
             const uint32_t hm = sc.ext[hit.prim].material;
             lit = hm != RAYCA_NONE && hm < sc.material_count && sc.materials[hm].emissive != 0u;
           }
@@ -162,12 +195,12 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
           lit = !(found && hit.t < t_stop);  // nee.rs:152-156
         }
         if (PARK) {
-          const Color sum = as_color(ctx_slot[6 * kBlock]) + (lit ? as_color(ctx_slot[5 * kBlock]) : black());
-          ctx_slot[6 * kBlock] = as_f4(sum);
+          const Color sum = as_color(ctx_slot[6 * kGenBlock]) + (lit ? as_color(ctx_slot[5 * kGenBlock]) : black());
+          ctx_slot[6 * kGenBlock] = as_f4(sum);
         } else {
           direct = direct + (lit ? ns_x : black());
         }
-        if (++k == fp.light_samples) {
+        if (++k == GEN_COLD(fp).light_samples) {
           k = 0;
           ++li;
         }
@@ -180,12 +213,13 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
         while (li < nee_lights) {
           // (its own LDS slot: no barrier; the compiler orders a lane's LDS accesses.  Fetched per trip: a context that stayed in
           // registers over the loop's back edge doubled the kernel's spills)
-          if (PARK) cx = unpark_ctx(ctx_slot);
-          const NeeSample ns = nee_prepare(sc, fp, cx, li, k, key, dim, ray);
+          if (PARK) cx = unpark_ctx<kGenBlock>(ctx_slot);
+          const FrameParams& fp = GEN_COLD(fp);
+          const NeeSample ns = nee_prepare(GEN_COLD(sc), fp, cx, li, k, key, dim, ray);
           const bool irrelevant = ORDERED && nee_irrelevant(ns);
           if (STATS) {  // booked at once by one lane: a counter of its own would be one more register the trace loop carries
             const unsigned long long m = __ballot(irrelevant);
-            if (m != 0ull && lane == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&counters->nee_irrelevant, (unsigned long long)__popcll(m));
+            if (m != 0ull && lane == (uint32_t)__ffsll((long long)m) - 1u) atomicAdd(&GEN_COLD(counters)->nee_irrelevant, (unsigned long long)__popcll(m));
           }
           if (irrelevant && fp.nee_skip) {
             if (++k == fp.light_samples) {
@@ -194,7 +228,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
             }
             continue;
           }
-          if (PARK) ctx_slot[5 * kBlock] = as_f4(ns.x);
+          if (PARK) ctx_slot[5 * kGenBlock] = as_f4(ns.x);
           else ns_x = ns.x;
           t_stop = ns.t_stop;
           pending = true;
@@ -207,8 +241,10 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
       }
     }
     if (FUSED) {
-      if (has_pixel) finalize_pixel(fp, direct, p, rgba8, rgba32f);
+      if (has_pixel) finalize_pixel(GEN_COLD(fp), direct, p, GEN_COLD(rgba8), GEN_COLD(rgba32f));
     } else if (MODE == kModePath) {
+      const FrameParams& fp = GEN_COLD(fp);
+      const PathBuffers& pb = GEN_COLD(pb);
       bool want_bounce = false;
       QueuedRay next{};
       if (tail) {
@@ -227,8 +263,8 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
           sdir = vec3(rc_cosf(omega_a) * st, rc_sinf(omega_a) * st, rc_cosf(theta));
         }
         if (PARK) {
-          cx = unpark_ctx(ctx_slot);
-          direct = as_color(ctx_slot[6 * kBlock]);
+          cx = unpark_ctx<kGenBlock>(ctx_slot);
+          direct = as_color(ctx_slot[6 * kGenBlock]);
         }
         pb.direct[slot] = as_f4(direct);
         if (depth < limit) {
@@ -262,7 +298,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
       // that reaches `tail` has traced all of its nee_lights x light_samples shadow rays
       n_shadow += (uint32_t)__popcll(__ballot(tail)) * nee_lights * fp.light_samples;
       n_bounce += (uint32_t)__popcll(__ballot(want_bounce));
-      push_ray(want_bounce, next, out_rays, out_count);
+      push_ray(want_bounce, next, GEN_COLD(out_rays), GEN_COLD(out_count));
     }
   }
   if (STATS) {
@@ -276,6 +312,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
       stt += __shfl_down(stt, off);
     }
     if (lane == 0) {
+      TraceCounters* const counters = GEN_COLD(counters);
       atomicAdd(&counters->boxes, b);
       atomicAdd(&counters->tris, t);
       atomicAdd(&counters->shaded, sh);
@@ -286,6 +323,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : 
   if (MODE == kModePath) {
     const unsigned long long s2 = n_shadow, b2 = n_bounce;  // already whole-wave sums
     if (lane == 0 && (s2 | b2)) {
+      TraceCounters* const counters = GEN_COLD(counters);
       atomicAdd(&counters->shadow, s2);
       atomicAdd(&counters->bounce, b2);
     }

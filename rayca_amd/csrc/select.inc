@@ -20,8 +20,7 @@ struct LaunchPlan {
 // use the instantiation without them
 
 // k_generation: every flavour; Flat is generation 0, fused (the kernel writes the pixel) or not; Path is never fused
-using GenKernel = void (*)(DevScene, FrameParams, uint32_t*, const QueuedRay*, const uint32_t*, QueuedRay*, uint32_t*, PathBuffers, uint32_t,
-                           uint8_t*, float4*, TraceCounters*, TraceLaunch);
+using GenKernel = void (*)(GenArgs);
 GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats) {
   const bool flat = mode == kModeFlat;
   return with_flavour([](auto T, auto FLAT, auto A, auto SPH, auto STATS) -> GenKernel {   // A: fused (Flat) / generation 0 (Path)
@@ -98,12 +97,13 @@ StackPlan plan_stack(uint32_t need, uint32_t max_entries = kMaxLdsEntries) {
   return p;
 }
 // A launch's node stack: the LDS part, and the spill area (a column per thread of the grid: entry e of thread t at
-// ovf[e * ovf_stride + t]) when the plan needs one.  The context's one spill area grows to the largest launch.
-int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch& tl) {
+// ovf[e * ovf_stride + t]) when the plan needs one.  `block_threads`: the workgroup the kernel is launched with (StackPlan.lds_bytes
+// is a 256-thread block's: fused_generation scales it for k_generation).  The context's one spill area grows to the largest launch.
+int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch& tl, uint32_t block_threads = kBlock) {
   tl = TraceLaunch{};
   tl.lds_entries = sp.lds_entries;
   if (sp.spill_entries) {
-    tl.ovf_stride = grid * kBlock;
+    tl.ovf_stride = grid * block_threads;
     const int32_t rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
     if (rc != RAYCA_OK) return rc;
     tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
@@ -273,23 +273,25 @@ int32_t kernel_registers(const void* k, uint32_t& regs) {
   return RAYCA_OK;
 }
 
-// Grid of a persistent kernel, whose blocks take batches (64 rays or one 8x8 tile) off a work counter until none are
-// left.  Persistent blocks need no co-residency (there are no inter-block waits), so the grid only has to fill every CU:
-// blocks per CU = what registers and LDS admit (one 256-thread block = one wave per SIMD; 512 VGPRs per lane per SIMD,
-// allocated in granules of 8; 160 KiB of LDS per CU), and no more blocks than the batches fill (4 per block).
-// `per_cu_forced` != 0 replaces the blocks per CU (RAYCA_GRID_MULT, for experiments).
-// `capped`: at most 8 blocks per CU, and fewer with frames in flight (the stack machine goes without both).  A frame
-// that takes every block slot of the chip keeps the next frame's blocks out until its own retire; with fewer slots per
-// frame the blocks of two frames are resident side by side and one frame's slow tiles run under the other's work
+// Grid of a persistent kernel, whose waves take batches (64 rays or one 8x8 tile) off a work counter until none are
+// left.  Persistent waves need no co-residency (there are no inter-block waits), so the grid only has to fill every CU.
+// The policy counts in units of four waves, one per SIMD -- a 256-thread block: units per CU = what registers and LDS admit
+// (512 VGPRs per lane per SIMD, allocated in granules of 8; 160 KiB of LDS per CU), and no more waves than there are batches.
+// `block_waves` (1, 2 or 4) is the workgroup the kernel is launched with: `lds_bytes` is one workgroup's, and the grid comes
+// out in workgroups -- the same waves per CU whatever the workgroup (k_generation: kGenWaves; every other kernel: 4).
+// `per_cu_forced` != 0 replaces the units per CU (RAYCA_GRID_MULT, for experiments).
+// `capped`: at most 8 units per CU, and fewer with frames in flight (the stack machine goes without both).  A frame
+// that takes every wave slot of the chip keeps the next frame's waves out until its own retire; with fewer slots per
+// frame the waves of two frames are resident side by side and one frame's slow tiles run under the other's work
 // (DESIGN.md, "the frames leave each other room"; tests/gpu_inflight_probe.py with RAYCA_GRID_MULT).
-int32_t persistent_grid(const RaycaScene* s, const void* kernel, size_t lds_bytes, uint32_t batches, bool capped, uint32_t in_flight,
-                        uint32_t per_cu_forced, uint32_t& grid) {
+// grid_policy is the arithmetic alone (no device: rayca_hip_selftest checks it), persistent_grid looks the registers up.
+uint32_t grid_policy(uint32_t regs, size_t lds_bytes, uint32_t batches, bool capped, uint32_t in_flight, uint32_t per_cu_forced, uint32_t cu_count,
+                     uint32_t block_waves) {
+  const uint32_t blocks_per_unit = 4u / block_waves;
   uint32_t per_cu = per_cu_forced;
   if (per_cu == 0) {
-    uint32_t regs = 0;
-    const int32_t rc = kernel_registers(kernel, regs);
-    if (rc != RAYCA_OK) return rc;
-    per_cu = std::min(512u / (((regs + 7u) / 8u) * 8u), lds_bytes ? (uint32_t)((160u * 1024u) / lds_bytes) : 8u);
+    const size_t unit_lds = lds_bytes * blocks_per_unit;
+    per_cu = std::min(512u / (((regs + 7u) / 8u) * 8u), unit_lds ? (uint32_t)((160u * 1024u) / unit_lds) : 8u);
     if (capped) {
       per_cu = std::max(1u, std::min(per_cu, 8u));
       if (in_flight >= 4u) per_cu = (per_cu + 1u) / 2u;
@@ -297,8 +299,71 @@ int32_t persistent_grid(const RaycaScene* s, const void* kernel, size_t lds_byte
     }
     per_cu = std::max(1u, per_cu);
   }
-  const uint32_t need = (batches + 3u) / 4u;
-  grid = std::min((uint32_t)s->cu_count * per_cu, need ? need : 1u);
+  const uint32_t need = (batches + block_waves - 1u) / block_waves;
+  return std::min(cu_count * per_cu * blocks_per_unit, need ? need : 1u);
+}
+int32_t persistent_grid(const RaycaScene* s, const void* kernel, size_t lds_bytes, uint32_t batches, bool capped, uint32_t in_flight,
+                        uint32_t per_cu_forced, uint32_t& grid, uint32_t block_waves = 4u) {
+  uint32_t regs = 0;
+  if (per_cu_forced == 0) {
+    const int32_t rc = kernel_registers(kernel, regs);
+    if (rc != RAYCA_OK) return rc;
+  }
+  grid = grid_policy(regs, lds_bytes, batches, capped, in_flight, per_cu_forced, (uint32_t)s->cu_count, block_waves);
+  return RAYCA_OK;
+}
+// work tickets (next_batch) of the fused engine: pairs of batches while every wave still gets four batches or more, single
+// batches for small frames
+uint32_t ticket_policy(uint32_t batches, uint32_t grid, uint32_t block_waves) { return batches >= 4u * block_waves * grid ? 2u : 1u; }
+
+// Self-test of grid_policy and ticket_policy (rayca_hip_selftest; no device): worked examples on a 256-CU chip, and for every
+// tuple of a sweep that the grid is the same number of waves whatever the workgroup, and never more waves than batches ask for.
+int32_t selftest_grid_policy(std::string& err) {
+  struct Case { uint32_t regs; size_t wave_lds; uint32_t batches; bool capped; uint32_t in_flight, forced, waves; const char* what; };
+  constexpr uint32_t kCus = 256u, kPathLds = 12u * 256u + 7u * 1024u;   // per wave: 12 stack rows + the parked context (fused_generation)
+  const Case cases[] = {
+      {125u, kPathLds, 32400u, true, 4u, 0u, 2048u, "the 1080p path frame, four in flight: 8 waves per CU"},
+      {125u, kPathLds, 32400u, true, 2u, 0u, 3072u, "the 1080p path frame, two in flight: 12 waves per CU"},
+      {125u, kPathLds, 32400u, true, 1u, 0u, 4096u, "the 1080p path frame alone: 16 waves per CU"},
+      {96u, 24u * 256u, 32400u, true, 1u, 0u, 5120u, "a Flat frame at 96 VGPRs: registers admit 5 waves per SIMD, LDS 6"},
+      {64u, 0u, 32400u, false, 1u, 0u, 8192u, "no LDS, uncapped: 8 waves per SIMD"},
+      {40u, 256u, 1u << 20, false, 1u, 0u, 12288u, "uncapped at 40 VGPRs and a little LDS: 12 waves per SIMD"},
+      {40u, 256u, 1u << 20, true, 1u, 0u, 8192u, "the same, capped: 8"},
+      {125u, kPathLds, 32400u, true, 4u, 3u, 3072u, "RAYCA_GRID_MULT=3 replaces the policy"},
+      {256u, 96u * 1024u, 32400u, true, 4u, 0u, 1024u, "a kernel nothing admits still gets one wave per SIMD"},
+  };
+  const auto fail_case = [&](const std::string& what) { err = "grid_policy: " + what; return RAYCA_ERR_BAD_ARG; };
+  for (const Case& c : cases)
+    for (uint32_t w : {1u, 2u, 4u}) {
+      const uint32_t grid = grid_policy(c.regs, c.wave_lds * w, c.batches, c.capped, c.in_flight, c.forced, kCus, w);
+      if (grid * w != c.waves) return fail_case(std::string(c.what) + ": " + std::to_string(grid) + " workgroups of " + std::to_string(w) + " waves, expected " + std::to_string(c.waves) + " waves");
+    }
+  // frames with fewer tiles than waves: one workgroup per `w` batches, rounded up; an empty frame still launches one
+  const uint32_t small[][4] = {{0u, 1u, 1u, 1u}, {1u, 1u, 1u, 1u}, {6u, 6u, 3u, 2u}, {42u, 42u, 21u, 11u}, {2047u, 2047u, 1024u, 512u}};   // batches; grid at 1, 2, 4 waves
+  for (const auto& r : small)
+    for (uint32_t i = 0; i < 3u; ++i)
+      if (const uint32_t grid = grid_policy(125u, kPathLds << i, r[0], true, 4u, 0u, kCus, 1u << i); grid != r[1 + i])
+        return fail_case(std::to_string(r[0]) + " batches in workgroups of " + std::to_string(1u << i) + " waves: " + std::to_string(grid) + " workgroups, expected " + std::to_string(r[1 + i]));
+  for (uint32_t regs : {24u, 64u, 96u, 125u, 128u, 200u})
+    for (uint32_t wave_lds : {0u, 1024u, 6144u, 10240u, 16384u})
+      for (uint32_t batches : {0u, 1u, 5u, 700u, 32400u, 129600u})
+        for (uint32_t in_flight : {1u, 2u, 3u, 4u, 8u})
+          for (int capped = 0; capped < 2; ++capped) {
+            const uint32_t w4 = grid_policy(regs, (size_t)wave_lds * 4u, 1u << 30, capped != 0, in_flight, 0u, kCus, 4u) * 4u;
+            for (uint32_t w : {1u, 2u, 4u}) {
+              const uint32_t full = grid_policy(regs, (size_t)wave_lds * w, 1u << 30, capped != 0, in_flight, 0u, kCus, w);
+              const uint32_t grid = grid_policy(regs, (size_t)wave_lds * w, batches, capped != 0, in_flight, 0u, kCus, w);
+              const std::string tuple = "(" + std::to_string(regs) + " VGPRs, " + std::to_string(wave_lds) + " B per wave, " + std::to_string(batches) + " batches, " +
+                                        std::to_string(in_flight) + " in flight, capped " + std::to_string(capped) + ", " + std::to_string(w) + " waves per workgroup)";
+              if (full * w != w4 || w4 % (4u * kCus) != 0u) return fail_case(tuple + ": " + std::to_string(full * w) + " waves fill the chip, " + std::to_string(w4) + " in 256-thread blocks");
+              if (grid == 0u || grid > full || (grid < full && grid != std::max(1u, (batches + w - 1u) / w))) return fail_case(tuple + ": " + std::to_string(grid) + " workgroups");
+            }
+          }
+  // tickets: pairs while every wave gets four batches or more
+  const uint32_t tickets[][4] = {{32400u, 2048u, 1u, 2u}, {32400u, 512u, 4u, 2u}, {32400u, 4096u, 1u, 2u}, {8192u, 2048u, 1u, 2u}, {8191u, 2048u, 1u, 1u}, {8191u, 512u, 4u, 1u}, {6u, 6u, 1u, 1u}};
+  for (const auto& t : tickets)
+    if (ticket_policy(t[0], t[1], t[2]) != t[3])
+      return fail_case("ticket_policy(" + std::to_string(t[0]) + " batches, " + std::to_string(t[1]) + " workgroups of " + std::to_string(t[2]) + " waves) is not " + std::to_string(t[3]));
   return RAYCA_OK;
 }
 

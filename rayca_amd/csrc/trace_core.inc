@@ -3,6 +3,15 @@
 // whole-ray traversal, HitInfo shading, the BRDFs, NEE preparation, camera rays, work tickets.  Included INSIDE
 // `namespace rayca { namespace {` after <hip/hip_runtime.h> and "device_types.hpp"; everything has internal linkage.
 constexpr int kBlock = 256;
+// k_generation's workgroup: one wave.  A persistent wave that finds the work counters dry ends on its own, and its registers
+// AND its LDS (stack rows + parked context) go to the next frame's waves at once; as one of four waves of a 256-thread block its
+// LDS stayed taken until the slowest of the four had ended.  -DRAYCA_GEN_WAVES_PER_BLOCK=4: the 256-thread block, for A/B runs.
+#ifndef RAYCA_GEN_WAVES_PER_BLOCK
+#define RAYCA_GEN_WAVES_PER_BLOCK 1
+#endif
+constexpr int kGenWaves = RAYCA_GEN_WAVES_PER_BLOCK;
+constexpr int kGenBlock = 64 * kGenWaves;
+static_assert(kGenWaves == 1 || kGenWaves == 2 || kGenWaves == 4, "k_generation's workgroup: 1, 2 or 4 waves");
 #ifndef RAYCA_TRACE_MIN_WAVES
 #define RAYCA_TRACE_MIN_WAVES 1
 #endif
@@ -21,6 +30,21 @@ __device__ __forceinline__ uint32_t rc_tid() { return __builtin_amdgcn_workitem_
 __device__ __forceinline__ uint32_t rc_bid() { return __builtin_amdgcn_workgroup_id_x(); }
 __device__ __forceinline__ uint32_t rc_bdim() { return __builtin_amdgcn_workgroup_size_x(); }
 __device__ __forceinline__ uint32_t rc_gdim() { return __builtin_amdgcn_grid_size_x() / __builtin_amdgcn_workgroup_size_x(); }
+
+// A kernel argument read where it is used.  A persistent kernel whose arguments add up to more dwords than a wave has SGPRs
+// gets them all loaded at entry and kept over its loop: k_generation spilled 72 of them into VGPR lanes and moved them back,
+// one v_readlane_b32 each, in the code that runs once per batch, vertex or sample.  cold_arg<T>(offset) is a reference to the
+// bytes at `offset` of the kernel-argument segment (offsetof in the kernel's one aggregate argument), in the constant address
+// space: what is read through it is a scalar load at the point of use.  The empty asm makes the pointer opaque there, so the
+// loads cannot be hoisted to the kernel's entry and merged with the by-value argument.  Only for fields read outside the
+// traversal loops; what those read stays an ordinary argument, in SGPRs.
+template <class T>
+__device__ __forceinline__ const T& cold_arg(uint32_t offset) {
+  typedef __attribute__((address_space(4))) const char ConstByte;
+  ConstByte* p = (ConstByte*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const T*)(p + offset);
+}
 
 struct DRay {
   F4 o, d, rd;  // origin (w=1), direction (w=0), zero-safe reciprocal
@@ -348,10 +372,11 @@ struct LaneCounters {   // (an aggregate: `LaneCounters cnt{};`)
 constexpr uint32_t kTerminated = 0x7FFFFFFFu;  // "no node left": an inner index that never exists (== kNoChild)
 
 // Per-lane node stack: the first `lds_entries` entries in LDS (entry-major: entry e of thread t at
-// lds[e*kBlock + t], so the 64 lanes of a wave always hit 64 different banks whatever their depths),
-// deeper entries in a global spill area laid out the same way.  The spill branch is cold: the LDS part
+// lds[e*STRIDE + t], so the 64 lanes of a wave always hit 64 different banks whatever their depths),
+// deeper entries in a global spill area laid out the same way.  STRIDE is the thread count of the kernel's workgroup: kBlock
+// everywhere but in k_generation, whose workgroups are kGenBlock threads.  The spill branch is cold: the LDS part
 // is sized from the tree on the host and covers every traversal of ordinary trees.
-template <bool SPILL>
+template <bool SPILL, int STRIDE = kBlock>
 struct NodeStack {
   uint32_t* lds;
   uint32_t* ovf;       // wave-uniform base of the spill area (a per-lane pointer would be two more registers in every loop)
@@ -373,21 +398,21 @@ struct NodeStack {
   typedef __attribute__((address_space(1))) uint32_t GlobalWord;
   __device__ __forceinline__ void put(uint32_t i, uint32_t v) {
 #if RAYCA_STACK_AS
-    if (!SPILL || i < lds_entries) ((LdsWord*)lds)[i * kBlock] = v;
+    if (!SPILL || i < lds_entries) ((LdsWord*)lds)[i * STRIDE] = v;
     else ((GlobalWord*)ovf)[(size_t)(i - lds_entries) * ovf_stride + gthread] = v;
 #else
-    if (!SPILL || i < lds_entries) lds[i * kBlock] = v;
+    if (!SPILL || i < lds_entries) lds[i * STRIDE] = v;
     else ovf[(size_t)(i - lds_entries) * ovf_stride + gthread] = v;
 #endif
   }
   __device__ __forceinline__ uint32_t get(uint32_t i) const {
 #if RAYCA_STACK_AS
     uint32_t v;
-    if (!SPILL || i < lds_entries) v = ((const LdsWord*)lds)[i * kBlock];
+    if (!SPILL || i < lds_entries) v = ((const LdsWord*)lds)[i * STRIDE];
     else v = ((const GlobalWord*)ovf)[(size_t)(i - lds_entries) * ovf_stride + gthread];
     return v;
 #else
-    return (!SPILL || i < lds_entries) ? lds[i * kBlock] : ovf[(size_t)(i - lds_entries) * ovf_stride + gthread];
+    return (!SPILL || i < lds_entries) ? lds[i * STRIDE] : ovf[(size_t)(i - lds_entries) * ovf_stride + gthread];
 #endif
   }
   __device__ __forceinline__ void push(uint32_t v) {
@@ -422,13 +447,13 @@ struct NodeStack {
       wr = wr && !deep;
       rd = rd && !deep;
     }
-    if (wr) ((LdsWord*)lds)[at * kBlock] = top;
+    if (wr) ((LdsWord*)lds)[at * STRIDE] = top;
     // (no instruction: `out`, what the caller hands on of the old `top`, is made in front of this point and the new `top` behind
     // it, in the old one's register.  Left to itself the compiler makes the new value beside the old one, which it reads last:
     // the read below then lands in a second register, and a wait for it and a move back stand in front of the next node's loads)
     asm volatile("" : "+v"(top), "+v"(out));
     top = keep ? top : v;
-    if (rd) top = ((const LdsWord*)lds)[at * kBlock];
+    if (rd) top = ((const LdsWord*)lds)[at * STRIDE];
   }
   // the binary step's bookkeeping, `cur` = none ? top : nearer child already made (and the next node's loads issued with it):
   // both children hit -> `far` becomes the newest entry and the one before it is stored; none -> the successor of the entry
@@ -448,9 +473,9 @@ struct NodeStack {
     return r;
   }
 };
-template <bool SPILL>
-__device__ __forceinline__ NodeStack<SPILL> make_stack(uint32_t* lds_base, const TraceLaunch& tl, uint32_t global_thread) {
-  NodeStack<SPILL> st;
+template <bool SPILL, int STRIDE = kBlock>
+__device__ __forceinline__ NodeStack<SPILL, STRIDE> make_stack(uint32_t* lds_base, const TraceLaunch& tl, uint32_t global_thread) {
+  NodeStack<SPILL, STRIDE> st;
   st.lds = lds_base + rc_tid();
   st.ovf = tl.ovf;
   st.gthread = global_thread;
@@ -496,8 +521,8 @@ __device__ __forceinline__ void test_leaf(const DevScene& sc, const DRay& r, con
 
 // One trip through the node loop: test the children of inner node `cur`, push what stays pending, return the
 // next node (inner, leaf or kTerminated).
-template <bool ORDERED, bool FAST, bool WIDE, bool SPILL, bool STATS, bool HALF, bool SLACK = true>
-__device__ __forceinline__ uint32_t node_step(const DevScene& sc, const DRay& r, const FastRay& fr, float limit, uint32_t cur, NodeStack<SPILL>& st,
+template <bool ORDERED, bool FAST, bool WIDE, bool SPILL, bool STATS, bool HALF, bool SLACK = true, int STRIDE = kBlock>
+__device__ __forceinline__ uint32_t node_step(const DevScene& sc, const DRay& r, const FastRay& fr, float limit, uint32_t cur, NodeStack<SPILL, STRIDE>& st,
                                               LaneCounters& cnt) {
   if (STATS && cnt.books()) cnt.slot_boxes += WIDE ? 256ull : 128ull;
   if (WIDE) {
@@ -652,8 +677,8 @@ key[i] = ka; key[j] = kb; ref[i] = ra; ref[j] = rb; \
 #ifndef RAYCA_LEAVE_K_BOUNCE
 #define RAYCA_LEAVE_K_BOUNCE 8    // bounce generations, shadow rays of the wavefront engine, the stack machine
 #endif
-template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF, int LEAVE_K, bool SLACK>
-__device__ __forceinline__ bool trace_search(const DevScene& sc, const DRay& r, const FastRay& fr, float t_stop, NodeStack<SPILL>& st, DHit& hit, LaneCounters& cnt) {
+template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF, int LEAVE_K, bool SLACK, int STRIDE = kBlock>
+__device__ __forceinline__ bool trace_search(const DevScene& sc, const DRay& r, const FastRay& fr, float t_stop, NodeStack<SPILL, STRIDE>& st, DHit& hit, LaneCounters& cnt) {
   hit.t = INFINITY;
   hit.prim = RAYCA_NONE;
   hit.u = hit.v = 0.0f;
@@ -744,8 +769,8 @@ __device__ __forceinline__ bool trace_search(const DevScene& sc, const DRay& r, 
 // those of the larger one); kSlackAlways: camera rays alone (Flat frames, generation 0 of the wavefront engine -- measured
 // neutral there); kSlackNever: bounce and shadow rays, whose origins lie on the scene's surfaces.
 constexpr int kSlackPerWave = 0, kSlackAlways = 1, kSlackNever = 2;
-template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF = false, int LEAVE_K = 0, int SLACK_FORM = kSlackPerWave>
-__device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t_stop, NodeStack<SPILL>& st, DHit& hit, LaneCounters& cnt) {
+template <bool ORDERED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF = false, int LEAVE_K = 0, int SLACK_FORM = kSlackPerWave, int STRIDE = kBlock>
+__device__ __forceinline__ bool trace(const DevScene& sc, const DRay& r, float t_stop, NodeStack<SPILL, STRIDE>& st, DHit& hit, LaneCounters& cnt) {
   const FastRay fr = make_fast(sc, r, HALF);
   if constexpr (!FAST || !RAYCA_RAY_SLACK || SLACK_FORM == kSlackNever) {
     return trace_search<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, LEAVE_K, false>(sc, r, fr, t_stop, st, hit, cnt);
@@ -856,21 +881,23 @@ struct ShadeCtx {
 // The path kernel keeps a vertex's ShadeCtx in LDS while its shadow rays are traversed (RAYCA_PARK_CTX): the struct is 27
 // registers that would otherwise have to survive the traversal loop, which at the 128 VGPRs of four waves per SIMD the
 // compiler could only do through scratch (54 spilled VGPRs, 219 MB of scratch writes per 1080p frame).  So do the pending
-// sample's contribution and the running sum of direct light (quads 5 and 6).  Seven float4 per lane, quantity-major (lane i of quantity q at [q * kBlock + i]): a wave's ds_read_b128 / ds_write_b128 touch 64
+// sample's contribution and the running sum of direct light (quads 5 and 6).  Seven float4 per lane, quantity-major (lane i of quantity q at [q * STRIDE + i], STRIDE = the workgroup's threads): a wave's ds_read_b128 / ds_write_b128 touch 64
 // consecutive 16-B slots, the conflict-free shape.  next_origin and the w lanes are recomputed (same operations, same bits).
 #ifndef RAYCA_PARK_CTX
 #define RAYCA_PARK_CTX 1
 #endif
 constexpr uint32_t kCtxQuads = 7;  // ShadeCtx (5) + the pending NEE sample's contribution + the running direct sum
+template <int STRIDE = kBlock>
 __device__ __forceinline__ void park_ctx(float4* slot, const ShadeCtx& c) {
-  slot[0 * kBlock] = make_float4(c.point.x, c.point.y, c.point.z, c.roughness);
-  slot[1 * kBlock] = make_float4(c.normal.x, c.normal.y, c.normal.z, c.shininess);
-  slot[2 * kBlock] = make_float4(c.view.x, c.view.y, c.view.z, __uint_as_float(c.kind));
-  slot[3 * kBlock] = make_float4(c.kd.r, c.kd.g, c.kd.b, c.kd.a);
-  slot[4 * kBlock] = make_float4(c.ks.r, c.ks.g, c.ks.b, c.ks.a);
+  slot[0 * STRIDE] = make_float4(c.point.x, c.point.y, c.point.z, c.roughness);
+  slot[1 * STRIDE] = make_float4(c.normal.x, c.normal.y, c.normal.z, c.shininess);
+  slot[2 * STRIDE] = make_float4(c.view.x, c.view.y, c.view.z, __uint_as_float(c.kind));
+  slot[3 * STRIDE] = make_float4(c.kd.r, c.kd.g, c.kd.b, c.kd.a);
+  slot[4 * STRIDE] = make_float4(c.ks.r, c.ks.g, c.ks.b, c.ks.a);
 }
+template <int STRIDE = kBlock>
 __device__ __forceinline__ ShadeCtx unpark_ctx(const float4* slot) {
-  const float4 q0 = slot[0 * kBlock], q1 = slot[1 * kBlock], q2 = slot[2 * kBlock], q3 = slot[3 * kBlock], q4 = slot[4 * kBlock];
+  const float4 q0 = slot[0 * STRIDE], q1 = slot[1 * STRIDE], q2 = slot[2 * STRIDE], q3 = slot[3 * STRIDE], q4 = slot[4 * STRIDE];
   ShadeCtx c;
   c.point = f4(q0.x, q0.y, q0.z, 1.0f);   // Hit.point is a Point3
   c.normal = vec3(q1.x, q1.y, q1.z);
