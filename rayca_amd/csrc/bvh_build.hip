@@ -977,7 +977,7 @@ __global__ void k_layout_emit(LayoutState ls, DevNode* out, uint32_t first, uint
     }
     d.left = refs[0]; d.right = refs[1]; d.pad0 = d.pad1 = 0u;
     out[first + ls.index[i]] = d;
-  } else if (nd.count > kLeafMaxPrims) {  // the chain of DevBuilder::emit_leaf
+  } else if (nd.count > kLeafMaxPrims) {  // the chain of DevBuilder::write_leaf_chain
     DevNode d;
     layout_box(d.q, nd, pad_rel, pad_abs);
     layout_box(d.q + 6, nd, pad_rel, pad_abs);

@@ -13,12 +13,10 @@
 
 #include <algorithm>
 #include <atomic>
-#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <future>
-#include <chrono>
 #include <cmath>
 #include <thread>
 
@@ -104,19 +102,21 @@ unsigned host_threads() {
 
 namespace {
 
+// worker(t) for t in [0, threads): threads - 1 of them on threads started here, worker(0) on the caller; all joined
+template <class Fn>
+void run_on_host_threads(unsigned threads, Fn worker) {
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < threads; ++t) pool.emplace_back([&worker, t] { worker(t); });
+  worker(0u);
+  for (std::thread& th : pool) th.join();
+}
+
 // fn(begin, end) over [0, n) on all host threads
 template <class Fn>
 void parallel_chunks(size_t n, Fn fn) {
   const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), n / 4096 + 1));
-  if (nt <= 1) {
-    fn(0, n);
-    return;
-  }
-  std::vector<std::thread> pool;
   const size_t per = (n + nt - 1) / nt;
-  for (unsigned t = 1; t < nt; ++t) pool.emplace_back([=, &fn] { fn(std::min(n, t * per), std::min(n, (t + 1) * per)); });
-  fn(0, std::min(n, per));
-  for (std::thread& th : pool) th.join();
+  run_on_host_threads(nt, [&](unsigned t) { fn(std::min(n, t * per), std::min(n, (t + 1) * per)); });
 }
 
 inline Box empty_box() { return Box{point3(FLT_MAX, FLT_MAX, FLT_MAX), point3(-FLT_MAX, -FLT_MAX, -FLT_MAX)}; }
@@ -457,7 +457,8 @@ struct DevBuilder {
   uint32_t leaf_max = kLeafCollapseMax;
   std::vector<uint32_t> plan_prims;   // per arena node of the BLAS being laid out: primitives below it
   std::vector<uint8_t> plan_leafed;   // 1: the subtree is one leaf, 2: inside such a subtree
-  void plan_leaves(const HostBlas& bl) {
+  // false: a child that is not behind its parent in the arena (both builders append them that way; every pass relies on it)
+  bool plan_leaves(const HostBlas& bl) {
     const std::vector<BuildNode>& a = bl.nodes;
     const size_t n = a.size();
     plan_prims.assign(n, 0u);
@@ -470,6 +471,7 @@ struct DevBuilder {
         cost[i] = (float)bn.count * area(bn.bounds);
         continue;
       }
+      if ((size_t)bn.left <= i || (size_t)bn.right <= i || (size_t)bn.left >= n || (size_t)bn.right >= n) return false;
       const uint32_t pl = plan_prims[bn.left], pr = plan_prims[bn.right];
       const float ar = area(bn.bounds), as_leaf = (float)(pl + pr) * ar, as_split = node_cost * ar + cost[bn.left] + cost[bn.right];
       const bool one_leaf = node_cost > 0.0f && pl + pr <= leaf_max && as_leaf <= as_split;
@@ -482,6 +484,7 @@ struct DevBuilder {
       if (bn.left < 0 || plan_leafed[i] == 0) continue;
       plan_leafed[bn.left] = plan_leafed[bn.right] = 2;
     }
+    return true;
   }
 
   void put_box(DevNode& n, int side, const Box& b0) {
@@ -518,60 +521,44 @@ struct DevBuilder {
     std::memset(&s.dev_nodes.back(), 0, sizeof(DevNode));
     return (uint32_t)s.dev_nodes.size() - 1;
   }
-  // Every emit_* returns the packed child reference and reports, through `need`, how many stack
-  // entries a traversal of that subtree can have pending at once: an inner node pushes one child and
-  // descends into the other, so need = 1 + max(need(left), need(right)) -- except for the chain nodes
-  // below, whose two boxes are identical so the left (leaf) child is always taken first and the
-  // pushed entry is popped before the rest of the chain is entered.
-  // a leaf range: one packed ref, or a chain of nodes re-testing the same box for > 64 primitives
-  uint32_t emit_leaf(uint32_t first, uint32_t count, const Box& box, uint32_t& need) {
-    if (count == 0) {
-      need = 0;
-      return kNoChild;  // a model without primitives: nothing to visit
-    }
-    if (count <= kLeafMaxPrims) {
-      need = 0;
-      return leaf_ref(first, count);
-    }
-    // iterative: chains can be thousands of nodes long with the reference's coarse leaves
-    const uint32_t head = new_node();
-    uint32_t cur = head;
-    for (;;) {
-      put_box(s.dev_nodes[cur], 0, box);
-      put_box(s.dev_nodes[cur], 1, box);
-      s.dev_nodes[cur].left = leaf_ref(first, kLeafMaxPrims);
+  // Every emit_* returns the packed child reference and reports, through `need`, how many stack entries a traversal of that
+  // subtree can have pending at once: an inner node pushes one child and descends into the other, so need = 1 +
+  // max(need(left), need(right)) -- except for the chain nodes below, whose two boxes are identical so the left (leaf) child
+  // is always taken first and the pushed entry is popped before the rest of the chain is entered.
+  std::string error;  // set by emit_blas for a tree it cannot lay out (an internal error: the caller hands it on)
+  // A leaf range of more than 64 primitives: ceil(count / 64) - 1 consecutive nodes from `cur` on that re-test the same box,
+  // 64 primitives to the left of each (a loop: chains can be thousands of nodes long with the reference's coarse leaves)
+  void write_leaf_chain(uint32_t cur, uint32_t first, uint32_t count, const Box& box) {
+    for (;; ++cur) {
+      DevNode& d = s.dev_nodes[cur];
+      std::memset(&d, 0, sizeof d);
+      put_box(d, 0, box);
+      put_box(d, 1, box);
+      d.left = leaf_ref(first, kLeafMaxPrims);
       first += kLeafMaxPrims;
       count -= kLeafMaxPrims;
       if (count <= kLeafMaxPrims) {
-        s.dev_nodes[cur].right = leaf_ref(first, count);
-        break;
+        d.right = leaf_ref(first, count);
+        return;
       }
-      const uint32_t nxt = new_node();
-      s.dev_nodes[cur].right = nxt;
-      cur = nxt;
+      d.right = cur + 1u;
     }
-    need = 1;
-    return head;
   }
-  // The BLAS below its root, without recursion.  Children sit behind their parents in the arena (both builders append
-  // them that way; checked), so one backward pass gives every subtree's device-node count and stack need, one forward
-  // pass gives every node its index -- the pre-order numbering the recursive form below produces: a node, its left
-  // subtree, its right subtree -- and then every node is written independently, by all host threads.  (The recursive
-  // walk over an arena in level order was 36 ms of cache misses for the atrium's 543 k nodes.)
-  bool allow_flat = true;  // (the self-test switches it off to compare against the recursive form)
-  bool emit_blas_flat(const HostBlas& bl, uint32_t base, uint32_t& root_ref, uint32_t& need) {
+  // A host-held BLAS below its root, without recursion.  Children sit behind their parents in the arena (plan_leaves has
+  // checked it), so one backward pass gives every subtree's device-node count and stack need, one forward pass gives every
+  // node its index -- pre-order: a node, its left subtree, its right subtree -- and then every node is written independently,
+  // by all host threads.  (A recursive walk over an arena in level order was 36 ms of cache misses for the atrium's 543 k nodes.)
+  uint32_t emit_blas_flat(const HostBlas& bl, uint32_t base, uint32_t& need) {
     const std::vector<BuildNode>& a = bl.nodes;
     const size_t n = a.size();
-    if (n < 4096 || !allow_flat) return false;  // small trees: the recursive form
     std::vector<uint32_t> size(n), stack_need(n);
     for (size_t i = n; i-- > 0;) {
       const BuildNode& bn = a[i];
-      if (bn.left < 0) {  // leaf: a packed reference, or a chain of ceil(count / 64) - 1 nodes
+      if (bn.left < 0) {  // leaf: nothing (its parent holds a packed reference), or a chain of ceil(count / 64) - 1 nodes
         const uint32_t chain = bn.count > kLeafMaxPrims ? (bn.count + kLeafMaxPrims - 1) / kLeafMaxPrims - 1 : 0u;
         size[i] = chain;
         stack_need[i] = chain ? 1u : 0u;
       } else {
-        if ((size_t)bn.left <= i || (size_t)bn.right <= i || (size_t)bn.left >= n || (size_t)bn.right >= n) return false;
         const bool one_leaf = plan_leafed[i] != 0;   // (its parent holds a leaf reference, it takes no nodes)
         size[i] = one_leaf ? 0u : 1u + size[bn.left] + size[bn.right];
         stack_need[i] = one_leaf ? 0u : 1u + std::max(stack_need[bn.left], stack_need[bn.right]);
@@ -590,7 +577,7 @@ struct DevBuilder {
     auto ref_of = [&](size_t i) -> uint32_t {  // what the parent stores for child i
       const BuildNode& bn = a[i];
       if (bn.left >= 0) return plan_leafed[i] == 1 ? leaf_ref(base + bn.offset, plan_prims[i]) : index[i];
-      if (bn.count == 0) return kNoChild;
+      if (bn.count == 0) return kNoChild;  // a model without primitives: nothing to visit
       return bn.count <= kLeafMaxPrims ? leaf_ref(base + bn.offset, bn.count) : index[i];
     };
     parallel_chunks(n, [&](size_t b, size_t e) {
@@ -604,68 +591,38 @@ struct DevBuilder {
           put_box(d, 1, a[bn.right].bounds);
           d.left = ref_of((size_t)bn.left);
           d.right = ref_of((size_t)bn.right);
-        } else if (bn.count > kLeafMaxPrims) {  // the chain of emit_leaf
-          uint32_t cur = index[i], f = base + bn.offset, count = bn.count;
-          for (;;) {
-            DevNode& d = s.dev_nodes[cur];
-            std::memset(&d, 0, sizeof d);
-            put_box(d, 0, bn.bounds);
-            put_box(d, 1, bn.bounds);
-            d.left = leaf_ref(f, kLeafMaxPrims);
-            f += kLeafMaxPrims;
-            count -= kLeafMaxPrims;
-            if (count <= kLeafMaxPrims) {
-              d.right = leaf_ref(f, count);
-              break;
-            }
-            d.right = cur + 1u;
-            ++cur;
-          }
+        } else if (bn.count > kLeafMaxPrims) {
+          write_leaf_chain(index[i], base + bn.offset, bn.count, bn.bounds);
         }
       }
     });
-    root_ref = ref_of(0);
     need = stack_need[0];
-    return true;
+    return ref_of(0);
   }
-  uint32_t emit_blas_node(const HostBlas& bl, uint32_t base, uint32_t idx, uint32_t& need) {
-    if (idx == 0 && bl.dev_tree) {  // built and kept on the device: a run of node indices is set aside, the device fills it
+  // One BLAS of the scene, its primitives from global slot `base` on
+  uint32_t emit_blas(const HostBlas& bl, uint32_t base, uint32_t& need) {
+    if (bl.dev_tree) {  // built and kept on the device: a run of node indices is set aside, the device fills it
       const uint32_t first = (uint32_t)s.dev_nodes.size();
       s.dev_nodes.resize((size_t)first + bl.dev_node_count);
       s.dev_segments.push_back(DeviceSegment{first, bl.dev_node_count, base, bl.dev_tree});
       need = bl.dev_need;
       return first;   // (more than 64 primitives: the root is an inner node or the head of a chain, node 0 of the run)
     }
-    if (idx == 0) {
-      plan_leaves(bl);
-      uint32_t ref = 0;
-      if (emit_blas_flat(bl, base, ref, need)) return ref;
-    }
-    const BuildNode& bn = bl.nodes[idx];
-    if (bn.left < 0) return emit_leaf(base + bn.offset, bn.count, bn.bounds, need);
-    if (plan_leafed[idx] == 1) {  // the whole subtree as one leaf
+    if (!plan_leaves(bl)) {
+      error = "internal error: a BLAS arena holds a child that is not behind its parent";
       need = 0;
-      return leaf_ref(base + bn.offset, plan_prims[idx]);
+      return kNoChild;
     }
-    const uint32_t n = new_node();
-    put_box(s.dev_nodes[n], 0, bl.nodes[bn.left].bounds);
-    put_box(s.dev_nodes[n], 1, bl.nodes[bn.right].bounds);
-    uint32_t nl = 0, nr = 0;
-    const uint32_t lr = emit_blas_node(bl, base, (uint32_t)bn.left, nl);
-    s.dev_nodes[n].left = lr;
-    const uint32_t rr = emit_blas_node(bl, base, (uint32_t)bn.right, nr);
-    s.dev_nodes[n].right = rr;
-    need = 1 + std::max(nl, nr);
-    return n;
+    return emit_blas_flat(bl, base, need);
   }
   // TLAS leaf holding blas [offset, offset+count): BLAS roots tested one after the other
   uint32_t emit_blas_chain(uint32_t offset, uint32_t count, const Box& leaf_box, uint32_t& need) {
-    if (count == 1) return emit_blas_node(s.blas[offset], blas_base[offset], 0, need);
+    if (count == 1) return emit_blas(s.blas[offset], blas_base[offset], need);
     const uint32_t n = new_node();
     put_box(s.dev_nodes[n], 0, s.blas[offset].nodes[0].bounds);
     put_box(s.dev_nodes[n], 1, leaf_box);
     uint32_t nl = 0, nr = 0;
-    const uint32_t lr = emit_blas_node(s.blas[offset], blas_base[offset], 0, nl);
+    const uint32_t lr = emit_blas(s.blas[offset], blas_base[offset], nl);
     s.dev_nodes[n].left = lr;
     const uint32_t rr = emit_blas_chain(offset + 1, count - 1, leaf_box, nr);
     s.dev_nodes[n].right = rr;
@@ -768,14 +725,9 @@ struct WideBuilder {
     if (allow_parallel && s.dev_nodes.size() >= 65536 && host_threads() > 1) {
       collect(bin_ref, 3);
       std::atomic<size_t> next{0};
-      auto worker = [&] {
+      run_on_host_threads((unsigned)std::min<size_t>(host_threads(), tasks.size()), [&](unsigned) {
         for (size_t t; (t = next.fetch_add(1)) < tasks.size();) build_into(tasks[t].nodes, tasks[t].bin_root, tasks[t].need, false);
-      };
-      std::vector<std::thread> pool;
-      const unsigned nt = (unsigned)std::min<size_t>(host_threads(), tasks.size());
-      for (unsigned i = 1; i < nt; ++i) pool.emplace_back(worker);
-      worker();
-      for (std::thread& th : pool) th.join();
+      });
       for (size_t t = 0; t < tasks.size(); ++t) task_of.push_back({tasks[t].bin_root, (uint32_t)t});
       std::sort(task_of.begin(), task_of.end());
     }
@@ -884,7 +836,7 @@ void set_ext(PrimExt& e, int k, Color c, F4 n, F4 t, F4 b, F2 uv) {
 
 }  // namespace
 
-// Self-check of the two parallel layout passes against their recursive forms on a random tree (uneven depths, mostly small leaves
+// Self-check of the two layout passes against their recursive forms on a random tree (uneven depths, mostly small leaves
 // and some of 65..264 primitives so that the 64-primitive chains occur): the arrays must be identical, byte for byte.
 int32_t selftest_device_layouts(std::string& err) {
   uint64_t rng = 0x9E3779B97F4A7C15ull;
@@ -919,6 +871,43 @@ int32_t selftest_device_layouts(std::string& err) {
     bl.nodes.push_back(r);
     bl.nodes[i].count = 0;
   }
+  // The literal statement of the binary layout, which the flat pass (DevBuilder::emit_blas) is held against: a node, then
+  // its left subtree, then its right one; a subtree the plan folds is one leaf reference; a leaf of more than 64 primitives
+  // is a chain of nodes that re-test its box, 64 primitives to the left of each.
+  struct Literal {
+    DevBuilder& db;
+    const HostBlas& bl;
+    uint32_t leaf(uint32_t first, uint32_t count, const Box& box, uint32_t& need) {
+      need = count > kLeafMaxPrims ? 1 : 0;   // (a chain's pushed right child is popped before the rest of the chain is entered)
+      if (count <= kLeafMaxPrims) return count ? DevBuilder::leaf_ref(first, count) : kNoChild;
+      const uint32_t n = db.new_node();
+      db.put_box(db.s.dev_nodes[n], 0, box);
+      db.put_box(db.s.dev_nodes[n], 1, box);
+      db.s.dev_nodes[n].left = DevBuilder::leaf_ref(first, kLeafMaxPrims);
+      uint32_t rest_need = 0;
+      const uint32_t rest = leaf(first + kLeafMaxPrims, count - kLeafMaxPrims, box, rest_need);
+      db.s.dev_nodes[n].right = rest;
+      return n;
+    }
+    uint32_t node(uint32_t idx, uint32_t& need) {
+      const BuildNode& bn = bl.nodes[idx];
+      if (bn.left < 0) return leaf(bn.offset, bn.count, bn.bounds, need);
+      if (db.plan_leafed[idx] == 1) {
+        need = 0;
+        return DevBuilder::leaf_ref(bn.offset, db.plan_prims[idx]);
+      }
+      const uint32_t n = db.new_node();
+      db.put_box(db.s.dev_nodes[n], 0, bl.nodes[bn.left].bounds);
+      db.put_box(db.s.dev_nodes[n], 1, bl.nodes[bn.right].bounds);
+      uint32_t nl = 0, nr = 0;
+      const uint32_t lr = node((uint32_t)bn.left, nl);
+      db.s.dev_nodes[n].left = lr;
+      const uint32_t rr = node((uint32_t)bn.right, nr);
+      db.s.dev_nodes[n].right = rr;
+      need = 1 + std::max(nl, nr);
+      return n;
+    }
+  };
   for (const float node_cost : {0.0f, kLeafNodeCost}) {   // the tree as built, and with subtrees laid out as single leaves
     HostScene a, b;
     uint32_t ref[2], need[2], ref4[2], need4[2];
@@ -930,23 +919,23 @@ int32_t selftest_device_layouts(std::string& err) {
       db.node_cost = node_cost;
       db.pad_rel = 1.52587890625e-05f;
       db.pad_abs = 1e-6f;
-      db.allow_flat = pass == 1;
-      ref[pass] = db.emit_blas_node(s.blas[0], 0, 0, need[pass]);
+      if (pass == 1) {
+        ref[pass] = db.emit_blas(s.blas[0], 0, need[pass]);
+      } else {
+        if (!db.plan_leaves(s.blas[0])) { err = "layout self-test: the random tree has a child in front of its parent"; return RAYCA_ERR_BAD_ARG; }
+        ref[pass] = Literal{db, s.blas[0]}.node(0, need[pass]);
+      }
+      if (!db.error.empty()) { err = "layout self-test: " + db.error; return RAYCA_ERR_BAD_ARG; }
       WideBuilder wb{s};
       wb.allow_parallel = pass == 1;
       ref4[pass] = wb.build(ref[pass], need4[pass]);
     }
     if (node_cost == 0.0f && a.dev_nodes.size() < 65536) { err = "layout self-test: the random tree came out too small to exercise the parallel passes"; return RAYCA_ERR_BAD_ARG; }
-    if (ref[0] != ref[1] || need[0] != need[1] || a.dev_nodes.size() != b.dev_nodes.size() ||
-        std::memcmp(a.dev_nodes.data(), b.dev_nodes.data(), a.dev_nodes.size() * sizeof(DevNode)) != 0) {
-      err = "layout self-test: the flat binary-node pass differs from the recursive one";
-      return RAYCA_ERR_BAD_ARG;
-    }
-    if (ref4[0] != ref4[1] || need4[0] != need4[1] || a.dev_nodes4.size() != b.dev_nodes4.size() ||
-        std::memcmp(a.dev_nodes4.data(), b.dev_nodes4.data(), a.dev_nodes4.size() * sizeof(DevNode4)) != 0) {
-      err = "layout self-test: the parallel 4-wide collapse differs from the sequential one";
-      return RAYCA_ERR_BAD_ARG;
-    }
+    auto same = [](const auto& x, const auto& y) { return x.size() == y.size() && std::memcmp(x.data(), y.data(), x.size() * sizeof(*x.data())) == 0; };
+    const char* differs = nullptr;
+    if (ref[0] != ref[1] || need[0] != need[1] || !same(a.dev_nodes, b.dev_nodes)) differs = "layout self-test: the flat binary-node pass differs from the recursive one";
+    else if (ref4[0] != ref4[1] || need4[0] != need4[1] || !same(a.dev_nodes4, b.dev_nodes4)) differs = "layout self-test: the parallel 4-wide collapse differs from the sequential one";
+    if (differs) { err = differs; return RAYCA_ERR_BAD_ARG; }
   }
   return RAYCA_OK;
 }
@@ -1014,14 +1003,7 @@ void finish_node_formats(HostScene& s, const std::atomic<bool>* cancel) {
   if (!s.other_formats_wanted) return;
   auto cancelled = [cancel] { return cancel && cancel->load(std::memory_order_relaxed); };
   if (cancelled()) return;
-  static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[rayca build] %-28s %8.1f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
+  Lap lap;
   // the 4-wide collapse reads the binary nodes and writes its own array: it runs next to the fp16 encoding of the binary
   // nodes below and is joined before its own fp16 copy is made
   std::thread wide_thread([&s] {
@@ -1249,20 +1231,15 @@ bool same_bytes_parallel(const std::vector<BytePair>& pairs) {
     }
   std::atomic<size_t> next{0};
   std::atomic<bool> differ{false};
-  auto work = [&] {
+  // (a thread costs some tens of microseconds to start: one per 1 MiB at most)
+  run_on_host_threads((unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), total >> 20)), [&](unsigned) {
     for (;;) {
       if (differ.load(std::memory_order_relaxed)) return;
       const size_t i = next.fetch_add(1, std::memory_order_relaxed);
       if (i >= chunks.size()) return;
       if (std::memcmp(chunks[i].a, chunks[i].b, chunks[i].bytes) != 0) differ.store(true, std::memory_order_relaxed);
     }
-  };
-  // (a thread costs some tens of microseconds to start: one per 1 MiB at most)
-  const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), total >> 20));
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
-  work();
-  for (std::thread& th : pool) th.join();
+  });
   return !differ.load();
 }
 
@@ -1295,14 +1272,9 @@ void KeptDesc::assign(const RaycaSceneDesc& d, bool use_bvh, SceneGraph&& g) {
   take(image_bytes.data(), d.image_bytes, d.image_byte_count);
   {
     std::atomic<size_t> next{0};
-    auto work = [&] {
+    run_on_host_threads((unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), pieces.size() / 2)), [&](unsigned) {
       for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < pieces.size();) std::memcpy(pieces[i].to, pieces[i].from, pieces[i].bytes);
-    };
-    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(host_threads(), pieces.size() / 2));
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
-    work();
-    for (std::thread& th : pool) th.join();
+    });
   }
   materials.assign(d.materials, d.materials + d.material_count);
   textures.assign(d.textures, d.textures + d.texture_count);
@@ -1398,53 +1370,84 @@ int32_t desc_compare(const RaycaSceneDesc& was, bool was_bvh, const SceneGraph* 
   return RAYCA_OK;
 }
 
-int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder, HostScene& s, std::string& err, const BuildHooks& hooks) {
-  // RAYCA_BUILD_TIMING=1: phase times of the host build on stderr
-  static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[rayca build] %-28s %8.1f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
-  if (d.abi_version != RAYCA_ABI_VERSION) { err = "abi version mismatch"; return RAYCA_ERR_BAD_ARG; }
-  if (d.node_count && !d.nodes) { err = "nodes is null"; return RAYCA_ERR_BAD_ARG; }
-  if (d.vertex_count && !d.positions) { err = "positions is null"; return RAYCA_ERR_BAD_ARG; }
+namespace {
 
+struct TriJob {  // a run of triangles of one mesh primitive under one node, and where its HostPrims go
+  uint32_t node, pi, first_tri, first_out, count;
+  Mat3 tangent_matrix, normal_matrix;
+  uint32_t model, blas_pos;   // its BLAS and the position of its first triangle in that BLAS's initial order
+};
+struct OtherPrim { uint32_t prim, model, blas_pos; };   // spheres, quad-light triangles: made where they are met, few
+using Soa = std::vector<float, DefaultInitAllocator<float>>;   // nine planes of n floats, one block, BLAS order
+
+// What passes between the phases of build_host_scene (below, in the order they run)
+struct HostBuild {
+  const RaycaSceneDesc& d;
+  const uint32_t builder;
+  const bool use_bvh;
+  const BuildHooks& hooks;
+  HostScene& s;       // what is being built
+  std::string& err;   // filled by the phase that returns an error
+  Lap lap;   // RAYCA_BUILD_TIMING=1: phase times of the host build on stderr
+  // the device builder (thread_local: read here, the trees are built by other threads) and the layout's settings
+  // (RAYCA_LEAF_NODE_COST / RAYCA_LEAF_MAX: experiments with the price of a node step -- 0 lays the tree out as built -- and
+  // with the cap on a folded leaf, which hardly ever binds: 4, 8, 16 and 32 give the same 135 379 nodes on the atrium)
+  const BlasBuildFn device_builder = g_device_builder;
+  const uint32_t device_ordinal = g_device_ordinal;
+  const float leaf_node_cost = [] { const char* e = getenv("RAYCA_LEAF_NODE_COST"); return e ? (float)atof(e) : kLeafNodeCost; }();
+  const uint32_t leaf_max = [] { const char* e = getenv("RAYCA_LEAF_MAX"); return e ? (uint32_t)std::min(std::max(atoi(e), 1), (int)kLeafMaxPrims) : kLeafCollapseMax; }();
   SceneGraph g;
-  if (const int32_t rc = scene_graph_pass(d, g, err); rc != RAYCA_OK) return rc;
+  std::vector<uint32_t> models;   // flatten_slots: ascending; one BLAS each, in that order until they move into s.blas in TLAS order
+  std::vector<HostBlas> blas;
+  std::vector<TriJob> jobs;       // what flatten_fill has to do
+  std::vector<OtherPrim> others;
+  // flatten_fill: what the device builder reads, world centroids and boxes of a BLAS's primitives in the BLAS's initial order
+  // (the two trees of a RAYCA_BUILDER_SAH scene start from the same order and share one copy); empty: built on the host
+  std::vector<Soa> soas;
+  // build_trees: the root boxes, and the reference's tree and order of the primitives inside each BLAS (RAYCA_BUILDER_SAH:
+  // the order is the tie rule, the leaves are the candidate filter)
+  std::vector<Box> blas_root;
+  std::vector<std::vector<uint32_t>> ref_prims;
+  std::vector<std::vector<BuildNode>> ref_nodes;
+  std::vector<TNode> tn;                                       // order_and_reference_tables: the TLAS, the BLASes in its order,
+  std::vector<uint32_t> blas_order, ref_rank, ref_leaf_flat;   // flatten index -> slot in the reference's global order / its leaf
+};
+
+// What every primitive and its shading record hold, whatever they are made from; in place (a mesh triangle's slot is not pre-zeroed)
+inline void init_prim(HostPrim& hp, PrimExt& ext, uint32_t kind, uint32_t node, uint32_t material, uint32_t src) {
+  hp.kind = kind; hp.node = node; hp.material = material; hp.src = src;
+  std::memset(&ext, 0, sizeof ext);
+  ext.kind = kind; ext.node = node; ext.material = material;
+}
+
+// SceneDrawInfo::new, then BvhScene::from_scene's order: models in ascending id; per model its meshes, then its quad lights.
+// Spheres and quad-light triangles are made here; a mesh triangle gets its slot (s.prims, s.ext, its BLAS's order) and a TriJob.
+int32_t flatten_slots(HostBuild& b) {
+  const RaycaSceneDesc& d = b.d;
+  HostScene& s = b.s;
+  if (const int32_t rc = scene_graph_pass(d, b.g, b.err); rc != RAYCA_OK) return rc;
   s.nodes.assign(d.nodes, d.nodes + d.node_count);
-  s.local_trs = std::move(g.local_trs);
-  s.world_trs = std::move(g.world_trs);
-  s.has_camera = g.has_camera;
-  s.camera_node = g.camera_node;
-  s.camera_yfov = g.camera_yfov;
-  s.lights = std::move(g.lights);
-  const std::vector<uint32_t>& mesh_nodes = g.mesh_nodes;
-  const std::vector<uint32_t>& light_nodes = g.light_nodes;
+  s.local_trs = std::move(b.g.local_trs);
+  s.world_trs = std::move(b.g.world_trs);
+  s.has_camera = b.g.has_camera;
+  s.camera_node = b.g.camera_node;
+  s.camera_yfov = b.g.camera_yfov;
+  s.lights = std::move(b.g.lights);
+  const std::vector<uint32_t>&mesh_nodes = b.g.mesh_nodes, &light_nodes = b.g.light_nodes;
   s.materials.assign(d.materials, d.materials + d.material_count);
   s.textures.assign(d.textures, d.textures + d.texture_count);
   s.images.assign(d.images, d.images + d.image_count);
   s.image_bytes.assign(d.image_bytes, d.image_bytes + d.image_byte_count);
 
-  // ---- BvhScene::from_scene: models in ascending id; per model meshes then quad lights ----------
-  std::vector<uint32_t> models;
+  std::vector<uint32_t>& models = b.models;
   for (uint32_t n : mesh_nodes) models.push_back(d.nodes[n].model);
   for (uint32_t n : light_nodes)
     if (d.lights[d.nodes[n].light].kind == RAYCA_LIGHT_QUAD) models.push_back(d.nodes[n].model);
   std::sort(models.begin(), models.end());
   models.erase(std::unique(models.begin(), models.end()), models.end());
 
-  struct TriJob {  // a run of triangles of one mesh primitive under one node, and where its HostPrims go
-    uint32_t node, pi, first_tri, first_out, count;
-    Mat3 tangent_matrix, normal_matrix;
-    uint32_t model, blas_pos;   // its BLAS and the position of its first triangle in that BLAS's initial order
-  };
-  struct OtherPrim { uint32_t prim, model, blas_pos; };   // spheres, quad-light triangles: made where they are met, few
-  std::vector<OtherPrim> others;
-  std::vector<TriJob> jobs;
-  std::vector<HostBlas> blas(models.size());
+  std::vector<HostBlas>& blas = b.blas;
+  blas.resize(models.size());
   {  // one allocation for the flatten-order array: growing it piecewise re-copied 0.5 KB per triangle several times over
     size_t total = 2 * light_nodes.size();
     for (uint32_t node : mesh_nodes) {
@@ -1457,6 +1460,12 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
   }
   for (size_t m = 0; m < models.size(); ++m) {
     blas[m].model = models[m];
+    auto push_other = [&](const HostPrim& hp, const PrimExt& ext) {  // a finished primitive at the end of the arrays and of BLAS m
+      b.others.push_back(OtherPrim{hp.src, (uint32_t)m, (uint32_t)blas[m].prims.size()});
+      blas[m].prims.push_back(hp.src);
+      s.prims.push_back(hp);
+      s.ext.push_back(ext);
+    };
     for (uint32_t node : mesh_nodes) {
       if (d.nodes[node].model != models[m]) continue;
       const RaycaMesh& mesh = d.meshes[d.nodes[node].mesh];
@@ -1464,35 +1473,25 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
       const Mat3 tangent_matrix = mat3_from_trs(trs);                             // primitive.rs:203-204
       const Mat3 normal_matrix = mat3_transpose(mat3_from_inverse_trs(trs));      // primitive.rs:206-207
       for (uint32_t pi = mesh.first_primitive; pi < mesh.first_primitive + mesh.primitive_count; ++pi) {
-        if (pi >= d.primitive_count) { err = "primitive index out of range"; return RAYCA_ERR_BAD_ARG; }
+        if (pi >= d.primitive_count) { b.err = "primitive index out of range"; return RAYCA_ERR_BAD_ARG; }
         const RaycaPrimitive& p = d.primitives[pi];
         if (p.geometry == RAYCA_GEOMETRY_SPHERE) {  // from_sphere  primitive.rs:262-274
           HostPrim hp{};
-          hp.kind = RAYCA_GEOMETRY_SPHERE;
-          hp.node = node;
-          hp.material = p.material;
+          PrimExt ext;
+          init_prim(hp, ext, RAYCA_GEOMETRY_SPHERE, node, p.material, (uint32_t)s.prims.size());
           hp.center = point3(p.sphere_center[0], p.sphere_center[1], p.sphere_center[2]);
           hp.radius = p.sphere_radius;
-          PrimExt ext;
-          std::memset(&ext, 0, sizeof ext);
-          ext.material = p.material;
-          ext.kind = hp.kind;
-          ext.node = node;
-          hp.src = (uint32_t)s.prims.size();
-          others.push_back(OtherPrim{hp.src, (uint32_t)m, (uint32_t)blas[m].prims.size()});
-          blas[m].prims.push_back(hp.src);
-          s.prims.push_back(hp);
-          s.ext.push_back(ext);
+          push_other(hp, ext);
           s.sphere_count++;
           continue;
         }
         // from_triangle_mesh_impl  primitive.rs:209-234: the triangles are independent -- slots are reserved
-        // here, in order, and filled by all host threads below
+        // here, in order, and filled by all host threads in flatten_fill
         const uint32_t ntri = p.index_count / 3;
         const uint32_t first_out = (uint32_t)s.prims.size();
         for (uint32_t at = 0; at < ntri; at += 8192)  // pieces, so that one huge mesh still feeds every thread
-          jobs.push_back(TriJob{node, pi, at, first_out + at, std::min<uint32_t>(8192u, ntri - at), tangent_matrix, normal_matrix, (uint32_t)m,
-                                (uint32_t)blas[m].prims.size() + at});
+          b.jobs.push_back(TriJob{node, pi, at, first_out + at, std::min<uint32_t>(8192u, ntri - at), tangent_matrix, normal_matrix, (uint32_t)m,
+                                  (uint32_t)blas[m].prims.size() + at});
         s.prims.resize((size_t)first_out + ntri);
         s.ext.resize((size_t)first_out + ntri);
         {
@@ -1509,67 +1508,63 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
       const F4 ab = vec3(l.ab[0], l.ab[1], l.ab[2]), ac = vec3(l.ac[0], l.ac[1], l.ac[2]);
       const F4 normal = normalized(cross(ab, ac));
       const F4 qa = point3(0, 0, 0);
-      const F4 a = qa, b = qa + ab, dd = (qa + ab) + ac, c = qa + ac;
-      const F4 tri[2][3] = {{a, dd, b}, {a, c, dd}};
+      const F4 a = qa, bb = qa + ab, dd = (qa + ab) + ac, c = qa + ac;
+      const F4 tri[2][3] = {{a, dd, bb}, {a, c, dd}};
       for (int t = 0; t < 2; ++t) {
         HostPrim hp{};
-        hp.kind = RAYCA_GEOMETRY_TRIANGLE_MESH;
-        hp.node = node;
-        hp.material = l.material;
         PrimExt ext;
-        std::memset(&ext, 0, sizeof ext);
+        init_prim(hp, ext, RAYCA_GEOMETRY_TRIANGLE_MESH, node, l.material, (uint32_t)s.prims.size());
         for (int k = 0; k < 3; ++k) {
           hp.p[k] = tri[t][k];
           set_ext(ext, k, white(), normal, vec3(0, 0, 0), vec3(0, 0, 0), F2{0, 0});
         }
         hp.centroid = ((to_vec(hp.p[0]) + to_vec(hp.p[1])) + to_vec(hp.p[2])) * 0.3333f;
-        ext.material = l.material;
-        ext.kind = hp.kind;
-        ext.node = node;
-        hp.src = (uint32_t)s.prims.size();
-        others.push_back(OtherPrim{hp.src, (uint32_t)m, (uint32_t)blas[m].prims.size()});
-        blas[m].prims.push_back(hp.src);
-        s.prims.push_back(hp);
-        s.ext.push_back(ext);
+        push_other(hp, ext);
         s.triangle_count++;
       }
     }
   }
-  lap("flatten: graph, slots");
-  // One pass over the triangles does everything that is per primitive: the flatten-order record and its shading record, the
-  // world-space vertices / centroid / box (cache_world), the 9 floats of the device's triangle array, and -- for a BLAS the
-  // device builds -- its row of the SoA the device builder reads.  (Three passes of all host threads before: each touched
-  // the 0.5 KB per primitive again and paid a round of thread starts.)
+  return RAYCA_OK;
+}
+
+// What follows from a primitive's model-space record: the world-space vertices / centroid / box (cache_world), the 9 floats of
+// the device's triangle array, and -- for a BLAS the device builds -- its row of the SoA the device builder reads
+inline void finish_prim(HostBuild& b, uint32_t prim, uint32_t model, uint32_t blas_pos) {
+  HostScene& s = b.s;
+  HostPrim& p = s.prims[prim];
+  cache_world(p, s.world_trs[p.node]);
+  float* tv = &s.tris[(size_t)prim * 9];
+  for (int k = 0; k < 3; ++k) {
+    tv[3 * k + 0] = p.wp[k].x;
+    tv[3 * k + 1] = p.wp[k].y;
+    tv[3 * k + 2] = p.wp[k].z;
+  }
+  Soa& soa = b.soas[model];
+  if (!soa.empty()) {
+    const size_t n = soa.size() / 9, i = blas_pos;
+    float* const q = soa.data();
+    q[i] = p.wcentroid.x; q[n + i] = p.wcentroid.y; q[2 * n + i] = p.wcentroid.z;
+    q[3 * n + i] = p.wmin.x; q[4 * n + i] = p.wmin.y; q[5 * n + i] = p.wmin.z;
+    q[6 * n + i] = p.wmax.x; q[7 * n + i] = p.wmax.y; q[8 * n + i] = p.wmax.z;
+  }
+}
+
+// One pass of all host threads fills the reserved triangle slots and finishes them; then the few others are finished.  (Three
+// passes before: each touched the 0.5 KB per primitive again and paid a round of thread starts.)
+int32_t flatten_fill(HostBuild& b) {
+  const RaycaSceneDesc& d = b.d;
+  HostScene& s = b.s;
   static const bool host_only = getenv("RAYCA_HOST_BUILD") != nullptr;
-  const BlasBuildFn device_builder = g_device_builder;   // (thread_local: captured here, the trees are built by other threads)
-  using Soa = std::vector<float, DefaultInitAllocator<float>>;   // nine planes of n floats, one block, BLAS order
-  std::vector<Soa> soas(blas.size());
-  for (size_t m = 0; m < blas.size(); ++m)
-    if (device_builder && !host_only && use_bvh && blas[m].prims.size() >= kDeviceBuildMin) soas[m].resize(9 * blas[m].prims.size());
+  b.soas.resize(b.blas.size());
+  for (size_t m = 0; m < b.blas.size(); ++m)
+    if (b.device_builder && !host_only && b.use_bvh && b.blas[m].prims.size() >= kDeviceBuildMin) b.soas[m].resize(9 * b.blas[m].prims.size());
   s.tris.resize(s.prims.size() * 9);
-  auto finish_prim = [&](uint32_t prim, uint32_t model, uint32_t blas_pos) {
-    HostPrim& p = s.prims[prim];
-    cache_world(p, s.world_trs[p.node]);
-    float* tv = &s.tris[(size_t)prim * 9];
-    for (int k = 0; k < 3; ++k) {
-      tv[3 * k + 0] = p.wp[k].x;
-      tv[3 * k + 1] = p.wp[k].y;
-      tv[3 * k + 2] = p.wp[k].z;
-    }
-    Soa& soa = soas[model];
-    if (!soa.empty()) {
-      const size_t n = soa.size() / 9, i = blas_pos;
-      float* const q = soa.data();
-      q[i] = p.wcentroid.x; q[n + i] = p.wcentroid.y; q[2 * n + i] = p.wcentroid.z;
-      q[3 * n + i] = p.wmin.x; q[4 * n + i] = p.wmin.y; q[5 * n + i] = p.wmin.z;
-      q[6 * n + i] = p.wmax.x; q[7 * n + i] = p.wmax.y; q[8 * n + i] = p.wmax.z;
-    }
-  };
-  if (!jobs.empty()) {  // fill the reserved triangle slots with all host threads
+  if (!b.jobs.empty()) {
+    const std::vector<TriJob>& jobs = b.jobs;
     std::atomic<int> failed{0};
     const char* first_error = nullptr;
     std::atomic<size_t> next_job{0};
-    auto worker = [&] {
+    run_on_host_threads(std::max(1u, std::min<unsigned>(host_threads(), (unsigned)jobs.size())), [&](unsigned) {
       for (;;) {
         const size_t j = next_job.fetch_add(1);
         if (j >= jobs.size() || failed.load(std::memory_order_relaxed)) return;
@@ -1578,13 +1573,10 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
         for (uint32_t t = 0; t < job.count; ++t) {
           const uint32_t tri = job.first_tri + t;
           HostPrim& hp = s.prims[job.first_out + t];  // written in place, every field (the array is not pre-zeroed)
-          hp.kind = RAYCA_GEOMETRY_TRIANGLE_MESH;
-          hp.node = job.node;
-          hp.material = p.material;
+          PrimExt& ext = s.ext[job.first_out + t];
+          init_prim(hp, ext, RAYCA_GEOMETRY_TRIANGLE_MESH, job.node, p.material, job.first_out + t);
           hp.center = point3(0, 0, 0);
           hp.radius = 0.0f;
-          PrimExt& ext = s.ext[job.first_out + t];
-          std::memset(&ext, 0, sizeof ext);
           const char* problem = nullptr;
           for (int k = 0; k < 3; ++k) {
             uint32_t idx;
@@ -1604,214 +1596,218 @@ int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder
             return;
           }
           hp.centroid = ((to_vec(hp.p[0]) + to_vec(hp.p[1])) + to_vec(hp.p[2])) * 0.3333f;  // triangle.rs:59-63
-          ext.material = p.material;
-          ext.kind = hp.kind;
-          ext.node = job.node;
-          hp.src = job.first_out + t;
-          finish_prim(job.first_out + t, job.model, job.blas_pos + t);
+          finish_prim(b, job.first_out + t, job.model, job.blas_pos + t);
         }
       }
-    };
-    const unsigned nthreads = std::max(1u, std::min<unsigned>(host_threads(), (unsigned)jobs.size()));
-    std::vector<std::thread> pool;
-    for (unsigned i = 1; i < nthreads; ++i) pool.emplace_back(worker);
-    worker();
-    for (std::thread& th : pool) th.join();
-    if (failed.load()) { err = first_error ? first_error : "bad triangle data"; return RAYCA_ERR_BAD_ARG; }
+    });
+    if (failed.load()) { b.err = first_error ? first_error : "bad triangle data"; return RAYCA_ERR_BAD_ARG; }
   }
-  for (const OtherPrim& o : others) finish_prim(o.prim, o.model, o.blas_pos);
-  lap("flatten primitives, world space, SoA");
-  if (hooks.on_prims_ready) hooks.on_prims_ready();
+  for (const OtherPrim& o : b.others) finish_prim(b, o.prim, o.model, o.blas_pos);
+  return RAYCA_OK;
+}
 
-  // ---- Tlas::new: one BLAS per model ------------------------------------------------------------
-  const unsigned hw = host_threads();
+// One tree over BLAS m's primitives, initially in `order`, on the host or -- where flatten_fill made an SoA -- by the device
+// builder.  `quiet`: the second tree of a BLAS, built beside the first: no lap lines, and the root box is the other's to write.
+bool build_blas(HostBuild& b, size_t m, bool seed_origin, std::vector<uint32_t>& order, std::vector<BuildNode>& nodes, std::string& build_err,
+                bool quiet, BlasDeviceTree* keep, void* stream) {
   unsigned par_levels = 0;
-  while ((1u << par_levels) < hw) ++par_levels;
-  std::vector<Box> blas_root(blas.size());
-  // reference order of every primitive inside its BLAS (needed by both builders: it is the tie rule)
-  std::vector<std::vector<uint32_t>> ref_prims(blas.size());
-  std::vector<std::vector<BuildNode>> ref_nodes(blas.size());
-  const uint32_t device_ordinal = g_device_ordinal;
-  std::mutex lap_mu;
+  while ((1u << par_levels) < host_threads()) ++par_levels;
+  BlasBuilder bb{&b.s, &order, b.use_bvh ? 255u : 0u, par_levels + 1, seed_origin};
+  std::vector<BuildNode> arena(1);
+  arena[0].offset = 0;
+  arena[0].count = (uint32_t)order.size();
+  arena[0].bounds = bb.range_bounds(0, arena[0].count);
+  const uint32_t n = arena[0].count;
+  const Soa& soa = b.soas[m];
+  if (soa.size() == 9 * (size_t)n && n > 0) {
+    // the same recursion, level by level on the GPU (bvh_build.hip): identical tree, boxes and order
+    BlasBuildInput in{};
+    for (int c = 0; c < 3; ++c) {
+      in.cent[c] = soa.data() + (size_t)c * n;
+      in.bmin[c] = soa.data() + (size_t)(3 + c) * n;
+      in.bmax[c] = soa.data() + (size_t)(6 + c) * n;
+    }
+    in.count = n;
+    in.root_min[0] = arena[0].bounds.a.x; in.root_min[1] = arena[0].bounds.a.y; in.root_min[2] = arena[0].bounds.a.z;
+    in.root_max[0] = arena[0].bounds.b.x; in.root_max[1] = arena[0].bounds.b.y; in.root_max[2] = arena[0].bounds.b.z;
+    in.seed_origin = seed_origin;
+    in.max_depth = 255u;
+    in.device = b.device_ordinal;
+    in.stream = stream;
+    in.layout_node_cost = seed_origin ? 0.0f : b.leaf_node_cost;
+    in.layout_leaf_max = b.leaf_max;
+    std::vector<uint32_t> perm;
+    // (the arena as the host builder would have made it -- or, with `keep`, the tree left on the device and only its root here)
+    if (!b.device_builder(in, perm, arena, build_err, keep)) return false;
+    b.lap("  gpu build (total)", quiet);
+    std::vector<uint32_t> permuted(n);
+    parallel_chunks(n, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) permuted[i] = order[perm[i]];
+    });
+    order.swap(permuted);
+  } else if (n > 0) {
+    bb.split(arena, 0, 0);
+  }
+  b.lap("  host: apply order, arena", quiet);
+  if (!quiet) b.blas_root[m] = arena[0].bounds;  // (the same box for both trees of a BLAS: written by one of them)
+  nodes.swap(arena);
+  return true;
+}
+
+// The traversed tree of a device-built BLAS that stayed on the device: the scene owns it, the BLAS knows its layout's size
+void adopt_kept_tree(HostBlas& bl, const BlasDeviceTree& kept, HostScene& s) {
+  if (!kept.handle) return;
+  s.dev_trees.push_back(kept.handle);
+  bl.dev_tree = kept.handle;
+  bl.dev_node_count = kept.node_count;
+  bl.dev_need = kept.need;
+}
+
+// Tlas::new: one BLAS per model.  RAYCA_BUILDER_SAH builds two independent trees over the same primitives side by side -- the
+// reference's (tie order + candidate filter) on a thread of its own -- so that one's host phases run under the other's GPU levels.
+int32_t build_trees(HostBuild& b) {
+  HostScene& s = b.s;
+  std::vector<HostBlas>& blas = b.blas;
+  b.blas_root.resize(blas.size());
+  b.ref_prims.resize(blas.size());
+  b.ref_nodes.resize(blas.size());
   // the traversed tree of a device-built BLAS stays on the device and is laid out there (HostBlas::dev_tree) -- unless the
   // other node formats are to be made right here, on the host, from the host's copy of the binary nodes
-  const bool keep_trees = !hooks.with_formats;
-  // (RAYCA_LEAF_NODE_COST / RAYCA_LEAF_MAX: experiments with the price of a node step -- 0 lays the tree out as built -- and
-  // with the cap on a folded leaf, which hardly ever binds: 4, 8, 16 and 32 give the same 135 379 nodes on the atrium)
-  static const float leaf_node_cost = [] { const char* e = getenv("RAYCA_LEAF_NODE_COST"); return e ? (float)atof(e) : kLeafNodeCost; }();
-  static const uint32_t leaf_max = [] { const char* e = getenv("RAYCA_LEAF_MAX"); return e ? (uint32_t)std::min(std::max(atoi(e), 1), (int)kLeafMaxPrims) : kLeafCollapseMax; }();
-  void* const bstream[2] = {hooks.build_streams ? hooks.build_streams[0] : nullptr, hooks.build_streams ? hooks.build_streams[1] : nullptr};
+  const bool keep_trees = !b.hooks.with_formats;
+  void* const bstream[2] = {b.hooks.build_streams ? b.hooks.build_streams[0] : nullptr, b.hooks.build_streams ? b.hooks.build_streams[1] : nullptr};
   s.dev_segments.clear();
   s.dev_trees.clear();
-  // what the device builder reads: world centroids and boxes of a BLAS's primitives, SoA, in the BLAS's initial order (the
-  // two trees of a RAYCA_BUILDER_SAH scene start from the same order and share one copy)
-  auto build_blas = [&](size_t m, bool seed_origin, std::vector<uint32_t>& order, std::vector<BuildNode>& nodes, std::string& build_err, bool quiet,
-                        const Soa& soa, BlasDeviceTree* keep, void* stream) {
-    auto lap = [&](const char* what) {
-      if (!timing || quiet) return;
-      std::lock_guard<std::mutex> lock(lap_mu);
-      const auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[rayca build] %-28s %8.1f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
-      t_prev = now;
-    };
-    BlasBuilder bb{&s, &order, use_bvh ? 255u : 0u, par_levels + 1, seed_origin};
-    std::vector<BuildNode> arena(1);
-    arena[0].offset = 0;
-    arena[0].count = (uint32_t)order.size();
-    arena[0].bounds = bb.range_bounds(0, arena[0].count);
-    const uint32_t n = arena[0].count;
-    if (soa.size() == 9 * (size_t)n && n > 0) {
-      // the same recursion, level by level on the GPU (bvh_build.hip): identical tree, boxes and order
-      BlasBuildInput in{};
-      for (int c = 0; c < 3; ++c) {
-        in.cent[c] = soa.data() + (size_t)c * n;
-        in.bmin[c] = soa.data() + (size_t)(3 + c) * n;
-        in.bmax[c] = soa.data() + (size_t)(6 + c) * n;
-      }
-      in.count = n;
-      in.root_min[0] = arena[0].bounds.a.x; in.root_min[1] = arena[0].bounds.a.y; in.root_min[2] = arena[0].bounds.a.z;
-      in.root_max[0] = arena[0].bounds.b.x; in.root_max[1] = arena[0].bounds.b.y; in.root_max[2] = arena[0].bounds.b.z;
-      in.seed_origin = seed_origin;
-      in.max_depth = 255u;
-      in.device = device_ordinal;
-      in.stream = stream;
-      in.layout_node_cost = seed_origin ? 0.0f : leaf_node_cost;
-      in.layout_leaf_max = leaf_max;
-      std::vector<uint32_t> perm;
-      // (the arena as the host builder would have made it -- or, with `keep`, the tree left on the device and only its
-      // root here)
-      if (!device_builder(in, perm, arena, build_err, keep)) return false;
-      lap("  gpu build (total)");
-      std::vector<uint32_t> permuted(n);
-      parallel_chunks(n, [&](size_t b, size_t e) {
-        for (size_t i = b; i < e; ++i) permuted[i] = order[perm[i]];
-      });
-      order.swap(permuted);
-    } else if (n > 0) {
-      bb.split(arena, 0, 0);
-    }
-    lap("  host: apply order, arena");
-    if (!quiet) blas_root[m] = arena[0].bounds;  // (the same box for both trees of a BLAS: written by one of them)
-    nodes.swap(arena);
-    return true;
-  };
+  const bool with_reference = b.builder == RAYCA_BUILDER_SAH;
   for (size_t m = 0; m < blas.size(); ++m) {
-    std::string e1, e2;
-    Soa& soa = soas[m];   // (filled by the flatten pass for the BLASes the device builds)
-    if (builder == RAYCA_BUILDER_SAH) {
-      // two independent trees over the same primitives -- the reference's (tie order + candidate filter) and the one that
-      // is traversed -- built side by side: one's host phases (SoA, order, layout) run under the other's GPU levels
-      ref_prims[m] = blas[m].prims;
-      bool ok_ref = false;
-      BlasDeviceTree kept;
-      std::thread ref_thread([&] { ok_ref = build_blas(m, true, ref_prims[m], ref_nodes[m], e1, true, soa, nullptr, bstream[0]); });
-      const bool ok = build_blas(m, false, blas[m].prims, blas[m].nodes, e2, false, soa, keep_trees ? &kept : nullptr, bstream[1]);
-      if (kept.handle) {
-        s.dev_trees.push_back(kept.handle);
-        blas[m].dev_tree = kept.handle;
-        blas[m].dev_node_count = kept.node_count;
-        blas[m].dev_need = kept.need;
-      }
-      ref_thread.join();
-      lap("reference tree + SAH tree");
-      if (!ok_ref || !ok) { err = !ok_ref ? e1 : e2; return RAYCA_ERR_HIP; }
-    } else {
-      BlasDeviceTree kept;
-      const bool ok = build_blas(m, true, blas[m].prims, blas[m].nodes, e1, false, soa, keep_trees ? &kept : nullptr, bstream[1]);
-      if (kept.handle) {
-        s.dev_trees.push_back(kept.handle);
-        blas[m].dev_tree = kept.handle;
-        blas[m].dev_node_count = kept.node_count;
-        blas[m].dev_need = kept.need;
-      }
-      if (!ok) { err = e1; return RAYCA_ERR_HIP; }
+    std::string e_ref, e;
+    bool ok_ref = true;
+    std::thread ref_thread;
+    if (with_reference) {
+      b.ref_prims[m] = blas[m].prims;
+      ref_thread = std::thread([&] { ok_ref = build_blas(b, m, true, b.ref_prims[m], b.ref_nodes[m], e_ref, true, nullptr, bstream[0]); });
     }
+    BlasDeviceTree kept;
+    const bool ok = build_blas(b, m, !with_reference, blas[m].prims, blas[m].nodes, e, false, keep_trees ? &kept : nullptr, bstream[1]);
+    adopt_kept_tree(blas[m], kept, s);
+    if (with_reference) {
+      ref_thread.join();
+      b.lap("reference tree + SAH tree");
+    }
+    if (!ok_ref || !ok) { b.err = !ok_ref ? e_ref : e; return RAYCA_ERR_HIP; }
   }
-  std::vector<uint32_t> blas_order(blas.size());
-  for (size_t i = 0; i < blas.size(); ++i) blas_order[i] = (uint32_t)i;
-  std::vector<TNode> tn(1);
-  if (!blas.empty()) tlas_split(tn, 0, blas_order, blas_root, 0, (uint32_t)blas.size());
-  // store BLASes in TLAS order so that a TLAS range [offset, offset+count) indexes s.blas directly
+  return RAYCA_OK;
+}
+
+// The TLAS over the BLAS root boxes, the BLASes moved into its order (a TLAS range [offset, offset + count) indexes s.blas
+// directly), and -- RAYCA_BUILDER_SAH -- the reference's tables by flatten index: rank in its global order, leaf, leaf boxes
+int32_t order_and_reference_tables(HostBuild& b) {
+  HostScene& s = b.s;
+  std::vector<HostBlas>& blas = b.blas;
+  b.blas_order.resize(blas.size());
+  for (size_t i = 0; i < blas.size(); ++i) b.blas_order[i] = (uint32_t)i;
+  b.tn.assign(1, TNode{});
+  if (!blas.empty()) tlas_split(b.tn, 0, b.blas_order, b.blas_root, 0, (uint32_t)blas.size());
   s.blas.clear();
-  std::vector<uint32_t> ref_rank;       // flatten index -> slot in the reference's global order
-  std::vector<uint32_t> ref_leaf_flat;  // flatten index -> reference leaf
   s.ref_leaf_boxes.clear();
-  if (builder == RAYCA_BUILDER_SAH) {
-    ref_rank.assign(s.prims.size(), 0);
-    ref_leaf_flat.assign(s.prims.size(), 0);
+  if (b.builder == RAYCA_BUILDER_SAH) {
+    b.ref_rank.assign(s.prims.size(), 0);
+    b.ref_leaf_flat.assign(s.prims.size(), 0);
     uint32_t slot = 0;
-    for (uint32_t b : blas_order) {
-      for (uint32_t pi : ref_prims[b]) ref_rank[pi] = slot++;
-      for (const BuildNode& rn : ref_nodes[b]) {
+    for (uint32_t bi : b.blas_order) {
+      for (uint32_t pi : b.ref_prims[bi]) b.ref_rank[pi] = slot++;
+      for (const BuildNode& rn : b.ref_nodes[bi]) {
         if (rn.left >= 0 || rn.count == 0) continue;  // inner node (or the root of an empty BLAS)
         const uint32_t leaf = (uint32_t)(s.ref_leaf_boxes.size() / 8);
         const float bx[8] = {rn.bounds.a.x, rn.bounds.a.y, rn.bounds.a.z, 0.0f, rn.bounds.b.x, rn.bounds.b.y, rn.bounds.b.z, 0.0f};
         s.ref_leaf_boxes.insert(s.ref_leaf_boxes.end(), bx, bx + 8);
-        for (uint32_t i = rn.offset; i < rn.offset + rn.count; ++i) ref_leaf_flat[ref_prims[b][i]] = leaf;
+        for (uint32_t i = rn.offset; i < rn.offset + rn.count; ++i) b.ref_leaf_flat[b.ref_prims[bi][i]] = leaf;
       }
     }
   }
-  for (uint32_t b : blas_order) s.blas.push_back(std::move(blas[b]));
+  for (uint32_t bi : b.blas_order) s.blas.push_back(std::move(blas[bi]));
+  return RAYCA_OK;
+}
 
-  lap("TLAS + reference tables");
-  // ---- device layout ----------------------------------------------------------------------------
+// The binary f32 nodes of the whole scene (DevBuilder), the slot order of the primitives, and the reference's tables by slot
+int32_t layout_binary(HostBuild& b) {
+  HostScene& s = b.s;
+  const std::vector<TNode>& tn = b.tn;
   s.dev_nodes.clear();
   s.prim_order.clear();
   s.max_depth = 0;
-  if (!s.blas.empty()) {
-    DevBuilder db{s, {}};
-    if (builder == RAYCA_BUILDER_SAH) {
-      // This tree's boxes only have to be conservative (the reference-leaf filter decides candidacy):
-      // pad them by 2^-16 of their magnitude plus 2^-20 of the scene diagonal, two orders of magnitude
-      // above the rounding of the slab and triangle arithmetic for a ray that starts within four scene
-      // diagonals of the origin, so that a triangle such a ray hits is never lost because an enclosing
-      // box rounds the other way.  The padding cannot know a ray's origin: rays from farther away carry
-      // a slack of their own through the steering tests (trace_core.inc, RAYCA_RAY_SLACK).
-      const F4 ext = as_vec(tn[0].bounds.b - tn[0].bounds.a);
-      const float diag = sqrtf(ext.x * ext.x + ext.y * ext.y + ext.z * ext.z);
-      db.pad_rel = 1.52587890625e-05f;
-      db.pad_abs = (diag == diag && diag < FLT_MAX) ? diag * 9.5367431640625e-07f : 0.0f;
-    }
-    s.pad_rel = db.pad_rel;
-    s.pad_abs = db.pad_abs;
-    db.node_cost = builder == RAYCA_BUILDER_SAH ? leaf_node_cost : 0.0f;
-    db.leaf_max = leaf_max;
-    uint32_t base = 0;
-    for (const HostBlas& bl : s.blas) {
-      db.blas_base.push_back(base);
-      for (uint32_t pi : bl.prims) s.prim_order.push_back(pi);
-      base += (uint32_t)bl.prims.size();
-    }
-    if (base > kLeafFirstMask) { err = "too many primitives for the packed leaf reference (max 33554431)"; return RAYCA_ERR_UNSUPPORTED; }
-    if (hooks.on_order_ready) hooks.on_order_ready();
-    s.root_min = tn[0].bounds.a;
-    s.root_max = tn[0].bounds.b;
-    uint32_t need = 0;
-    s.root_ref = db.emit_tlas(tn, 0, need);
-    s.max_depth = need;
-    lap("  binary nodes");
-    s.tie_rank.clear();
-    s.ref_leaf_of.clear();
-    if (builder == RAYCA_BUILDER_SAH) {
-      s.tie_rank.resize(s.prim_order.size());
-      s.ref_leaf_of.resize(s.prim_order.size());
-      parallel_chunks(s.prim_order.size(), [&](size_t b, size_t e) {
-        for (size_t slot = b; slot < e; ++slot) {
-          s.tie_rank[slot] = ref_rank[s.prim_order[slot]];
-          s.ref_leaf_of[slot] = ref_leaf_flat[s.prim_order[slot]];
-        }
-      });
-    }
+  if (s.blas.empty()) return RAYCA_OK;
+  DevBuilder db{s, {}};
+  if (b.builder == RAYCA_BUILDER_SAH) {
+    // This tree's boxes only have to be conservative (the reference-leaf filter decides candidacy):
+    // pad them by 2^-16 of their magnitude plus 2^-20 of the scene diagonal, two orders of magnitude
+    // above the rounding of the slab and triangle arithmetic for a ray that starts within four scene
+    // diagonals of the origin, so that a triangle such a ray hits is never lost because an enclosing
+    // box rounds the other way.  The padding cannot know a ray's origin: rays from farther away carry
+    // a slack of their own through the steering tests (trace_core.inc, RAYCA_RAY_SLACK).
+    const F4 ext = as_vec(tn[0].bounds.b - tn[0].bounds.a);
+    const float diag = sqrtf(ext.x * ext.x + ext.y * ext.y + ext.z * ext.z);
+    db.pad_rel = 1.52587890625e-05f;
+    db.pad_abs = (diag == diag && diag < FLT_MAX) ? diag * 9.5367431640625e-07f : 0.0f;
   }
+  s.pad_rel = db.pad_rel;
+  s.pad_abs = db.pad_abs;
+  db.node_cost = b.builder == RAYCA_BUILDER_SAH ? b.leaf_node_cost : 0.0f;
+  db.leaf_max = b.leaf_max;
+  uint32_t base = 0;
+  for (const HostBlas& bl : s.blas) {
+    db.blas_base.push_back(base);
+    for (uint32_t pi : bl.prims) s.prim_order.push_back(pi);
+    base += (uint32_t)bl.prims.size();
+  }
+  if (base > kLeafFirstMask) { b.err = "too many primitives for the packed leaf reference (max 33554431)"; return RAYCA_ERR_UNSUPPORTED; }
+  if (b.hooks.on_order_ready) b.hooks.on_order_ready();
+  s.root_min = tn[0].bounds.a;
+  s.root_max = tn[0].bounds.b;
+  uint32_t need = 0;
+  s.root_ref = db.emit_tlas(tn, 0, need);
+  if (!db.error.empty()) { b.err = db.error; return RAYCA_ERR_BAD_ARG; }
+  s.max_depth = need;
+  b.lap("  binary nodes");
+  s.tie_rank.clear();
+  s.ref_leaf_of.clear();
+  if (b.builder == RAYCA_BUILDER_SAH) {
+    s.tie_rank.resize(s.prim_order.size());
+    s.ref_leaf_of.resize(s.prim_order.size());
+    parallel_chunks(s.prim_order.size(), [&](size_t lo, size_t hi) {
+      for (size_t slot = lo; slot < hi; ++slot) {
+        s.tie_rank[slot] = b.ref_rank[s.prim_order[slot]];
+        s.ref_leaf_of[slot] = b.ref_leaf_flat[s.prim_order[slot]];
+      }
+    });
+  }
+  return RAYCA_OK;
+}
+
+}  // namespace
+
+int32_t build_host_scene(const RaycaSceneDesc& d, bool use_bvh, uint32_t builder, HostScene& s, std::string& err, const BuildHooks& hooks) {
+  if (d.abi_version != RAYCA_ABI_VERSION) { err = "abi version mismatch"; return RAYCA_ERR_BAD_ARG; }
+  if (d.node_count && !d.nodes) { err = "nodes is null"; return RAYCA_ERR_BAD_ARG; }
+  if (d.vertex_count && !d.positions) { err = "positions is null"; return RAYCA_ERR_BAD_ARG; }
+  HostBuild b{d, builder, use_bvh, hooks, s, err};
+  int32_t rc;
+  if ((rc = flatten_slots(b)) != RAYCA_OK) return rc;
+  b.lap("flatten: graph, slots");
+  if ((rc = flatten_fill(b)) != RAYCA_OK) return rc;
+  b.lap("flatten primitives, world space, SoA");
+  if (hooks.on_prims_ready) hooks.on_prims_ready();
+  if ((rc = build_trees(b)) != RAYCA_OK) return rc;
+  if ((rc = order_and_reference_tables(b)) != RAYCA_OK) return rc;
+  b.lap("TLAS + reference tables");
+  if ((rc = layout_binary(b)) != RAYCA_OK) return rc;
+  // the other three node formats are only ever traversed next to the reference-leaf filter
   s.dev_nodes4.clear();
   s.dev_nodes_h.clear();
   s.dev_nodes4_h.clear();
-  s.root_ref4 = 0;
-  s.max_depth4 = 0;
-  // the other three node formats are only ever traversed next to the reference-leaf filter
+  s.root_ref4 = s.max_depth4 = 0;
   s.other_formats_wanted = builder == RAYCA_BUILDER_SAH && !s.blas.empty();
   if (hooks.with_formats) finish_node_formats(s);
-  lap("device node layouts");
+  b.lap("device node layouts");
   return RAYCA_OK;
 }
 

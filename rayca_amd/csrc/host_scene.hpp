@@ -4,11 +4,14 @@
 #pragma once
 
 #include <atomic>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <utility>
@@ -262,6 +265,27 @@ struct HostScene {
 // share of a node; std::thread::hardware_concurrency() reports the whole machine, and a few hundred threads for a 50 ms
 // phase cost more than they do), RAYCA_HOST_THREADS overrides.
 unsigned host_threads();
+
+// RAYCA_BUILD_TIMING=1 (read once per process): lap("what") prints, on stderr, the time since the previous lap of this
+// object -- or since it was made -- as "[rayca <tag>] <what> <ms> ms".  One object may be called from two threads (the two
+// trees of a BLAS are built side by side); a quiet call prints nothing and leaves the clock alone.
+struct Lap {
+  Lap(const char* tag = "build", int label_width = 28, int decimals = 1) : tag_(tag), width_(label_width), decimals_(decimals) {}
+  void operator()(const char* what, bool quiet = false) {
+    static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
+    if (!timing || quiet) return;
+    std::lock_guard<std::mutex> lock(mu_);
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[rayca %s] %-*s %8.*f ms\n", tag_, width_, what, decimals_, std::chrono::duration<float, std::milli>(now - t_prev_).count());
+    t_prev_ = now;
+  }
+
+ private:
+  const char* tag_;
+  int width_, decimals_;
+  std::mutex mu_;
+  std::chrono::steady_clock::time_point t_prev_ = std::chrono::steady_clock::now();
+};
 
 // Returns RAYCA_OK or an error code with `err` filled.
 struct BuildHooks {

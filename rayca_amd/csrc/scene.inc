@@ -634,14 +634,7 @@ int32_t rayca_hip_scene_reap(void) {
 namespace {
 
 int32_t scene_destroy_now(RaycaScene* s) {
-  static const bool timing = getenv("RAYCA_BUILD_TIMING") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[rayca destroy] %-26s %8.2f ms\n", what, std::chrono::duration<float, std::milli>(now - t_prev).count());
-    t_prev = now;
-  };
+  Lap lap("destroy", 26, 2);
   if (s->ctx_thread.joinable()) s->ctx_thread.join();
   {
     s->formats_cancel.store(true, std::memory_order_relaxed);
