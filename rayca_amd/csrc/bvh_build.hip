@@ -18,8 +18,6 @@
 // Checked bit for bit against the host builder (tree, boxes, order) in tests/test_gpu_parity.py.
 #include <hip/hip_runtime.h>
 
-#include <thread>
-
 #include <algorithm>
 #include <cfloat>
 #include <cstddef>
@@ -27,7 +25,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "host_scene.hpp"
@@ -37,8 +38,8 @@ namespace rayca {
 namespace {
 
 constexpr int kB = 256;
-// k_build_level runs with 256 threads per node, and with 1024 on the levels that hold nodes above kBig primitives: their
-// partition is one workgroup's loop over the node's range (levels 0-4 of the atrium: 9.0 ms of the 14 with 256 threads)
+// k_build_level runs with 256 threads per node, and with 1024 on the levels that may still hold nodes above kBig primitives.  Such a node only takes
+// its decision there (k_bin_big bins it, k_big_* partition it): the wider workgroup serves those levels' other nodes, of up to kBig primitives, which it bins and partitions whole.
 constexpr int kBuildLevelMaxBlock = 1024;
 #ifndef RAYCA_KBIG
 #define RAYCA_KBIG 16384
@@ -47,6 +48,7 @@ constexpr uint32_t kBig = RAYCA_KBIG;    // nodes above this size are binned by 
 constexpr uint32_t kChunk = 4096;
 constexpr uint32_t kBinWords = 3 * 64 * 7;  // per node: count + min xyz + max xyz for 64 bins on 3 axes
 constexpr uint32_t kSeq = 16;  // subtrees of at most this many primitives are finished by ONE wave (k_build_small)
+constexpr uint32_t kLevelBatch = 8;   // levels the host queues between two read-backs of the level records
 
 // The host builder's BuildNode, field for field (host_scene.hpp: two points with w = 1, range, children): the finished
 // array is copied straight into the host arena.
@@ -60,14 +62,9 @@ static_assert(sizeof(DNode) == sizeof(BuildNode) && offsetof(DNode, b) == offset
               offsetof(DNode, left) == offsetof(BuildNode, left) && offsetof(DNode, right) == offsetof(BuildNode, right),
               "DNode is downloaded into a std::vector<BuildNode>");
 
-// RAYCA_BIG_PARTITION: the swap partition of a node that is binned by many workgroups (more than kBig primitives) is solved by
-// many workgroups too -- one per kChunk positions, the chunks k_bin_big already works through -- in a handful of small
-// launches per level (k_big_*), instead of by the ONE workgroup that runs the node in k_build_level: that workgroup took
-// 2.4 ms for the atrium's root and the top levels were half of the level loop.  Same destinations (same ranks of holes and
-// fillers), so the same order.
-#ifndef RAYCA_BIG_PARTITION
-#define RAYCA_BIG_PARTITION 1
-#endif
+// The swap partition of a node that is binned by many workgroups (more than kBig primitives) is solved by many workgroups
+// too -- one per kChunk positions, the chunks k_bin_big already works through -- in a handful of small launches per level
+// (k_big_*), not by the ONE workgroup that runs the node in k_build_level.  Same destinations (partition_dest), so the same order.
 struct BigSplit {          // one big node of the current level, by its bin slot
   uint32_t node, axis, ok, nl, n, off, holes;
   uint32_t chunk_first;    // its first entry in the level's chunk list (written when the list was made, a level earlier)
@@ -126,6 +123,33 @@ __device__ __forceinline__ uint32_t block_prefix(bool flag, uint32_t* wave_tot, 
   }
   total = tot;
   return before + in_wave;
+}
+
+// ---- the swap partition, solved: the one statement of where an element goes, for the one-workgroup form (k_build_level) and the
+// chunked form (k_big_*).  A node's range is [off, off + n), positions p count from its start; left-class = centroid on axis `cax`
+// below `pos`, nl of them.  Holes are the right-class elements below nl, fillers the left-class elements from nl on: K of each, ranked
+// (rank, hole_pos, filler_pos) by the caller.  Everything right of the plane: the loop rotates the range (first to the end, the others down by one).
+__device__ __forceinline__ uint32_t rotate_dest(uint32_t p, uint32_t n) { return p == 0u ? n - 1u : p - 1u; }
+// Where primitive `id` at position p ends up (nl < n: with everything left of the plane the loop never swaps).
+__device__ __forceinline__ uint32_t partition_dest(const BuildState& st, const float* cax, float pos, uint32_t off, uint32_t p, uint32_t id, uint32_t nl, uint32_t n, uint32_t K) {
+  if (nl == 0u) return rotate_dest(p, n);
+  const bool left = cax[id] < pos;
+  if (p < nl) {
+    if (left) return p;
+    const uint32_t k = st.rank[off + p];   // the k-th hole: to the end, or to one below the (k-1)-th filler
+    return k == 0 ? n - 1 : st.filler_pos[off + k - 1] - 1;
+  }
+  if (left) return st.hole_pos[off + st.rank[off + p]];         // a filler: to its hole
+  if (p == nl) return (K == 0 ? n : st.filler_pos[off + K - 1]) - 1;   // acts as hole K+1
+  return p - 1;
+}
+// The children's boxes, [child][min / max][xyz], encoded: one position's primitive taken in.
+__device__ __forceinline__ void child_boxes_add(const BuildState& st, uint32_t (*box)[2][3], uint32_t p, uint32_t id, uint32_t nl) {
+  const uint32_t child = p < nl ? 0u : 1u;
+  for (int c = 0; c < 3; ++c) {
+    atomicMin(&box[child][0][c], enc(st.bmin[c][id]));
+    atomicMax(&box[child][1][c], enc(st.bmax[c][id]));
+  }
 }
 
 __device__ __forceinline__ void init_bins(const DNode& nd, uint32_t (*s_cnt)[64], uint32_t (*s_min)[64][3], uint32_t (*s_max)[64][3], float (*s_pos)[64]) {
@@ -366,7 +390,6 @@ __global__ __launch_bounds__(kBuildLevelMaxBlock) void k_build_level(BuildState 
     s_left = 0;
   }
   __syncthreads();
-#if RAYCA_BIG_PARTITION
   if (nd_big != RAYCA_NONE) {  // the decision only: k_big_* partition the range and make the children
     if (tid == 0) {
       BigSplit& d = st.splits[level & 1u][nd_big];
@@ -380,7 +403,6 @@ __global__ __launch_bounds__(kBuildLevelMaxBlock) void k_build_level(BuildState 
     }
     return;
   }
-#endif
   if (!s_split_ok) return;  // a leaf: primitives stay as they are
 
   // ---- 3. the swap partition, solved ------------------------------------------------------------------------------
@@ -395,7 +417,7 @@ __global__ __launch_bounds__(kBuildLevelMaxBlock) void k_build_level(BuildState 
     // everything on one side.  All left: the loop never swaps.  All right: it rotates the range (first element to
     // the end, the others down by one) -- and the node stays a leaf either way (blas.rs:291-293).
     if (nl == 0 && n > 1) {
-      for (uint32_t s = tid; s < n; s += blockDim.x) st.tmp[off + (s == 0 ? n - 1 : s - 1)] = st.order[off + s];
+      for (uint32_t s = tid; s < n; s += blockDim.x) st.tmp[off + rotate_dest(s, n)] = st.order[off + s];
       __syncthreads();
       for (uint32_t s = tid; s < n; s += blockDim.x) st.order[off + s] = st.tmp[off + s];
     }
@@ -433,22 +455,7 @@ __global__ __launch_bounds__(kBuildLevelMaxBlock) void k_build_level(BuildState 
   __syncthreads();
   for (uint32_t p = tid; p < n; p += blockDim.x) {
     const uint32_t id = st.order[off + p];
-    const bool left = cax[id] < pos;
-    uint32_t dest;
-    if (p < nl) {
-      if (left) dest = p;
-      else {
-        const uint32_t k = st.rank[off + p];
-        dest = k == 0 ? n - 1 : st.filler_pos[off + k - 1] - 1;
-      }
-    } else if (left) {
-      dest = st.hole_pos[off + st.rank[off + p]];
-    } else if (p == nl) {
-      dest = (K == 0 ? n : st.filler_pos[off + K - 1]) - 1;
-    } else {
-      dest = p - 1;
-    }
-    st.tmp[off + dest] = id;
+    st.tmp[off + partition_dest(st, cax, pos, off, p, id, nl, n, K)] = id;
   }
   __syncthreads();
   for (uint32_t p = tid; p < n; p += blockDim.x) st.order[off + p] = st.tmp[off + p];
@@ -458,19 +465,11 @@ __global__ __launch_bounds__(kBuildLevelMaxBlock) void k_build_level(BuildState 
     s_red[child][mm][c] = mm ? enc(-FLT_MAX) : enc(FLT_MAX);
   }
   __syncthreads();
-  for (uint32_t p = tid; p < n; p += blockDim.x) {
-    const uint32_t id = st.tmp[off + p];
-    const uint32_t child = p < nl ? 0u : 1u;
-    for (int c = 0; c < 3; ++c) {
-      atomicMin(&s_red[child][0][c], enc(st.bmin[c][id]));
-      atomicMax(&s_red[child][1][c], enc(st.bmax[c][id]));
-    }
-  }
+  for (uint32_t p = tid; p < n; p += blockDim.x) child_boxes_add(st, s_red, p, st.tmp[off + p], nl);
   __syncthreads();
   if (tid == 0) make_children(st, node_id, off, n, nl, &s_red[0][0][0], next, next_count, next_chunks, level);
 }
 
-#if RAYCA_BIG_PARTITION
 // ---- the partition of the big nodes, one workgroup per chunk (the level's chunk list; lc[1] entries, lc[2] slots) ---------------
 __device__ __forceinline__ bool big_job(const BuildState& st, const uint2* chunks, const uint32_t* lc, uint32_t level, uint2& job, BigSplit*& d, uint32_t& begin, uint32_t& end) {
   if (blockIdx.x >= lc[1]) return false;   // (block-uniform)
@@ -585,26 +584,7 @@ __global__ __launch_bounds__(kB) void k_big_scatter(BuildState st, const uint2* 
   const float pos = d->pos;
   for (uint32_t p = begin + threadIdx.x; p < end; p += blockDim.x) {
     const uint32_t id = st.order[off + p];
-    uint32_t dest;
-    if (nl == 0u) {   // everything right: the loop rotates the range (first element to the end, the others down by one)
-      dest = p == 0u ? n - 1u : p - 1u;
-    } else {
-      const bool left = cax[id] < pos;
-      if (p < nl) {
-        if (left) dest = p;
-        else {
-          const uint32_t k = st.rank[off + p];
-          dest = k == 0 ? n - 1 : st.filler_pos[off + k - 1] - 1;
-        }
-      } else if (left) {
-        dest = st.hole_pos[off + st.rank[off + p]];
-      } else if (p == nl) {
-        dest = (K == 0 ? n : st.filler_pos[off + K - 1]) - 1;
-      } else {
-        dest = p - 1;
-      }
-    }
-    st.tmp[off + dest] = id;
+    st.tmp[off + partition_dest(st, cax, pos, off, p, id, nl, n, K)] = id;
   }
 }
 // back into the order, and the children's boxes
@@ -622,13 +602,7 @@ __global__ __launch_bounds__(kB) void k_big_finish(BuildState st, const uint2* c
   for (uint32_t p = begin + threadIdx.x; p < end; p += blockDim.x) {
     const uint32_t id = st.tmp[off + p];
     st.order[off + p] = id;
-    if (nl != 0u) {
-      const uint32_t child = p < nl ? 0u : 1u;
-      for (int c = 0; c < 3; ++c) {
-        atomicMin(&s_red[child][0][c], enc(st.bmin[c][id]));
-        atomicMax(&s_red[child][1][c], enc(st.bmax[c][id]));
-      }
-    }
+    if (nl != 0u) child_boxes_add(st, s_red, p, id, nl);
   }
   __syncthreads();
   if (nl != 0u && threadIdx.x < 12) {
@@ -645,7 +619,6 @@ __global__ void k_big_children(BuildState st, uint32_t* next, uint32_t* next_cou
   if (!d.ok || d.nl == 0u || d.nl == d.n) return;   // a leaf (blas.rs:291-293 for the one-sided cases)
   make_children(st, d.node, d.off, d.n, d.nl, &d.box[0][0][0], next, next_count, next_chunks, level);
 }
-#endif
 
 // A subtree of at most kSeq primitives, finished by one WAVE: the reference's recursion as it stands -- every candidate
 // plane evaluated by a loop over the primitives (evaluate_sah, blas.rs:64-89: the same counts and boxes the bins give,
@@ -828,16 +801,6 @@ __global__ __launch_bounds__(64) void k_build_small(BuildState st, uint32_t n_sm
   }
 }
 
-#define HB_TRY(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t e__ = (expr);                                                               \
-    if (e__ != hipSuccess) {                                                               \
-      err = std::string("gpu bvh build: ") + #expr + ": " + hipGetErrorString(e__);        \
-      cleanup();                                                                           \
-      return false;                                                                        \
-    }                                                                                      \
-  } while (0)
-
 }  // namespace
 
 const void* gpu_builder_any_kernel() { return reinterpret_cast<const void*>(k_build_small); }
@@ -999,99 +962,129 @@ __global__ void k_layout_emit(LayoutState ls, DevNode* out, uint32_t first, uint
   }
 }
 
-// a finished tree that stays on the device until its layout has been written (BlasDeviceTree::handle)
+// What a build holds on its device -- the pool every buffer is carved from, the stream it runs on -- released here and nowhere else.
+// A finished tree that stays on the device until its layout is written (BlasDeviceTree::handle) is this object, with the layout's state.
 struct KeptTree {
   void* pool = nullptr;
   hipStream_t stream = nullptr;
-  bool own_stream = true;
+  bool own_stream = true;   // (a caller's stream is only drained here, never destroyed)
   int device = 0;
   LayoutState ls{};
-};
-
-// BlasBuildFn: see host_scene.hpp
-bool gpu_build_blas(const BlasBuildInput& in, std::vector<uint32_t>& order, std::vector<BuildNode>& arena, std::string& err, BlasDeviceTree* keep) {
-  const uint32_t n = in.count;
-  // One device allocation, carved up here, and a stream of its own: a RAYCA_BUILDER_SAH scene builds two trees at the same
-  // time from two host threads (host_scene.cpp), and each build is a chain of small launches with a counter read-back per
-  // level -- on the null stream the two chains would queue behind each other, and two dozen hipMalloc / hipFree pairs cost
-  // more than some of the levels.
-  void* pool = nullptr;
-  hipStream_t stream = static_cast<hipStream_t>(in.stream);
-  const bool own_stream = stream == nullptr;   // (a caller's stream is only drained here, never destroyed)
-  auto cleanup = [&] {
+  KeptTree() = default;
+  KeptTree(const KeptTree&) = delete; KeptTree& operator=(const KeptTree&) = delete;
+  ~KeptTree() {
     if (stream) {
       (void)hipStreamSynchronize(stream);
       if (own_stream) (void)hipStreamDestroy(stream);
-      stream = nullptr;
     }
     if (pool) (void)hipFree(pool);
-    pool = nullptr;
-  };
-  static const bool verbose = getenv("RAYCA_BUILD_TIMING") != nullptr;
-  auto tp = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!verbose) return;
-    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
+
+namespace {
+
+// The pieces of the pool, 256-B aligned: take() states a piece's size and the pointer that is to point at it -- offsets first --
+// and place() fills the pointers in once the pool exists.
+struct PoolPlan {
+  std::vector<std::pair<void*, size_t>> pieces;   // (where the pointer to fill is, offset of its piece)
+  size_t bytes = 0;
+  template <typename T> void take(T*& p, size_t count) {
+    pieces.push_back({static_cast<void*>(&p), bytes});
+    bytes += (std::max<size_t>(sizeof(T) * count, 4) + 255) / 256 * 256;
+  }
+  void place(void* pool) const {
+    for (const auto& pc : pieces) {
+      char* at = static_cast<char*>(pool) + pc.second;
+      std::memcpy(pc.first, &at, sizeof at);   // (the pointer at pc.first, whatever it points to)
+    }
+  }
+};
+
+// What the steps of one gpu_build_blas share.  A step returns true, or false with `err` filled; whatever way the build ends, the
+// owner's destructor is what releases the device's side of it.
+struct BlasBuild {
+  const BlasBuildInput& in;
+  std::vector<uint32_t>& order; std::vector<BuildNode>& arena; std::string& err;   // (the caller's)
+  BlasDeviceTree* keep;
+  BuildState st{};
+  uint32_t* level_counts = nullptr;            // [level][open nodes, chunks, big slots, -]
+  uint32_t* lists[2] = {nullptr, nullptr};     // the open nodes of this level / the next level (level parity)
+  uint32_t max_slots = 0, max_chunks = 0;      // big nodes / chunks of big nodes a level can hold
+  uint32_t levels_run = 0, blocks_run = 0, n_active = 0, node_count = 0;
+  bool big_possible = false;   // (a big node only has big ancestors: once a level has none, no later level has)
+  std::vector<uint32_t> lc_host;
+  StagedCopier staged;             // (page-locked staging blocks: staging.hpp)
+  std::unique_ptr<KeptTree> own;   // (declared last: released first)
+  std::chrono::steady_clock::time_point tp = std::chrono::steady_clock::now();
+  bool fail(const std::string& what) { err = "gpu bvh build: " + what; return false; }
+  static bool verbose() { static const bool v = getenv("RAYCA_BUILD_TIMING") != nullptr; return v; }
+  void lap(const char* what) {
+    if (!verbose()) return;
+    if (own && own->stream) (void)hipStreamSynchronize(own->stream);
     const auto now = std::chrono::steady_clock::now();
     fprintf(stderr, "[rayca build]     gpu %-22s %7.2f ms\n", what, std::chrono::duration<float, std::milli>(now - tp).count());
     tp = now;
-  };
-  HB_TRY(hipSetDevice((int)in.device));
-  if (own_stream) HB_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  const uint32_t max_slots = n / kBig + 2, max_chunks = n / kChunk + max_slots + 2;
-  size_t pool_bytes = 0;
-  auto reserve = [&](size_t bytes) {  // offsets first, pointers once the pool exists; 256-B aligned pieces
-    const size_t at = pool_bytes;
-    pool_bytes += (std::max<size_t>(bytes, 4) + 255) / 256 * 256;
-    return at;
-  };
-  size_t off_f[9], off_u[9];
-  for (int i = 0; i < 9; ++i) off_f[i] = reserve(sizeof(float) * n);
-  for (int i = 0; i < 9; ++i) off_u[i] = reserve(sizeof(uint32_t) * ((size_t)n + 2));
-  const size_t off_nodes = reserve(sizeof(DNode) * (2 * (size_t)n + 2)), off_big = reserve(sizeof(uint32_t) * (2 * (size_t)n + 2)), off_counts = reserve(64), off_levels = reserve(sizeof(uint32_t) * 4u * ((size_t)in.max_depth + 2u)), off_gbins = reserve((size_t)max_slots * kBinWords * 4);
-  const size_t off_chunks[2] = {reserve((size_t)max_chunks * sizeof(uint2)), reserve((size_t)max_chunks * sizeof(uint2))};
-  const size_t off_splits = reserve(2 * (size_t)max_slots * sizeof(BigSplit)), off_chcnt = reserve(2 * (size_t)max_chunks * sizeof(uint32_t)),
-               off_chbase = reserve(2 * (size_t)max_chunks * sizeof(uint32_t));
-  size_t off_layout[8] = {};
-  if (keep)
-    for (size_t& o : off_layout) o = reserve(sizeof(uint32_t) * (2 * (size_t)n + 2));
-  HB_TRY(hipMalloc(&pool, pool_bytes));
-  char* base = static_cast<char*>(pool);
-  BuildState st{};
-  float* f[9];
-  for (int i = 0; i < 9; ++i) f[i] = reinterpret_cast<float*>(base + off_f[i]);
-  const float* src[9] = {in.cent[0], in.cent[1], in.cent[2], in.bmin[0], in.bmin[1], in.bmin[2], in.bmax[0], in.bmax[1], in.bmax[2]};
-  StagedCopier staged;   // (page-locked staging blocks: staging.hpp)
-  for (int i = 0; i < 9; ++i) HB_TRY(staged.copy(f[i], src[i], sizeof(float) * n, stream));
-  for (int c = 0; c < 3; ++c) {
-    st.cent[c] = f[c];
-    st.bmin[c] = f[3 + c];
-    st.bmax[c] = f[6 + c];
   }
-  uint32_t* u[9];
-  for (int i = 0; i < 9; ++i) u[i] = reinterpret_cast<uint32_t*>(base + off_u[i]);
-  st.order = u[0]; st.tmp = u[1]; st.rank = u[2]; st.hole_pos = u[3]; st.filler_pos = u[4];
-  uint32_t* lists[2] = {u[5], u[6]};
-  st.small_nodes = u[7];
-  st.small_levels = u[8];
-  st.nodes = reinterpret_cast<DNode*>(base + off_nodes);
-  st.big = reinterpret_cast<uint32_t*>(base + off_big);
-  st.node_count = reinterpret_cast<uint32_t*>(base + off_counts);
-  st.chunk_count = st.node_count + 3;
-  st.slot_count = st.node_count + 4;
-  st.gbins = reinterpret_cast<uint32_t*>(base + off_gbins);
-  for (int i = 0; i < 2; ++i) st.chunks[i] = reinterpret_cast<uint2*>(base + off_chunks[i]);
-  for (int i = 0; i < 2; ++i) st.splits[i] = reinterpret_cast<BigSplit*>(base + off_splits) + (size_t)i * max_slots;
-  st.ch_cnt = reinterpret_cast<uint32_t*>(base + off_chcnt);
-  st.ch_base = reinterpret_cast<uint32_t*>(base + off_chbase);
-  st.small_count = st.node_count + 2;
-  uint32_t* const level_counts = reinterpret_cast<uint32_t*>(base + off_levels);   // [level][open nodes, chunks, big slots, -]
-  st.seed_origin = in.seed_origin ? 1u : 0u;
-  st.max_depth = in.max_depth;
+};
 
+// (inside a step: needs the step's `BlasBuild& b`, and returns false from the step with the error text)
+#define HB_TRY(expr)                                                                        \
+  do {                                                                                      \
+    const hipError_t e__ = (expr);                                                          \
+    if (e__ != hipSuccess) return b.fail(std::string(#expr ": ") + hipGetErrorString(e__)); \
+  } while (0)
+
+// One device allocation, carved up here, and a stream of its own: a RAYCA_BUILDER_SAH scene builds two trees at the same time from
+// two host threads (host_scene.cpp), each a chain of small launches with a read-back per batch of levels -- on the null stream the two
+// chains would queue behind each other, and two dozen hipMalloc / hipFree pairs cost more than some levels.  The SoA goes up behind it.
+bool reserve_and_upload(BlasBuild& b) {
+  const BlasBuildInput& in = b.in;
+  BuildState& st = b.st;
+  const uint32_t n = in.count;
+  b.own = std::make_unique<KeptTree>();
+  KeptTree& own = *b.own;
+  own.device = (int)in.device;
+  own.stream = static_cast<hipStream_t>(in.stream); own.own_stream = own.stream == nullptr;
+  HB_TRY(hipSetDevice((int)in.device));
+  if (own.own_stream) HB_TRY(hipStreamCreateWithFlags(&own.stream, hipStreamNonBlocking));
+  b.max_slots = n / kBig + 2; b.max_chunks = n / kChunk + b.max_slots + 2;
+  const size_t per_prim = (size_t)n + 2, per_node = 2 * (size_t)n + 2;
+  const float* const* src[3] = {in.cent, in.bmin, in.bmax};
+  const float** soa[3] = {st.cent, st.bmin, st.bmax};
+  PoolPlan plan;
+  for (int i = 0; i < 9; ++i) plan.take(soa[i / 3][i % 3], n);
+  for (uint32_t** p : {&st.order, &st.tmp, &st.rank, &st.hole_pos, &st.filler_pos, &b.lists[0], &b.lists[1], &st.small_nodes, &st.small_levels})
+    plan.take(*p, per_prim);
+  plan.take(st.nodes, per_node);
+  plan.take(st.big, per_node);
+  plan.take(st.node_count, 16);   // the build's counters: [0] nodes, [2] small subtrees, [3] / [4] chunks and slots outside the levels
+  plan.take(b.level_counts, 4u * ((size_t)in.max_depth + 2u));
+  plan.take(st.gbins, (size_t)b.max_slots * kBinWords);
+  for (uint2** p : {&st.chunks[0], &st.chunks[1]}) plan.take(*p, b.max_chunks);
+  plan.take(st.splits[0], 2 * (size_t)b.max_slots);   // both parities: [1] follows [0]
+  for (uint32_t** p : {&st.ch_cnt, &st.ch_base}) plan.take(*p, 2 * (size_t)b.max_chunks);
+  if (b.keep) {   // the layout's arrays, per node
+    for (uint32_t** p : {&own.ls.parent, &own.ls.arrived, &own.ls.index, &own.ls.leafed}) plan.take(*p, per_node);
+    plan.take(own.ls.rec, (per_node + 63) / 64 * 64);   // (whole KiB: four words per node, each word's share a 256-B multiple)
+  }
+  HB_TRY(hipMalloc(&own.pool, plan.bytes));
+  plan.place(own.pool);
+  st.splits[1] = st.splits[0] + b.max_slots;
+  st.small_count = st.node_count + 2; st.chunk_count = st.node_count + 3; st.slot_count = st.node_count + 4;   // (the last two: outside the levels only)
+  st.seed_origin = in.seed_origin ? 1u : 0u; st.max_depth = in.max_depth;
+  for (int i = 0; i < 9; ++i) HB_TRY(b.staged.copy(const_cast<float*>(soa[i / 3][i % 3]), src[i / 3][i % 3], sizeof(float) * n, own.stream));
+  return true;
+}
+
+// The root: its node, its big slot and chunks, level record 0, the identity order.
+bool seed_root(BlasBuild& b) {
+  const BlasBuildInput& in = b.in;
+  const BuildState& st = b.st;
+  const hipStream_t stream = b.own->stream;
+  const uint32_t n = in.count;
   std::vector<uint32_t> ident(n);
   for (uint32_t i = 0; i < n; ++i) ident[i] = i;
-  HB_TRY(staged.copy(st.order, ident.data(), sizeof(uint32_t) * n, stream));
+  HB_TRY(b.staged.copy(st.order, ident.data(), sizeof(uint32_t) * n, stream));
   DNode root{};
   for (int c = 0; c < 3; ++c) {
     root.a[c] = in.root_min[c];
@@ -1105,168 +1098,175 @@ bool gpu_build_blas(const BlasBuildInput& in, std::vector<uint32_t>& order, std:
   const uint32_t init[5] = {1u, 0u, 0u, 0u, 0u};
   HB_TRY(hipMemcpyAsync(st.node_count, init, sizeof init, hipMemcpyHostToDevice, stream));
   const uint32_t zero = 0;
-  HB_TRY(hipMemcpyAsync(lists[0], &zero, 4, hipMemcpyHostToDevice, stream));  // level 0: the root
+  HB_TRY(hipMemcpyAsync(b.lists[0], &zero, 4, hipMemcpyHostToDevice, stream));  // level 0: the root
   // the level records: all zero but the root's {one open node, its chunks, one big slot}
-  HB_TRY(hipMemsetAsync(level_counts, 0, sizeof(uint32_t) * 4u * ((size_t)in.max_depth + 2u), stream));
-  HB_TRY(hipMemsetAsync(st.splits[0], 0, 2 * (size_t)max_slots * sizeof(BigSplit), stream));   // (the root's chunk_first = 0)
+  HB_TRY(hipMemsetAsync(b.level_counts, 0, sizeof(uint32_t) * 4u * ((size_t)in.max_depth + 2u), stream));
+  HB_TRY(hipMemsetAsync(st.splits[0], 0, 2 * (size_t)b.max_slots * sizeof(BigSplit), stream));   // (the root's chunk_first = 0)
   const uint32_t root_chunks = n > kBig ? (n + kChunk - 1) / kChunk : 0u;
   const uint32_t record0[4] = {n > 0 ? 1u : 0u, root_chunks, n > kBig ? 1u : 0u, 0u};
-  HB_TRY(hipMemcpyAsync(level_counts, record0, sizeof record0, hipMemcpyHostToDevice, stream));
+  HB_TRY(hipMemcpyAsync(b.level_counts, record0, sizeof record0, hipMemcpyHostToDevice, stream));
   std::vector<uint2> rc(root_chunks);
   for (uint32_t k = 0; k < root_chunks; ++k) rc[k] = make_uint2(0u, k);
   if (root_chunks) HB_TRY(hipMemcpyAsync(st.chunks[0], rc.data(), sizeof(uint2) * root_chunks, hipMemcpyHostToDevice, stream));
   HB_TRY(hipStreamSynchronize(stream));  // (the sources above are locals and caller memory: staged before they go away)
-  staged.finish();
-
-  lap("alloc + upload");
-  // Levels: every level's record {open nodes, chunks, big slots} lives on the device (level_counts, zeroed once); the
-  // kernels of level L read record L for their bounds and count into record L + 1.  The host queues kLevelBatch levels at
-  // a time with grids that bound the work (an open node holds more than kSeq primitives, a level has at most 2^L nodes)
-  // and reads the records back once per batch -- round 2 read three counters back after EVERY level: 19 stream
-  // synchronisations for the atrium, a third of the build.
-  constexpr uint32_t kLevelBatch = 8;
-  uint32_t levels_run = 0, blocks_run = 0;
-  uint32_t n_active = n > 0 ? 1u : 0u;
-  bool big_possible = n > kBig;   // (a big node only has big ancestors: once a level has none, no later level has)
-  std::vector<uint32_t> lc_host;
-  for (uint32_t level0 = 0; level0 < in.max_depth && n_active > 0; level0 += kLevelBatch) {
-    const uint32_t batch = std::min<uint32_t>(kLevelBatch, in.max_depth - level0);
-    const auto lt0 = std::chrono::steady_clock::now();
-    for (uint32_t level = level0; level < level0 + batch; ++level) {
-      const uint32_t* lc = level_counts + 4u * level;
-      uint32_t* lc_next = level_counts + 4u * (level + 1u);
-      const uint64_t by_depth = level < 31u ? (1ull << level) : ~0ull;
-      const uint32_t bound = (uint32_t)std::min<uint64_t>(by_depth, (uint64_t)n / (kSeq + 1u) + 1u);
-      BuildState sl = st;
-      sl.chunk_count = lc_next + 1;
-      sl.slot_count = lc_next + 2;
-      if (big_possible) {  // big nodes of this level: bins by many workgroups
-        hipLaunchKernelGGL(k_bin_init, dim3((std::min<uint64_t>(by_depth, max_slots) * 3 * 64 + kB - 1) / kB), dim3(kB), 0, stream, sl, lc);
-        hipLaunchKernelGGL(k_bin_big, dim3((uint32_t)std::min<uint64_t>(by_depth * ((n + kChunk - 1) / kChunk), max_chunks)), dim3(kB), 0, stream, sl, sl.chunks[level & 1], lc);
-        HB_TRY(hipGetLastError());
-      }
-      hipLaunchKernelGGL(k_build_level, dim3(bound), dim3(big_possible ? kBuildLevelMaxBlock : kB), 0, stream, sl, lists[level & 1], lists[(level + 1) & 1], lc_next,
-                         sl.chunks[(level + 1) & 1], level, lc);
-      HB_TRY(hipGetLastError());
-#if RAYCA_BIG_PARTITION
-      if (big_possible) {  // the big nodes' partitions and children, by their chunks (k_build_level has left the decisions)
-        const dim3 cgrid((uint32_t)std::min<uint64_t>(by_depth * ((n + kChunk - 1) / kChunk), max_chunks)), sgrid((uint32_t)((std::min<uint64_t>(by_depth, max_slots) + 63u) / 64u));
-        const uint2* cl = sl.chunks[level & 1];
-        hipLaunchKernelGGL(k_big_count, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
-        hipLaunchKernelGGL(k_big_classify, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
-        hipLaunchKernelGGL(k_big_scan, sgrid, dim3(64), 0, stream, sl, lc, level);
-        hipLaunchKernelGGL(k_big_rank, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
-        hipLaunchKernelGGL(k_big_scatter, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
-        hipLaunchKernelGGL(k_big_finish, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
-        hipLaunchKernelGGL(k_big_children, sgrid, dim3(64), 0, stream, sl, lists[(level + 1) & 1], lc_next, sl.chunks[(level + 1) & 1], level, lc);
-        HB_TRY(hipGetLastError());
-      }
-#endif
-    }
-    lc_host.resize(4u * (batch + 1u));
-    HB_TRY(hipMemcpyAsync(lc_host.data(), level_counts + 4u * level0, sizeof(uint32_t) * lc_host.size(), hipMemcpyDeviceToHost, stream));
-    HB_TRY(hipStreamSynchronize(stream));
-    for (uint32_t k = 0; k < batch; ++k) {
-      if (lc_host[4 * k] == 0) break;
-      ++levels_run;
-      blocks_run += lc_host[4 * k];
-    }
-    for (uint32_t k = 1; k <= batch; ++k)
-      if (lc_host[4 * k + 2] > max_slots || lc_host[4 * k + 1] > max_chunks) {
-        err = "gpu bvh build: big-node bookkeeping overflow";
-        cleanup();
-        return false;
-      }
-    n_active = lc_host[4 * batch];
-    big_possible = big_possible && lc_host[4 * batch + 1] != 0;
-    if (verbose && getenv("RAYCA_BUILD_LEVELS"))
-      fprintf(stderr, "[rayca build]     levels %2u..%2u: %7.2f ms, %u open nodes left\n", level0, level0 + batch - 1,
-              std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - lt0).count(), n_active);
-  }
-  lap("levels");
-  uint32_t n_small = 0;
-  HB_TRY(hipMemcpyAsync(&n_small, st.small_count, 4, hipMemcpyDeviceToHost, stream));
-  HB_TRY(hipStreamSynchronize(stream));
-  if (verbose) fprintf(stderr, "[rayca build]   gpu: %u primitives, %u levels, %u node blocks, %u small subtrees\n", n, levels_run, blocks_run, n_small);
-  if (n_small) {
-    hipLaunchKernelGGL(k_build_small, dim3(n_small), dim3(64), 0, stream, st, n_small);
-    HB_TRY(hipGetLastError());
-  }
-  lap("small subtrees");
-  uint32_t node_count = 0;
-  HB_TRY(hipMemcpyAsync(&node_count, st.node_count, 4, hipMemcpyDeviceToHost, stream));
-  HB_TRY(hipStreamSynchronize(stream));
-  if (keep) {  // the tree stays here: work out the layout's size and stack need, hand the pool over
-    LayoutState ls{};
-    ls.nodes = st.nodes;
-    ls.node_count = node_count;
-    uint32_t** parts[4] = {&ls.parent, &ls.arrived, &ls.index, &ls.leafed};
-    for (int i = 0; i < 4; ++i) *parts[i] = reinterpret_cast<uint32_t*>(base + off_layout[i]);
-    ls.rec = reinterpret_cast<uint4*>(base + off_layout[4]);   // (four words per node: off_layout[4..7], contiguous and 256-B aligned)
-    ls.node_cost = in.layout_node_cost;
-    ls.leaf_max = std::min<uint32_t>(std::max<uint32_t>(in.layout_leaf_max, 1u), kLeafMaxPrims);
-    const dim3 grid((node_count + kB - 1) / kB), block(kB);
-    hipLaunchKernelGGL(k_layout_parents, grid, block, 0, stream, ls);
-    hipLaunchKernelGGL(k_layout_sizes, grid, block, 0, stream, ls);
-    hipLaunchKernelGGL(k_layout_index, grid, block, 0, stream, ls);
-    HB_TRY(hipGetLastError());
-    uint32_t root_rec[4] = {0, 0, 0, 0};
-    HB_TRY(hipMemcpyAsync(root_rec, ls.rec, sizeof root_rec, hipMemcpyDeviceToHost, stream));
-    order.resize(n);
-    HB_TRY(staged.copy_back(order.data(), st.order, sizeof(uint32_t) * n, stream));   // (through the staging blocks, like the uploads)
-    HB_TRY(hipStreamSynchronize(stream));
-    staged.finish();
-    lap("layout sizes + order");
-    KeptTree* kt = new KeptTree();
-    kt->pool = pool;
-    kt->stream = stream;
-    kt->own_stream = own_stream;
-    kt->device = (int)in.device;
-    kt->ls = ls;
-    pool = nullptr;     // (cleanup() below must not release what the handle now owns)
-    stream = nullptr;
-    keep->handle = kt;
-    keep->node_count = root_rec[0];
-    keep->need = root_rec[1];
-    return true;
-  }
-  arena.resize(node_count);   // DNode == BuildNode (asserted above): no conversion pass
-  order.resize(n);
-  HB_TRY(staged.copy_back(static_cast<void*>(arena.data()), st.nodes, sizeof(DNode) * node_count, stream));
-  HB_TRY(staged.copy_back(order.data(), st.order, sizeof(uint32_t) * n, stream));
-  HB_TRY(hipStreamSynchronize(stream));
-  staged.finish();
-  lap("download");
-  cleanup();
-  lap("free");
+  b.staged.finish();
+  b.n_active = n > 0 ? 1u : 0u; b.big_possible = n > kBig;
+  b.lap("alloc + upload");
   return true;
 }
 
-void gpu_release_tree(void* tree) {
-  KeptTree* kt = static_cast<KeptTree*>(tree);
-  if (!kt) return;
-  (void)hipSetDevice(kt->device);
-  if (kt->stream) {
-    (void)hipStreamSynchronize(kt->stream);
-    if (kt->own_stream) (void)hipStreamDestroy(kt->stream);
+// ONE level's launches, with grids that bound the level's work (an open node holds more than kSeq primitives, a level has at
+// most 2^L nodes): the kernels of level L read record L for their counts and count into record L + 1.
+bool queue_level(BlasBuild& b, uint32_t level) {
+  const hipStream_t stream = b.own->stream;
+  const uint32_t n = b.in.count, max_slots = b.max_slots, max_chunks = b.max_chunks;
+  const uint32_t* lc = b.level_counts + 4u * level;
+  uint32_t* lc_next = b.level_counts + 4u * (level + 1u);
+  const uint64_t by_depth = level < 31u ? (1ull << level) : ~0ull;
+  const uint32_t bound = (uint32_t)std::min<uint64_t>(by_depth, (uint64_t)n / (kSeq + 1u) + 1u);
+  BuildState sl = b.st;
+  sl.chunk_count = lc_next + 1; sl.slot_count = lc_next + 2;
+  if (b.big_possible) {  // big nodes of this level: bins by many workgroups
+    hipLaunchKernelGGL(k_bin_init, dim3((std::min<uint64_t>(by_depth, max_slots) * 3 * 64 + kB - 1) / kB), dim3(kB), 0, stream, sl, lc);
+    hipLaunchKernelGGL(k_bin_big, dim3((uint32_t)std::min<uint64_t>(by_depth * ((n + kChunk - 1) / kChunk), max_chunks)), dim3(kB), 0, stream, sl, sl.chunks[level & 1], lc);
+    HB_TRY(hipGetLastError());
   }
-  if (kt->pool) (void)hipFree(kt->pool);
-  delete kt;
+  hipLaunchKernelGGL(k_build_level, dim3(bound), dim3(b.big_possible ? kBuildLevelMaxBlock : kB), 0, stream, sl, b.lists[level & 1], b.lists[(level + 1) & 1], lc_next,
+                     sl.chunks[(level + 1) & 1], level, lc);
+  HB_TRY(hipGetLastError());
+  if (b.big_possible) {  // the big nodes' partitions and children, by their chunks (k_build_level has left the decisions)
+    const dim3 cgrid((uint32_t)std::min<uint64_t>(by_depth * ((n + kChunk - 1) / kChunk), max_chunks)), sgrid((uint32_t)((std::min<uint64_t>(by_depth, max_slots) + 63u) / 64u));
+    const uint2* cl = sl.chunks[level & 1];
+    hipLaunchKernelGGL(k_big_count, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
+    hipLaunchKernelGGL(k_big_classify, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
+    hipLaunchKernelGGL(k_big_scan, sgrid, dim3(64), 0, stream, sl, lc, level);
+    hipLaunchKernelGGL(k_big_rank, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
+    hipLaunchKernelGGL(k_big_scatter, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
+    hipLaunchKernelGGL(k_big_finish, cgrid, dim3(kB), 0, stream, sl, cl, lc, level);
+    hipLaunchKernelGGL(k_big_children, sgrid, dim3(64), 0, stream, sl, b.lists[(level + 1) & 1], lc_next, sl.chunks[(level + 1) & 1], level, lc);
+    HB_TRY(hipGetLastError());
+  }
+  return true;
+}
+
+// The records of levels [level0, level0 + batch] read back and checked: what ran, and what the next batch starts from.
+bool read_batch(BlasBuild& b, uint32_t level0, uint32_t batch) {
+  const hipStream_t stream = b.own->stream;
+  std::vector<uint32_t>& lc_host = b.lc_host;
+  lc_host.resize(4u * (batch + 1u));
+  HB_TRY(hipMemcpyAsync(lc_host.data(), b.level_counts + 4u * level0, sizeof(uint32_t) * lc_host.size(), hipMemcpyDeviceToHost, stream));
+  HB_TRY(hipStreamSynchronize(stream));
+  for (uint32_t k = 0; k < batch; ++k) {
+    if (lc_host[4 * k] == 0) break;
+    ++b.levels_run;
+    b.blocks_run += lc_host[4 * k];
+  }
+  for (uint32_t k = 1; k <= batch; ++k)
+    if (lc_host[4 * k + 2] > b.max_slots || lc_host[4 * k + 1] > b.max_chunks) return b.fail("big-node bookkeeping overflow");
+  b.n_active = lc_host[4 * batch];
+  b.big_possible = b.big_possible && lc_host[4 * batch + 1] != 0;
+  return true;
+}
+
+// Levels: every level's record {open nodes, chunks, big slots} lives on the device (level_counts, zeroed once).  The host queues
+// kLevelBatch levels at a time and reads the records once per batch (after EVERY level it was 19 synchronisations for the atrium).
+bool run_levels(BlasBuild& b) {
+  for (uint32_t level0 = 0; level0 < b.in.max_depth && b.n_active > 0; level0 += kLevelBatch) {
+    const uint32_t batch = std::min<uint32_t>(kLevelBatch, b.in.max_depth - level0);
+    const auto lt0 = std::chrono::steady_clock::now();
+    for (uint32_t level = level0; level < level0 + batch; ++level)
+      if (!queue_level(b, level)) return false;
+    if (!read_batch(b, level0, batch)) return false;
+    if (b.verbose() && getenv("RAYCA_BUILD_LEVELS"))
+      fprintf(stderr, "[rayca build]     levels %2u..%2u: %7.2f ms, %u open nodes left\n", level0, level0 + batch - 1,
+              std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - lt0).count(), b.n_active);
+  }
+  b.lap("levels");
+  return true;
+}
+
+// The subtrees of at most kSeq primitives the levels have set aside, one wave each; behind them the arena is complete.
+bool small_subtrees(BlasBuild& b) {
+  const hipStream_t stream = b.own->stream;
+  uint32_t n_small = 0;
+  HB_TRY(hipMemcpyAsync(&n_small, b.st.small_count, 4, hipMemcpyDeviceToHost, stream));
+  HB_TRY(hipStreamSynchronize(stream));
+  if (b.verbose()) fprintf(stderr, "[rayca build]   gpu: %u primitives, %u levels, %u node blocks, %u small subtrees\n", b.in.count, b.levels_run, b.blocks_run, n_small);
+  if (n_small) {
+    hipLaunchKernelGGL(k_build_small, dim3(n_small), dim3(64), 0, stream, b.st, n_small);
+    HB_TRY(hipGetLastError());
+  }
+  b.lap("small subtrees");
+  HB_TRY(hipMemcpyAsync(&b.node_count, b.st.node_count, 4, hipMemcpyDeviceToHost, stream));   // (final now)
+  HB_TRY(hipStreamSynchronize(stream));
+  return true;
+}
+
+// `keep`: the tree stays on the device -- the layout's size and stack need are worked out there, the order comes back, the owner goes to the handle.
+bool layout_sizes_and_order(BlasBuild& b) {
+  const BlasBuildInput& in = b.in;
+  const hipStream_t stream = b.own->stream;
+  LayoutState& ls = b.own->ls;
+  ls.nodes = b.st.nodes; ls.node_count = b.node_count;
+  ls.node_cost = in.layout_node_cost;
+  ls.leaf_max = std::min<uint32_t>(std::max<uint32_t>(in.layout_leaf_max, 1u), kLeafMaxPrims);
+  const dim3 grid((ls.node_count + kB - 1) / kB), block(kB);
+  hipLaunchKernelGGL(k_layout_parents, grid, block, 0, stream, ls);
+  hipLaunchKernelGGL(k_layout_sizes, grid, block, 0, stream, ls);
+  hipLaunchKernelGGL(k_layout_index, grid, block, 0, stream, ls);
+  HB_TRY(hipGetLastError());
+  uint32_t root_rec[4] = {0, 0, 0, 0};
+  HB_TRY(hipMemcpyAsync(root_rec, ls.rec, sizeof root_rec, hipMemcpyDeviceToHost, stream));
+  b.order.resize(in.count);
+  HB_TRY(b.staged.copy_back(b.order.data(), b.st.order, sizeof(uint32_t) * in.count, stream));   // (through the staging blocks, like the uploads)
+  HB_TRY(hipStreamSynchronize(stream));
+  b.staged.finish();
+  b.lap("layout sizes + order");
+  b.keep->handle = b.own.release();
+  b.keep->node_count = root_rec[0]; b.keep->need = root_rec[1];
+  return true;
+}
+
+// No `keep`: the arena and the order come to the host, and the build's device side ends here.
+bool download(BlasBuild& b) {
+  const hipStream_t stream = b.own->stream;
+  b.arena.resize(b.node_count);   // DNode == BuildNode (asserted above): no conversion pass
+  b.order.resize(b.in.count);
+  HB_TRY(b.staged.copy_back(static_cast<void*>(b.arena.data()), b.st.nodes, sizeof(DNode) * b.node_count, stream));
+  HB_TRY(b.staged.copy_back(b.order.data(), b.st.order, sizeof(uint32_t) * b.in.count, stream));
+  HB_TRY(hipStreamSynchronize(stream));
+  b.staged.finish();
+  b.lap("download");
+  b.own.reset();
+  b.lap("free");
+  return true;
+}
+
+}  // namespace
+
+// BlasBuildFn: see host_scene.hpp
+bool gpu_build_blas(const BlasBuildInput& in, std::vector<uint32_t>& order, std::vector<BuildNode>& arena, std::string& err, BlasDeviceTree* keep) {
+  BlasBuild b{in, order, arena, err, keep};
+  return reserve_and_upload(b) && seed_root(b) && run_levels(b) && small_subtrees(b) && (keep ? layout_sizes_and_order(b) : download(b));
+}
+
+void gpu_release_tree(KeptTree* tree) {
+  if (!tree) return;
+  (void)hipSetDevice(tree->device);
+  delete tree;
 }
 
 // Writes the tree's binary nodes into device_nodes[first, first + node_count) -- child indices absolute, leaf references
-// from prim_base on, boxes padded like DevBuilder::put_box pads them -- and releases the tree.
-bool gpu_emit_tree(void* tree, DevNode* device_nodes, uint32_t first, uint32_t prim_base, float pad_rel, float pad_abs, std::string& err) {
-  KeptTree* kt = static_cast<KeptTree*>(tree);
-  if (!kt) { err = "gpu bvh layout: no tree"; return false; }
-  hipError_t e = hipSetDevice(kt->device);
+// from prim_base on, boxes padded like DevBuilder::put_box pads them.  The tree stays its owner's.
+bool gpu_emit_tree(const KeptTree* tree, DevNode* device_nodes, uint32_t first, uint32_t prim_base, float pad_rel, float pad_abs, std::string& err) {
+  if (!tree) { err = "gpu bvh layout: no tree"; return false; }
+  hipError_t e = hipSetDevice(tree->device);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_layout_emit, dim3((kt->ls.node_count + kB - 1) / kB), dim3(kB), 0, kt->stream, kt->ls, device_nodes, first, prim_base, pad_rel, pad_abs);
+    hipLaunchKernelGGL(k_layout_emit, dim3((tree->ls.node_count + kB - 1) / kB), dim3(kB), 0, tree->stream, tree->ls, device_nodes, first, prim_base, pad_rel, pad_abs);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(kt->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(tree->stream);
   if (e != hipSuccess) err = std::string("gpu bvh layout: ") + hipGetErrorString(e);
-  gpu_release_tree(kt);
   return e == hipSuccess;
 }
 

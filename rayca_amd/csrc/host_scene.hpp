@@ -101,20 +101,23 @@ struct HostLight {
   Trs local;  // node-LOCAL transform: what the samplers use (nee.rs:85,133-134)
 };
 
+struct KeptTree;   // a finished tree held on the device (bvh_build.hip); the host code only passes the pointer on
+
 struct HostBlas {
   uint32_t model = 0;
   std::vector<BuildNode> nodes;     // arena, root at 0
   std::vector<uint32_t> prims;      // indices into HostScene::prims (post-build order)
   // A BLAS built by the device builder stays on the device (BlasDeviceTree): `nodes` then holds the root only, and the
-  // device lays its nodes out straight into the scene's node array (DeviceSegment, gpu_emit_tree).
-  void* dev_tree = nullptr;
+  // device lays its nodes out straight into the scene's node array (DeviceSegment, gpu_emit_tree).  A view: the tree belongs
+  // to HostScene::dev_trees.
+  KeptTree* dev_tree = nullptr;
   uint32_t dev_node_count = 0, dev_need = 0;
 };
 // A run of the scene's binary node array that the device writes itself, from a tree it still holds.
 struct DeviceSegment {
   uint32_t first = 0, count = 0;    // DevNode indices [first, first + count)
   uint32_t prim_base = 0;           // first global primitive slot of the BLAS
-  void* tree = nullptr;
+  KeptTree* tree = nullptr;         // a view: the tree belongs to HostScene::dev_trees
 };
 
 struct HostPrim {
@@ -238,7 +241,9 @@ struct HostScene {
   // runs of dev_nodes that are NOT filled in here but written on the device (the library emits them into the uploaded
   // array and copies them back when the host needs them: finish_node_formats), and the box padding they are written with
   std::vector<DeviceSegment> dev_segments;
-  std::vector<void*> dev_trees;     // every device tree handed out during the build, for the owner to release
+  // every device tree handed out during the build: the ONE owning list (HostBlas::dev_tree and DeviceSegment::tree point into
+  // it); whoever holds the scene releases them (gpu_release_tree) once the segments are written, or on the way out of a failure
+  std::vector<KeptTree*> dev_trees;
   float pad_rel = 0.0f, pad_abs = 0.0f;
   uint32_t root_ref = 0;            // packed ref of the root
   F4 root_min, root_max;            // root box (tested before anything else, blas.rs:136-139)
@@ -333,9 +338,9 @@ constexpr float kLeafNodeCost = 0.5f;
 constexpr uint32_t kLeafCollapseMax = 8;
 // `keep` non-null: the finished tree is not copied to the host (arena is left alone) but kept on the device, with the size of
 // its binary-node layout (pre-order, as DevBuilder::emit_blas_flat numbers it) and its stack need already worked out;
-// gpu_emit_tree writes that layout into a device node array and releases the tree, gpu_release_tree only releases it.
+// gpu_emit_tree writes that layout into a device node array, gpu_release_tree releases the tree.
 struct BlasDeviceTree {
-  void* handle = nullptr;
+  KeptTree* handle = nullptr;
   uint32_t node_count = 0;   // DevNodes the layout takes (inner nodes + the chains of leaves above 64 primitives)
   uint32_t need = 0;         // stack entries a traversal of it can have pending
 };
@@ -344,8 +349,8 @@ void set_device_blas_builder(BlasBuildFn fn, uint32_t device);
 int32_t selftest_half_rounding(std::string& err);
 int32_t selftest_device_layouts(std::string& err);
 bool gpu_build_blas(const BlasBuildInput& in, std::vector<uint32_t>& order, std::vector<BuildNode>& arena, std::string& err, BlasDeviceTree* keep);
-bool gpu_emit_tree(void* tree, DevNode* device_nodes, uint32_t first, uint32_t prim_base, float pad_rel, float pad_abs, std::string& err);
-void gpu_release_tree(void* tree);
+bool gpu_emit_tree(const KeptTree* tree, DevNode* device_nodes, uint32_t first, uint32_t prim_base, float pad_rel, float pad_abs, std::string& err);
+void gpu_release_tree(KeptTree* tree);
 const void* gpu_builder_any_kernel();  // host stub of one kernel of bvh_build.hip (to load that code object ahead of time)
 
 }  // namespace rayca

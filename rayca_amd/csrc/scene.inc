@@ -226,9 +226,10 @@ struct SceneBuild {
   bool build_on_host() const { return opts && opts->build_on_host; }
 };
 
-// (device-built trees still held on the device: released by upload_binary_nodes, or by abandon on every way out before it)
+// (device-built trees still held on the device, all owned by host.dev_trees: released by upload_binary_nodes once every
+// segment is written, or by abandon on every other way out)
 void release_device_trees(RaycaScene* s) {
-  for (void* t : s->host.dev_trees) gpu_release_tree(t);
+  for (KeptTree* t : s->host.dev_trees) gpu_release_tree(t);
   s->host.dev_trees.clear();
   for (HostBlas& bl : s->host.blas) bl.dev_tree = nullptr;
   for (DeviceSegment& seg : s->host.dev_segments) seg.tree = nullptr;
@@ -320,12 +321,9 @@ int32_t upload_binary_nodes(SceneBuild& b) {
   node_copier.finish();
   for (const DeviceSegment& seg : h.dev_segments) {
     std::string lerr;
-    const bool ok = gpu_emit_tree(seg.tree, dnodes, seg.first, seg.prim_base, h.pad_rel, h.pad_abs, lerr);   // (releases the tree)
-    auto& trees = s->host.dev_trees;
-    trees.erase(std::remove(trees.begin(), trees.end(), seg.tree), trees.end());
-    if (!ok) return fail(RAYCA_ERR_HIP, lerr);
+    if (!gpu_emit_tree(seg.tree, dnodes, seg.first, seg.prim_base, h.pad_rel, h.pad_abs, lerr)) return fail(RAYCA_ERR_HIP, lerr);   // (abandon releases the trees)
   }
-  release_device_trees(s);   // (nothing left unless a BLAS was built but never placed)
+  release_device_trees(s);
   s->dev.nodes = reinterpret_cast<const float4*>(dnodes);
   return RAYCA_OK;
 }

@@ -291,6 +291,33 @@ def test_create_that_fails_with_trees_held_on_the_device(gpu):
     orc.close()
 
 
+def test_create_that_fails_with_two_trees_held_on_the_device(gpu):
+    # two device-built models (5 000 triangles each): two kept trees in the scene's list when the texture table is refused, all
+    # released on the way out; the good scene's node array is then written from two device segments
+    def soups(bad):
+        scene = scenes.soup_scene(5000, seed=0xA11CE, extent=0.08)
+        other = scenes.soup_scene(5000, seed=0xB0B, extent=0.06)
+        n = scene.push_model(other.models[0])
+        scene.nodes[n].trs = Trs(translation=(0.4, -0.2, 0.3), scale=(0.7, 0.7, 0.7))
+        if bad:
+            scene.models[0].textures.push(Texture(image=0))     # (the model has no image)
+        return flatten(scene)
+    for _ in range(2):
+        with pytest.raises(RaycaError) as e:
+            DeviceScene(soups(True), Config(), builder=abi.BUILDER_SAH)
+        assert e.value.code == abi.ERR_BAD_ARG and str(e.value).endswith(": texture references a missing image")
+    desc = soups(False)
+    ds = DeviceScene(desc, Config(), builder=abi.BUILDER_SAH)
+    assert ds.info()["blas_count"] == 2
+    orc = ol.OracleScene(desc, Config(), build=ol.BUILD_BINNED)
+    _, f32, _ = ds.render(FLAT, 128, 128)
+    _, of32, _ = orc.render(FLAT, 128, 128)
+    assert_exact(f32, of32)
+    assert (f32[..., :3].sum(-1) > 0).sum() > 500
+    ds.close()
+    orc.close()
+
+
 def _quad_light_room():
     """Phong room lit by an emissive quad light (the SDTF-style setup, light/quad.rs + nee.rs:72-125)."""
     model = Model()
