@@ -585,8 +585,9 @@ int32_t rayca_hip_render_multi(RaycaScene* const* scenes, uint32_t count, const 
  * The drop-in host loop (draw.rs:7-9 called per frame) is `issue(ctx = f % 4)`, `wait(ctx = (f + 1) % 4)`. */
 int32_t rayca_hip_render_multi_issue(RaycaScene* const* scenes, uint32_t count, const RaycaConfig* cfg, uint32_t width,
                                      uint32_t height, const RaycaMultiOptions* opts, void* rgba8_out);
-/* Waits until the frame last issued with frame context `context` on these scenes has landed in its rgba8_out; returns
- * that frame's status.  RAYCA_OK at once if there is none. */
+/* Waits until the frame last issued with frame context `context` on these scenes has landed in its rgba8_out.  A frame's
+ * errors are returned by its issue; the wait returns only an error of the synchronisation itself (the frame then stays
+ * pending), and RAYCA_OK at once if nothing is pending on that context. */
 int32_t rayca_hip_render_multi_wait(RaycaScene* const* scenes, uint32_t count, uint32_t context);
 
 /* RAYCA_OK if librccl can be opened and offers what RAYCA_GATHER_RCCL uses, else RAYCA_ERR_RCCL with the reason in

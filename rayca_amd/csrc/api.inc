@@ -1,6 +1,10 @@
 // api.inc -- extern "C" entry points of librayca_hip.so (declared in include/rayca_hip.h).
-// Included at the end of kernels.hip so that the kernels' anonymous namespace is visible.  The kernels the entry points launch
-// themselves are in aux_kernels.inc, a scene's lifetime (create, destroy, finish, info, update, read-backs) in scene.inc.
+// Included at the end of kernels.hip so that the kernels' anonymous namespace is visible.  Here: the owners of device resources
+// (DeviceBuffer, FrameCtx, and the types of the several-devices frame that RaycaScene holds), the one way a context's buffer is
+// sized (ensure, grow_behind_pass), the pass protocol (ContextPass), the frame driver and the single-device entry points.  The
+// kernels the entry points launch themselves are in aux_kernels.inc, kernel selection in select.inc, a scene's lifetime (create,
+// destroy, finish, info, update, read-backs) in scene.inc, the several-devices frame (rayca_hip_render_multi and its issue /
+// wait forms) in multi.inc, the image-space post passes in post.inc.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -39,9 +43,22 @@ int32_t fail(int32_t code, const std::string& msg) {
                   std::string(#expr) + ": " + hipGetErrorString(e__));                                        \
   } while (0)
 
+// A device allocation and its owner.  ensure() (and grow_behind_pass on top of it) is the one way to size it; release() frees it
+// early, the destructor with its owner.  Move-only and not assignable: a buffer is emptied by release(), never by writing an
+// empty one over it.
 struct DeviceBuffer {
   void* ptr = nullptr;
   size_t bytes = 0;
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  ~DeviceBuffer() { release(); }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+  }
 };
 
 }  // namespace
@@ -51,6 +68,8 @@ struct DeviceBuffer {
 // on first use, so that several frames of the same scene can be in flight on different streams: the tail of one
 // frame (a few slow waves) then overlaps the head of the next (measured on the atrium, 1080p depth-1:
 // 0.63 -> 0.48 ms per frame with two frames in flight).
+// The context owns all of it and gives it back in one place, release(); the stream alone may leave before that (scene_destroy_now
+// hands an idle stream to the StreamSetPool and clears the pointer).
 constexpr uint32_t kMaxContexts = 8;
 struct FrameCtx {
   bool ready = false;
@@ -70,6 +89,28 @@ struct FrameCtx {
   bool frame_pending = false;         // ev_done has been recorded at least once
   std::vector<hipEvent_t> ev_trace;   // pairs around the timed launches of a frame (LaunchLog)
   std::mutex mu;
+  // Everything back to the device, the stream included if it is still here.  The caller has waited for the context's last pass
+  // and made its device current.  (A buffer this list forgets is not leaked: its own destructor frees it, with the context.)
+  void release() {
+    for (DeviceBuffer* b : {&path_direct, &path_brdf, &path_state, &accum, &queue[0], &queue[1], &out8, &out32, &ray_io, &stack_spill, &frames, &mis_samples,
+                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1]})
+      b->release();
+    if (heads_alloc) (void)hipFree(heads_alloc);
+    if (counters) (void)hipFree(counters);
+    heads_alloc = heads = heads_b = nullptr;
+    counters = nullptr;
+    shade_stats = nullptr;
+    for (hipEvent_t* e : {&ev_begin, &ev_end, &ev_done}) {
+      if (*e) (void)hipEventDestroy(*e);
+      *e = nullptr;
+    }
+    for (hipEvent_t e : ev_trace) (void)hipEventDestroy(e);
+    ev_trace.clear();
+    if (stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+    ready = frame_pending = heads_clean = false;
+  }
+  ~FrameCtx() { release(); }
 };
 
 // One host thread per part of rayca_hip_render_multi beyond the first: it issues that part's launches (a frame is 3-20
@@ -119,8 +160,9 @@ struct PartWorker {
   }
 };
 
-// State of rayca_hip_render_multi, kept by the scene that assembles the frame (scenes[0]): per frame context the events
-// and buffers of the frame in flight on it, and for the set of devices the communicators and issue threads.
+// State of rayca_hip_render_multi (multi.inc), kept by the scene that assembles the frame (scenes[0]): per frame context the events
+// and buffers of the frame in flight on it, and for the set of devices the communicators and issue threads.  All of it is made
+// for one set of devices and given back by MultiCtx::release: when another set is adopted, and with the scene.
 struct MultiFrame {
   std::vector<hipEvent_t> done;      // per part: its rows are rendered
   hipEvent_t gathered = nullptr;     // scenes[0]'s device: exchange, de-interleave and copy-out of this context's last frame are done
@@ -128,8 +170,7 @@ struct MultiFrame {
   DeviceBuffer gather, frame;        // [part][max_rows][W][4] and [H][W][4] on scenes[0]'s device
   bool pending = false;              // a frame has been issued and not waited for
   bool rccl = false;                 // ... with the RCCL transport (its senders' streams are drained by the wait too)
-  int32_t status = 0;
-  std::string error;
+  void release(const std::vector<int>& devices);   // (done[i] is an event of devices[i])
 };
 struct MultiCtx {
   std::vector<int> devices;          // device of every part, in part order
@@ -137,6 +178,8 @@ struct MultiCtx {
   MultiFrame frames[kMaxContexts];
   std::vector<std::unique_ptr<PartWorker>> workers;   // parts 1..n-1
   bool peer_enabled = false;
+  void release();   // the caller has waited for the frames in flight (MultiFrame::gathered)
+  ~MultiCtx() { release(); }
 };
 
 struct RaycaScene {
@@ -250,12 +293,18 @@ int32_t formats_wait(RaycaScene* s) {
 
 int32_t ensure(DeviceBuffer& b, size_t bytes) {
   if (b.bytes >= bytes && b.ptr) return RAYCA_OK;
-  if (b.ptr) (void)hipFree(b.ptr);
-  b.ptr = nullptr;
-  b.bytes = 0;
+  b.release();
   HIP_TRY(hipMalloc(&b.ptr, bytes));
   b.bytes = bytes;
   return RAYCA_OK;
+}
+// The growth rule: a buffer of a frame context at `bytes` or more.  An earlier pass of the context that has not been waited for
+// may still be working in the buffer to be replaced -- on another stream -- so regrowing waits for the context's ev_done first.
+// Every buffer of a FrameCtx is sized through here; plain ensure is for buffers no context pass uses.  A call that does not
+// regrow costs the one comparison.  (The context's mutex is held and its device current.)
+int32_t grow_behind_pass(FrameCtx* c, DeviceBuffer& b, size_t bytes) {
+  if (b.bytes < bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
+  return ensure(b, bytes);
 }
 
 // The streams of all frame contexts of a scene, made in one go.  HIP runs a process's streams over four hardware queues per
@@ -464,8 +513,10 @@ int32_t timed_launch(LaunchLog& log, hipStream_t stream, int cls, bool timed, bo
 // It starts behind the context's previous pass ON THE DEVICE -- that one may still be running on another stream and owns the
 // same work buffers -- and behind opts.wait_event; it leaves the context's ev_done (and opts.record_event) behind its last
 // launch.  ev_done is what rayca_hip_scene_update, scene_destroy and every regrowth of a buffer that a pass in flight may
-// use wait for, before they overwrite or free it.  The context's own stream is not the caller's to wait on, so a pass on it
-// is synchronous; so is a pass that reports statistics.
+// use wait for, before they overwrite or free it.  The regrowth is spelled once: grow_behind_pass, through which every buffer of
+// a FrameCtx is sized -- by a pass for itself, and by the calls that stage through a context's buffers (rayca_hip_render, the
+// parts of the several-devices frame).  The context's own stream is not the caller's to wait on, so a pass on it is synchronous;
+// so is a pass that reports statistics.
 //   pass_acquire ... [buffers, memsets] ... ev_begin when timing ... launches ... pass_retire ... pass_finish
 // ev_begin is where kernel_ms starts: behind whatever the pass clears or prepares first, so every entry records it itself.
 struct ContextPass {
@@ -601,12 +652,12 @@ int32_t wavefront_generation(Frame& f, uint32_t g, const GenQueues& q) {
   const uint32_t nls = (f.plan.mode == kModePath && f.cfg.direct_sampler == RAYCA_SAMPLER_NEE) ? (uint32_t)s->host.lights.size() * f.cfg.light_samples : 0u;
   int32_t rc;
   WfBuffers wb{};
-  if ((rc = ensure(c->wf_hits, (size_t)npix * 16u)) != RAYCA_OK) return rc;
+  if ((rc = grow_behind_pass(c, c->wf_hits, (size_t)npix * 16u)) != RAYCA_OK) return rc;
   wb.hits = static_cast<float4*>(c->wf_hits.ptr);
   wb.nls = nls;
   if (nls) {
-    if ((rc = ensure(c->wf_sh_ray, (size_t)npix * nls * 32u)) != RAYCA_OK) return rc;
-    if ((rc = ensure(c->wf_sh_x, (size_t)npix * nls * 16u)) != RAYCA_OK) return rc;
+    if ((rc = grow_behind_pass(c, c->wf_sh_ray, (size_t)npix * nls * 32u)) != RAYCA_OK) return rc;
+    if ((rc = grow_behind_pass(c, c->wf_sh_x, (size_t)npix * nls * 16u)) != RAYCA_OK) return rc;
     wb.sh_ray = static_cast<float4*>(c->wf_sh_ray.ptr);
     wb.sh_x = static_cast<float4*>(c->wf_sh_x.ptr);
   }
@@ -763,10 +814,10 @@ int32_t stack_machine(Frame& f) {
   GFrameStore store{};
   store.threads = grid * kBlock;
   store.levels = levels + 1u;
-  if ((rc = ensure(c->frames, (size_t)store.levels * 8u * store.threads * 16u)) != RAYCA_OK) return rc;
+  if ((rc = grow_behind_pass(c, c->frames, (size_t)store.levels * 8u * store.threads * 16u)) != RAYCA_OK) return rc;
   store.frames = static_cast<float4*>(c->frames.ptr);
   if (cfg.direct_sampler == RAYCA_SAMPLER_MIS) {
-    if ((rc = ensure(c->mis_samples, (size_t)2u * kMisMaxSamples * store.threads * 16u)) != RAYCA_OK) return rc;
+    if ((rc = grow_behind_pass(c, c->mis_samples, (size_t)2u * kMisMaxSamples * store.threads * 16u)) != RAYCA_OK) return rc;
     store.samples = static_cast<float4*>(c->mis_samples.ptr);
   }
   TraceLaunch tl{};
@@ -971,16 +1022,16 @@ int32_t frame_begin(Frame& f, const ContextPass& pass, void* d_rgba8, void* d_rg
   const size_t records = (size_t)npix * (plan.generations ? plan.generations : 1);
   const bool path = plan.mode == kModePath, bounces = path && plan.generations > 1;
   if (!f.fused) {
-    if ((rc = ensure(c->path_direct, records * 16)) != RAYCA_OK) return rc;
-    if ((rc = ensure(c->path_state, records * 4)) != RAYCA_OK) return rc;
-    if (path && (rc = ensure(c->path_brdf, records * 16)) != RAYCA_OK) return rc;
-    if (f.cfg.samples_per_pixel > 1 && (rc = ensure(c->accum, (size_t)npix * 16)) != RAYCA_OK) return rc;
+    if ((rc = grow_behind_pass(c, c->path_direct, records * 16)) != RAYCA_OK) return rc;
+    if ((rc = grow_behind_pass(c, c->path_state, records * 4)) != RAYCA_OK) return rc;
+    if (path && (rc = grow_behind_pass(c, c->path_brdf, records * 16)) != RAYCA_OK) return rc;
+    if (f.cfg.samples_per_pixel > 1 && (rc = grow_behind_pass(c, c->accum, (size_t)npix * 16)) != RAYCA_OK) return rc;
     pb.direct = static_cast<float4*>(c->path_direct.ptr);
     pb.brdf = static_cast<float4*>(c->path_brdf.ptr);
     pb.state = static_cast<uint32_t*>(c->path_state.ptr);
   }
-  if (bounces && (rc = ensure(c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
-  if ((bounces || f.rays) && (rc = ensure(c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+  if (bounces && (rc = grow_behind_pass(c, c->queue[0], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
+  if ((bounces || f.rays) && (rc = grow_behind_pass(c, c->queue[1], (size_t)npix * sizeof(QueuedRay))) != RAYCA_OK) return rc;
   return RAYCA_OK;
 }
 
@@ -1087,87 +1138,12 @@ int32_t render_impl(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, uint3
 
 }  // namespace
 
-// ---- rayca_hip_render_multi ----------------------------------------------------------------------------------------------
+// ---- the kernels of the host API, and the several-devices frame ------------------------------------------------------------
 namespace {
-
-// RCCL is opened at first use: the library has no link-time dependency on it, and a process that already has one loaded
-// (PyTorch ships its own librccl) keeps using that one.
-struct Rccl {
-  using Comm = void*;
-  int (*CommInitAll)(Comm*, int, const int*) = nullptr;
-  int (*CommDestroy)(Comm) = nullptr;
-  int (*GroupStart)() = nullptr;
-  int (*GroupEnd)() = nullptr;
-  int (*Send)(const void*, size_t, int, int, Comm, hipStream_t) = nullptr;
-  int (*Recv)(void*, size_t, int, int, Comm, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(int) = nullptr;
-  bool ok = false;
-  std::string why;
-  static constexpr int kUint8 = 1;  // ncclUint8 (rccl.h)
-  Rccl() {
-    void* h = nullptr;
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-      if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL)) != nullptr) break;
-    if (!h) {
-      const char* e = dlerror();
-      why = std::string("librccl could not be opened: ") + (e ? e : "?");
-      return;
-    }
-    auto sym = [&](const char* n) { return dlsym(h, n); };
-    CommInitAll = reinterpret_cast<decltype(CommInitAll)>(sym("ncclCommInitAll"));
-    CommDestroy = reinterpret_cast<decltype(CommDestroy)>(sym("ncclCommDestroy"));
-    GroupStart = reinterpret_cast<decltype(GroupStart)>(sym("ncclGroupStart"));
-    GroupEnd = reinterpret_cast<decltype(GroupEnd)>(sym("ncclGroupEnd"));
-    Send = reinterpret_cast<decltype(Send)>(sym("ncclSend"));
-    Recv = reinterpret_cast<decltype(Recv)>(sym("ncclRecv"));
-    GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-    ok = CommInitAll && CommDestroy && GroupStart && GroupEnd && Send && Recv && GetErrorString;
-    if (!ok) why = "librccl lacks one of ncclCommInitAll / ncclGroupStart / ncclSend / ncclRecv";
-  }
-};
-Rccl& rccl() {
-  static Rccl r;
-  return r;
-}
-#define RCCL_TRY(expr)                                                                                         \
-  do {                                                                                                         \
-    const int r__ = (expr);                                                                                    \
-    if (r__ != 0) return fail(RAYCA_ERR_RCCL, std::string(#expr) + ": " + rccl().GetErrorString(r__));        \
-  } while (0)
-
 #include "aux_kernels.inc"
-
-void multi_release(RaycaScene* s) {
-  MultiCtx& m = s->multi;
-  m.workers.clear();   // (joins the issue threads)
-  if (!m.comms.empty() && rccl().ok)
-    for (void* c : m.comms)
-      if (c) (void)rccl().CommDestroy(c);
-  m.comms.clear();
-  for (MultiFrame& f : m.frames) {
-    for (size_t i = 0; i < f.done.size(); ++i) {
-      if (i < m.devices.size()) (void)hipSetDevice(m.devices[i]);
-      if (f.done[i]) (void)hipEventDestroy(f.done[i]);
-    }
-    f.done.clear();
-    (void)hipSetDevice(s->device);
-    if (f.gathered) (void)hipEventDestroy(f.gathered);
-    f.gathered = nullptr;
-    f.gathered_valid = false;
-    if (f.gather.ptr) (void)hipFree(f.gather.ptr);
-    if (f.frame.ptr) (void)hipFree(f.frame.ptr);
-    f.gather = DeviceBuffer{};
-    f.frame = DeviceBuffer{};
-    f.pending = false;
-    f.status = RAYCA_OK;
-    f.error.clear();
-  }
-  (void)hipSetDevice(s->device);
-  m.devices.clear();
-  m.peer_enabled = false;
-}
-
 }  // namespace
+
+#include "multi.inc"
 
 extern "C" {
 
@@ -1250,9 +1226,8 @@ int32_t rayca_hip_render(RaycaScene* s, const RaycaConfig* cfg, uint32_t width, 
   };
   if ((rc = ensure_ctx(s, c)) != RAYCA_OK) return rc;
   lap("frame context");
-  if (c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));  // before out8/out32 may be freed and regrown
-  if (rgba8_out && (rc = ensure(c->out8, npix * 4 + 16)) != RAYCA_OK) return rc;
-  if (rgba32f_out && (rc = ensure(c->out32, npix * 16 + 16)) != RAYCA_OK) return rc;
+  if (rgba8_out && (rc = grow_behind_pass(c, c->out8, npix * 4 + 16)) != RAYCA_OK) return rc;
+  if (rgba32f_out && (rc = grow_behind_pass(c, c->out32, npix * 16 + 16)) != RAYCA_OK) return rc;
   lap("staging buffers");
   // (no statistics unless asked for: they cost two event records per launch, a stream synchronisation and a read-back)
   rc = render_body(s, cfg, width, height, &o, rgba8_out ? c->out8.ptr : nullptr, rgba32f_out ? c->out32.ptr : nullptr, stats_out, true);
@@ -1415,263 +1390,6 @@ int32_t rayca_hip_scene_desc_compare(const RaycaSceneDesc* resident, uint32_t re
   return RAYCA_OK;
 }
 
-
-int32_t rayca_hip_rccl_status(void) { return rccl().ok ? RAYCA_OK : fail(RAYCA_ERR_RCCL, rccl().why); }
-
-}  // extern "C"
-
-namespace {
-
-// Frame context `context` of every scene, locked in ADDRESS order: two calls that share scenes in different orders (or
-// with a different scenes[0]) cannot wait for each other in a cycle.
-std::vector<std::unique_lock<std::mutex>> lock_contexts(RaycaScene* const* scenes, uint32_t count, uint32_t context) {
-  std::vector<RaycaScene*> order(scenes, scenes + count);
-  std::sort(order.begin(), order.end(), [](const RaycaScene* a, const RaycaScene* b) { return std::less<const RaycaScene*>()(a, b); });
-  std::vector<std::unique_lock<std::mutex>> locks;
-  for (RaycaScene* sc : order) locks.emplace_back(sc->ctx[context].mu);
-  return locks;
-}
-
-int32_t multi_validate(RaycaScene* const* scenes, uint32_t count, const RaycaMultiOptions& mo) {
-  if (!scenes || count == 0) return fail(RAYCA_ERR_BAD_ARG, "null argument");
-  if (count > 64) return fail(RAYCA_ERR_BAD_ARG, "more than 64 devices");
-  if (mo.gather > RAYCA_GATHER_PEER_COPY) return fail(RAYCA_ERR_BAD_ARG, "unknown gather transport");
-  if (mo.context >= kMaxContexts) return fail(RAYCA_ERR_BAD_ARG, "context out of range");
-  for (uint32_t i = 0; i < count; ++i)
-    if (!scenes[i]) return fail(RAYCA_ERR_BAD_ARG, "null scene");
-  for (uint32_t i = 0; i < count; ++i)
-    for (uint32_t j = i + 1; j < count; ++j) {
-      if (scenes[i] == scenes[j]) return fail(RAYCA_ERR_BAD_ARG, "the same scene handle twice");
-      if (mo.gather == RAYCA_GATHER_RCCL && scenes[i]->device == scenes[j]->device)
-        return fail(RAYCA_ERR_BAD_ARG, "RCCL needs every part on its own device (two scenes share one)");
-    }
-  return RAYCA_OK;
-}
-
-// every part's stream of this context drained: nothing of a frame that failed half-way may still be writing the gather /
-// staging buffers when the caller gets the error (the next call may free and regrow them)
-void multi_drain(RaycaScene* const* scenes, uint32_t count, uint32_t context) {
-  for (uint32_t i = 0; i < count; ++i) {
-    if (hipSetDevice(scenes[i]->device) != hipSuccess) continue;
-    if (scenes[i]->ctx[context].stream) (void)hipStreamSynchronize(scenes[i]->ctx[context].stream);
-  }
-  (void)hipSetDevice(scenes[0]->device);
-  (void)hipGetLastError();
-}
-
-// The whole frame queued on the devices: every part's kernels, the one exchange, the de-interleave, the copy-out.  `sync_stats`
-// (rayca_hip_render_multi with statistics): every part's render call waits for its own kernels to read its counters.
-int32_t multi_issue(RaycaScene* const* scenes, uint32_t count, const RaycaConfig* cfg, uint32_t width, uint32_t height, const RaycaMultiOptions& mo,
-                    void* rgba8_out, RaycaStats* stats_out, bool asynchronous) {
-  if (!cfg || !rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "null argument");
-  if (width == 0 || height == 0) return fail(RAYCA_ERR_BAD_ARG, "empty image");
-  const uint32_t band = mo.band_rows ? mo.band_rows : 8u;
-  const uint32_t ctx = mo.context;
-  RaycaScene* s0 = scenes[0];
-  std::lock_guard<std::mutex> multi_lock(s0->multi_mu);
-  std::vector<std::unique_lock<std::mutex>> ctx_locks = lock_contexts(scenes, count, ctx);
-
-  // per-part geometry (rayca_hip_tile_rows: the same arithmetic the kernels and rayca_amd/distributed.py use)
-  std::vector<uint32_t> rows(count);
-  uint32_t max_rows = 0;
-  for (uint32_t i = 0; i < count; ++i) {
-    rows[i] = tile_rows(RaycaTile{i, count, band, 0}, height);
-    max_rows = std::max(max_rows, rows[i]);
-  }
-  MultiCtx& m = s0->multi;
-  std::vector<int> devices(count);
-  for (uint32_t i = 0; i < count; ++i) devices[i] = scenes[i]->device;
-  if (m.devices != devices) {  // first call, or another set of devices: communicators, events and issue threads are per set
-    // (frames of the previous set still in flight: their exchange and copy-out end with `gathered`, an event of this scene)
-    (void)hipSetDevice(s0->device);
-    for (MultiFrame& old : m.frames)
-      if (old.pending && old.gathered) (void)hipEventSynchronize(old.gathered);
-    multi_release(s0);
-    m.devices = devices;
-    for (uint32_t i = 1; i < count; ++i) m.workers.emplace_back(new PartWorker());
-  }
-  MultiFrame& f = m.frames[ctx];
-  if (f.done.size() != count) {
-    f.done.assign(count, nullptr);
-    for (uint32_t i = 0; i < count; ++i) {
-      HIP_TRY(hipSetDevice(devices[i]));
-      HIP_TRY(hipEventCreateWithFlags(&f.done[i], hipEventDisableTiming));
-    }
-  }
-  HIP_TRY(hipSetDevice(s0->device));
-  if (!f.gathered) HIP_TRY(hipEventCreateWithFlags(&f.gathered, hipEventDisableTiming));
-  int32_t rc;
-  // (a buffer is only freed and regrown once the frame that may still be using it has finished)
-  const size_t frame_bytes = (size_t)width * height * 4u, gather_bytes = (size_t)count * max_rows * width * 4u;
-  if (f.pending && (f.frame.bytes < frame_bytes || (count > 1 && f.gather.bytes < gather_bytes))) multi_drain(scenes, count, ctx);
-  if ((rc = ensure(f.frame, frame_bytes)) != RAYCA_OK) return rc;
-  if (count > 1 && (rc = ensure(f.gather, gather_bytes)) != RAYCA_OK) return rc;
-  if (count > 1 && mo.gather == RAYCA_GATHER_RCCL && m.comms.empty()) {
-    if (!rccl().ok) return fail(RAYCA_ERR_RCCL, rccl().why);
-    m.comms.assign(count, nullptr);
-    RCCL_TRY(rccl().CommInitAll(m.comms.data(), (int)count, devices.data()));
-  }
-  if (count > 1 && mo.gather == RAYCA_GATHER_PEER_COPY && !m.peer_enabled) {
-    for (uint32_t i = 1; i < count; ++i) {
-      if (devices[i] == s0->device) continue;
-      int can = 0;
-      HIP_TRY(hipDeviceCanAccessPeer(&can, s0->device, devices[i]));
-      if (can) {
-        const hipError_t e = hipDeviceEnablePeerAccess(devices[i], 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_TRY(e);
-        (void)hipGetLastError();
-      }
-    }
-    m.peer_enabled = true;
-  }
-
-  // Part 0 renders straight into its slot of the gather buffer (or, alone, into the frame); the others into their own
-  // context's staging buffer, which the exchange reads: their next frame of this context must not start before it has.
-  std::vector<int32_t> part_rc(count, RAYCA_OK);
-  std::vector<std::string> part_err(count);
-  std::vector<void*> part_dst(count, nullptr);
-  for (uint32_t i = 0; i < count; ++i) {
-    FrameCtx* c = &scenes[i]->ctx[ctx];
-    HIP_TRY(hipSetDevice(devices[i]));
-    if ((rc = ensure_ctx(scenes[i], c)) != RAYCA_OK) return rc;
-    if (i == 0) part_dst[0] = count == 1 ? f.frame.ptr : f.gather.ptr;
-    else {
-      const size_t need = (size_t)max_rows * width * 4u + 16u;
-      if (c->out8.bytes < need && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
-      if ((rc = ensure(c->out8, need)) != RAYCA_OK) return rc;
-      part_dst[i] = c->out8.ptr;
-      if (f.gathered_valid) HIP_TRY(hipStreamWaitEvent(c->stream, f.gathered, 0));
-    }
-  }
-  auto work = [&](uint32_t i) {
-    RaycaRenderOptions o{};
-    o.traversal = mo.traversal;
-    o.collect_stats = mo.collect_stats;
-    o.engine = mo.engine;
-    o.context = ctx;
-    o.tile = RaycaTile{i, count, band, 0};
-    // an asynchronous frame names its stream, so that the scene sees the frames the host keeps in flight (frames_in_flight_hint)
-    o.stream = asynchronous ? static_cast<void*>(scenes[i]->ctx[ctx].stream) : nullptr;
-    if (hipSetDevice(devices[i]) != hipSuccess) {
-      part_rc[i] = RAYCA_ERR_HIP;
-      part_err[i] = "hipSetDevice failed";
-      return;
-    }
-    part_rc[i] = render_body(scenes[i], cfg, width, height, &o, rows[i] ? part_dst[i] : nullptr, nullptr, stats_out ? &stats_out[i] : nullptr, true);
-    if (part_rc[i] != RAYCA_OK) part_err[i] = g_last_error;
-    else if (hipEventRecord(f.done[i], scenes[i]->ctx[ctx].stream) != hipSuccess) {
-      part_rc[i] = RAYCA_ERR_HIP;
-      part_err[i] = "hipEventRecord failed";
-    }
-  };
-  for (uint32_t i = 1; i < count; ++i) m.workers[i - 1]->post([&work, i] { work(i); });
-  work(0);
-  for (uint32_t i = 1; i < count; ++i) m.workers[i - 1]->wait();
-  for (uint32_t i = 0; i < count; ++i)
-    if (part_rc[i] != RAYCA_OK) {
-      multi_drain(scenes, count, ctx);   // the parts that did start are not left running into the buffers
-      f.pending = false;
-      return fail(part_rc[i], "part " + std::to_string(i) + ": " + part_err[i]);
-    }
-
-  HIP_TRY(hipSetDevice(s0->device));
-  hipStream_t stream0 = s0->ctx[ctx].stream;
-  auto queue_exchange = [&]() -> int32_t {
-    if (count > 1) {
-      char* gather = static_cast<char*>(f.gather.ptr);
-      const size_t slot = (size_t)max_rows * width * 4u;
-      if (mo.gather == RAYCA_GATHER_RCCL) {
-        // the single exchange of the frame: every other part sends its packed rows, part 0 receives them into their slots
-        RCCL_TRY(rccl().GroupStart());
-        for (uint32_t i = 1; i < count; ++i) {
-          if (!rows[i]) continue;
-          const size_t bytes = (size_t)rows[i] * width * 4u;
-          RCCL_TRY(rccl().Send(part_dst[i], bytes, Rccl::kUint8, 0, m.comms[i], scenes[i]->ctx[ctx].stream));
-          RCCL_TRY(rccl().Recv(gather + i * slot, bytes, Rccl::kUint8, (int)i, m.comms[0], stream0));
-        }
-        RCCL_TRY(rccl().GroupEnd());
-        HIP_TRY(hipSetDevice(s0->device));
-      } else {
-        for (uint32_t i = 1; i < count; ++i) {
-          if (!rows[i]) continue;
-          HIP_TRY(hipStreamWaitEvent(stream0, f.done[i], 0));
-          HIP_TRY(hipMemcpyPeerAsync(gather + i * slot, s0->device, part_dst[i], devices[i], (size_t)rows[i] * width * 4u, stream0));
-        }
-      }
-      const uint32_t npix = width * height;
-      hipLaunchKernelGGL(k_deinterleave, dim3((npix + 255u) / 256u), dim3(256), 0, stream0, static_cast<const uint32_t*>(f.gather.ptr),
-                         static_cast<uint32_t*>(f.frame.ptr), width, height, count, band, max_rows);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(rgba8_out, f.frame.ptr, (size_t)width * height * 4u, mo.output_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream0));
-    HIP_TRY(hipEventRecord(f.gathered, stream0));
-    return RAYCA_OK;
-  };
-  rc = queue_exchange();
-  if (rc != RAYCA_OK) {
-    const std::string why = g_last_error;
-    multi_drain(scenes, count, ctx);
-    f.pending = false;
-    return fail(rc, why);
-  }
-  f.gathered_valid = true;
-  f.pending = true;
-  f.rccl = count > 1 && mo.gather == RAYCA_GATHER_RCCL;
-  f.status = RAYCA_OK;
-  return RAYCA_OK;
-}
-
-int32_t multi_wait(RaycaScene* const* scenes, uint32_t count, uint32_t context) {
-  RaycaScene* s0 = scenes[0];
-  std::lock_guard<std::mutex> multi_lock(s0->multi_mu);
-  MultiFrame& f = s0->multi.frames[context];
-  if (!f.pending) return RAYCA_OK;
-  f.pending = false;
-  HIP_TRY(hipSetDevice(s0->device));
-  HIP_TRY(hipEventSynchronize(f.gathered));
-  if (f.rccl) {  // the senders' streams have finished too once the receives have (grouped send/recv complete together); make it explicit
-    for (uint32_t i = 1; i < count; ++i) {
-      HIP_TRY(hipSetDevice(scenes[i]->device));
-      if (scenes[i]->ctx[context].stream) HIP_TRY(hipStreamSynchronize(scenes[i]->ctx[context].stream));
-    }
-    HIP_TRY(hipSetDevice(s0->device));
-  }
-  return RAYCA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t rayca_hip_render_multi(RaycaScene* const* scenes, uint32_t count, const RaycaConfig* cfg, uint32_t width, uint32_t height,
-                               const RaycaMultiOptions* opts_in, void* rgba8_out, RaycaStats* stats_out) {
-  RaycaMultiOptions mo{};
-  if (opts_in) mo = *opts_in;
-  int32_t rc = multi_validate(scenes, count, mo);
-  if (rc != RAYCA_OK) return rc;
-  if ((rc = multi_issue(scenes, count, cfg, width, height, mo, rgba8_out, stats_out, false)) != RAYCA_OK) return rc;
-  return multi_wait(scenes, count, mo.context);
-}
-
-int32_t rayca_hip_render_multi_issue(RaycaScene* const* scenes, uint32_t count, const RaycaConfig* cfg, uint32_t width, uint32_t height,
-                                     const RaycaMultiOptions* opts_in, void* rgba8_out) {
-  RaycaMultiOptions mo{};
-  if (opts_in) mo = *opts_in;
-  const int32_t rc = multi_validate(scenes, count, mo);
-  if (rc != RAYCA_OK) return rc;
-  if (mo.collect_stats) return fail(RAYCA_ERR_BAD_ARG, "statistics need a synchronisation per frame: rayca_hip_render_multi");
-  return multi_issue(scenes, count, cfg, width, height, mo, rgba8_out, nullptr, true);
-}
-
-int32_t rayca_hip_render_multi_wait(RaycaScene* const* scenes, uint32_t count, uint32_t context) {
-  RaycaMultiOptions mo{};
-  mo.context = context;
-  mo.gather = RAYCA_GATHER_PEER_COPY;   // (validation of the handles only: the transport was fixed by the issue)
-  const int32_t rc = multi_validate(scenes, count, mo);
-  if (rc != RAYCA_OK) return rc;
-  return multi_wait(scenes, count, context);
-}
-
 int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint32_t count, const float* rays, float* t_out, uint32_t* prim_out,
                              float* uv_out, RaycaStats* stats_out) {
   if (!s || !rays || !t_out || !prim_out || !uv_out) return fail(RAYCA_ERR_BAD_ARG, "null argument");
@@ -1686,7 +1404,7 @@ int32_t rayca_hip_trace_rays(RaycaScene* s, const RaycaRenderOptions* opts, uint
   const bool ordered = !opts || opts->traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
   const bool stats = opts && opts->collect_stats;
   const size_t in_bytes = (size_t)count * 24, out_bytes = (size_t)count * 16;
-  rc = ensure(c->ray_io, in_bytes + out_bytes);
+  rc = grow_behind_pass(c, c->ray_io, in_bytes + out_bytes);
   if (rc != RAYCA_OK) return rc;
   char* base = static_cast<char*>(c->ray_io.ptr);
   float* d_rays = reinterpret_cast<float*>(base);

@@ -50,13 +50,6 @@ bool finite_f32(float x) { return x - x == 0.0f; }
 // where the guides of a tap stand in a kernel table: [no guide, normal, normal + point]
 int guide_index(bool normal, bool point) { return point ? 2 : (normal ? 1 : 0); }
 
-// A buffer of the context at `bytes` or more.  An earlier pass of this context that has not been waited for may still be
-// working in the buffer to be replaced, so growing waits for it.  (The context's mutex is held and its device current.)
-int32_t grow_behind_pass(FrameCtx* c, DeviceBuffer& b, size_t bytes) {
-  if (b.bytes < bytes && c->frame_pending) HIP_TRY(hipEventSynchronize(c->ev_done));
-  return ensure(b, bytes);
-}
-
 // ---- what the two denoisers share: their scratch images and the launches around their iterations ----------------------------
 // The first `images` scratch images of the context, and with `planes` its two variance planes: run_pass's preparation step,
 // since they have to be there before the pass queues its waits.

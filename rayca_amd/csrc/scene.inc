@@ -651,7 +651,7 @@ int32_t scene_destroy_now(RaycaScene* s) {
   for (uint32_t c = 0; c < kMaxContexts; ++c)   // frames of the several-devices entry still in flight (this scene assembling them)
     if (s->multi.frames[c].pending && s->multi.frames[c].gathered) (void)hipEventSynchronize(s->multi.frames[c].gathered);
   lap("last frames");
-  multi_release(s);
+  s->multi.release();
   for (void* p : s->allocations) (void)hipFree(p);
   for (void* p : s->formats_allocations) (void)hipFree(p);
   // the streams go to the next scene on this device (make_scene_streams) if their set is complete and there is room
@@ -668,25 +668,15 @@ int32_t scene_destroy_now(RaycaScene* s) {
       for (int i = 0; i < 2; ++i) set.build[i] = s->build_streams[i];
       for (uint32_t i = 0; i < kMaxContexts; ++i) set.ctx[i] = s->ctx[i].stream;
       kept.push_back(set);
-    } else {
-      keep_streams = false;
+      // handed over: the scene and its contexts no longer own them
+      for (hipStream_t& b : s->build_streams) b = nullptr;
+      for (FrameCtx& cx : s->ctx) cx.stream = nullptr;
     }
   }
   (void)hipGetLastError();
-  for (hipStream_t b : s->build_streams)
-    if (b && !keep_streams) (void)hipStreamDestroy(b);
-  for (FrameCtx& cx : s->ctx) {
-    FrameCtx* c = &cx;
-    for (DeviceBuffer* b : {&c->path_direct, &c->path_brdf, &c->path_state, &c->accum, &c->queue[0], &c->queue[1], &c->out8, &c->out32, &c->ray_io, &c->stack_spill, &c->frames, &c->mis_samples, &c->wf_hits, &c->wf_sh_ray, &c->wf_sh_x, &c->denoise[0], &c->denoise[1], &c->denoise_var[0], &c->denoise_var[1]})
-      if (b->ptr) (void)hipFree(b->ptr);
-    if (c->heads_alloc) (void)hipFree(c->heads_alloc);
-    if (c->counters) (void)hipFree(c->counters);
-    if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
-    if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    for (hipEvent_t e : c->ev_trace) (void)hipEventDestroy(e);
-    if (c->stream && !keep_streams) (void)hipStreamDestroy(c->stream);
-  }
+  for (hipStream_t b : s->build_streams)   // (what was not handed over)
+    if (b) (void)hipStreamDestroy(b);
+  for (FrameCtx& cx : s->ctx) cx.release();   // here and not inside `delete s`: device memory is this lap's
   lap("device memory, streams");
   delete s;
   lap("host memory");

@@ -104,7 +104,7 @@ int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch&
   tl.lds_entries = sp.lds_entries;
   if (sp.spill_entries) {
     tl.ovf_stride = grid * block_threads;
-    const int32_t rc = ensure(c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
+    const int32_t rc = grow_behind_pass(c, c->stack_spill, (size_t)sp.spill_entries * tl.ovf_stride * 4u);
     if (rc != RAYCA_OK) return rc;
     tl.ovf = static_cast<uint32_t*>(c->stack_spill.ptr);
   }

@@ -1,7 +1,8 @@
 """The protocol every pass on a frame context follows (ContextPass in rayca_amd/csrc/api.inc), seen from outside: a query, a
 surface call, the camera-ray export and the denoiser start behind RaycaRenderOptions.wait_event and leave record_event behind
 their last launch, as a frame does (tests/test_gpu_multi.py); and rayca_hip_trace_rays queues behind a frame in flight on
-context 0, whose buffers it shares.  The Cornell room, 64 x 36: 2304 rays, hit records and pixels."""
+context 0, whose buffers it shares; a frame that has to regrow the context's buffers waits for the frame in flight on them.  The
+Cornell room, 64 x 36: 2304 rays, hit records and pixels."""
 import ctypes as C
 
 import numpy as np
@@ -132,3 +133,33 @@ def test_trace_rays_behind_a_frame_in_flight(room):
     assert (st1["rays_primary"], st1["kernel_launches"], st1["trace_kernel_launches"]) == (N, 1, 1) and st1["kernel_ms"] > 0
     assert (st1["boxes_tested"], st1["triangles_tested"]) == (st0["boxes_tested"], st0["triangles_tested"])
     assert np.array_equal(frame.cpu().numpy(), alone)
+
+
+def test_a_larger_frame_behind_a_smaller_one_held_back_on_the_same_context(room):
+    """A depth-2 frame at 64 x 36 on a side stream on context 0 of a new scene, held back by a fill, and a depth-2 frame at 256 x 144 on
+    a second stream and the same context straight behind it: the second has to replace the path records and both queues, which
+    the first has not even started to use.  Regrowing waits for the context's earlier pass (grow_behind_pass), so both frames
+    are the ones rendered alone.  A comparison of results, as above."""
+    import torch
+    cfg = Config(max_depth=2)
+    sizes = ((W, H), (256, 144))
+    alone = [room["ds"].render(cfg, w, h, want_f32=False)[0] for w, h in sizes]   # (the same scene: built the same way from the same description)
+    ds = DeviceScene(flatten(scenes.cornell_scene()), Config(), builder=abi.BUILDER_SAH)   # context 0 has no buffers yet
+    s_fill, s_small, s_large = (torch.cuda.Stream() for _ in range(3))
+    big = torch.empty(1 << 28, dtype=torch.uint8, device="cuda")
+    frames = [torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda") for w, h in sizes]
+    ev_filled = torch.cuda.Event()
+    ev_filled.record(s_fill)
+    torch.cuda.synchronize()
+    issue_small = ds.prepare_device(cfg, *sizes[0], frames[0].data_ptr(), 0, stream=s_small.cuda_stream, context=0, wait_event=ev_filled.cuda_event)
+    issue_large = ds.prepare_device(cfg, *sizes[1], frames[1].data_ptr(), 0, stream=s_large.cuda_stream, context=0)
+    with torch.cuda.stream(s_fill):
+        big.fill_(7)
+        frames[0].fill_(9)
+        ev_filled.record(s_fill)
+    issue_small()
+    issue_large()
+    torch.cuda.synchronize()
+    for frame, want in zip(frames, alone):
+        assert np.array_equal(frame.cpu().numpy(), want)
+    ds.close()

@@ -91,6 +91,91 @@ def test_frames_in_flight_through_the_multi_entry(gpu, parts):
         hd.close()
 
 
+# ---- who owns what when a frame fails, the set of parts changes or a frame grows under a frame in flight ----------------------
+# Cornell, RAYCA_BUILDER_SAH, peer copies on one device.  The smallest shapes at which the row split is ragged: the widths (70, 200)
+# are no multiple of 64, the heights (37, 121) no multiple of band x parts (4 x 2, 4 x 3) nor of the band.
+RAGGED, RAGGED_LARGE, BAND = (70, 37), (200, 121), 4
+DEPTH1 = Config(max_depth=1)
+
+
+def cornell_handles(n):
+    desc = flatten(scenes.cornell_scene())
+    return [DeviceScene(desc, Config(), builder=abi.BUILDER_SAH) for _ in range(n)]
+
+
+def frames_loop(handles, size):
+    from rayca_amd.renderer import MultiFrames
+    return MultiFrames(handles, DEPTH1, *size, band_rows=BAND, gather=abi.GATHER_PEER_COPY)
+
+
+@pytest.mark.gpu
+def test_a_failing_part_leaves_the_handles_usable(gpu):
+    """Part 1 of three is a scene without a camera: the frame is refused with that part's error (a refusal on the host: parts 0
+    and 2 are queued and drained), and straight after the good handles render the frame, through the synchronous entry and
+    through issue / wait on a context of their own -- the set of parts changed, so the state was adopted again."""
+    import os
+    from rayca_amd import Scene
+    w, h = RAGGED
+    g0, g1 = cornell_handles(2)
+    scene = Scene()
+    scene.push_model(scenes.load_gltf(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "box.gltf")))
+    blind = DeviceScene(flatten(scene), Config())
+    want = g0.render(DEPTH1, w, h, want_f32=False)[0]
+    refused = f"rayca_hip error {abi.ERR_NO_CAMERA}: part 1: "
+    with pytest.raises(RaycaError) as e:
+        render_multi([g0, blind, g1], DEPTH1, w, h, band_rows=BAND, gather=abi.GATHER_PEER_COPY)
+    assert e.value.code == abi.ERR_NO_CAMERA and str(e.value).startswith(refused), str(e.value)
+    got, _ = render_multi([g0, g1], DEPTH1, w, h, band_rows=BAND, gather=abi.GATHER_PEER_COPY)
+    assert np.array_equal(got, want)
+    bad, good = frames_loop([g0, blind, g1], RAGGED), frames_loop([g0, g1], RAGGED)
+    out = np.zeros((h, w, 4), np.uint8)
+    with pytest.raises(RaycaError) as e:
+        bad.issue(2, out)
+    assert e.value.code == abi.ERR_NO_CAMERA and str(e.value).startswith(refused), str(e.value)
+    bad.wait(2)                  # nothing is pending on the context: returns at once
+    good.issue(2, out)
+    good.wait(2)
+    assert np.array_equal(out, want)
+    for hd in (g0, g1, blind):
+        hd.close()
+
+
+@pytest.mark.gpu
+def test_the_set_of_parts_changes_under_a_frame_in_flight(gpu):
+    """Three parts issued on context 1 and, without a wait, two parts on the same context with the same scenes[0]: adopting the new
+    set waits for the frame in flight before its events and buffers are released.  Both arrays hold the single-device frame."""
+    w, h = RAGGED
+    handles = cornell_handles(3)
+    want = handles[0].render(DEPTH1, w, h, want_f32=False)[0]
+    three, two = frames_loop(handles, RAGGED), frames_loop(handles[:2], RAGGED)
+    a, b = np.zeros((h, w, 4), np.uint8), np.zeros((h, w, 4), np.uint8)
+    three.issue(1, a)
+    two.issue(1, b)
+    two.wait(1)
+    assert np.array_equal(a, want)
+    assert np.array_equal(b, want)
+    for hd in handles:
+        hd.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("parts", [1, 3])
+def test_a_contexts_frame_grows_behind_a_frame_in_flight(gpu, parts):
+    """70 x 37 issued on context 0 and, without a wait, 200 x 121 on the same context: the frame and gather buffers and the parts'
+    staging buffers are replaced by larger ones only once the frame in flight has left them."""
+    handles = cornell_handles(parts)
+    want = [handles[0].render(DEPTH1, w, h, want_f32=False, context=1)[0] for w, h in (RAGGED, RAGGED_LARGE)]
+    small, large = frames_loop(handles, RAGGED), frames_loop(handles, RAGGED_LARGE)
+    a, b = (np.zeros((h, w, 4), np.uint8) for w, h in (RAGGED, RAGGED_LARGE))
+    small.issue(0, a)
+    large.issue(0, b)
+    large.wait(0)
+    assert np.array_equal(a, want[0])
+    assert np.array_equal(b, want[1])
+    for hd in handles:
+        hd.close()
+
+
 @pytest.mark.gpu
 def test_render_device_waits_for_and_records_the_callers_events(gpu):
     """RaycaRenderOptions.wait_event / record_event: one native call per frame of a frame loop.  The frame must not start
