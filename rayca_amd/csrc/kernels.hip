@@ -77,15 +77,15 @@ struct GenArgs {
 #define GEN_COLD(member) (a.member)
 #endif
 template <int MODE, bool GEN0, bool ORDERED, bool FUSED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF>
-__global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : RAYCA_MIN_WAVES) void k_generation(GenArgs a) {
+__global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : path_waves(STATS, SPH)) void k_generation(GenArgs a) {
   const TraceLaunch& tl = a.tl;
   uint32_t* const heads = a.heads;
   const uint32_t depth = a.depth;
   extern __shared__ uint32_t lds_stack[];
   // (workgroups of kGenBlock threads: the stride of the stack rows and of the parked context; no barrier, nothing shared between waves)
   NodeStack<SPILL, kGenBlock> stack = make_stack<SPILL, kGenBlock>(lds_stack, tl, rc_bid() * kGenBlock + rc_tid());
-  // behind the stack rows: this lane's parked ShadeCtx (path frames only; the host sizes the allocation)
-  float4* const ctx_slot = reinterpret_cast<float4*>(lds_stack + tl.lds_entries * kGenBlock) + rc_tid();
+  // behind the stack rows: the workgroup's parked ShadeCtx, one slot a lane (path frames only; the host sizes the allocation)
+  const CtxSlot ctx_slot{lds_stack + tl.lds_entries * kGenBlock};
   constexpr bool PARK = RAYCA_PARK_CTX && MODE == kModePath;
   const uint32_t lane = __lane_id();
   const uint32_t home = xcc_id();
@@ -129,8 +129,8 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
     // means "closest hit wanted": camera and bounce rays, and the shadow ray of a quad light (NeeSample.quad)
     float t_stop = FLT_MAX;
     ShadeCtx cx;
-    Color ns_x = black();  // the pending NEE sample's contribution if its light turns out to be visible   (PARK: quad 5)
-    Color direct = black();  // sum of the direct samples so far                                           (PARK: quad 6)
+    Color ns_x = black();  // the pending NEE sample's contribution if its light turns out to be visible   (PARK: park_sample)
+    Color direct = black();  // sum of the direct samples so far                                           (PARK: park_sum_add)
     uint32_t li = 0, k = 0, dim = 0;
     // FUSED (Flat only): a lane that finishes leaves its pixel sum in `direct`; the gamma + quantise + store tail runs
     // once per batch with the wave reconverged, not inside the divergent state machine
@@ -171,13 +171,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
             in_shadow = true;  // enter the NEE loop (possibly empty)
             if (PARK) {
               park_ctx<kGenBlock>(ctx_slot, cx);
-              // (black(), made here from a zero the compiler cannot hoist: as a loop-invariant float4 it sat in four registers over
-              // the whole batch loop, which the counting instantiations could only afford through scratch: with the pipelined node
-              // loop k_generation<1, true, true, false, true, SPH, false, false, true, HALF> went from 0-2 to 4 spilled VGPRs and
-              // k_generation<1, true, false, false, FAST, *, false, true, true, false> from 0-4 to 2-5 -- tests/kernel_resources.py)
-              float zero = 0.0f;
-              asm volatile("" : "+v"(zero));
-              ctx_slot[6 * kGenBlock] = make_float4(zero, zero, zero, 1.0f);
+              park_sum_reset<kGenBlock>(ctx_slot);
             }
           }
         }
@@ -195,8 +189,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
           lit = !(found && hit.t < t_stop);  // nee.rs:152-156
         }
         if (PARK) {
-          const Color sum = as_color(ctx_slot[6 * kGenBlock]) + (lit ? as_color(ctx_slot[5 * kGenBlock]) : black());
-          ctx_slot[6 * kGenBlock] = as_f4(sum);
+          park_sum_add<kGenBlock>(ctx_slot, lit);
         } else {
           direct = direct + (lit ? ns_x : black());
         }
@@ -228,7 +221,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
             }
             continue;
           }
-          if (PARK) ctx_slot[5 * kGenBlock] = as_f4(ns.x);
+          if (PARK) park_sample<kGenBlock>(ctx_slot, ns.x);
           else ns_x = ns.x;
           t_stop = ns.t_stop;
           pending = true;
@@ -264,7 +257,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
         }
         if (PARK) {
           cx = unpark_ctx<kGenBlock>(ctx_slot);
-          direct = as_color(ctx_slot[6 * kGenBlock]);
+          direct = unpark_sum<kGenBlock>(ctx_slot);
         }
         pb.direct[slot] = as_f4(direct);
         if (depth < limit) {

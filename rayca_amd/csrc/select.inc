@@ -112,8 +112,15 @@ int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch&
 }
 
 // ---- the environment knobs that steer selection and planning: read once, at the first call that needs any of them --------------
+// A path frame's LDS rows by the waves per SIMD its kernel is compiled for (trace_core.inc path_waves): at five, with the compact
+// parked context, four rows -- 7 680 B per wave, twenty waves per CU; at four, twelve -- 9 728 B (10 KiB with seven quads), sixteen
+// waves, the rows cost no wave there and four rows alone cost 1 % (DESIGN 4.1, r8).  RAYCA_PATH_LDS_ENTRIES in the environment
+// replaces both.
 #ifndef RAYCA_PATH_LDS_ENTRIES
-#define RAYCA_PATH_LDS_ENTRIES 12
+#define RAYCA_PATH_LDS_ENTRIES (RAYCA_CTX_COMPACT ? 4 : 12)
+#endif
+#ifndef RAYCA_PATH_LDS_ENTRIES_FOUR_WAVES
+#define RAYCA_PATH_LDS_ENTRIES_FOUR_WAVES 12
 #endif
 struct Knobs {
   int format;                 // RAYCA_NODE_FORMAT=0..3: the node format of every generation, bit 0 = 4-wide, bit 1 = fp16 boxes (RAYCA_WIDE=0/1: the older spelling, f32 formats); -1 = the scene times them
@@ -123,7 +130,7 @@ struct Knobs {
   int refill;                 // RAYCA_REFILL=0/1: Flat camera rays on k_generation / k_flat_refill; -1 = the scene times them
   uint32_t grid_mult;         // RAYCA_GRID_MULT: blocks per CU of the fused engine's persistent grids (experiments); 0 = what the kernel admits
   uint32_t ticket;            // RAYCA_TICKET: batches per work ticket of the fused engine; 0 = by the size of the frame
-  uint32_t path_lds_entries;  // RAYCA_PATH_LDS_ENTRIES: LDS part of a path frame's node stack, clamped to 4..kMaxLdsEntries
+  uint32_t path_lds_entries;  // RAYCA_PATH_LDS_ENTRIES: LDS part of a path frame's node stack, clamped to 4..kMaxLdsEntries; 0 = by the kernel's waves
 };
 const Knobs& knobs() {
   static const Knobs k = [] {
@@ -136,7 +143,7 @@ const Knobs& knobs() {
     n.refill = getenv("RAYCA_REFILL") ? (env("RAYCA_REFILL", 0) != 0 ? 1 : 0) : -1;
     n.grid_mult = (uint32_t)env("RAYCA_GRID_MULT", 0);
     n.ticket = (uint32_t)env("RAYCA_TICKET", 0);
-    n.path_lds_entries = std::min(std::max((uint32_t)env("RAYCA_PATH_LDS_ENTRIES", RAYCA_PATH_LDS_ENTRIES), 4u), kMaxLdsEntries);
+    n.path_lds_entries = getenv("RAYCA_PATH_LDS_ENTRIES") ? std::min(std::max((uint32_t)env("RAYCA_PATH_LDS_ENTRIES", 0), 4u), kMaxLdsEntries) : 0u;
     return n;
   }();
   return k;
@@ -157,7 +164,10 @@ bool use_wide(uint32_t generation) {
   const int forced = wide_forced();
   return forced >= 0 ? forced != 0 : generation > 0;
 }
-uint32_t path_lds_entries() { return knobs().path_lds_entries; }
+uint32_t path_lds_entries(int waves_per_simd) {
+  if (const uint32_t forced = knobs().path_lds_entries) return forced;
+  return std::min(std::max((uint32_t)(waves_per_simd >= 5 ? RAYCA_PATH_LDS_ENTRIES : RAYCA_PATH_LDS_ENTRIES_FOUR_WAVES), 4u), kMaxLdsEntries);
+}
 
 // What plan_traversal reads of a scene.
 struct TreeFacts {
@@ -320,16 +330,20 @@ uint32_t ticket_policy(uint32_t batches, uint32_t grid, uint32_t block_waves) { 
 // tuple of a sweep that the grid is the same number of waves whatever the workgroup, and never more waves than batches ask for.
 int32_t selftest_grid_policy(std::string& err) {
   struct Case { uint32_t regs; size_t wave_lds; uint32_t batches; bool capped; uint32_t in_flight, forced, waves; const char* what; };
-  constexpr uint32_t kCus = 256u, kPathLds = 12u * 256u + 7u * 1024u;   // per wave: 12 stack rows + the parked context (fused_generation)
+  constexpr uint32_t kCus = 256u, kPathLds = 4u * 256u + 104u * 64u;   // per wave: 4 stack rows + the parked context = 7 680 B (fused_generation)
   const Case cases[] = {
-      {125u, kPathLds, 32400u, true, 4u, 0u, 2048u, "the 1080p path frame, four in flight: 8 waves per CU"},
-      {125u, kPathLds, 32400u, true, 2u, 0u, 3072u, "the 1080p path frame, two in flight: 12 waves per CU"},
-      {125u, kPathLds, 32400u, true, 1u, 0u, 4096u, "the 1080p path frame alone: 16 waves per CU"},
+      {96u, kPathLds, 32400u, true, 4u, 0u, 3072u, "the 1080p path frame, four in flight: 12 waves per CU"},
+      {96u, kPathLds, 32400u, true, 2u, 0u, 4096u, "the 1080p path frame, two in flight: 16 waves per CU"},
+      {96u, kPathLds, 32400u, true, 1u, 0u, 5120u, "the 1080p path frame alone: 20 waves per CU, by its 96 registers and by its LDS"},
+      {64u, kPathLds, 32400u, false, 1u, 0u, 5120u, "its LDS alone admits 20 waves per CU (21 in single waves: counted in units of four)"},
+      {120u, 12u * 256u + 104u * 64u, 32400u, true, 1u, 0u, 4096u, "a counting or sphere path frame, four waves per SIMD and twelve rows, 9 728 B: 16 waves per CU"},
+      {112u, 12u * 256u + 7u * 1024u, 32400u, true, 4u, 0u, 2048u, "the path frame with seven quads, twelve rows and 112 registers, four in flight: 8 waves per CU"},
+      {112u, 12u * 256u + 7u * 1024u, 32400u, true, 1u, 0u, 4096u, "the same alone: 16 waves per CU"},
       {96u, 24u * 256u, 32400u, true, 1u, 0u, 5120u, "a Flat frame at 96 VGPRs: registers admit 5 waves per SIMD, LDS 6"},
       {64u, 0u, 32400u, false, 1u, 0u, 8192u, "no LDS, uncapped: 8 waves per SIMD"},
       {40u, 256u, 1u << 20, false, 1u, 0u, 12288u, "uncapped at 40 VGPRs and a little LDS: 12 waves per SIMD"},
       {40u, 256u, 1u << 20, true, 1u, 0u, 8192u, "the same, capped: 8"},
-      {125u, kPathLds, 32400u, true, 4u, 3u, 3072u, "RAYCA_GRID_MULT=3 replaces the policy"},
+      {96u, kPathLds, 32400u, true, 4u, 2u, 2048u, "RAYCA_GRID_MULT=2 replaces the policy"},
       {256u, 96u * 1024u, 32400u, true, 4u, 0u, 1024u, "a kernel nothing admits still gets one wave per SIMD"},
   };
   const auto fail_case = [&](const std::string& what) { err = "grid_policy: " + what; return RAYCA_ERR_BAD_ARG; };
@@ -342,7 +356,7 @@ int32_t selftest_grid_policy(std::string& err) {
   const uint32_t small[][4] = {{0u, 1u, 1u, 1u}, {1u, 1u, 1u, 1u}, {6u, 6u, 3u, 2u}, {42u, 42u, 21u, 11u}, {2047u, 2047u, 1024u, 512u}};   // batches; grid at 1, 2, 4 waves
   for (const auto& r : small)
     for (uint32_t i = 0; i < 3u; ++i)
-      if (const uint32_t grid = grid_policy(125u, kPathLds << i, r[0], true, 4u, 0u, kCus, 1u << i); grid != r[1 + i])
+      if (const uint32_t grid = grid_policy(96u, kPathLds << i, r[0], true, 4u, 0u, kCus, 1u << i); grid != r[1 + i])
         return fail_case(std::to_string(r[0]) + " batches in workgroups of " + std::to_string(1u << i) + " waves: " + std::to_string(grid) + " workgroups, expected " + std::to_string(r[1 + i]));
   for (uint32_t regs : {24u, 64u, 96u, 125u, 128u, 200u})
     for (uint32_t wave_lds : {0u, 1024u, 6144u, 10240u, 16384u})

@@ -18,9 +18,17 @@ static_assert(kGenWaves == 1 || kGenWaves == 2 || kGenWaves == 4, "k_generation'
 #ifndef RAYCA_MIN_WAVES_FLAT
 #define RAYCA_MIN_WAVES_FLAT 5
 #endif
+// the path k_generation's waves per SIMD (its __launch_bounds__): 5 = 96 VGPRs, for which the compiler keeps six registers of the
+// bench instantiation in scratch (28 B; its non-SPILL sibling four, 20 B).  None is touched inside a node or leaf loop, but they
+// are inside the batch loop: the ray's RNG key is reloaded once behind every trace() call, the lane number and push_ray's
+// lanes-below mask once per batch in the tail (profiles/r08_five_waves_resources.txt).  The fifth wave hides more of a node
+// fetch's latency.  -DRAYCA_MIN_WAVES=4: 112 registers, the kernel as it was.  path_waves: the bound an instantiation gets --
+// the counting and the sphere ones keep four (at five they would need 7 to 45 registers in scratch, and no timed frame runs them);
+// the host gives a launch its stack rows by the same function (fused_generation).
 #ifndef RAYCA_MIN_WAVES
-#define RAYCA_MIN_WAVES 4
+#define RAYCA_MIN_WAVES 5
 #endif
+constexpr int path_waves(bool stats, bool sph) { return stats || sph ? 4 : RAYCA_MIN_WAVES; }
 
 // Thread and block indices from the compiler's builtins.  threadIdx.x and its kin go through functions of the device library,
 // and a function only inlines into one whose target features contain its own: in the RAYCA_NO_PK_F32 functions (no_pk.hpp)
@@ -881,22 +889,68 @@ struct ShadeCtx {
 // The path kernel keeps a vertex's ShadeCtx in LDS while its shadow rays are traversed (RAYCA_PARK_CTX): the struct is 27
 // registers that would otherwise have to survive the traversal loop, which at the 128 VGPRs of four waves per SIMD the
 // compiler could only do through scratch (54 spilled VGPRs, 219 MB of scratch writes per 1080p frame).  So do the pending
-// sample's contribution and the running sum of direct light (quads 5 and 6).  Seven float4 per lane, quantity-major (lane i of quantity q at [q * STRIDE + i], STRIDE = the workgroup's threads): a wave's ds_read_b128 / ds_write_b128 touch 64
+// sample's contribution and the running sum of direct light.  float4 quads per lane, quantity-major (lane i of quantity q at
+// [q * STRIDE + i], STRIDE = the workgroup's threads): a wave's ds_read_b128 / ds_write_b128 touch 64
 // consecutive 16-B slots, the conflict-free shape.  next_origin and the w lanes are recomputed (same operations, same bits).
 #ifndef RAYCA_PARK_CTX
 #define RAYCA_PARK_CTX 1
 #endif
-constexpr uint32_t kCtxQuads = 7;  // ShadeCtx (5) + the pending NEE sample's contribution + the running direct sum
+// RAYCA_CTX_COMPACT (default 1): the parked words cut to what the vertex still needs, 104 B per lane instead of 112, so that a wave's
+// context and four stack rows are 7 680 B and twenty waves fit a CU's 160 KiB (fused_generation).  Five quads and six words:
+//   quad 0  point.xyz, roughness OR shininess   surf_brdf reads shininess only for Phong and roughness only otherwise: one word, chosen by kind
+//   quad 1  normal.xyz, kind
+//   quad 2  view.xyz, (free)
+//   quad 3  kd            quad 4  ks
+//   words 0-2  the pending sample as x.rgb * x.a -- all operator+ ever reads of it; "not lit" adds +0.0f, which is black()'s 0 * 1
+//   words 3-5  the running direct sum's r, g, b -- its alpha is 1.0 throughout (it starts as black() and operator+ keeps the left alpha)
+// The words are quantity-major like the quads (word w of lane i at [w * STRIDE + i]): a wave's ds_read / ds_write touch 64 consecutive
+// dwords.  With -ffp-contract=off the product and the sum round separately in both layouts: the same bits.
+// -DRAYCA_CTX_COMPACT=0: seven whole quads (the context's five, the sample, the sum), the layout as it was, for A/B runs.
+#ifndef RAYCA_CTX_COMPACT
+#define RAYCA_CTX_COMPACT 1
+#endif
+#if RAYCA_CTX_COMPACT
+constexpr uint32_t kCtxQuads = 5, kCtxWords = 6;
+#else
+constexpr uint32_t kCtxQuads = 7, kCtxWords = 0;  // ShadeCtx (5) + the pending NEE sample's contribution + the running direct sum
+#endif
+constexpr uint32_t kCtxBytes = kCtxQuads * 16u + kCtxWords * 4u;  // per lane
+// A workgroup's parked contexts: the quads, and the words behind them.  A lane's slot of either is found where it is used,
+// from the lane's number made on the spot in a one-wave workgroup (two v_mbcnt; the empty-input asm cannot be hoisted or merged):
+// as pointers made at the kernel's entry the two slots were two registers live over the traversal loops, which at 96 registers the
+// compiler kept in scratch across every trace() call.
+struct CtxSlot {
+  uint32_t* base;
+};
+template <int STRIDE>
+__device__ __forceinline__ uint32_t ctx_tid() {
+  if (STRIDE != 64) return rc_tid();
+  uint32_t l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+template <int STRIDE>
+__device__ __forceinline__ float4* ctx_quads(const CtxSlot& s) { return reinterpret_cast<float4*>(s.base) + ctx_tid<STRIDE>(); }
+template <int STRIDE>
+__device__ __forceinline__ float* ctx_words(const CtxSlot& s) { return reinterpret_cast<float*>(s.base + kCtxQuads * 4u * STRIDE) + ctx_tid<STRIDE>(); }
 template <int STRIDE = kBlock>
-__device__ __forceinline__ void park_ctx(float4* slot, const ShadeCtx& c) {
+__device__ __forceinline__ void park_ctx(const CtxSlot& s, const ShadeCtx& c) {
+  float4* const slot = ctx_quads<STRIDE>(s);
+#if RAYCA_CTX_COMPACT
+  slot[0 * STRIDE] = make_float4(c.point.x, c.point.y, c.point.z, c.kind == RAYCA_MATERIAL_PHONG ? c.shininess : c.roughness);
+  slot[1 * STRIDE] = make_float4(c.normal.x, c.normal.y, c.normal.z, __uint_as_float(c.kind));
+  slot[2 * STRIDE] = make_float4(c.view.x, c.view.y, c.view.z, 0.0f);
+#else
   slot[0 * STRIDE] = make_float4(c.point.x, c.point.y, c.point.z, c.roughness);
   slot[1 * STRIDE] = make_float4(c.normal.x, c.normal.y, c.normal.z, c.shininess);
   slot[2 * STRIDE] = make_float4(c.view.x, c.view.y, c.view.z, __uint_as_float(c.kind));
+#endif
   slot[3 * STRIDE] = make_float4(c.kd.r, c.kd.g, c.kd.b, c.kd.a);
   slot[4 * STRIDE] = make_float4(c.ks.r, c.ks.g, c.ks.b, c.ks.a);
 }
 template <int STRIDE = kBlock>
-__device__ __forceinline__ ShadeCtx unpark_ctx(const float4* slot) {
+__device__ __forceinline__ ShadeCtx unpark_ctx(const CtxSlot& s) {
+  const float4* const slot = ctx_quads<STRIDE>(s);
   const float4 q0 = slot[0 * STRIDE], q1 = slot[1 * STRIDE], q2 = slot[2 * STRIDE], q3 = slot[3 * STRIDE], q4 = slot[4 * STRIDE];
   ShadeCtx c;
   c.point = f4(q0.x, q0.y, q0.z, 1.0f);   // Hit.point is a Point3
@@ -905,10 +959,77 @@ __device__ __forceinline__ ShadeCtx unpark_ctx(const float4* slot) {
   c.next_origin = c.point + c.normal * kRayBias;  // hit.rs:164-171, as in shade_hit
   c.kd = Color{q3.x, q3.y, q3.z, q3.w};
   c.ks = Color{q4.x, q4.y, q4.z, q4.w};
+#if RAYCA_CTX_COMPACT
+  c.roughness = c.shininess = q0.w;   // (the one surf_brdf reads for this kind)
+  c.kind = __float_as_uint(q1.w);
+#else
   c.roughness = q0.w;
   c.shininess = q1.w;
   c.kind = __float_as_uint(q2.w);
+#endif
   return c;
+}
+// The running sum of a vertex's direct samples and the pending sample, behind the context.
+// park_sum_reset: the sum = black().  (Made from a zero the compiler cannot hoist: as a loop-invariant value it sat in registers over
+// the whole batch loop, which the counting instantiations could only afford through scratch: with the pipelined node
+// loop k_generation<1, true, true, false, true, SPH, false, false, true, HALF> went from 0-2 to 4 spilled VGPRs and
+// k_generation<1, true, false, false, FAST, *, false, true, true, false> from 0-4 to 2-5 -- tests/kernel_resources.py)
+template <int STRIDE = kBlock>
+__device__ __forceinline__ void park_sum_reset(const CtxSlot& s) {
+  float zero = 0.0f;
+  asm volatile("" : "+v"(zero));
+#if RAYCA_CTX_COMPACT
+  float* const words = ctx_words<STRIDE>(s);
+  words[3 * STRIDE] = zero;
+  words[4 * STRIDE] = zero;
+  words[5 * STRIDE] = zero;
+#else
+  ctx_quads<STRIDE>(s)[6 * STRIDE] = make_float4(zero, zero, zero, 1.0f);
+#endif
+}
+// park_sample: the contribution the pending sample makes if its light turns out to be visible
+template <int STRIDE = kBlock>
+__device__ __forceinline__ void park_sample(const CtxSlot& s, Color x) {
+#if RAYCA_CTX_COMPACT
+  float* const words = ctx_words<STRIDE>(s);
+  words[0 * STRIDE] = x.r * x.a;
+  words[1 * STRIDE] = x.g * x.a;
+  words[2 * STRIDE] = x.b * x.a;
+#else
+  ctx_quads<STRIDE>(s)[5 * STRIDE] = make_float4(x.r, x.g, x.b, x.a);
+#endif
+}
+// park_sum_add: sum = sum + (lit ? the pending sample : black())
+template <int STRIDE = kBlock>
+__device__ __forceinline__ void park_sum_add(const CtxSlot& s, bool lit) {
+#if RAYCA_CTX_COMPACT
+  float* const words = ctx_words<STRIDE>(s);
+  const float r = words[3 * STRIDE] + (lit ? words[0 * STRIDE] : 0.0f);
+  const float g = words[4 * STRIDE] + (lit ? words[1 * STRIDE] : 0.0f);
+  const float b = words[5 * STRIDE] + (lit ? words[2 * STRIDE] : 0.0f);
+  words[3 * STRIDE] = r;
+  words[4 * STRIDE] = g;
+  words[5 * STRIDE] = b;
+#else
+  float4* const quads = ctx_quads<STRIDE>(s);
+  const float4 a = quads[6 * STRIDE], x = quads[5 * STRIDE];
+  const Color sum = Color{a.x, a.y, a.z, a.w} + (lit ? Color{x.x, x.y, x.z, x.w} : black());
+  quads[6 * STRIDE] = make_float4(sum.r, sum.g, sum.b, sum.a);
+#endif
+}
+template <int STRIDE = kBlock>
+__device__ __forceinline__ Color unpark_sum(const CtxSlot& s) {
+#if RAYCA_CTX_COMPACT
+  const float* const words = ctx_words<STRIDE>(s);
+  // (the alpha made here, like park_sum_reset's zero: as a loop-invariant lane of the colour's register tuple it went to scratch
+  // at the kernel's entry and came back, with the whole tuple, once per vertex)
+  float one = 1.0f;
+  asm volatile("" : "+v"(one));
+  return Color{words[3 * STRIDE], words[4 * STRIDE], words[5 * STRIDE], one};
+#else
+  const float4 a = ctx_quads<STRIDE>(s)[6 * STRIDE];
+  return Color{a.x, a.y, a.z, a.w};
+#endif
 }
 
 // get_color (primitive.rs:142-148) always; the rest only when `full` (Pathtracer).
