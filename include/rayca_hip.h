@@ -46,7 +46,8 @@ extern "C" {
                                   rayca_hip_denoise_variance_device; guided upsampling: RaycaUpsample,
                                   rayca_hip_upsample_device; exposure metering and tone mapping: RaycaMeter,
                                   rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_;
-                                  radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device */
+                                  radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device;
+                                  nearest-point queries: RaycaNearest, rayca_hip_nearest_device, RAYCA_NEAREST_ */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -352,7 +353,7 @@ enum {
   RAYCA_KERNEL_WF_SHADE = 4,      /* k_wf_shade: shading, NEE set-up, bounce sampling (wavefront.inc)                */
   RAYCA_KERNEL_WF_SHADOW = 5,     /* k_wf_shadow: shadow rays + direct sum, one pixel per lane (wavefront.inc)       */
   RAYCA_KERNEL_SHADOW_REFILL = 6, /* k_shadow_refill: the same with lane refill (refill.hip)                         */
-  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays, k_surface */
+  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays, k_surface, k_nearest */
   RAYCA_KERNEL_CLASSES = 8
 };
 
@@ -640,6 +641,76 @@ struct RaycaQuery {
 typedef struct RaycaQuery RaycaQuery;
 int32_t rayca_hip_query_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaQuery* query,
                                RaycaStats* stats_out);
+
+/* Nearest-point queries on DEVICE memory: for `count` caller-supplied points the nearest point of the scene's surface within a
+ * radius, and how far away it is -- distance fields, clearance and collision tests, snapping samples onto a mesh, picking by
+ * proximity.  Points, radii and results stay on the device and the call is asynchronous on the caller's stream.
+ *
+ * The specification, in f32 with every operation rounded on its own (+ - * /, comparisons and selects; no square root, which
+ * is why the SQUARED distance is returned).  x.y = (x0*y0 + x1*y1) + x2*y2.
+ *   Candidates: every triangle slot of the scene (post-build primitive order; the two triangles of a quad light count, as they
+ *   do for closest hits).  A scene with spheres is refused: RAYCA_ERR_UNSUPPORTED.
+ *   Nearest point q on triangle (a, b, c) = the slot's world-space vertices 0, 1, 2, to the point p (Ericson, Real-Time
+ *   Collision Detection 5.1.5):
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c                        (componentwise)
+ *     d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp
+ *     vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4
+ *     the first of these tests that holds decides (s, t):
+ *       d1 <= 0 and d2 <= 0                          vertex a   (s, t) = (0, 0)
+ *       d3 >= 0 and d4 <= d3                         vertex b   (s, t) = (1, 0)
+ *       vc <= 0 and d1 >= 0 and d3 <= 0              edge ab    s = d1 / (d1 - d3), t = 0
+ *       d6 >= 0 and d5 <= d6                         vertex c   (s, t) = (0, 1)
+ *       vb <= 0 and d2 >= 0 and d6 <= 0              edge ac    s = 0, t = d2 / (d2 - d6)
+ *       va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    edge bc    t = (d4 - d3) / ((d4 - d3) + (d5 - d6)), s = 1 - t
+ *       none                                         interior   s = vb / ((va + vb) + vc), t = vc / ((va + vb) + vc), then
+ *                                                               s = s < 0 ? 0 : s, s = s > 1 ? 1 : s, t = t < 0 ? 0 : t,
+ *                                                               t = t > 1 - s ? 1 - s : t
+ *     (the selects of the interior branch change nothing unless rounding has left va, vb, vc with mixed signs -- a point very
+ *     far away, a needle -- and then keep q on the triangle)
+ *     q = (a + ab*s) + ac*t componentwise; in the three vertex regions q is the vertex itself.  d = p - q, dist2 = d.d.
+ *     A candidate whose dist2 is NaN is no candidate: a degenerate triangle whose quotient is 0 / 0 (two equal vertices in the
+ *     region of their edge, va + vb + vc = 0 in the interior branch), vertices whose products overflow (a NaN fails every
+ *     comparison it enters and ends in the interior branch).  Other degenerate triangles are the segment or point they are.
+ *   Bound: r2 = radius * radius.  A candidate counts iff dist2 < r2, strictly.  radius = +inf or FLT_MAX is unbounded (r2 =
+ *   +inf); a candidate with dist2 = +inf never counts.  A radius that is NaN or <= 0 gives a miss; a point with a coordinate
+ *   that is not finite gives a miss.
+ *   Result: among the candidates that count the smallest dist2 wins; on equal dist2 the lowest slot.  (Ties are common: the
+ *   nearest points of two triangles that share a vertex or an edge are often the same three floats.  Slots differ between
+ *   builders, and so may the winner of a tie.)
+ *   RAYCA_NEAREST_CLOSEST  per point dist2, the slot, q and (u, v) = ((1 - s) - t, s): the weights of vertex 0 and vertex 1,
+ *                          the convention of hit records, so that prim_out / uv_out can be handed to
+ *                          rayca_hip_surface_device as they are (colour, material, flags).  A miss is dist2 = FLT_MAX,
+ *                          prim = RAYCA_NONE, zeros elsewhere.  Any of the four outputs may be NULL, not all.
+ *   RAYCA_NEAREST_WITHIN   one byte per point: 1 iff CLOSEST with the same radius reports a hit.  A point's search ends at the
+ *                          first candidate that counts.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event,
+ * collect_stats and traversal as for rayca_hip_query_device; RAYCA_TRAVERSAL_EXHAUSTIVE visits every node and every triangle
+ * without the cull, gives the same results bit for bit and is offered for CLOSEST only (RAYCA_ERR_UNSUPPORTED for WITHIN);
+ * tile, engine and camera_rays must be zero.  Ordered on its context like a query.  With stats_out the call waits: the kernel's
+ * time under RAYCA_KERNEL_OTHER (with collect_stats it includes reading the counters back), kernel_launches = 1, boxes_tested
+ * and triangles_tested under collect_stats, every rays_* field 0.  count == 0 is RAYCA_OK and launches nothing; nothing outside
+ * [0, count) of an output is written.
+ * RAYCA_ERR_BAD_ARG, before any GPU work and before the scene is looked at, in this order: NULL scene / query, NULL points,
+ * unknown kind, non-zero reserved, no output for the kind; then context > 7, a non-zero field of opts that does not apply;
+ * then RAYCA_ERR_UNSUPPORTED for EXHAUSTIVE with WITHIN.  Then (count != 0) RAYCA_ERR_EMPTY_SCENE as the query, and
+ * RAYCA_ERR_UNSUPPORTED for a scene with spheres. */
+enum { RAYCA_NEAREST_CLOSEST = 0, RAYCA_NEAREST_WITHIN = 1 };
+struct RaycaNearest {
+  uint32_t kind;        /* RAYCA_NEAREST_* */
+  uint32_t count;
+  const void* points;   /* DEVICE: count x 3 f32 */
+  const void* radius;   /* DEVICE: count f32, or NULL => radius_all for every point */
+  float radius_all;
+  uint32_t reserved;    /* must be zero */
+  void* dist2_out;      /* CLOSEST, DEVICE: count f32, SQUARED distance, FLT_MAX on a miss */
+  void* prim_out;       /* CLOSEST, DEVICE: count u32 slot (post-build primitive order), RAYCA_NONE on a miss */
+  void* point_out;      /* CLOSEST, DEVICE: count x 3 f32, the nearest point, 0 on a miss */
+  void* uv_out;         /* CLOSEST, DEVICE: count x 2 f32 in the convention of hit records, 0 on a miss */
+  void* within_out;     /* WITHIN, DEVICE: count u8, 1 / 0 */
+};
+typedef struct RaycaNearest RaycaNearest;
+int32_t rayca_hip_nearest_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaNearest* query,
+                                 RaycaStats* stats_out);
 
 /* Surface records for hit records, on DEVICE memory: what is AT a hit, where rayca_hip_query_device says where the hit is.  Per
  * record (the ray, t, prim, u, v exactly as RAYCA_QUERY_CLOSEST writes them) the values a render kernel has in hand at the same

@@ -73,6 +73,9 @@ pub const RAYCA_KERNEL_CLASSES: u32 = 8;
 // RaycaQuery.kind
 pub const RAYCA_QUERY_CLOSEST: u32 = 0;
 pub const RAYCA_QUERY_OCCLUDED: u32 = 1;
+// RaycaNearest.kind
+pub const RAYCA_NEAREST_CLOSEST: u32 = 0;
+pub const RAYCA_NEAREST_WITHIN: u32 = 1;
 // RaycaTonemap.op
 pub const RAYCA_TONEMAP_LINEAR: u32 = 0;
 pub const RAYCA_TONEMAP_REINHARD: u32 = 1;
@@ -301,6 +304,23 @@ pub struct RaycaQuery {
     pub prim_out: *mut c_void,
     pub uv_out: *mut c_void,
     pub occluded_out: *mut c_void,
+}
+
+// rayca_hip_nearest_device: points, radii and results in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaNearest {
+    pub kind: u32,
+    pub count: u32,
+    pub points: *const c_void,
+    pub radius: *const c_void,
+    pub radius_all: f32,
+    pub reserved: u32,
+    pub dist2_out: *mut c_void,
+    pub prim_out: *mut c_void,
+    pub point_out: *mut c_void,
+    pub uv_out: *mut c_void,
+    pub within_out: *mut c_void,
 }
 
 // rayca_hip_surface_device: hit records in, surface records out, all in DEVICE memory
@@ -560,6 +580,7 @@ extern "C" {
     pub fn rayca_hip_tile_rows(tile: *const RaycaTile, height: u32) -> u32;
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_nearest_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaNearest, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;

@@ -43,6 +43,7 @@ KERNEL_GENERATION, KERNEL_FLAT_REFILL, KERNEL_WF_TRACE, KERNEL_QUEUE_REFILL, KER
 KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill", "k_wf_shade", "k_wf_shadow", "k_shadow_refill", "other")
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # RaycaQuery.kind
+NEAREST_CLOSEST, NEAREST_WITHIN = 0, 1   # RaycaNearest.kind
 TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
 TONEMAP_NAMES = ("linear", "reinhard", "aces")
 METER_WORDS, METER_COUNTED, METER_BLACK, METER_NOT_FINITE = 260, 256, 257, 258   # hist_out of rayca_hip_meter_device
@@ -294,6 +295,23 @@ class RaycaQuery(C.Structure):
         ("prim_out", C.c_void_p),
         ("uv_out", C.c_void_p),
         ("occluded_out", C.c_void_p),
+    ]
+
+
+class RaycaNearest(C.Structure):
+    """rayca_hip_nearest_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("count", C.c_uint32),
+        ("points", C.c_void_p),
+        ("radius", C.c_void_p),
+        ("radius_all", C.c_float),
+        ("reserved", C.c_uint32),
+        ("dist2_out", C.c_void_p),
+        ("prim_out", C.c_void_p),
+        ("point_out", C.c_void_p),
+        ("uv_out", C.c_void_p),
+        ("within_out", C.c_void_p),
     ]
 
 
@@ -601,6 +619,8 @@ def bind_product_signatures(lib):
                                          C.c_void_p, C.c_void_p, P(RaycaStats)]
     lib.rayca_hip_query_device.restype = C.c_int32
     lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
+    lib.rayca_hip_nearest_device.restype = C.c_int32
+    lib.rayca_hip_nearest_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaNearest), P(RaycaStats)]
     lib.rayca_hip_surface_device.restype = C.c_int32
     lib.rayca_hip_surface_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceQuery), P(RaycaStats)]
     lib.rayca_hip_camera_rays_device.restype = C.c_int32
@@ -641,7 +661,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_version", "rayca_hip_device_count", "rayca_hip_selftest", "rayca_hip_last_error", "rayca_hip_config_default",
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
-    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device",
+    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device",

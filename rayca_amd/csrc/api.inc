@@ -1534,6 +1534,68 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   return RAYCA_OK;
 }
 
+// Nearest-point queries (nearest.inc k_nearest): one point per lane on the binary f32 nodes, which every scene has from
+// scene_create on, so the call never waits for the formats thread.  A pass on its context (run_pass), which clears the work
+// counters on the launch stream when they are read.
+int32_t rayca_hip_nearest_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaNearest* nin, RaycaStats* stats_out) {
+  if (!s || !nin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaNearest");
+  const RaycaNearest& rn = *nin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (!rn.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaNearest.points: null points");
+  if (rn.kind != RAYCA_NEAREST_CLOSEST && rn.kind != RAYCA_NEAREST_WITHIN) return fail(RAYCA_ERR_BAD_ARG, "RaycaNearest.kind: unknown kind");
+  if (rn.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaNearest.reserved must be zero");
+  const bool within = rn.kind == RAYCA_NEAREST_WITHIN;
+  if (within ? !rn.within_out : (!rn.dist2_out && !rn.prim_out && !rn.point_out && !rn.uv_out))
+    return fail(RAYCA_ERR_BAD_ARG, "no output for this kind of nearest-point query");
+  int32_t rc = pass_options(o, "a nearest-point query", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  const bool cull = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
+  if (within && !cull) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: RAYCA_NEAREST_WITHIN ends at its first candidate: there is no exhaustive form");
+  if (rn.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  if (s->host.sphere_count != 0)
+    return fail(RAYCA_ERR_UNSUPPORTED, "a scene with spheres has no nearest-point query: a sphere under a non-uniform scale is an ellipsoid, whose nearest point has no closed form");
+  NearestIo io{};
+  io.points = static_cast<const float*>(rn.points);
+  io.radius = static_cast<const float*>(rn.radius);
+  io.radius_all = rn.radius_all;
+  io.count = rn.count;
+  if (within) {
+    io.within_out = static_cast<uint8_t*>(rn.within_out);
+  } else {
+    io.dist2_out = static_cast<float*>(rn.dist2_out);
+    io.prim_out = static_cast<uint32_t*>(rn.prim_out);
+    io.point_out = static_cast<float*>(rn.point_out);
+    io.uv_out = static_cast<float*>(rn.uv_out);
+  }
+  const bool stats = o.collect_stats != 0;
+  const StackPlan sp = plan_stack(s->host.max_depth);   // (as k_query_rays is launched: one pending sibling per level)
+  const uint32_t grid = (uint32_t)(((uint64_t)rn.count + kBlock - 1u) / kBlock);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  rc = run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    TraceLaunch tl{};
+    if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+    if (stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+    hipLaunchKernelGGL(pick_nearest_kernel(within, cull, sp.spill_entries != 0, stats), dim3(grid), dim3(kBlock), sp.lds_bytes, stream,
+                       formats_ready(s) ? s->dev_full : s->dev, io, c->counters, tl);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+    if (stats && stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+    return RAYCA_OK;
+  });
+  if (rc != RAYCA_OK || !stats_out || !stats) return rc;
+  stats_out->boxes_tested = tc.boxes;
+  stats_out->triangles_tested = tc.tris;
+  return RAYCA_OK;
+}
+
 // Surface records for hit records (surface.inc k_surface): no traversal, one launch.  A pass on its context (ContextPass), so
 // that a rayca_hip_scene_update of materials never overwrites a table this kernel is still reading.
 int32_t rayca_hip_surface_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSurfaceQuery* qin, RaycaStats* stats_out) {

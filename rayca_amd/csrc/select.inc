@@ -77,6 +77,12 @@ SurfaceKernel pick_surface_kernel(bool sph) {
   return with_flags([](auto SPH) -> SurfaceKernel { return k_surface<SPH>; }, sph);
 }
 
+// k_nearest (nearest.inc): flags only.  WITHIN ends at the first candidate that counts, so it has the culled form alone
+using NearestKernel = void (*)(DevScene, NearestIo, TraceCounters*, TraceLaunch);
+NearestKernel pick_nearest_kernel(bool within, bool cull, bool spill, bool stats) {
+  return with_flags([](auto WITHIN, auto CULL, auto SPILL, auto STATS) -> NearestKernel { return k_nearest<WITHIN && CULL, CULL, SPILL, STATS>; }, within, cull, spill, stats);
+}
+
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
 // else 24 entries + a global spill area for the rest
 #ifndef RAYCA_MAX_LDS_ENTRIES
@@ -440,6 +446,8 @@ int32_t selftest_kernel_selection(std::string& err) {
        [&](Trav, uint32_t i) { return (i & 7u) | (!b(i, 2) && (b(i, 1) ? b(i, 4) : b(i, 3)) ? 8u : 0u); }},   // a caller's rays: neither gen0 nor fused is read
       {"pick_general_kernel(fast, sph, stats)", none, 3, [&](Trav, uint32_t i) { return P(pick_general_kernel(b(i, 0), b(i, 1), b(i, 2))); }, every},
       {"pick_surface_kernel(sph)", none, 1, [&](Trav, uint32_t i) { return P(pick_surface_kernel(b(i, 0))); }, every},
+      {"pick_nearest_kernel(within, cull, spill, stats)", none, 4, [&](Trav, uint32_t i) { return P(pick_nearest_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
+       [&](Trav, uint32_t i) { return b(i, 1) ? i : i & ~1u; }},   // the exhaustive form does not read within
       {"flat_refill_kernel(trav; sph, stats)", fast, 2, [&](Trav t, uint32_t i) { return flat_refill_kernel(RefillFlavour{t, b(i, 0), b(i, 1)}); }, every},
       {"queue_refill_kernel(sph, stats, slack)", none, 3, [&](Trav, uint32_t i) { return queue_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"query_refill_kernel(occluded, sph, stats)", none, 3, [&](Trav, uint32_t i) { return query_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},

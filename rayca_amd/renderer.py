@@ -226,6 +226,62 @@ class DeviceScene:
             return result
         return (result, stats) if occluded else (*result, stats)
 
+    def nearest(self, points, *, radius=None, kind="closest", stream=None, context=0, out=None, want_stats=False,
+                traversal=abi.TRAVERSAL_ORDERED, collect_stats=False):
+        """rayca_hip_nearest_device: the nearest surface point to points that live in device memory, asynchronously.
+
+        points: torch tensor (N, 3) float32 on this scene's device.  radius: None (unbounded), a float for every point, or an
+        (N,) float32 tensor; a surface point counts iff its SQUARED distance is below radius * radius.  kind "closest" returns
+        (dist2, prim, point, uv): float32 (N,) squared distances with FLT_MAX on a miss, int32 (N,) holding the u32 primitive
+        slot (abi.NONE, i.e. -1, on a miss), float32 (N, 3) nearest points and float32 (N, 2) in the convention of hit records
+        -- prim and uv go to surface() as they are; kind "within" returns a uint8 (N,) mask.  `out`: the tensor(s) to write
+        instead of new ones (for "closest" a 4-tuple: None makes a new tensor, False leaves that output out; not all four).
+        Scenes with spheres are refused (ERR_UNSUPPORTED).  Stream handling and statistics as query()."""
+        if kind not in ("closest", "within"):
+            raise ValueError(f"kind must be 'closest' or 'within', not {kind!r}")
+        within = kind == "within"
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+        n = points.shape[0]
+        if n > 0xFFFFFFFF:
+            raise ValueError("points: more than 2**32 - 1 points")
+        q = abi.RaycaNearest()
+        q.kind, q.count = (abi.NEAREST_WITHIN if within else abi.NEAREST_CLOSEST), n
+        if within:
+            result = call.output(out, "out", torch.uint8, (n,))
+            q.within_out = result.data_ptr()
+        else:
+            o_d, o_prim, o_point, o_uv = out if out is not None else (None, None, None, None)
+            result = (call.output(o_d, "out[0] (dist2)", torch.float32, (n,), optional=o_d is False),
+                      call.output(o_prim, "out[1] (prim)", torch.int32, (n,), optional=o_prim is False),
+                      call.output(o_point, "out[2] (point)", torch.float32, (n, 3), optional=o_point is False),
+                      call.output(o_uv, "out[3] (uv)", torch.float32, (n, 2), optional=o_uv is False))
+            if all(x is None for x in result):
+                raise ValueError("out: at least one of the four outputs must be asked for")
+            q.dist2_out, q.prim_out, q.point_out, q.uv_out = (_ptr(x) for x in result)
+        q.points = call.input(points, "points", torch.float32, (n, 3)).data_ptr()
+        if radius is None:
+            q.radius_all = float("inf")
+        elif isinstance(radius, torch.Tensor):
+            q.radius = call.input(radius, "radius", torch.float32, (n,)).data_ptr()
+        else:
+            q.radius_all = float(radius)
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_nearest_device, q, context=context, want_stats=want_stats or collect_stats,
+                             traversal=traversal, collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is None:
+            return result
+        return (result, stats) if within else (*result, stats)
+
     # ---- surface queries: what is at a hit (rayca_hip_surface_device), and the rays of a frame (rayca_hip_camera_rays_device) ----
     SURFACE_OUTPUTS = {"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
                        "specular": ("float32", 4), "rough": ("float32", 2), "material": ("int32", 0), "flags": ("int32", 0)}
