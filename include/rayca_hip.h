@@ -47,7 +47,8 @@ extern "C" {
                                   rayca_hip_upsample_device; exposure metering and tone mapping: RaycaMeter,
                                   rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_;
                                   radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device;
-                                  nearest-point queries: RaycaNearest, rayca_hip_nearest_device, RAYCA_NEAREST_ */
+                                  nearest-point queries: RaycaNearest, rayca_hip_nearest_device, RAYCA_NEAREST_;
+                                  ambient occlusion: RaycaAmbient, rayca_hip_ambient_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -710,6 +711,74 @@ struct RaycaNearest {
 };
 typedef struct RaycaNearest RaycaNearest;
 int32_t rayca_hip_nearest_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaNearest* query,
+                                 RaycaStats* stats_out);
+
+/* Ambient occlusion on DEVICE memory: how open the scene is at `count` caller-supplied points -- `samples` occlusion rays over the
+ * hemisphere of each point's normal, folded into one record per point: ambient occlusion on a G-buffer, sky visibility, per-vertex
+ * baking, contact shadows.  The rays are made in registers inside the traversal kernel: no ray buffer is written or read, and the
+ * surface records of rayca_hip_surface_device (point, normal) go in as they are.  Asynchronous on the caller's stream.
+ *
+ * The specification, in f32 with every operation rounded on its own (+ - * /, comparisons and selects; no square root, no
+ * trigonometry).
+ *   Per point i: position p; normal n (expected unit length, not checked); optionally a rotation (c, s); optionally a radius.
+ *   Per call: a table `dirs` of dir_count local directions (lx, ly, lz), z along the normal; samples = S, 1 <= S <= 64; dir_first
+ *   with dir_first + S <= dir_count; bias; radius_all.
+ *   Frame (the branch-free basis of Duff et al. 2017, its sign taken by a comparison):
+ *     sg = n.z >= 0 ? 1 : -1
+ *     a  = -1 / (sg + n.z)
+ *     b  = (n.x * n.y) * a
+ *     T  = (1 + ((sg * n.x) * n.x) * a,  sg * b,  (-sg) * n.x)
+ *     B  = (b,  sg + (n.y * n.y) * a,  -n.y)
+ *   Sample j of point i:
+ *     (lx, ly, lz) = dirs[dir_first + j]
+ *     rx = c * lx - s * ly
+ *     ry = s * lx + c * ly          (without a rotation array: rx = lx, ry = ly, and no operation is performed)
+ *     d  = ((T * rx) + (B * ry)) + n * lz        componentwise
+ *     o  = p + n * bias                          componentwise
+ *   Occlusion: sample j is occluded iff rayca_hip_query_device(RAYCA_QUERY_OCCLUDED) reports 1 for the ray (o, d) with tmax = the
+ *   point's radius: the same traversal, the same strict t < tmax, +inf / FLT_MAX unbounded, a radius that is NaN or <= 0 never
+ *   occluded.  t is the ray parameter: a distance only as far as |d| is 1.
+ *   Inactive points: a point is inactive iff n.x == 0 && n.y == 0 && n.z == 0, or any of the six inputs p, n is not finite.  (The
+ *   zero test is what rayca_hip_surface_device writes for a miss: a G-buffer goes in as it is.)  An inactive point traces nothing
+ *   and has every sample unoccluded.
+ *   Outputs (any may be NULL, not all), per point:
+ *     mask_out  u64      bit j = sample j occluded
+ *     hits_out  u32      popcount of the mask
+ *     open_out  f32      float(S - hits) / float(S)
+ *     bent_out  3 x f32  acc = 0; for j ascending: if not occluded, acc = acc + d_j  (unnormalised: the caller normalises)
+ *   An inactive point gives mask 0, hits 0, open 1, bent 0.  Results do not depend on the order in which rays are traced: the
+ *   mask is assembled with integer OR only, and bent is summed from the finished mask in j order.
+ * opts (may be NULL): stream, context, wait_event, record_event and collect_stats as for rayca_hip_query_device; traversal must be
+ * RAYCA_TRAVERSAL_ORDERED (RAYCA_ERR_UNSUPPORTED for EXHAUSTIVE, as for an OCCLUDED query); tile, engine and camera_rays must be
+ * zero.  Ordered on its context like a query.  Without mask_out the mask words live in the context's work buffers.  With
+ * stats_out the call waits: rays_shadow = count x S, the time (clearing the mask words included) under RAYCA_KERNEL_OTHER,
+ * kernel_launches = the kernels launched (the trace kernel, and the fold unless mask_out is the only output), boxes_tested and
+ * triangles_tested under collect_stats.  count == 0 is RAYCA_OK and launches nothing; nothing outside [0, count) of an output is
+ * written.  Scenes with spheres are served.
+ * Refusals, before any GPU work and before the scene is looked at, in this order.  RAYCA_ERR_BAD_ARG: NULL scene / struct; NULL
+ * points, normals, dirs; samples 0 or > 64; dir_first + samples > dir_count; non-zero reserved; no output; mask_out not aligned to
+ * 8 bytes; bias not finite; count x samples >= 2^32; then context > 7, a non-zero field of opts that does not apply.  Then
+ * RAYCA_ERR_UNSUPPORTED for EXHAUSTIVE.  Then (count != 0) RAYCA_ERR_EMPTY_SCENE as the query. */
+struct RaycaAmbient {
+  uint32_t count;
+  uint32_t samples;       /* S: 1 .. 64 */
+  const void* points;     /* DEVICE: count x 3 f32 */
+  const void* normals;    /* DEVICE: count x 3 f32; (0, 0, 0) marks an inactive point */
+  const void* rotations;  /* DEVICE: count x 2 f32 (cos, sin), or NULL => no rotation */
+  const void* radius;     /* DEVICE: count f32, or NULL => radius_all for every point */
+  const void* dirs;       /* DEVICE: dir_count x 3 f32 local directions, z along the normal */
+  uint32_t dir_count;
+  uint32_t dir_first;     /* sample j takes dirs[dir_first + j] */
+  float radius_all;
+  float bias;             /* o = p + n * bias; finite */
+  uint32_t reserved;      /* must be zero */
+  void* mask_out;         /* DEVICE: count u64, aligned to 8 bytes */
+  void* hits_out;         /* DEVICE: count u32 */
+  void* open_out;         /* DEVICE: count f32 */
+  void* bent_out;         /* DEVICE: count x 3 f32 */
+};
+typedef struct RaycaAmbient RaycaAmbient;
+int32_t rayca_hip_ambient_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaAmbient* ambient,
                                  RaycaStats* stats_out);
 
 /* Surface records for hit records, on DEVICE memory: what is AT a hit, where rayca_hip_query_device says where the hit is.  Per

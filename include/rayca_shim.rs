@@ -323,6 +323,28 @@ pub struct RaycaNearest {
     pub within_out: *mut c_void,
 }
 
+// rayca_hip_ambient_device: points, normals and a direction table in, one record per point out, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaAmbient {
+    pub count: u32,
+    pub samples: u32,
+    pub points: *const c_void,
+    pub normals: *const c_void,
+    pub rotations: *const c_void,
+    pub radius: *const c_void,
+    pub dirs: *const c_void,
+    pub dir_count: u32,
+    pub dir_first: u32,
+    pub radius_all: f32,
+    pub bias: f32,
+    pub reserved: u32,
+    pub mask_out: *mut c_void,
+    pub hits_out: *mut c_void,
+    pub open_out: *mut c_void,
+    pub bent_out: *mut c_void,
+}
+
 // rayca_hip_surface_device: hit records in, surface records out, all in DEVICE memory
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -581,6 +603,7 @@ extern "C" {
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_nearest_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaNearest, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_ambient_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, ambient: *const RaycaAmbient, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;

@@ -315,6 +315,28 @@ class RaycaNearest(C.Structure):
     ]
 
 
+class RaycaAmbient(C.Structure):
+    """rayca_hip_ambient_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("points", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("rotations", C.c_void_p),
+        ("radius", C.c_void_p),
+        ("dirs", C.c_void_p),
+        ("dir_count", C.c_uint32),
+        ("dir_first", C.c_uint32),
+        ("radius_all", C.c_float),
+        ("bias", C.c_float),
+        ("reserved", C.c_uint32),
+        ("mask_out", C.c_void_p),
+        ("hits_out", C.c_void_p),
+        ("open_out", C.c_void_p),
+        ("bent_out", C.c_void_p),
+    ]
+
+
 class RaycaSurfaceQuery(C.Structure):
     """rayca_hip_surface_device: every pointer is DEVICE memory."""
     _fields_ = [
@@ -621,6 +643,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
     lib.rayca_hip_nearest_device.restype = C.c_int32
     lib.rayca_hip_nearest_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaNearest), P(RaycaStats)]
+    lib.rayca_hip_ambient_device.restype = C.c_int32
+    lib.rayca_hip_ambient_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaAmbient), P(RaycaStats)]
     lib.rayca_hip_surface_device.restype = C.c_int32
     lib.rayca_hip_surface_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceQuery), P(RaycaStats)]
     lib.rayca_hip_camera_rays_device.restype = C.c_int32
@@ -662,6 +686,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device",
+    "rayca_hip_ambient_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device",

@@ -82,6 +82,7 @@ struct FrameCtx {
   DeviceBuffer path_direct, path_brdf, path_state, accum, queue[2], out8, out32, ray_io, stack_spill, frames, mis_samples, wf_hits, wf_sh_ray, wf_sh_x;
   DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
   DeviceBuffer denoise_var[2];        // rayca_hip_denoise_variance_device: the two variance planes that go with them (4 B a pixel)
+  DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
                                       // previous frame cleared them): generation 0 needs no memset launch
@@ -93,7 +94,7 @@ struct FrameCtx {
   // and made its device current.  (A buffer this list forgets is not leaked: its own destructor frees it, with the context.)
   void release() {
     for (DeviceBuffer* b : {&path_direct, &path_brdf, &path_state, &accum, &queue[0], &queue[1], &out8, &out32, &ray_io, &stack_spill, &frames, &mis_samples,
-                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1]})
+                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask})
       b->release();
     if (heads_alloc) (void)hipFree(heads_alloc);
     if (counters) (void)hipFree(counters);
@@ -1593,6 +1594,116 @@ int32_t rayca_hip_nearest_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   if (rc != RAYCA_OK || !stats_out || !stats) return rc;
   stats_out->boxes_tested = tc.boxes;
   stats_out->triangles_tested = tc.tris;
+  return RAYCA_OK;
+}
+
+// Hemisphere visibility at points (ambient.inc, refill.hip k_ambient_refill): count x samples occlusion rays made in registers, one
+// mask word per point, folded by k_ambient_finish.  The trace kernel is chosen as rayca_hip_query_device chooses an OCCLUDED query's:
+// the lane-refill form on the 4-wide fp16 nodes for a RAYCA_BUILDER_SAH scene whose formats are there, else one ray per lane on
+// the binary f32 nodes.  The mask words live in mask_out, or in the context's scratch (grown before the pass queues its waits);
+// they are cleared on the launch stream in front of the trace kernel.  A pass on its context (run_pass).
+int32_t rayca_hip_ambient_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaAmbient* ain, RaycaStats* stats_out) {
+  if (!s || !ain) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaAmbient");
+  const RaycaAmbient& ra = *ain;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (!ra.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.points: null points");
+  if (!ra.normals) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.normals: null normals");
+  if (!ra.dirs) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.dirs: null dirs");
+  if (ra.samples == 0 || ra.samples > 64) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.samples: 1 .. 64 samples (one bit of the mask word each)");
+  if (ra.dir_first > ra.dir_count || ra.samples > ra.dir_count - ra.dir_first)
+    return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.dir_first + samples exceeds dir_count");
+  if (ra.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.reserved must be zero");
+  if (!ra.mask_out && !ra.hits_out && !ra.open_out && !ra.bent_out) return fail(RAYCA_ERR_BAD_ARG, "no output for an ambient call");
+  if (reinterpret_cast<uintptr_t>(ra.mask_out) % 8u != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.mask_out must be aligned to 8 bytes");
+  if (!std::isfinite(ra.bias)) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.bias is not finite");
+  if ((uint64_t)ra.count * ra.samples >= (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaAmbient.count x samples must stay below 2^32");
+  int32_t rc = pass_options(o, "an ambient call", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE)
+    return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: an occlusion ray ends at its first hit: there is no exhaustive form");
+  if (ra.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  AmbientIo io{};
+  io.points = static_cast<const float*>(ra.points);
+  io.normals = static_cast<const float*>(ra.normals);
+  io.rotations = static_cast<const float*>(ra.rotations);
+  io.radius = static_cast<const float*>(ra.radius);
+  io.dirs = static_cast<const float*>(ra.dirs) + 3ull * ra.dir_first;
+  io.radius_all = ra.radius_all;
+  io.bias = ra.bias;
+  io.count = ra.count;
+  io.samples = ra.samples;
+  io.mask_out = static_cast<unsigned long long*>(ra.mask_out);
+  io.hits_out = static_cast<uint32_t*>(ra.hits_out);
+  io.open_out = static_cast<float*>(ra.open_out);
+  io.bent_out = static_cast<float*>(ra.bent_out);
+  const bool stats = o.collect_stats != 0, sph = s->host.sphere_count != 0, rot = ra.rotations != nullptr, bent = ra.bent_out != nullptr;
+  const bool fold = ra.hits_out || ra.open_out || bent;   // (mask_out alone is the trace kernel's own work)
+  const uint32_t total = ra.count * ra.samples, batches = (total + 63u) / 64u;
+  const size_t mask_bytes = (size_t)ra.count * sizeof(unsigned long long);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  uint32_t node_format = 0;
+  rc = run_pass(
+      s, o, stats_out,
+      [&](FrameCtx* ctx) -> int32_t {
+        if (io.mask_out) return RAYCA_OK;
+        HIP_TRY(hipSetDevice(s->device));
+        return grow_behind_pass(ctx, ctx->ambient_mask, mask_bytes);
+      },
+      [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+        io.mask = io.mask_out ? io.mask_out : static_cast<unsigned long long*>(c->ambient_mask.ptr);
+        const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+        const bool all_formats = formats_ready(s);
+        const bool refill = fast && all_formats;           // (rayca_hip_query_device's rule for an ordered query)
+        uint32_t grid = (batches + 3u) / 4u;               // one ray per lane; the persistent grid below replaces it
+        StackPlan sp{};
+        node_format = all_formats ? 0u : 2048u;
+        if (refill) {
+          sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
+          const uint32_t in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
+          if (const int32_t grc = persistent_grid(s, ambient_refill_kernel(rot, sph, stats), sp.lds_bytes, batches, true, in_flight, 0u, grid); grc != RAYCA_OK) return grc;
+          node_format |= (RAYCA_WF_BOUNCE_WIDE ? 1u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 4u : 0u);
+        } else {
+          sp = plan_stack(s->host.max_depth);
+          if (fast && RAYCA_NODE_CH && RAYCA_NODE_CH48 && s->dev.nodes_ch) node_format |= 4096u;
+        }
+        TraceLaunch tl{};
+        if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+        if (stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+        HIP_TRY(hipMemsetAsync(io.mask, 0, mask_bytes, stream));
+        if (refill) {
+          tl.ticket = 1u;
+          HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
+          c->heads_clean = false;   // the next frame of this context clears them for itself
+          launch_ambient_refill(rot, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, io, c->heads, c->counters, tl);
+        } else {
+          hipLaunchKernelGGL(pick_ambient_kernel(fast, sph, stats, rot), dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, io,
+                             c->counters, tl);
+        }
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        if (fold) {
+          hipLaunchKernelGGL(pick_ambient_finish(bent, rot), dim3((ra.count + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, io);
+          HIP_TRY(hipGetLastError());
+          ++launches;
+        }
+        // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+        if (stats && stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+        return RAYCA_OK;
+      });
+  if (rc != RAYCA_OK || !stats_out) return rc;
+  stats_out->rays_shadow = total;
+  stats_out->boxes_tested = tc.boxes;
+  stats_out->triangles_tested = tc.tris;
+  stats_out->wave_box_slots = tc.box_slots;
+  stats_out->wave_triangle_slots = tc.tri_slots;
+  stats_out->node_format = node_format;
   return RAYCA_OK;
 }
 

@@ -128,6 +128,22 @@ struct QueryIo {
   uint8_t* occluded_out;
 };
 
+// points, normals and the hemisphere table in, one record per point out, all in DEVICE memory (rayca_hip_ambient_device)
+struct AmbientIo {
+  const float* points;     // count x 3
+  const float* normals;    // count x 3
+  const float* rotations;  // count x 2 (cos, sin), or nullptr: no rotation
+  const float* radius;     // count, or nullptr: radius_all for every point
+  const float* dirs;       // samples x 3 local directions: the table from dir_first on
+  float radius_all, bias;
+  uint32_t count, samples;
+  unsigned long long* mask;      // count words the trace kernels OR into (cleared in front of them): mask_out, or the context's scratch
+  unsigned long long* mask_out;  // what k_ambient_finish writes: any may be nullptr
+  uint32_t* hits_out;
+  float* open_out;
+  float* bent_out;
+};
+
 // per generation, per pixel record used to fold the path back in the reference's evaluation order
 enum : uint32_t { kVertexNone = 0, kVertexLit = 1, kVertexEmissive = 2, kVertexLitNoIndirect = 3 };
 

@@ -18,6 +18,9 @@
 //   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
 //   k_nearest         nearest-point queries: the closest surface point to points in device memory, within a radius
 //                     (nearest.inc: rayca_hip_nearest_device).
+//   k_ambient_rays,   hemisphere visibility at points: occlusion rays made in registers, one per lane, and the fold of a point's
+//   k_ambient_finish  mask word into hits, openness and the bent normal (ambient.inc: rayca_hip_ambient_device; the lane-refill
+//                     form is refill.hip k_ambient_refill).
 //   tile_pixel, ...   what the image-space passes below share: the 64 x 4 tile prologue, the guide terms of a tap, luminance,
 //                     albedo (de)modulation and the output stage (image_pass.inc; their entry points are in post.inc).
 //   k_atrous,         the edge-avoiding a-trous denoiser on a frame and its G-buffer in device memory
@@ -444,6 +447,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "wavefront.inc"
 #include "surface.inc"
 #include "nearest.inc"
+#include "ambient.inc"
 RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "image_pass.inc"
 #include "denoise.inc"

@@ -27,6 +27,12 @@ const void* query_refill_kernel(bool occluded, bool sph, bool stats);
 void launch_query_refill(bool occluded, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const QueryIo& q,
                          uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl);
 
+// the same for the hemisphere rays of rayca_hip_ambient_device: made in registers from points, normals and a direction table, one bit
+// of the point's mask word per occluded ray.  rot: the call has a rotation array
+const void* ambient_refill_kernel(bool rot, bool sph, bool stats);
+void launch_ambient_refill(bool rot, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const AmbientIo& a,
+                           uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl);
+
 // and for the shadow-ray pass of a generation (k_wf_shadow's work)
 struct ShadowRefillArgs {
   float4* sh_ray;

@@ -83,6 +83,18 @@ NearestKernel pick_nearest_kernel(bool within, bool cull, bool spill, bool stats
   return with_flags([](auto WITHIN, auto CULL, auto SPILL, auto STATS) -> NearestKernel { return k_nearest<WITHIN && CULL, CULL, SPILL, STATS>; }, within, cull, spill, stats);
 }
 
+// k_ambient_rays (ambient.inc, rayca_hip_ambient_device where k_ambient_refill of refill.hip cannot run): ordered, binary f32 nodes
+// with the spill path, as pick_query_kernel's OCCLUDED forms -- so kTravFastSpill or kTravExact: the scene's FAST alone; flags only
+using AmbientKernel = void (*)(DevScene, AmbientIo, TraceCounters*, TraceLaunch);
+AmbientKernel pick_ambient_kernel(bool fast, bool sph, bool stats, bool rot) {
+  return with_flags([](auto FAST, auto SPH, auto STATS, auto ROT) -> AmbientKernel { return k_ambient_rays<FAST, SPH, STATS, ROT>; }, fast, sph, stats, rot);
+}
+// k_ambient_finish: the fold without the direction loop reads no rotation
+using AmbientFinishKernel = void (*)(AmbientIo);
+AmbientFinishKernel pick_ambient_finish(bool bent, bool rot) {
+  return with_flags([](auto BENT, auto ROT) -> AmbientFinishKernel { return k_ambient_finish<BENT, BENT && ROT>; }, bent, rot);
+}
+
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
 // else 24 entries + a global spill area for the rest
 #ifndef RAYCA_MAX_LDS_ENTRIES
@@ -448,9 +460,13 @@ int32_t selftest_kernel_selection(std::string& err) {
       {"pick_surface_kernel(sph)", none, 1, [&](Trav, uint32_t i) { return P(pick_surface_kernel(b(i, 0))); }, every},
       {"pick_nearest_kernel(within, cull, spill, stats)", none, 4, [&](Trav, uint32_t i) { return P(pick_nearest_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
        [&](Trav, uint32_t i) { return b(i, 1) ? i : i & ~1u; }},   // the exhaustive form does not read within
+      {"pick_ambient_kernel(fast, sph, stats, rot)", none, 4, [&](Trav, uint32_t i) { return P(pick_ambient_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); }, every},
+      {"pick_ambient_finish(bent, rot)", none, 2, [&](Trav, uint32_t i) { return P(pick_ambient_finish(b(i, 0), b(i, 1))); },
+       [&](Trav, uint32_t i) { return b(i, 0) ? i : 0u; }},   // without bent_out no direction is made: rot is not read
       {"flat_refill_kernel(trav; sph, stats)", fast, 2, [&](Trav t, uint32_t i) { return flat_refill_kernel(RefillFlavour{t, b(i, 0), b(i, 1)}); }, every},
       {"queue_refill_kernel(sph, stats, slack)", none, 3, [&](Trav, uint32_t i) { return queue_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"query_refill_kernel(occluded, sph, stats)", none, 3, [&](Trav, uint32_t i) { return query_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
+      {"ambient_refill_kernel(rot, sph, stats)", none, 3, [&](Trav, uint32_t i) { return ambient_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"shadow_refill_kernel(gen0, sph, stats)", none, 3, [&](Trav, uint32_t i) { return shadow_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
   };
   for (const PickerFamily& f : families)

@@ -361,6 +361,105 @@ class DeviceScene:
         g["t"], g["prim"] = t, prim
         return {k: v.reshape(height, width, *v.shape[1:]) for k, v in g.items()}
 
+    # ---- ambient occlusion: hemisphere visibility at points (rayca_hip_ambient_device) ----
+    AMBIENT_OUTPUTS = {"mask": ("int64", 0), "hits": ("int32", 0), "open": ("float32", 0), "bent": ("float32", 3)}
+
+    def _ambient_table(self, call, n):
+        """cosine_directions(n) on the scene's device, made once per n"""
+        cache = self.__dict__.setdefault("_ambient_tables", {})
+        if n not in cache:
+            from .ambient import cosine_directions
+            cache[n] = call.torch.from_numpy(cosine_directions(n)).to(call.dev)
+        return cache[n]
+
+    def ambient(self, points, normals, *, samples=16, radius=None, bias=0.0, dirs=None, dir_first=0, rotations=None,
+                want=("open",), stream=None, context=0, out=None, want_stats=False, collect_stats=False):
+        """rayca_hip_ambient_device: how open the scene is at points in device memory -- `samples` occlusion rays over the
+        hemisphere of each normal, made inside the traversal kernel, one record per point -- asynchronously.
+
+        points, normals: torch tensors (N, 3) float32 on this scene's device, as surface() / gbuffer() return them (a zero normal,
+        surface()'s miss, or a value that is not finite marks an inactive point: open 1).  samples: 1..64.  radius: None
+        (unbounded), a float for every point, or an (N,) float32 tensor; a ray is occluded iff it hits at t < radius.  bias: the
+        origin is point + normal * bias.  dirs: (M, 3) float32 local directions, z along the normal (None: cosine_directions(samples),
+        kept on the device); sample j takes dirs[dir_first + j].  rotations: (N, 2) float32 (cos, sin) that turn the table about
+        the normal per point (pixel_rotations), or None.  Returns a dict with one tensor per name in `want`: "mask" (N,) int64
+        holding the u64 whose bit j says sample j is occluded, "hits" (N,) int32, "open" (N,) float32 = (samples - hits) /
+        samples, "bent" (N, 3) float32, the unnormalised sum of the unoccluded directions.  `out`: a dict of tensors to write
+        instead of new ones.  Stream handling as query(); `want_stats` / `collect_stats` wait and add "stats"."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.AMBIENT_OUTPUTS]
+        if unknown or not want or len(set(want)) != len(want):
+            raise ValueError(f"want: a non-empty selection without repeats of {tuple(self.AMBIENT_OUTPUTS)}, not {want!r}")
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+        n = points.shape[0]
+        if not 1 <= samples <= 64:
+            raise ValueError(f"samples: {samples}, expected 1..64")
+        if n * samples >= 1 << 32:
+            raise ValueError("points: the number of points x samples must stay below 2**32")
+        if dirs is None:
+            dirs, dir_first = self._ambient_table(call, samples), 0
+        if not isinstance(dirs, torch.Tensor):
+            raise TypeError(f"dirs: a torch tensor on {call.dev} is expected, not {type(dirs).__name__}")
+        if dirs.dim() != 2 or dirs.shape[1] != 3:
+            raise ValueError(f"dirs: shape {tuple(dirs.shape)}, expected (M, 3)")
+        m = dirs.shape[0]
+        if dir_first < 0 or dir_first + samples > m:
+            raise ValueError(f"dir_first: {dir_first} + samples {samples} exceeds the {m} directions of dirs")
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in want]
+        if stray:
+            raise ValueError(f"out: {stray} not in want")
+        a = abi.RaycaAmbient()
+        a.count, a.samples, a.dir_count, a.dir_first, a.bias = n, samples, m, dir_first, float(bias)
+        result = {}
+        for name in want:
+            dtype, width = self.AMBIENT_OUTPUTS[name]
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), (n, width) if width else (n,))
+            setattr(a, name + "_out", result[name].data_ptr() or None)
+        a.points = call.input(points, "points", torch.float32, (n, 3)).data_ptr()
+        a.normals = call.input(normals, "normals", torch.float32, (n, 3)).data_ptr()
+        a.dirs = call.input(dirs, "dirs", torch.float32, (m, 3)).data_ptr()
+        if rotations is not None:
+            a.rotations = call.input(rotations, "rotations", torch.float32, (n, 2)).data_ptr()
+        if radius is None:
+            a.radius_all = float("inf")
+        elif isinstance(radius, torch.Tensor):
+            a.radius = call.input(radius, "radius", torch.float32, (n,)).data_ptr()
+        else:
+            a.radius_all = float(radius)
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_ambient_device, a, context=context, want_stats=want_stats or collect_stats,
+                             collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
+    def render_ambient(self, config: Config, width: int, height: int, *, samples=16, radius=None, bias=1e-3, rotate=True,
+                       stream=None, context=0):
+        """An ambient-occlusion image without a render call: gbuffer() -> ambient() on one stream, nothing waited for in between.
+        Returns the (height, width) float32 openness, 1 where nothing is occluded; a pixel whose camera ray misses is exactly 1
+        (its normal is zero: an inactive point).  bias, in world units, lifts the origins off the surface; `rotate` turns the
+        direction table per pixel (pixel_rotations)."""
+        call = _DeviceCall(self, stream)
+        g = self.gbuffer(config, width, height, want=("point", "normal"), stream=stream, context=context)
+        rotations = None
+        if rotate:
+            from .ambient import pixel_rotations
+            rotations = call.torch.from_numpy(pixel_rotations(width, height).reshape(-1, 2)).to(call.dev)
+        a = self.ambient(g["point"].reshape(-1, 3), g["normal"].reshape(-1, 3), samples=samples, radius=radius, bias=bias, rotations=rotations,
+                         stream=stream, context=context)
+        return a["open"].reshape(height, width)
+
     # ---- radiance along the caller's rays (rayca_hip_radiance_device) ----
     def radiance(self, rays, config: Config, *, sample=0, first_index=0, rgba8=False, out=None, stream=None, context=0,
                  want_stats=False, collect_stats=False):
