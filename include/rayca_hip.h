@@ -48,7 +48,8 @@ extern "C" {
                                   rayca_hip_meter_device, RaycaTonemap, rayca_hip_tonemap_device, RAYCA_TONEMAP_;
                                   radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device;
                                   nearest-point queries: RaycaNearest, rayca_hip_nearest_device, RAYCA_NEAREST_;
-                                  ambient occlusion: RaycaAmbient, rayca_hip_ambient_device */
+                                  ambient occlusion: RaycaAmbient, rayca_hip_ambient_device;
+                                  multi-hit ray queries: RaycaHits, rayca_hip_hits_device, RAYCA_HITS_ */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -354,7 +355,7 @@ enum {
   RAYCA_KERNEL_WF_SHADE = 4,      /* k_wf_shade: shading, NEE set-up, bounce sampling (wavefront.inc)                */
   RAYCA_KERNEL_WF_SHADOW = 5,     /* k_wf_shadow: shadow rays + direct sum, one pixel per lane (wavefront.inc)       */
   RAYCA_KERNEL_SHADOW_REFILL = 6, /* k_shadow_refill: the same with lane refill (refill.hip)                         */
-  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays, k_surface, k_nearest */
+  RAYCA_KERNEL_OTHER = 7,         /* k_general (the stack machine), k_resolve, k_trace_rays, k_query_refill / _rays, k_surface, k_nearest, k_hits */
   RAYCA_KERNEL_CLASSES = 8
 };
 
@@ -712,6 +713,74 @@ struct RaycaNearest {
 typedef struct RaycaNearest RaycaNearest;
 int32_t rayca_hip_nearest_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaNearest* query,
                                  RaycaStats* stats_out);
+
+/* Multi-hit ray queries on DEVICE memory: for `count` caller-supplied rays the first k hits along each ray, in order, or the
+ * number of all of them -- thickness and transmission through layers, crossing counts, picking through a surface, x-ray and
+ * depth-peeling views, inside / outside tests.  One traversal and one launch, where k closest-hit queries restarted "a little
+ * past" the last hit cost k of each and either skip coincident surfaces or find the same one again.  Rays, bounds and results
+ * stay on the device and the call is asynchronous on the caller's stream.
+ *
+ * The specification.  Every operation is f32 and rounded on its own.
+ *   The hits of a ray: a hit is a primitive slot (post-build primitive order) whose test accepts the ray and whose hit the
+ *   reference would have seen -- exactly the set RAYCA_QUERY_CLOSEST takes its minimum over:
+ *     the test      Triangle::intersects on the slot's world-space vertices (v0, v1, v2) (rayca-geometry/src/triangle.rs:84-159,
+ *                   which culls back faces), Sphere::intersects for a sphere slot (sphere.rs:101-163); it yields t and (u, v);
+ *     "seen"        AABB::intersects (bvh/aabb.rs:74-93) accepts the ray on the box of the reference's leaf that holds the
+ *                   primitive.  The boxes above a leaf in the reference's trees are nested and the box test is monotone in the
+ *                   corners, so this is what the reference's own descent decides; a RAYCA_BUILDER_REFERENCE scene runs that
+ *                   descent itself.
+ *   A hit counts iff t < tmax, strictly.  tmax = +inf or FLT_MAX is unbounded, and unbounded means t < +inf: a t that is NaN
+ *   or +inf never counts.  A tmax that is NaN or <= 0 leaves the ray without hits, and so does an origin or direction component
+ *   that is not finite.
+ *   Order: by (t, tie rank) -- t compared as floats; on equal t the primitive that comes first in the reference's primitive
+ *   order (rayca_hip_scene_primitive_order) goes first, the rule closest hits resolve exact ties by.  Ranks are unique, so the
+ *   order is total and the result does not depend on the order in which a traversal visits anything.
+ *   Faces:
+ *     RAYCA_HITS_FRONT  the test as it stands.
+ *     RAYCA_HITS_BOTH   additionally, a triangle that the test rejects by its back-face line -- n = cross(v1 - v0, v2 - v0),
+ *                       dot(d, n) > 0 -- is tested as the triangle (v0, v2, v1) with the same test.  That test yields t and
+ *                       (u', v'), the weights of v0 and v2; the hit is reported with (u, v) = (u', (1 - u') - v') -- two
+ *                       subtractions in this order -- the weights of vertex 0 and vertex 1 as every hit record carries them, and
+ *                       with face = 1.  Every other hit has face = 0.  A sphere slot is one hit as Sphere::intersects computes
+ *                       it under either setting, face 0.  "Seen" is the same for both faces.
+ *   Result per ray: the first k counting hits in order, entry j of ray i at index i * k + j of each record output (ray-major):
+ *   t, prim (the slot), (u, v), face.  Unused entries are the miss record (t = FLT_MAX, prim = RAYCA_NONE, u = v = 0, face = 0).
+ *     count_all == 0  n_out = min(number of counting hits, k).
+ *     count_all == 1  n_out = the number of ALL counting hits; the entries are the same.  The search is then bounded by tmax
+ *                     alone.  k == 0 is allowed here: a crossing count with no record outputs.
+ *   Consequences (for rays whose components are finite):
+ *     with FRONT and k >= 1, entry 0 is bit for bit the record RAYCA_QUERY_CLOSEST writes for the same ray and tmax;
+ *     n_out > 0 iff RAYCA_QUERY_OCCLUDED says 1;
+ *     the first k entries of a call with k' > k are the entries of the call with k.
+ * Any output may be NULL, not all; with k == 0 only n_out may be given, and it must be.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event,
+ * collect_stats and traversal as for rayca_hip_nearest_device; RAYCA_TRAVERSAL_EXHAUSTIVE visits every node the reference's boxes
+ * admit without the distance cull and gives the same results bit for bit; tile, engine and camera_rays must be zero.  Ordered on
+ * its context like a query.  With stats_out the call waits: rays_primary = count, kernel_launches = 1, the kernel's time under
+ * RAYCA_KERNEL_OTHER (with collect_stats it includes reading the counters back), boxes_tested and triangles_tested under
+ * collect_stats.  count == 0 is RAYCA_OK and launches nothing; nothing outside [0, count * k) of a record output or [0, count) of
+ * n_out is written.  Scenes with spheres are served.
+ * RAYCA_ERR_BAD_ARG, before any GPU work and before the scene is looked at, in this order: NULL scene / query; NULL rays;
+ * k > RAYCA_HITS_MAX; unknown faces; count_all > 1; non-zero reserved; k == 0 without count_all; no output, or a record output
+ * with k == 0; context > 7; a non-zero field of opts that does not apply.  Then (count != 0) RAYCA_ERR_EMPTY_SCENE as the query. */
+#define RAYCA_HITS_MAX 16u
+enum { RAYCA_HITS_FRONT = 0, RAYCA_HITS_BOTH = 1 };
+struct RaycaHits {
+  uint32_t count, k;    /* k in 0..RAYCA_HITS_MAX; k == 0 needs count_all */
+  const void* rays;     /* DEVICE: count x 6 f32, as RaycaQuery.rays */
+  const void* tmax;     /* DEVICE: count f32, or NULL => tmax_all for every ray */
+  float tmax_all;
+  uint32_t faces;       /* RAYCA_HITS_* */
+  uint32_t count_all;   /* 0 / 1 */
+  uint32_t reserved;    /* must be zero */
+  void* t_out;          /* DEVICE: count x k f32, FLT_MAX in unused entries */
+  void* prim_out;       /* DEVICE: count x k u32 slot (post-build primitive order), RAYCA_NONE in unused entries */
+  void* uv_out;         /* DEVICE: count x k x 2 f32 in the convention of hit records, 0 in unused entries */
+  void* face_out;       /* DEVICE: count x k u8, 1 for a hit on the back of a triangle (RAYCA_HITS_BOTH), else 0 */
+  void* n_out;          /* DEVICE: count u32 */
+};
+typedef struct RaycaHits RaycaHits;
+int32_t rayca_hip_hits_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaHits* query, RaycaStats* stats_out);
 
 /* Ambient occlusion on DEVICE memory: how open the scene is at `count` caller-supplied points -- `samples` occlusion rays over the
  * hemisphere of each point's normal, folded into one record per point: ambient occlusion on a G-buffer, sky visibility, per-vertex

@@ -76,6 +76,10 @@ pub const RAYCA_QUERY_OCCLUDED: u32 = 1;
 // RaycaNearest.kind
 pub const RAYCA_NEAREST_CLOSEST: u32 = 0;
 pub const RAYCA_NEAREST_WITHIN: u32 = 1;
+// RaycaHits.faces, and the largest RaycaHits.k
+pub const RAYCA_HITS_FRONT: u32 = 0;
+pub const RAYCA_HITS_BOTH: u32 = 1;
+pub const RAYCA_HITS_MAX: u32 = 16;
 // RaycaTonemap.op
 pub const RAYCA_TONEMAP_LINEAR: u32 = 0;
 pub const RAYCA_TONEMAP_REINHARD: u32 = 1;
@@ -321,6 +325,25 @@ pub struct RaycaNearest {
     pub point_out: *mut c_void,
     pub uv_out: *mut c_void,
     pub within_out: *mut c_void,
+}
+
+// rayca_hip_hits_device: rays, bounds and results in DEVICE memory; entry j of ray i at index i * k + j
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaHits {
+    pub count: u32,
+    pub k: u32,
+    pub rays: *const c_void,
+    pub tmax: *const c_void,
+    pub tmax_all: f32,
+    pub faces: u32,
+    pub count_all: u32,
+    pub reserved: u32,
+    pub t_out: *mut c_void,
+    pub prim_out: *mut c_void,
+    pub uv_out: *mut c_void,
+    pub face_out: *mut c_void,
+    pub n_out: *mut c_void,
 }
 
 // rayca_hip_ambient_device: points, normals and a direction table in, one record per point out, all in DEVICE memory
@@ -603,6 +626,7 @@ extern "C" {
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_nearest_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaNearest, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_hits_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaHits, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_ambient_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, ambient: *const RaycaAmbient, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;

@@ -44,6 +44,8 @@ KERNEL_NAMES = ("k_generation", "k_flat_refill", "k_wf_trace", "k_queue_refill",
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # RaycaQuery.kind
 NEAREST_CLOSEST, NEAREST_WITHIN = 0, 1   # RaycaNearest.kind
+HITS_FRONT, HITS_BOTH = 0, 1   # RaycaHits.faces
+HITS_MAX = 16   # RAYCA_HITS_MAX: the largest RaycaHits.k
 TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
 TONEMAP_NAMES = ("linear", "reinhard", "aces")
 METER_WORDS, METER_COUNTED, METER_BLACK, METER_NOT_FINITE = 260, 256, 257, 258   # hist_out of rayca_hip_meter_device
@@ -312,6 +314,25 @@ class RaycaNearest(C.Structure):
         ("point_out", C.c_void_p),
         ("uv_out", C.c_void_p),
         ("within_out", C.c_void_p),
+    ]
+
+
+class RaycaHits(C.Structure):
+    """rayca_hip_hits_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("k", C.c_uint32),
+        ("rays", C.c_void_p),
+        ("tmax", C.c_void_p),
+        ("tmax_all", C.c_float),
+        ("faces", C.c_uint32),
+        ("count_all", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("t_out", C.c_void_p),
+        ("prim_out", C.c_void_p),
+        ("uv_out", C.c_void_p),
+        ("face_out", C.c_void_p),
+        ("n_out", C.c_void_p),
     ]
 
 
@@ -643,6 +664,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
     lib.rayca_hip_nearest_device.restype = C.c_int32
     lib.rayca_hip_nearest_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaNearest), P(RaycaStats)]
+    lib.rayca_hip_hits_device.restype = C.c_int32
+    lib.rayca_hip_hits_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaHits), P(RaycaStats)]
     lib.rayca_hip_ambient_device.restype = C.c_int32
     lib.rayca_hip_ambient_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaAmbient), P(RaycaStats)]
     lib.rayca_hip_surface_device.restype = C.c_int32
@@ -685,7 +708,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_version", "rayca_hip_device_count", "rayca_hip_selftest", "rayca_hip_last_error", "rayca_hip_config_default",
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
-    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device",
+    "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device", "rayca_hip_hits_device",
     "rayca_hip_ambient_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",

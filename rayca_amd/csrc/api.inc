@@ -1597,6 +1597,76 @@ int32_t rayca_hip_nearest_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   return RAYCA_OK;
 }
 
+// What RaycaHits alone decides, in the header's order; the first rule broken is the one reported.  No scene, no device.
+int32_t check_hits(const RaycaHits& rh) {
+  if (!rh.rays) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.rays: null rays");
+  if (rh.k > RAYCA_HITS_MAX) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.k: more than RAYCA_HITS_MAX hits per ray");
+  if (rh.faces != RAYCA_HITS_FRONT && rh.faces != RAYCA_HITS_BOTH) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.faces: unknown faces");
+  if (rh.count_all > 1u) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.count_all must be 0 or 1");
+  if (rh.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.reserved must be zero");
+  if (rh.k == 0 && !rh.count_all) return fail(RAYCA_ERR_BAD_ARG, "RaycaHits.k: k == 0 needs count_all");
+  const bool records = rh.t_out || rh.prim_out || rh.uv_out || rh.face_out;
+  if (!records && !rh.n_out) return fail(RAYCA_ERR_BAD_ARG, "no output for this multi-hit query");
+  if (rh.k == 0 && records) return fail(RAYCA_ERR_BAD_ARG, "no output for this multi-hit query: k == 0 writes n_out alone, a record output has no entries");
+  return RAYCA_OK;
+}
+
+// Multi-hit ray queries (hits.inc k_hits): one ray per lane on the binary f32 nodes, which every scene has from scene_create on,
+// so the call never waits for the formats thread.  The kernel's LDS is the node stack's part and the lists' 2 k rows behind it
+// (hits_lds_bytes).  A pass on its context (run_pass), which clears the work counters on the launch stream when they are read.
+int32_t rayca_hip_hits_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaHits* hin, RaycaStats* stats_out) {
+  if (!s || !hin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaHits");
+  const RaycaHits& rh = *hin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  int32_t rc = check_hits(rh);
+  if (rc != RAYCA_OK) return rc;
+  if ((rc = pass_options(o, "a multi-hit query", kOptTraversal | kOptCollectStats)) != RAYCA_OK) return rc;
+  if (rh.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  HitsIo io{};
+  io.rays = static_cast<const float*>(rh.rays);
+  io.tmax = static_cast<const float*>(rh.tmax);
+  io.tmax_all = rh.tmax_all;
+  io.count = rh.count;
+  io.k = rh.k;
+  io.t_out = static_cast<float*>(rh.t_out);
+  io.prim_out = static_cast<uint32_t*>(rh.prim_out);
+  io.uv_out = static_cast<float*>(rh.uv_out);
+  io.face_out = static_cast<uint8_t*>(rh.face_out);
+  io.n_out = static_cast<uint32_t*>(rh.n_out);
+  const bool stats = o.collect_stats != 0, ordered = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
+  const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+  const Trav trav = !ordered ? (fast ? kTravFastAll : kTravExactAll) : (fast ? kTravFastSpill : kTravExact);   // (as k_query_rays is chosen)
+  const StackPlan sp = plan_stack(s->host.max_depth);
+  const uint32_t grid = (uint32_t)(((uint64_t)rh.count + kBlock - 1u) / kBlock);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  rc = run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    TraceLaunch tl{};
+    if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+    if (stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+    hipLaunchKernelGGL(pick_hits_kernel(trav, s->host.sphere_count != 0, stats, rh.faces == RAYCA_HITS_BOTH, rh.count_all != 0), dim3(grid), dim3(kBlock),
+                       hits_lds_bytes(sp, rh.k), stream, formats_ready(s) ? s->dev_full : s->dev, io, c->counters, tl);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+    if (stats && stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+    return RAYCA_OK;
+  });
+  if (rc != RAYCA_OK || !stats_out) return rc;
+  stats_out->rays_primary = rh.count;
+  if (stats) {
+    stats_out->boxes_tested = tc.boxes;
+    stats_out->triangles_tested = tc.tris;
+  }
+  return RAYCA_OK;
+}
+
 // Hemisphere visibility at points (ambient.inc, refill.hip k_ambient_refill): count x samples occlusion rays made in registers, one
 // mask word per point, folded by k_ambient_finish.  The trace kernel is chosen as rayca_hip_query_device chooses an OCCLUDED query's:
 // the lane-refill form on the 4-wide fp16 nodes for a RAYCA_BUILDER_SAH scene whose formats are there, else one ray per lane on

@@ -18,6 +18,8 @@
 //   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
 //   k_nearest         nearest-point queries: the closest surface point to points in device memory, within a radius
 //                     (nearest.inc: rayca_hip_nearest_device).
+//   k_hits            multi-hit ray queries: the first k hits along rays in device memory, in order, or their number
+//                     (hits.inc: rayca_hip_hits_device).
 //   k_ambient_rays,   hemisphere visibility at points: occlusion rays made in registers, one per lane, and the fold of a point's
 //   k_ambient_finish  mask word into hits, openness and the bent normal (ambient.inc: rayca_hip_ambient_device; the lane-refill
 //                     form is refill.hip k_ambient_refill).
@@ -447,6 +449,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "wavefront.inc"
 #include "surface.inc"
 #include "nearest.inc"
+#include "hits.inc"
 #include "ambient.inc"
 RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "image_pass.inc"

@@ -83,6 +83,15 @@ NearestKernel pick_nearest_kernel(bool within, bool cull, bool spill, bool stats
   return with_flags([](auto WITHIN, auto CULL, auto SPILL, auto STATS) -> NearestKernel { return k_nearest<WITHIN && CULL, CULL, SPILL, STATS>; }, within, cull, spill, stats);
 }
 
+// k_hits (hits.inc): ORDERED and FAST of the flavour on the binary f32 nodes with the spill path, as pick_query_kernel -- so
+// kTravExact, kTravExactAll and kTravFastAll have a form of their own and every other flavour is kTravFastSpill's
+using HitsKernel = void (*)(DevScene, HitsIo, TraceCounters*, TraceLaunch);
+HitsKernel pick_hits_kernel(Trav t, bool sph, bool stats, bool both, bool count_all) {
+  return with_flavour([](auto T, auto SPH, auto STATS, auto BOTH, auto COUNT_ALL) -> HitsKernel {
+    return k_hits<T.ORDERED, T.FAST, SPH, STATS, BOTH, COUNT_ALL>;
+  }, t, sph, stats, both, count_all);
+}
+
 // k_ambient_rays (ambient.inc, rayca_hip_ambient_device where k_ambient_refill of refill.hip cannot run): ordered, binary f32 nodes
 // with the spill path, as pick_query_kernel's OCCLUDED forms -- so kTravFastSpill or kTravExact: the scene's FAST alone; flags only
 using AmbientKernel = void (*)(DevScene, AmbientIo, TraceCounters*, TraceLaunch);
@@ -128,6 +137,10 @@ int32_t bind_stack(FrameCtx* c, const StackPlan& sp, uint32_t grid, TraceLaunch&
   }
   return RAYCA_OK;
 }
+
+// The dynamic LDS of a k_hits launch: the node stack's rows, then the list's -- k rows of t and k rows of slots, kBlock words each
+// (k <= RAYCA_HITS_MAX: at most 24 + 32 rows, 56 KiB)
+size_t hits_lds_bytes(const StackPlan& sp, uint32_t k) { return sp.lds_bytes + (size_t)2u * k * kBlock * sizeof(uint32_t); }
 
 // ---- the environment knobs that steer selection and planning: read once, at the first call that needs any of them --------------
 // A path frame's LDS rows by the waves per SIMD its kernel is compiled for (trace_core.inc path_waves): at five, with the compact
@@ -460,6 +473,8 @@ int32_t selftest_kernel_selection(std::string& err) {
       {"pick_surface_kernel(sph)", none, 1, [&](Trav, uint32_t i) { return P(pick_surface_kernel(b(i, 0))); }, every},
       {"pick_nearest_kernel(within, cull, spill, stats)", none, 4, [&](Trav, uint32_t i) { return P(pick_nearest_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
        [&](Trav, uint32_t i) { return b(i, 1) ? i : i & ~1u; }},   // the exhaustive form does not read within
+      {"pick_hits_kernel(trav; sph, stats, both, count_all)", all, 4, [&](Trav t, uint32_t i) { return P(pick_hits_kernel(t, b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
+       [&](Trav t, uint32_t i) { return (uint32_t)query_of(t) << 8 | i; }},
       {"pick_ambient_kernel(fast, sph, stats, rot)", none, 4, [&](Trav, uint32_t i) { return P(pick_ambient_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); }, every},
       {"pick_ambient_finish(bent, rot)", none, 2, [&](Trav, uint32_t i) { return P(pick_ambient_finish(b(i, 0), b(i, 1))); },
        [&](Trav, uint32_t i) { return b(i, 0) ? i : 0u; }},   // without bent_out no direction is made: rot is not read

@@ -282,6 +282,72 @@ class DeviceScene:
             return result
         return (result, stats) if within else (*result, stats)
 
+    # ---- multi-hit queries: the first k hits along a ray, in order (rayca_hip_hits_device) ----
+    HITS_OUTPUTS = {"t": ("float32", 0), "prim": ("int32", 0), "uv": ("float32", 2), "face": ("uint8", 0), "n": ("int32", None)}
+
+    def hits(self, rays, k, *, tmax=None, faces="front", count_all=False, outputs=("t", "prim", "uv", "face", "n"), stream=None, context=0,
+             out=None, want_stats=False, traversal=abi.TRAVERSAL_ORDERED, collect_stats=False):
+        """rayca_hip_hits_device: the first k hits along rays that live in device memory, in order, asynchronously.
+
+        rays: torch tensor (N, 6) float32 on this scene's device.  k: 0 .. abi.HITS_MAX hits per ray (0 only with count_all and
+        "n" alone).  tmax: None (unbounded), a float for every ray, or an (N,) float32 tensor; a hit counts iff t < tmax.
+        faces: "front" (back faces culled, as closest hits) or "both" (a hit on the back of a triangle has face 1).  Returns a
+        dict with one tensor per name in `outputs`: t (N, k) float32 with FLT_MAX in unused entries, prim (N, k) int32 holding the
+        u32 slot (abi.NONE, i.e. -1, unused), uv (N, k, 2) float32, face (N, k) uint8 and n (N,) int32: min(hits, k), or the number
+        of all hits in front of tmax with count_all.  Hits are ordered by (t, the reference's primitive order); entry 0 with
+        "front" is query(kind="closest")'s record; t, prim and uv of an entry go to surface() as they are.  `out`: a dict of
+        tensors to write instead of new ones.  Stream handling and statistics as query(): `want_stats` / `collect_stats` wait and
+        add "stats"."""
+        if faces not in ("front", "both"):
+            raise ValueError(f"faces must be 'front' or 'both', not {faces!r}")
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= abi.HITS_MAX:
+            raise ValueError(f"k: an int in 0 .. {abi.HITS_MAX} is expected, not {k!r}")
+        outputs = tuple(outputs)
+        unknown = [w for w in outputs if w not in self.HITS_OUTPUTS]
+        if unknown or not outputs or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs: a non-empty selection without repeats of {tuple(self.HITS_OUTPUTS)}, not {outputs!r}")
+        if k == 0 and (not count_all or outputs != ("n",)):
+            raise ValueError("k == 0 counts crossings: it needs count_all=True and outputs=('n',)")
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError(f"rays: a torch tensor on {call.dev} is expected, not {type(rays).__name__}")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError(f"rays: shape {tuple(rays.shape)}, expected (N, 6)")
+        n = rays.shape[0]
+        if n > 0xFFFFFFFF:
+            raise ValueError("rays: more than 2**32 - 1 rays")
+        q = abi.RaycaHits()
+        q.count, q.k, q.faces, q.count_all = n, k, (abi.HITS_BOTH if faces == "both" else abi.HITS_FRONT), 1 if count_all else 0
+        out = dict(out) if out is not None else {}
+        stray = [w for w in out if w not in outputs]
+        if stray:
+            raise ValueError(f"out: {stray} not in outputs")
+        result = {}
+        for name in outputs:
+            dtype, width = self.HITS_OUTPUTS[name]
+            shape = (n,) if width is None else ((n, k, width) if width else (n, k))
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), shape)
+            setattr(q, name + "_out", result[name].data_ptr() or None)
+        q.rays = call.input(rays, "rays", torch.float32, (n, 6)).data_ptr()
+        if tmax is None:
+            q.tmax_all = float("inf")
+        elif isinstance(tmax, torch.Tensor):
+            q.tmax = call.input(tmax, "tmax", torch.float32, (n,)).data_ptr()
+        else:
+            q.tmax_all = float(tmax)
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_hits_device, q, context=context, want_stats=want_stats or collect_stats,
+                             traversal=traversal, collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
     # ---- surface queries: what is at a hit (rayca_hip_surface_device), and the rays of a frame (rayca_hip_camera_rays_device) ----
     SURFACE_OUTPUTS = {"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
                        "specular": ("float32", 4), "rough": ("float32", 2), "material": ("int32", 0), "flags": ("int32", 0)}
