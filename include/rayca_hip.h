@@ -49,7 +49,9 @@ extern "C" {
                                   radiance along caller-supplied rays: RaycaRadiance, rayca_hip_radiance_device;
                                   nearest-point queries: RaycaNearest, rayca_hip_nearest_device, RAYCA_NEAREST_;
                                   ambient occlusion: RaycaAmbient, rayca_hip_ambient_device;
-                                  multi-hit ray queries: RaycaHits, rayca_hip_hits_device, RAYCA_HITS_ */
+                                  multi-hit ray queries: RaycaHits, rayca_hip_hits_device, RAYCA_HITS_;
+                                  adaptive sampling: RaycaSamplePlan, rayca_hip_sample_plan_device, RaycaFilmFold,
+                                  rayca_hip_film_fold_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -1322,6 +1324,101 @@ struct RaycaTonemap {
 };
 typedef struct RaycaTonemap RaycaTonemap;
 int32_t rayca_hip_tonemap_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaTonemap* t, RaycaStats* stats_out);
+
+/* Adaptive sampling, the plan: a film's own error estimate decides where the next `budget` rays go, everything in DEVICE memory
+ * and nothing read back.  `color`, `variance` and `length` are a film's color_out, variance_out and length_out
+ * (rayca_hip_accumulate_device); the plan gives every pixel an integer weight, turns the weights into ray offsets by an exact
+ * prefix sum and, with rays_out, writes the camera rays themselves in the layout rayca_hip_query_device and
+ * rayca_hip_radiance_device read.  `budget` (B) is fixed on the host, so the radiance call behind the plan takes its count without
+ * a round trip.  No reference counterpart.  The weights and offsets read no scene; the rays read its camera.
+ * The weight is f32, every operation rounds once, in the association written here; every comparison is written so that a NaN
+ * fails it; max() and min() are maxNum and minNum.  Everything behind the weight is integer arithmetic and no result depends on
+ * an order of execution, so a literal restatement (tests/adaptive_literal.py) gives the same words.  For pixel p (raster order,
+ * p = y * W + x), c = color[p]:
+ *   weight     l = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b, d = max(l, lum_floor)
+ *              v = max(variance[p], 0), L = length[p]
+ *              e = (v / max(L, 1)) / (d * d)                      the relative variance of the pixel's mean
+ *              r = e / (target * target)                          (the product is formed on the host, once)
+ *              q = floor(min(r, 255)) where r >= 0, else 0
+ *              w = min(base_weight + (uint)q, 255)
+ *              where !(L >= (float)min_history): w = max(w, fresh_weight)   (one sample has variance 0 and must not look converged)
+ *   offsets    S = sum of the weights, exactly; if S == 0 every weight counts as 1 (then S = W * H)
+ *              P(p) = the sum of the weights of the pixels in front of p
+ *              offset_out[p] = (uint32)((uint64)P(p) * B / S), offset_out[W * H] = B
+ *              so pixel p receives n_p = offset_out[p + 1] - offset_out[p] rays, all n_p sum to B exactly, and
+ *              |n_p - w_p B / S| < 1
+ *   rays       ray j belongs to the pixel p with offset_out[p] <= j < offset_out[p + 1] and is its sample k = j - offset_out[p]
+ *              stratum s = (first_stratum + k) mod n^2 of the n x n stratified sub-pixel positions, n = jitter:
+ *              ix = s mod n, iy = s / n, step 1 / n, offset 0.5 / n -- a frame's own positions for samples_per_pixel n^2
+ *              rays_out[j] = row p of rayca_hip_camera_rays_device(cfg with samples_per_pixel n^2, sample s), bit for bit
+ *              pixel_out[j] = p
+ * Rays and pixel indices are made only for the outputs that are given; rays_out needs a camera.  budget == 0 is RAYCA_OK: every
+ * offset is 0 and there are no rays.  Outputs must not overlap inputs or each other: undefined.
+ * opts (may be NULL): stream (NULL => the context's own stream, and the call waits for it), context, wait_event, record_event as
+ * for rayca_hip_surface_device; every other field, tile included, must be zero.  Ordered on its context like a frame; asynchronous
+ * unless stats_out is given: then the call waits and reports its launches under RAYCA_KERNEL_OTHER -- three (weights, the scan of
+ * the segment sums, offsets) and a fourth for rays_out or pixel_out when budget > 0.  The context keeps a scratch word a pixel
+ * (without weight_out) and one per 64 pixels of a row.
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments, non-zero reserved, width or
+ * height 0, width x height > 2^32 - 1, budget > 2^31, jitter not in 1..8, base_weight or fresh_weight above 255, target or lum_floor
+ * not > 0, NULL color / variance / length / offset_out, a misaligned image (color 16 bytes, every other 4), context > 7, a non-zero
+ * field of opts that does not apply.  RAYCA_ERR_UNSUPPORTED: width x height x 256 > 2^32 (the sum of the weights must fit 32 bits
+ * and its product with the budget 64).  RAYCA_ERR_NO_CAMERA: rays_out on a scene without a camera. */
+struct RaycaSamplePlan {
+  uint32_t width, height;   /* the whole frame, W x H */
+  uint32_t budget;          /* B: the rays this pass traces, <= 2^31 */
+  uint32_t jitter;          /* n, 1..8: the rays go through the n x n stratified sub-pixel positions */
+  uint32_t first_stratum;   /* a pixel's first ray takes this stratum (mod n^2), the next ones those behind it */
+  uint32_t base_weight;     /* 0..255: what every pixel weighs before its variance adds to it */
+  uint32_t fresh_weight;    /* 0..255: the least weight of a pixel whose history is shorter than min_history */
+  uint32_t min_history;
+  float target;             /* > 0: the relative standard error of a pixel's mean that adds one step of weight */
+  float lum_floor;          /* > 0: the luminance the error is measured against is at least this */
+  uint32_t reserved;        /* must be zero */
+  const void* color;        /* DEVICE H x W x 4 f32, required: the film, gamma 1 */
+  const void* variance;     /* DEVICE H x W f32, required */
+  const void* length;       /* DEVICE H x W f32, required */
+  void* weight_out;         /* DEVICE H x W u32 or NULL */
+  void* offset_out;         /* DEVICE (H x W + 1) u32, required */
+  void* rays_out;           /* DEVICE B x 6 f32 or NULL: origin xyz, direction xyz */
+  void* pixel_out;          /* DEVICE B u32 or NULL */
+};
+typedef struct RaycaSamplePlan RaycaSamplePlan;
+int32_t rayca_hip_sample_plan_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaSamplePlan* plan, RaycaStats* stats_out);
+
+/* Adaptive sampling, the fold: a ragged list of samples into a history, one pixel-local pass in DEVICE memory.  `samples` is
+ * what rayca_hip_radiance_device wrote (gamma 1) for a plan's rays, `offset` that plan's offset_out; the history and the outputs
+ * are rayca_hip_accumulate_device's.  The scene is not read.  Per pixel p, with the arithmetic, the finiteness test and the
+ * luminance of rayca_hip_accumulate_device:
+ *   state      h = hist_color[p], L = hist_length[p], m = hist_moments[p]; present iff L > 0, as identity mode takes a history
+ *   samples    for j = offset[p] .. offset[p + 1] - 1, in this order: the blend rows of rayca_hip_accumulate_device with
+ *              c = samples[j] (history present or not, sample finite or not), max_history as there; the step's outputs are the
+ *              next step's history -- what offset[p + 1] - offset[p] calls of rayca_hip_accumulate_device in identity mode give
+ *   no sample  color_out, length_out and moments_out are the history's, as they stand
+ *   variance_out = max(m2 - m1 * m1, 0) of the moments written
+ * The pass is pixel-local: color_out may be hist_color, length_out hist_length, moments_out hist_moments.  Any other overlap is
+ * undefined.  opts, ordering, stats_out: as for rayca_hip_accumulate_device; one launch, no scratch.
+ * RAYCA_ERR_BAD_ARG (before any GPU work, the message names the field): NULL scene / arguments, non-zero reserved, width or
+ * height 0, width x height > 2^32 - 1, NULL samples / offset / color_out / length_out / hist_color / hist_length, moments_out
+ * without hist_moments, variance_out without moments_out, a misaligned image (samples, hist_color and color_out 16 bytes, every
+ * other 4), context > 7, a non-zero field of opts that does not apply.  RAYCA_ERR_UNSUPPORTED: a frame whose 64 x 4 pixel tiles
+ * number 2^24 or more. */
+struct RaycaFilmFold {
+  uint32_t width, height;   /* the whole frame */
+  uint32_t max_history;     /* as RaycaAccumulate.max_history */
+  uint32_t reserved;        /* must be zero */
+  const void* samples;      /* DEVICE B x 4 f32, required: B = offset[H x W] */
+  const void* offset;       /* DEVICE (H x W + 1) u32, required: non-decreasing, offset[0] = 0 */
+  const void* hist_color;   /* DEVICE H x W x 4 f32, required */
+  const void* hist_length;  /* DEVICE H x W f32, required */
+  const void* hist_moments; /* DEVICE H x W x 2 f32 or NULL; read only with moments_out */
+  void* color_out;          /* DEVICE H x W x 4 f32, required */
+  void* length_out;         /* DEVICE H x W f32, required */
+  void* moments_out;        /* DEVICE H x W x 2 f32 or NULL; requires hist_moments */
+  void* variance_out;       /* DEVICE H x W f32 or NULL; needs moments_out */
+};
+typedef struct RaycaFilmFold RaycaFilmFold;
+int32_t rayca_hip_film_fold_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaFilmFold* fold, RaycaStats* stats_out);
 
 /* Post-build BVH read-back for parity tests against the oracle's literal SAH build:
  * `prim_order[i]` = index (in flatten order) of the primitive stored at slot i.  Buffers may be

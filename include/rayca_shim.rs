@@ -550,6 +550,49 @@ pub struct RaycaTonemap {
     pub rgba8_out: *mut c_void,
 }
 
+// rayca_hip_sample_plan_device: a film's variance into per-pixel weights, ray offsets and camera rays, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaSamplePlan {
+    pub width: u32,
+    pub height: u32,
+    pub budget: u32,
+    pub jitter: u32,
+    pub first_stratum: u32,
+    pub base_weight: u32,
+    pub fresh_weight: u32,
+    pub min_history: u32,
+    pub target: f32,
+    pub lum_floor: f32,
+    pub reserved: u32,
+    pub color: *const c_void,
+    pub variance: *const c_void,
+    pub length: *const c_void,
+    pub weight_out: *mut c_void,
+    pub offset_out: *mut c_void,
+    pub rays_out: *mut c_void,
+    pub pixel_out: *mut c_void,
+}
+
+// rayca_hip_film_fold_device: the samples traced along a plan's rays, folded into a history, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaFilmFold {
+    pub width: u32,
+    pub height: u32,
+    pub max_history: u32,
+    pub reserved: u32,
+    pub samples: *const c_void,
+    pub offset: *const c_void,
+    pub hist_color: *const c_void,
+    pub hist_length: *const c_void,
+    pub hist_moments: *const c_void,
+    pub color_out: *mut c_void,
+    pub length_out: *mut c_void,
+    pub moments_out: *mut c_void,
+    pub variance_out: *mut c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct RaycaStats {
@@ -638,6 +681,8 @@ extern "C" {
     pub fn rayca_hip_upsample_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, u: *const RaycaUpsample, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_meter_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, m: *const RaycaMeter, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_tonemap_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, t: *const RaycaTonemap, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_sample_plan_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, plan: *const RaycaSamplePlan, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_film_fold_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, fold: *const RaycaFilmFold, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
 }

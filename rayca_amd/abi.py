@@ -49,6 +49,9 @@ HITS_MAX = 16   # RAYCA_HITS_MAX: the largest RaycaHits.k
 TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
 TONEMAP_NAMES = ("linear", "reinhard", "aces")
 METER_WORDS, METER_COUNTED, METER_BLACK, METER_NOT_FINITE = 260, 256, 257, 258   # hist_out of rayca_hip_meter_device
+# rayca_hip_sample_plan_device: the pixels of a first-level scan unit (a wave's 64-pixel row segment), and the segment sums one
+# trip of the one-block scan over them covers (adaptive.inc kPlanScanChunk)
+PLAN_SEGMENT, PLAN_SCAN_CHUNK = 64, 4096
 # the resident draw (rayca_hip_renderer_draw): what it did, and the indices of rayca_hip_renderer_last_draw's two arrays
 DRAW_REUSED, DRAW_UPDATED, DRAW_REBUILT = 0, 1, 2
 DRAW_NAMES = ("reused", "updated", "rebuilt")
@@ -544,6 +547,49 @@ class RaycaTonemap(C.Structure):
     ]
 
 
+class RaycaSamplePlan(C.Structure):
+    """rayca_hip_sample_plan_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("budget", C.c_uint32),
+        ("jitter", C.c_uint32),
+        ("first_stratum", C.c_uint32),
+        ("base_weight", C.c_uint32),
+        ("fresh_weight", C.c_uint32),
+        ("min_history", C.c_uint32),
+        ("target", C.c_float),
+        ("lum_floor", C.c_float),
+        ("reserved", C.c_uint32),
+        ("color", C.c_void_p),
+        ("variance", C.c_void_p),
+        ("length", C.c_void_p),
+        ("weight_out", C.c_void_p),
+        ("offset_out", C.c_void_p),
+        ("rays_out", C.c_void_p),
+        ("pixel_out", C.c_void_p),
+    ]
+
+
+class RaycaFilmFold(C.Structure):
+    """rayca_hip_film_fold_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("max_history", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("samples", C.c_void_p),
+        ("offset", C.c_void_p),
+        ("hist_color", C.c_void_p),
+        ("hist_length", C.c_void_p),
+        ("hist_moments", C.c_void_p),
+        ("color_out", C.c_void_p),
+        ("length_out", C.c_void_p),
+        ("moments_out", C.c_void_p),
+        ("variance_out", C.c_void_p),
+    ]
+
+
 class SceneDesc:
     """Owns the buffers behind one RaycaSceneDesc."""
 
@@ -688,6 +734,10 @@ def bind_product_signatures(lib):
     lib.rayca_hip_meter_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaMeter), P(RaycaStats)]
     lib.rayca_hip_tonemap_device.restype = C.c_int32
     lib.rayca_hip_tonemap_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaTonemap), P(RaycaStats)]
+    lib.rayca_hip_sample_plan_device.restype = C.c_int32
+    lib.rayca_hip_sample_plan_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSamplePlan), P(RaycaStats)]
+    lib.rayca_hip_film_fold_device.restype = C.c_int32
+    lib.rayca_hip_film_fold_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaFilmFold), P(RaycaStats)]
     lib.rayca_hip_scene_primitive_order.restype = C.c_int32
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
@@ -712,7 +762,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_ambient_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
-    "rayca_hip_meter_device", "rayca_hip_tonemap_device",
+    "rayca_hip_meter_device", "rayca_hip_tonemap_device", "rayca_hip_sample_plan_device", "rayca_hip_film_fold_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",

@@ -83,6 +83,8 @@ struct FrameCtx {
   DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
   DeviceBuffer denoise_var[2];        // rayca_hip_denoise_variance_device: the two variance planes that go with them (4 B a pixel)
   DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
+  DeviceBuffer plan_weight;           // rayca_hip_sample_plan_device without weight_out: the weights its offsets kernel reads back (4 B a pixel)
+  DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
                                       // previous frame cleared them): generation 0 needs no memset launch
@@ -94,7 +96,7 @@ struct FrameCtx {
   // and made its device current.  (A buffer this list forgets is not leaked: its own destructor frees it, with the context.)
   void release() {
     for (DeviceBuffer* b : {&path_direct, &path_brdf, &path_state, &accum, &queue[0], &queue[1], &out8, &out32, &ray_io, &stack_spill, &frames, &mis_samples,
-                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask})
+                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask, &plan_weight, &plan_sums})
       b->release();
     if (heads_alloc) (void)hipFree(heads_alloc);
     if (counters) (void)hipFree(counters);
@@ -967,10 +969,17 @@ int32_t camera_frame_params(const RaycaScene* s, uint32_t width, uint32_t height
   fp.camera = s->host.world_trs[s->host.camera_node];
   return RAYCA_OK;
 }
-void camera_sample_params(uint32_t spp, uint32_t sample, FrameParams& fp) {
+// (the strata of a pixel: `count` a side, `step` apart, the first one `offset` in -- what rayca_hip_sample_plan_device hands its ray
+// kernel, which picks a stratum per ray)
+struct SubPixelGrid { float step, offset; uint32_t count; };
+SubPixelGrid sub_pixel_grid(uint32_t spp) {
   const float strate = sqrtf((float)spp);  // scene.rs:125-127
-  const float sub_offset = 0.5f / strate, sub_step = 1.0f / strate;
-  const uint32_t sc_i = (uint32_t)strate;
+  return SubPixelGrid{1.0f / strate, 0.5f / strate, (uint32_t)strate};
+}
+void camera_sample_params(uint32_t spp, uint32_t sample, FrameParams& fp) {
+  const SubPixelGrid grid = sub_pixel_grid(spp);
+  const float sub_offset = grid.offset, sub_step = grid.step;
+  const uint32_t sc_i = grid.count;
   const float ix = (float)(sample % sc_i), iy = (float)(sample / sc_i);  // scene.rs:130-131
   fp.sample = sample;
   fp.sub_step_x = ix * sub_step;

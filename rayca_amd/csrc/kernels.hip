@@ -29,6 +29,9 @@
 //   k_denoise_*       (denoise.inc: rayca_hip_denoise_device).
 //   k_accumulate      temporal accumulation of a frame into a history, with reprojection through the previous camera
 //                     (temporal.inc: rayca_hip_accumulate_device).
+//   k_plan_*,         adaptive sampling: a film's variance into per-pixel weights, ray offsets (an exact prefix sum) and camera
+//   k_film_fold       rays, and the fold of the samples traced along them back into the film
+//                     (adaptive.inc: rayca_hip_sample_plan_device, rayca_hip_film_fold_device).
 //   k_variance_init,  the variance-guided a-trous filter: the film's luminance variance steers the luminance weight and is
 //   k_atrous_var      filtered along with the colour (denoise_variance.inc: rayca_hip_denoise_variance_device).
 //   k_upsample        a low-resolution frame onto a full-size G-buffer: a joint bilateral upsample
@@ -456,6 +459,7 @@ RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole 
 #include "denoise.inc"
 #include "denoise_variance.inc"
 #include "temporal.inc"
+#include "adaptive.inc"
 #include "upsample.inc"
 #include "tonemap.inc"
 

@@ -1,5 +1,5 @@
 // post.inc -- the entry points of the image-space post passes (included from api.inc behind its last entry point): denoise,
-// accumulate, denoise_variance, upsample, meter and tonemap, their kernel pickers, and the checks they share.  A pass reads
+// accumulate, denoise_variance, upsample, meter, tonemap, sample_plan and film_fold, their kernel pickers, and the checks they share.  A pass reads
 // and writes images in device memory; its scene handle gives the device and the frame context (stream, scratch, ordering
 // against the context's frames and queries), and nothing is read through it before the pass runs.
 //
@@ -523,6 +523,132 @@ int32_t rayca_hip_tonemap_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   io.inv_white2 = t.white != 0.0f ? 1.0f / (t.white * t.white) : 0.0f;
   io.inv_gamma = 1.0f / t.gamma;   // (as a frame's: color/mod.rs:175-176)
   const auto kernel = pick_tonemap_kernel(t.op, io.rgba32f != nullptr, io.rgba8 != nullptr);
+  return run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) { return launch_tiles(stream, kernel, f, io, launches); });
+}
+
+// The sample plan (adaptive.inc): k_plan_weights -> k_plan_scan (one block) -> k_plan_offsets over the frame's tiles and, for
+// rays_out or pixel_out, k_plan_rays over the budget, each behind the other on the pass's stream.  The weights go through
+// weight_out or the context's scratch, the segment sums through the context's scratch; only the ray kernel reads the scene (its
+// camera, taken under the context's lock like a camera-ray export's).
+int32_t rayca_hip_sample_plan_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSamplePlan* pin, RaycaStats* stats_out) {
+  if (!s || !pin) return fail(RAYCA_ERR_BAD_ARG, "null scene or sample-plan arguments");
+  const RaycaSamplePlan& a = *pin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSamplePlan.reserved must be zero");
+  FrameTiles f{};
+  int32_t rc = frame_tiles(a.width, a.height, "RaycaSamplePlan", f);
+  if (rc != RAYCA_OK) return rc;
+  if ((uint64_t)f.count * 256u > (1ull << 32))
+    return fail(RAYCA_ERR_UNSUPPORTED, "RaycaSamplePlan.width x height x 256 exceeds 2^32: the sum of the weights must fit 32 bits, its product with the budget 64");
+  if (a.budget > (1u << 31)) return fail(RAYCA_ERR_BAD_ARG, "RaycaSamplePlan.budget exceeds 2^31");
+  if (a.jitter == 0 || a.jitter > 8) return fail(RAYCA_ERR_BAD_ARG, "jitter must be 1..8");
+  if (a.base_weight > 255) return fail(RAYCA_ERR_BAD_ARG, "base_weight above 255");
+  if (a.fresh_weight > 255) return fail(RAYCA_ERR_BAD_ARG, "fresh_weight above 255");
+  if (!(a.target > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "target must be > 0");
+  if (!(a.lum_floor > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "lum_floor must be > 0");
+  if (!a.color) return fail(RAYCA_ERR_BAD_ARG, "null color");
+  if (!a.variance) return fail(RAYCA_ERR_BAD_ARG, "null variance");
+  if (!a.length) return fail(RAYCA_ERR_BAD_ARG, "null length");
+  if (!a.offset_out) return fail(RAYCA_ERR_BAD_ARG, "null offset_out");
+  if ((rc = check_alignment({a.color}, "alignment: color is read 16 bytes a pixel", {a.variance, a.length, a.weight_out, a.offset_out, a.rays_out, a.pixel_out},
+                               "alignment: every image but color is read and written 4 bytes an element")) != RAYCA_OK) return rc;
+  if ((rc = pass_options(o, "a sample-plan call, which weighs a whole frame", 0u)) != RAYCA_OK) return rc;
+  if (a.rays_out && !s->host.has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109): rays_out needs one");
+  const uint32_t segments = f.tiles_x * a.height;   // (<= width x height <= 2^24)
+  PlanIo io{};
+  io.color = static_cast<const float4*>(a.color);
+  io.variance = static_cast<const float*>(a.variance);
+  io.length = static_cast<const float*>(a.length);
+  io.weight = static_cast<uint32_t*>(a.weight_out);
+  io.offset = static_cast<uint32_t*>(a.offset_out);
+  io.width = a.width;
+  io.height = a.height;
+  io.tiles_x = f.tiles_x;
+  io.count = f.count;
+  io.budget = a.budget;
+  io.base_weight = a.base_weight;
+  io.fresh_weight = a.fresh_weight;
+  io.min_history = (float)a.min_history;
+  io.target2 = a.target * a.target;
+  io.lum_floor = a.lum_floor;
+  const bool rays = a.budget != 0 && (a.rays_out || a.pixel_out);
+  const SubPixelGrid grid = sub_pixel_grid(a.jitter * a.jitter);
+  PlanRaysIo rio{io.offset, static_cast<float*>(a.rays_out), static_cast<uint32_t*>(a.pixel_out), f.count, a.budget, a.jitter, a.jitter * a.jitter,
+                 a.first_stratum % (a.jitter * a.jitter), grid.step};
+  FrameParams fp{};
+  return run_pass(
+      s, o, stats_out,
+      [&](FrameCtx* c) -> int32_t {
+        HIP_TRY(hipSetDevice(s->device));
+        int32_t prc = RAYCA_OK;
+        if (!io.weight && (prc = grow_behind_pass(c, c->plan_weight, (size_t)f.count * sizeof(uint32_t))) != RAYCA_OK) return prc;
+        if ((prc = grow_behind_pass(c, c->plan_sums, ((size_t)segments + 1u) * sizeof(uint32_t))) != RAYCA_OK) return prc;
+        if (rays && rio.rays) {   // (the camera is the scene's to move: read under the context's lock)
+          if ((prc = camera_frame_params(s, a.width, a.height, RaycaTile{}, fp)) != RAYCA_OK) return prc;
+          fp.sub_offset = grid.offset;
+        }
+        return RAYCA_OK;
+      },
+      [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+        FrameCtx* c = &s->ctx[o.context];
+        if (!io.weight) io.weight = static_cast<uint32_t*>(c->plan_weight.ptr);
+        io.sums = static_cast<uint32_t*>(c->plan_sums.ptr);
+        if ((rc = launch_tiles(stream, k_plan_weights, f, io, launches)) != RAYCA_OK) return rc;
+        hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(kPlanScanBlock), 0, stream, io.sums, segments);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        hipLaunchKernelGGL(k_plan_offsets, dim3(f.tiles), dim3(kBlock), 0, stream, io, segments);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        if (rays) {
+          hipLaunchKernelGGL(k_plan_rays, dim3(flat_grid(a.budget)), dim3(kBlock), 0, stream, fp, rio);
+          HIP_TRY(hipGetLastError());
+          ++launches;
+        }
+        return RAYCA_OK;
+      });
+}
+
+// The fold of a plan's samples into a history (adaptive.inc): one launch of k_film_fold, pixel-local, no scratch image.
+int32_t rayca_hip_film_fold_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaFilmFold* fin, RaycaStats* stats_out) {
+  if (!s || !fin) return fail(RAYCA_ERR_BAD_ARG, "null scene or fold arguments");
+  const RaycaFilmFold& a = *fin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaFilmFold.reserved must be zero");
+  FrameTiles f{};
+  int32_t rc = frame_tiles(a.width, a.height, "RaycaFilmFold", f);
+  if (rc != RAYCA_OK) return rc;
+  if (!a.samples) return fail(RAYCA_ERR_BAD_ARG, "null samples");
+  if (!a.offset) return fail(RAYCA_ERR_BAD_ARG, "null offset");
+  if (!a.color_out) return fail(RAYCA_ERR_BAD_ARG, "null color_out");
+  if (!a.length_out) return fail(RAYCA_ERR_BAD_ARG, "null length_out");
+  if (!a.hist_color || !a.hist_length) return fail(RAYCA_ERR_BAD_ARG, "hist_color and hist_length are both required: a fold continues a history");
+  if (a.moments_out && !a.hist_moments) return fail(RAYCA_ERR_BAD_ARG, "moments_out needs hist_moments");
+  if (a.variance_out && !a.moments_out) return fail(RAYCA_ERR_BAD_ARG, "variance_out needs moments_out");
+  if ((rc = check_alignment({a.samples, a.hist_color, a.color_out}, "alignment: samples, hist_color and color_out are read and written 16 bytes a pixel",
+                               {a.offset, a.hist_length, a.hist_moments, a.length_out, a.moments_out, a.variance_out},
+                               "alignment: every image but samples, hist_color and color_out is read and written 4 bytes an element")) != RAYCA_OK) return rc;
+  if ((rc = pass_options(o, "a fold call, which continues a whole frame's history", 0u)) != RAYCA_OK) return rc;
+  FoldIo io{};
+  io.samples = static_cast<const float4*>(a.samples);
+  io.offset = static_cast<const uint32_t*>(a.offset);
+  io.hist_color = static_cast<const float4*>(a.hist_color);
+  io.hist_length = static_cast<const float*>(a.hist_length);
+  io.color_out = static_cast<float4*>(a.color_out);
+  io.length_out = static_cast<float*>(a.length_out);
+  const bool moments = a.moments_out != nullptr;
+  if (moments) {
+    io.hist_moments = static_cast<const float*>(a.hist_moments);
+    io.moments_out = static_cast<float*>(a.moments_out);
+    io.variance_out = static_cast<float*>(a.variance_out);
+  }
+  io.width = a.width;
+  io.height = a.height;
+  io.tiles_x = f.tiles_x;
+  io.cap = (float)a.max_history;
+  const auto kernel = moments ? k_film_fold<true> : k_film_fold<false>;
   return run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) { return launch_tiles(stream, kernel, f, io, launches); });
 }
 

@@ -30,6 +30,31 @@ struct AccumulateIo {
   float rx, ry, rz, ux, uy, uz, bx, by, bz;   // right, up, back
 };
 
+// The blend: one sample c (finite or not, luminance lum) into a pixel's state -- whether it has a history, and that history's
+// colour h, length len and moments (mx, my) -- by the four rows of the header's table.  `cap` is (float)max_history, 0: unbounded.
+// k_accumulate applies it once a pixel, k_film_fold (adaptive.inc) once per sample of a pixel's list.
+__device__ __forceinline__ void film_blend(bool present, float4 h, float len, float mx, float my, float4 c, bool finite, float lum, float cap,
+                                           float4& o, float& n_out, float& m1, float& m2) {
+  if (present) {
+    if (finite) {
+      float n = len + 1.0f;
+      if (cap > 0.0f) n = fminf(n, cap);
+      const float a = 1.0f / n;
+      o = make_float4(h.x + (c.x - h.x) * a, h.y + (c.y - h.y) * a, h.z + (c.z - h.z) * a, h.w + (c.w - h.w) * a);
+      n_out = n;
+      m1 = mx + (lum - mx) * a;
+      m2 = my + (lum * lum - my) * a;
+    } else {
+      o = h; n_out = len; m1 = mx; m2 = my;
+    }
+  } else {
+    o = c;
+    n_out = finite ? 1.0f : 0.0f;
+    m1 = finite ? lum : 0.0f;
+    m2 = finite ? lum * lum : 0.0f;
+  }
+}
+
 // One pixel per lane, the denoiser's 64 x 4 tile per block: a wave is 64 consecutive pixels of a row, so that under a small
 // camera motion the taps of neighbouring lanes are neighbouring addresses -- a colour tap is a 1-KiB run of 16-B loads.  In
 // identity mode the pass is pixel-local: p's history is read before anything of p is written, which is what lets an output be
@@ -136,24 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(AccumulateIo io) {
 
   float4 o;
   float n_out, m1, m2;
-  if (present) {
-    if (finite) {
-      float n = len + 1.0f;
-      if (io.cap > 0.0f) n = fminf(n, io.cap);
-      const float a = 1.0f / n;
-      o = make_float4(h.x + (c.x - h.x) * a, h.y + (c.y - h.y) * a, h.z + (c.z - h.z) * a, h.w + (c.w - h.w) * a);
-      n_out = n;
-      m1 = mx + (lum - mx) * a;
-      m2 = my + (lum * lum - my) * a;
-    } else {
-      o = h; n_out = len; m1 = mx; m2 = my;
-    }
-  } else {
-    o = c;
-    n_out = finite ? 1.0f : 0.0f;
-    m1 = finite ? lum : 0.0f;
-    m2 = finite ? lum * lum : 0.0f;
-  }
+  film_blend(present, h, len, mx, my, c, finite, lum, io.cap, o, n_out, m1, m2);
   io.color_out[p] = o;
   io.length_out[p] = n_out;
   if (MOMENTS) {

@@ -121,6 +121,48 @@ class Film:
         self.frames_added += 1
         return dst["color"]
 
+    def add_adaptive(self, config: Config, budget=None, *, jitter=1, target=0.05, stream=None, context=0, **plan_kw):
+        """One more pass of `budget` rays (default: one a pixel) that the film's own variance deals out: DeviceScene.sample_plan
+        on the film's colour, variance and length, DeviceScene.radiance along the plan's rays -- gamma 1, seed (config.seed +
+        frames_added) mod 2^32 and sample frames_added mod jitter^2, which is also the plan's first_stratum -- and
+        DeviceScene.fold into the other history set.  `target` and `plan_kw` (lum_floor, base_weight, fresh_weight,
+        min_history) are sample_plan's.  With equal weights and budget = W x H the pass is add(config, jitter=jitter), bit for
+        bit.  It continues a history pixel by pixel, so the film must keep moments, hold at least one frame, and the camera must
+        stand where the last frame left it: anything else is add()'s business (ValueError).  The budget is the host's: nothing
+        is read back, nothing is waited for.  Returns the film's colour, as add() does."""
+        n = self.width * self.height
+        budget = n if budget is None else budget
+        if not isinstance(jitter, int) or isinstance(jitter, bool) or not 1 <= jitter <= 8:
+            raise ValueError(f"jitter: an integer 1..8, not {jitter!r}")
+        stray = [k for k in plan_kw if k not in ("lum_floor", "base_weight", "fresh_weight", "min_history")]
+        if stray:
+            raise ValueError(f"plan_kw: {stray} are not sample_plan's weight parameters")
+        if not self.with_moments:
+            raise ValueError("add_adaptive: the film keeps no moments (moments=True), so it has no variance to plan with; use add()")
+        if not self.frames_added:
+            raise ValueError("add_adaptive: the film is empty; add() a frame first")
+        b, s = self._buffers, self.scene
+        if bytes(s.camera_pose()) != self._pose:
+            raise ValueError("add_adaptive: the camera moved since the last frame; the reprojection is add()'s")
+        import torch
+        plan = b.get("plan")
+        if plan is None or plan["rays"].shape[0] != budget:
+            dev = b["frame"].device
+            plan = b["plan"] = {"offset": torch.empty((n + 1,), dtype=torch.int32, device=dev), "rays": torch.empty((budget, 6), dtype=torch.float32, device=dev),
+                                "samples": torch.empty((budget, 4), dtype=torch.float32, device=dev)}
+        self._gamma = config.gamma
+        cfg = dataclasses.replace(config, gamma=1.0, seed=(config.seed + self.frames_added) % 2 ** 32)
+        sub = self.frames_added % (jitter * jitter)
+        src, dst = b["hist"][self._hist], b["hist"][self._hist ^ 1]
+        s.sample_plan(src["color"], src["variance"], src["length"], budget, jitter=jitter, first_stratum=sub, target=target, want=("offset", "rays"),
+                      out={"offset": plan["offset"], "rays": plan["rays"]}, stream=stream, context=context, **plan_kw)
+        s.radiance(plan["rays"], cfg, sample=sub, out=plan["samples"], stream=stream, context=context)
+        s.fold(plan["samples"], plan["offset"], {k: v for k, v in src.items() if k != "variance"}, max_history=self.max_history, out=dst,
+               stream=stream, context=context)
+        self._hist ^= 1
+        self.frames_added += 1
+        return dst["color"]
+
     def _current(self, name):
         if not self.frames_added:
             raise ValueError("the film is empty: add() a frame first")

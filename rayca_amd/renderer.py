@@ -879,6 +879,93 @@ class DeviceScene:
             result["stats"] = stats
         return result
 
+    # ---- adaptive sampling: a film's variance decides where the next rays go (rayca_hip_sample_plan_device, rayca_hip_film_fold_device) ----
+    def sample_plan(self, color, variance, length, budget, *, jitter=1, first_stratum=0, target=0.05, lum_floor=1e-3, base_weight=0,
+                    fresh_weight=255, min_history=4, want=("offset", "rays", "pixel"), out=None, stream=None, context=0, want_stats=False):
+        """rayca_hip_sample_plan_device: where the next `budget` rays of a film go, asynchronously, everything in device memory.
+
+        color (H, W, 4), variance (H, W), length (H, W) float32: a film's colour, luminance variance and history length
+        (accumulate(), Film).  Every pixel gets an integer weight 0..255: base_weight plus one step for every `target`^2 of the
+        relative variance of its mean (variance / length over the squared luminance, the luminance at least lum_floor), and at
+        least fresh_weight where the history is shorter than min_history.  The budget is dealt out in proportion to the
+        weights, exactly: pixel p gets offset[p + 1] - offset[p] rays, which sum to `budget`.  Returns a dict of the outputs in
+        `want`: "weight" (H, W) int32, "offset" (H * W + 1,) int32, "rays" (budget, 6) float32 -- ray j of pixel p goes through
+        stratum (first_stratum + j - offset[p]) mod jitter^2 of the jitter x jitter sub-pixel positions, and is the row p of
+        camera_rays() for that sample of a jitter^2-spp frame -- and "pixel" (budget,) int32, the pixel of every ray; "offset"
+        is always made.  `out`: a dict of tensors to write instead of new ones.  The budget is the host's, so radiance() takes
+        the rays without a readback.  Stream handling as query(); with `want_stats` (which waits) the stats dict is "stats"."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        h, w = call.image(color)
+        known = ("weight", "offset", "rays", "pixel")
+        out = dict(out or {})
+        stray = [k for k in tuple(want) + tuple(out) if k not in known]
+        if stray:
+            raise ValueError(f"want / out: {stray} not in {known}")
+        if not isinstance(budget, int) or isinstance(budget, bool) or not 0 <= budget <= 1 << 31:
+            raise ValueError(f"budget: an integer 0..2**31, not {budget!r}")
+        shapes = {"weight": (torch.int32, (h, w)), "offset": (torch.int32, (h * w + 1,)), "rays": (torch.float32, (budget, 6)),
+                  "pixel": (torch.int32, (budget,))}
+        a = abi.RaycaSamplePlan()
+        a.width, a.height, a.budget, a.jitter, a.first_stratum = w, h, budget, jitter, first_stratum
+        a.base_weight, a.fresh_weight, a.min_history, a.target, a.lum_floor = base_weight, fresh_weight, min_history, target, lum_floor
+        result = {}
+        for name in known:
+            if name == "offset" or name in want or name in out:
+                result[name] = call.output(out.get(name), f"out[{name!r}]", *shapes[name])
+                setattr(a, name + "_out", result[name].data_ptr() or None)   # (an empty tensor has no pointer: budget 0 makes no rays)
+        a.color = call.input(color, "color", torch.float32, (h, w, 4)).data_ptr()
+        a.variance = call.input(variance, "variance", torch.float32, (h, w)).data_ptr()
+        a.length = call.input(length, "length", torch.float32, (h, w)).data_ptr()
+        stats = call.run(self._lib.rayca_hip_sample_plan_device, a, context=context, want_stats=want_stats)
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
+    def fold(self, samples, offset, history, *, max_history=0, moments=True, variance=True, out=None, stream=None, context=0, want_stats=False):
+        """rayca_hip_film_fold_device: the samples of a plan's rays into a history, asynchronously, everything in device memory.
+
+        samples (B, 4) float32: what radiance() returned for sample_plan()'s rays, with gamma 1; offset (H * W + 1,) int32: that
+        plan's offsets; history: a dict as accumulate() returns one -- "color" (H, W, 4), "length" (H, W) and, for moments,
+        "moments" (H, W, 2).  Pixel p's samples offset[p] .. offset[p + 1] - 1 enter its history one after the other, each as
+        accumulate() without prev_camera would blend a frame that held it; a pixel without samples keeps its history.
+        max_history, moments, variance and `out` as accumulate(): the outputs may be the history's own tensors.  Stream handling
+        as query().  Returns a dict: color, length, [moments], [variance], [stats]."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        history, out = dict(history or {}), dict(out or {})
+        for name, d, known in (("history", history, ("color", "length", "moments")), ("out", out, ("color", "length", "moments", "variance"))):
+            stray = [k for k in d if k not in known]
+            if stray:
+                raise ValueError(f"{name}: {stray} not in {known}")
+        if "color" not in history or "length" not in history:
+            raise ValueError("history: color and length are required (a fold continues a history; accumulate() starts one)")
+        h, w = call.image(history["color"], "history['color']")
+        if variance and not moments:
+            raise ValueError("variance: needs moments")
+        if moments and "moments" not in history:
+            raise ValueError("moments: the history has none")
+        if not isinstance(samples, torch.Tensor) or samples.dim() != 2 or samples.shape[1] != 4:
+            raise ValueError("samples: a (B, 4) float32 tensor is expected")
+        shapes = {"color": (torch.float32, (h, w, 4)), "length": (torch.float32, (h, w)), "moments": (torch.float32, (h, w, 2)),
+                  "variance": (torch.float32, (h, w))}
+        a = abi.RaycaFilmFold()
+        a.width, a.height, a.max_history = w, h, max_history
+        result = {}
+        for name in ("color", "length") + (("moments",) if moments else ()) + (("variance",) if variance else ()):
+            result[name] = call.output(out.get(name), f"out[{name!r}]", *shapes[name])
+            setattr(a, name + "_out", result[name].data_ptr())
+        # (an empty sample list has no pointer; no offset then leads into it, and the call still wants one that is not NULL)
+        a.samples = call.input(samples, "samples", torch.float32, (samples.shape[0], 4)).data_ptr() or result["color"].data_ptr()
+        a.offset = call.input(offset, "offset", torch.int32, (h * w + 1,)).data_ptr()
+        for name, x in history.items():
+            if name != "moments" or moments:
+                setattr(a, "hist_" + name, call.input(x, f"history[{name!r}]", *shapes[name]).data_ptr())
+        stats = call.run(self._lib.rayca_hip_film_fold_device, a, context=context, want_stats=want_stats)
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
 
 class _DeviceCall:
     """One call of a device entry point on torch tensors: the device and stream handling that query(), surface(), camera_rays()
