@@ -51,7 +51,8 @@ extern "C" {
                                   ambient occlusion: RaycaAmbient, rayca_hip_ambient_device;
                                   multi-hit ray queries: RaycaHits, rayca_hip_hits_device, RAYCA_HITS_;
                                   adaptive sampling: RaycaSamplePlan, rayca_hip_sample_plan_device, RaycaFilmFold,
-                                  rayca_hip_film_fold_device */
+                                  rayca_hip_film_fold_device;
+                                  irradiance gathering: RaycaGather, rayca_hip_gather_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -950,6 +951,86 @@ struct RaycaRadiance {
 typedef struct RaycaRadiance RaycaRadiance;
 int32_t rayca_hip_radiance_device(RaycaScene* scene, const RaycaConfig* cfg, const RaycaRenderOptions* opts, const RaycaRadiance* radiance,
                                   RaycaStats* stats_out);
+
+/* Irradiance gathering on DEVICE memory: the light that arrives AT `count` caller-supplied points -- the radiance along `samples`
+ * rays over the hemisphere (or, with a table that covers it, the sphere) of each point's normal, folded into one irradiance record
+ * and nine spherical-harmonic coefficients per point: lightmap baking, irradiance probes, a final gather on a G-buffer.  The rays
+ * are rayca_hip_ambient_device's, made in registers; the radiance is rayca_hip_radiance_device's, run by the same frame driver; the
+ * fold has a fixed order.  No ray buffer is written or read, and the per-ray radiance is held for one internal frame at a time.
+ *
+ * The specification, in f32 with every operation rounded on its own.
+ *   Rays.  Ray j of point i is sample j of point i of RaycaAmbient's comment, word for word: the same frame (T, B), the same
+ *   rotation (c, s) -- without a rotation array rx = lx, ry = ly and no operation is performed --, the same
+ *     d  = ((T * rx) + (B * ry)) + n * lz        with (lx, ly, lz) = dirs[dir_first + j]
+ *     o  = p + n * bias
+ *   (one function makes both calls' rays).  A point is inactive by the same rule: n.x == 0 && n.y == 0 && n.z == 0, or any of the
+ *   six inputs p, n not finite.  There is no radius.  Keeping d unit is the caller's business: unit normals and unit dirs.
+ *   Radiance.  L(i, j) is, bit for bit, what rayca_hip_radiance_device writes to rgba32f_out for the ray (o, d), the same cfg and
+ *   `sample`, and the pixel index first_index + i * S + j (the path draws from the stream of (cfg->seed, that index, sample)).
+ *   The Configs of that call are served, with its refusals; in addition cfg->gamma must be exactly 1 (a mean of gamma-encoded
+ *   values means nothing): RAYCA_ERR_UNSUPPORTED naming RaycaConfig.gamma otherwise.
+ *   Fold, per point, j ascending:
+ *     kept = 0; E = (0, 0, 0); H[k] = (0, 0, 0) for k = 0 .. 8
+ *     sample j counts iff L.r, L.g and L.b are all finite (x - x == 0 for each: a NaN or infinite sample stays out)
+ *     for a sample that counts:
+ *       c    = w[dir_first + j] * L     per r, g, b   (without `weights`: c = L, and no operation is performed)
+ *       E    = E + c
+ *       H[k] = H[k] + c * Y_k(d_j)      k = 0 .. 8, d_j the traced direction
+ *       kept = kept + 1
+ *     Y0 = 0.2820948f                    Y1 = 0.4886025f * d.y              Y2 = 0.4886025f * d.z
+ *     Y3 = 0.4886025f * d.x              Y4 = 1.0925484f * (d.x * d.y)      Y5 = 1.0925484f * (d.y * d.z)
+ *     Y6 = 0.3153916f * ((3.0f * (d.z * d.z)) - 1.0f)
+ *     Y7 = 1.0925484f * (d.x * d.z)      Y8 = 0.5462742f * ((d.x * d.x) - (d.y * d.y))
+ *     kept > 0: E = E / float(kept), H[k] = H[k] / float(kept), componentwise; otherwise they stay 0
+ *   Outputs (any may be NULL, not all), per point:
+ *     irradiance_out  4 x f32      (E.r, E.g, E.b, float(kept) / float(S))
+ *     sh_out          9 x 4 x f32  [k] = (H[k].r, H[k].g, H[k].b, 0)
+ *     kept_out        u32          kept
+ *     samples_out     S x 4 x f32  L(i, j) itself, as the radiance call writes it
+ *   An inactive point gives zeros everywhere, its S rows of samples_out included.  With cosine-distributed dirs and no weights E is
+ *   the irradiance / pi; any other scale (a solid-angle weight for a uniform table, say) is the caller's, through `weights`.
+ *   Inactive points in the queue: their S slots are queued as the ray o = d = (0, 0, 0), traced and shaded like any degenerate ray
+ *   of a radiance call, and the result is discarded -- the queue of an internal frame is dense, entry = i * S + j.  Hence
+ *   RaycaStats.rays_primary = count x S, inactive points included.
+ *   Chunks.  The call runs whole points per internal frame: at most 2^22 rays a frame (at least one point), and at most
+ *   chunk_points points where that is not zero.  The per-ray radiance lives in samples_out when given, else in a scratch of the
+ *   frame context sized by the chunk, not by count x S.  The radiance call's results do not depend on chunking (its "chunks"
+ *   above), and a point's fold reads its own S records alone, so every output is the same bits for every chunk_points.
+ * opts (may be NULL), ordering and statistics as for rayca_hip_radiance_device: stream, context, wait_event, record_event,
+ * collect_stats; tile, engine and camera_rays must be zero; ordered on its context like a frame; asynchronous unless stats_out is
+ * given.  RaycaStats are a wavefront frame's, summed over the internal frames (node_format: ORed; rows_rendered: the number of
+ * frames); the pass that queues the rays and the fold are under RAYCA_KERNEL_OTHER.  count == 0 is RAYCA_OK and launches nothing;
+ * nothing outside [0, count) of an output is written.
+ * Refusals, before any GPU work and before the scene is looked at, in this order.  RAYCA_ERR_BAD_ARG: NULL scene / cfg / struct;
+ * NULL points, normals, dirs; samples 0 or > 64; dir_first + samples > dir_count; non-zero reserved; no output; irradiance_out,
+ * sh_out or samples_out not 16-byte aligned; bias not finite; first_index + count x S above 2^32, or count x S above 2^31; then
+ * the Config as the radiance call checks it (unknown integrator or sampler, light_samples == 0); then opts: context > 7, a
+ * non-zero field that does not apply.  Then RAYCA_ERR_UNSUPPORTED: RAYCA_TRAVERSAL_EXHAUSTIVE, the Configs the radiance call
+ * does not serve, gamma != 1.  count == 0 is then RAYCA_OK.  Then the scene: RAYCA_ERR_EMPTY_SCENE, RAYCA_ERR_UNSUPPORTED for a
+ * directional light under NEE, as the radiance call. */
+struct RaycaGather {
+  uint32_t count;         /* points */
+  uint32_t samples;       /* S: 1 .. 64 rays a point */
+  const void* points;     /* DEVICE: count x 3 f32 */
+  const void* normals;    /* DEVICE: count x 3 f32; (0, 0, 0) marks an inactive point (a G-buffer's miss) */
+  const void* rotations;  /* DEVICE: count x 2 f32 (cos, sin), or NULL => no rotation */
+  const void* dirs;       /* DEVICE: dir_count x 3 f32 local directions, z along the normal */
+  const void* weights;    /* DEVICE: dir_count f32, or NULL => no weighting */
+  uint32_t dir_count;
+  uint32_t dir_first;     /* sample j takes dirs / weights [dir_first + j] */
+  float bias;             /* o = p + n * bias; finite */
+  uint32_t sample;        /* RNG stream of the paths, as RaycaRadiance.sample */
+  uint32_t first_index;   /* ray (i, j) is "pixel" first_index + i * S + j of a radiance call */
+  uint32_t chunk_points;  /* 0: the library's choice; else at most this many points per internal frame */
+  uint32_t reserved[2];   /* must be zero */
+  void* irradiance_out;   /* DEVICE: count x 4 f32, 16-byte aligned, or NULL */
+  void* sh_out;           /* DEVICE: count x 9 x 4 f32, 16-byte aligned, or NULL */
+  void* kept_out;         /* DEVICE: count u32, or NULL */
+  void* samples_out;      /* DEVICE: count x S x 4 f32, 16-byte aligned, or NULL */
+};
+typedef struct RaycaGather RaycaGather;
+int32_t rayca_hip_gather_device(RaycaScene* scene, const RaycaConfig* cfg, const RaycaRenderOptions* opts, const RaycaGather* gather,
+                                RaycaStats* stats_out);
 
 /* The edge-avoiding a-trous wavelet denoiser, on a frame and its G-buffer in DEVICE memory: what rayca_hip_render_device wrote to
  * d_rgba32f_out (rendered with gamma 1) and what rayca_hip_surface_device wrote for the frame's camera rays go in, the filtered

@@ -401,6 +401,30 @@ pub struct RaycaRadiance {
     pub rgba8_out: *mut c_void,
 }
 
+// rayca_hip_gather_device: points, normals and a direction table in, irradiance and SH coefficients per point out, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaGather {
+    pub count: u32,
+    pub samples: u32,
+    pub points: *const c_void,
+    pub normals: *const c_void,
+    pub rotations: *const c_void,
+    pub dirs: *const c_void,
+    pub weights: *const c_void,
+    pub dir_count: u32,
+    pub dir_first: u32,
+    pub bias: f32,
+    pub sample: u32,
+    pub first_index: u32,
+    pub chunk_points: u32,
+    pub reserved: [u32; 2],
+    pub irradiance_out: *mut c_void,
+    pub sh_out: *mut c_void,
+    pub kept_out: *mut c_void,
+    pub samples_out: *mut c_void,
+}
+
 // rayca_hip_denoise_device: the a-trous filter on a frame and its G-buffer, all in DEVICE memory
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -674,6 +698,7 @@ extern "C" {
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_gather_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, gather: *const RaycaGather, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;

@@ -361,6 +361,30 @@ class RaycaAmbient(C.Structure):
     ]
 
 
+class RaycaGather(C.Structure):
+    """rayca_hip_gather_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("samples", C.c_uint32),
+        ("points", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("rotations", C.c_void_p),
+        ("dirs", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("dir_count", C.c_uint32),
+        ("dir_first", C.c_uint32),
+        ("bias", C.c_float),
+        ("sample", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("chunk_points", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+        ("irradiance_out", C.c_void_p),
+        ("sh_out", C.c_void_p),
+        ("kept_out", C.c_void_p),
+        ("samples_out", C.c_void_p),
+    ]
+
+
 class RaycaSurfaceQuery(C.Structure):
     """rayca_hip_surface_device: every pointer is DEVICE memory."""
     _fields_ = [
@@ -720,6 +744,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_camera_rays_device.argtypes = [C.c_void_p, P(RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, P(RaycaRenderOptions), C.c_void_p]
     lib.rayca_hip_radiance_device.restype = C.c_int32
     lib.rayca_hip_radiance_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaRadiance), P(RaycaStats)]
+    lib.rayca_hip_gather_device.restype = C.c_int32
+    lib.rayca_hip_gather_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaGather), P(RaycaStats)]
     lib.rayca_hip_denoise_device.restype = C.c_int32
     lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
     lib.rayca_hip_scene_camera.restype = C.c_int32
@@ -760,7 +786,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device", "rayca_hip_hits_device",
     "rayca_hip_ambient_device",
-    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_denoise_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device", "rayca_hip_sample_plan_device", "rayca_hip_film_fold_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",

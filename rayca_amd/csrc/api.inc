@@ -85,6 +85,7 @@ struct FrameCtx {
   DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
   DeviceBuffer plan_weight;           // rayca_hip_sample_plan_device without weight_out: the weights its offsets kernel reads back (4 B a pixel)
   DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment)
+  DeviceBuffer gather_samples;        // rayca_hip_gather_device without samples_out: the radiance records of one internal frame (16 B a ray)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
                                       // previous frame cleared them): generation 0 needs no memset launch
@@ -96,7 +97,7 @@ struct FrameCtx {
   // and made its device current.  (A buffer this list forgets is not leaked: its own destructor frees it, with the context.)
   void release() {
     for (DeviceBuffer* b : {&path_direct, &path_brdf, &path_state, &accum, &queue[0], &queue[1], &out8, &out32, &ray_io, &stack_spill, &frames, &mis_samples,
-                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask, &plan_weight, &plan_sums})
+                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask, &plan_weight, &plan_sums, &gather_samples})
       b->release();
     if (heads_alloc) (void)hipFree(heads_alloc);
     if (counters) (void)hipFree(counters);
@@ -604,6 +605,15 @@ int32_t pass_options(const RaycaRenderOptions& o, const char* what, uint32_t acc
 // generation class, index of the event pair, the format launched; refill: -1 = a format calibration, 0/1 = a kernel calibration
 struct TuneEvent { int cls; size_t ev; int format; int refill; };
 
+// What feeds generation 0 of a frame whose rays are not the camera's: a ray array (rayca_hip_radiance_device, k_enqueue_rays) or the
+// inputs the rays are made from (one internal frame of rayca_hip_gather_device, k_enqueue_gather).  Ray i of the feed is "pixel" i of
+// the frame and draws from the stream of (cfg.seed, first_index + i, sample).
+struct RayFeed {
+  const float* rays;        // DEVICE: 6 f32 a ray, or nullptr:
+  const GatherIo* gather;   // ... the points, normals and table of the frame (its first_index is the feed's)
+  uint32_t first_index, sample;
+};
+
 // What the steps of one frame share.
 struct Frame {
   RaycaScene* s;
@@ -617,7 +627,7 @@ struct Frame {
   const DevScene* dscene;           // s->dev_full once the other node formats are there, else s->dev
   uint8_t* rgba8;
   float4* rgba32f;
-  const RaycaRadiance* rays;        // rayca_hip_radiance_device: generation 0 reads these rays from a queue, not the camera's (null for a frame)
+  const RayFeed* rays;              // rayca_hip_radiance_device, rayca_hip_gather_device: generation 0 reads this feed's rays from a queue, not the camera's (null for a frame)
   uint32_t in_flight;               // frames_in_flight_hint
   bool fused;                       // one generation, one sample: the generation kernel writes the pixel (no k_resolve)
   bool timing;                     // RaycaStats asked for: every launch timed
@@ -947,6 +957,25 @@ int32_t fill_stats(Frame& f, RaycaStats* out) {
   return RAYCA_OK;
 }
 
+// The statistics of several frames that one call ran (rayca_hip_gather_device's internal frames) as one: every counter, time and
+// launch count summed -- rows_rendered becomes the number of frames where each is one row -- and node_format ORed.  Every field of
+// RaycaStats is named here: the size pins the list, so that a field added to the struct is added here too.
+void stats_add(RaycaStats& total, const RaycaStats& s) {
+  static_assert(sizeof(RaycaStats) == 8 * sizeof(uint64_t) + 2 * sizeof(float) + 4 * sizeof(uint32_t) + RAYCA_KERNEL_CLASSES * (sizeof(float) + sizeof(uint32_t)),
+                "RaycaStats has a field that stats_add does not sum");
+  total.rays_primary += s.rays_primary; total.rays_shadow += s.rays_shadow; total.rays_bounce += s.rays_bounce;
+  total.boxes_tested += s.boxes_tested; total.triangles_tested += s.triangles_tested; total.hits_shaded += s.hits_shaded;
+  total.wave_box_slots += s.wave_box_slots; total.wave_triangle_slots += s.wave_triangle_slots;
+  total.kernel_ms += s.kernel_ms; total.trace_kernel_ms += s.trace_kernel_ms;
+  total.kernel_launches += s.kernel_launches; total.trace_kernel_launches += s.trace_kernel_launches;
+  total.rows_rendered += s.rows_rendered;
+  total.node_format |= s.node_format;
+  for (int k = 0; k < RAYCA_KERNEL_CLASSES; ++k) {
+    total.class_ms[k] += s.class_ms[k];
+    total.class_launches[k] += s.class_launches[k];
+  }
+}
+
 // What camera_ray() and the pixel <-> packed-row mapping of the kernels read from FrameParams, for every call that makes a
 // frame's camera rays (render_body, rayca_hip_camera_rays_device).  The two halves of one set-up: per frame the tile, the
 // image geometry and the camera -- RAYCA_ERR_BAD_ARG for a tile that names no part; fp.rows == 0 means "nothing to do" --
@@ -1004,7 +1033,7 @@ void config_frame_params(const Frame& f, FrameParams& fp) {
 // ---- the frame driver: what render_body and rayca_hip_radiance_device run behind their own checks and pass_acquire ---------
 // A frame and a radiance query are the same passes over the same buffers: frame_begin, frame_run, frame_finish.  They differ
 // in three places, all read off f.rays: generation 0's input (nothing for camera rays; queue 1, which one k_enqueue_rays
-// launch fills, for a caller's), queue 1 (a caller's rays need it even at depth 1 and for Flat), and where the Frame gets its
+// launch fills, for a caller's -- or one k_enqueue_gather launch, for the rays rayca_hip_gather_device makes), queue 1 (a caller's rays need it even at depth 1 and for Flat), and where the Frame gets its
 // shape (the caller sets the geometry of f.fp: the camera and tile, or one row of `count` pixels).
 
 // The Frame of an acquired pass and its path buffers.  The caller has set s, cfg, opts, plan, rays and the geometry of fp.
@@ -1079,10 +1108,13 @@ int32_t frame_run(Frame& f) {
                         static_cast<QueuedRay*>(c->queue[g & 1].ptr), q_count + (g & 1)};
       if (g != 0) HIP_TRY(hipMemsetAsync(q.out_count, 0, sizeof(uint32_t), stream));
       else if (f.rays) {
-        const RaycaRadiance& rr = *f.rays;
+        const RayFeed& feed = *f.rays;
         rc = timed_launch(f.log, stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
-          hipLaunchKernelGGL(k_enqueue_rays, dim3((npix + kBlock - 1u) / kBlock), dim3(kBlock), 0, stream, static_cast<const float*>(rr.rays), npix, rr.first_index,
-                             f.cfg.seed, rr.sample, q.in, q.in_count);
+          const dim3 grid((npix + kBlock - 1u) / kBlock);
+          if (feed.gather)
+            hipLaunchKernelGGL(pick_gather_enqueue(feed.gather->a.rotations != nullptr), grid, dim3(kBlock), 0, stream, *feed.gather, f.cfg.seed, feed.sample, q.in, q.in_count);
+          else
+            hipLaunchKernelGGL(k_enqueue_rays, grid, dim3(kBlock), 0, stream, feed.rays, npix, feed.first_index, f.cfg.seed, feed.sample, q.in, q.in_count);
           return RAYCA_OK;
         });
         if (rc != RAYCA_OK) return rc;
@@ -1863,6 +1895,52 @@ int32_t rayca_hip_camera_rays_device(RaycaScene* s, const RaycaConfig* cfg, uint
   });
 }
 
+}  // extern "C"
+
+// ---- what the two ray-fed calls (rayca_hip_radiance_device, rayca_hip_gather_device) check and set up alike ------------------
+namespace {
+
+// The Config's values, from the struct alone (RAYCA_ERR_BAD_ARG).
+int32_t ray_fed_config_args(const RaycaConfig& cfg) {
+  if (cfg.integrator > RAYCA_INTEGRATOR_PATHTRACER) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.integrator: unknown integrator");
+  if (cfg.direct_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.direct_sampler: unknown sampler");
+  if (cfg.indirect_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.indirect_sampler: unknown sampler");
+  if (cfg.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.light_samples must be > 0");
+  return RAYCA_OK;
+}
+// What the queue-fed generation kernels do not cover (the per-pixel stack machine and the exhaustive instantiations have no
+// queue-fed form): RAYCA_ERR_UNSUPPORTED, behind the options.  `what`: "a radiance query", ...
+int32_t ray_fed_unsupported(const RaycaRenderOptions& o, const RaycaConfig& cfg, const char* what) {
+  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_UNSUPPORTED, std::string("RaycaRenderOptions.traversal: ") + what + " has no exhaustive form");
+  if (const char* field = generation_kernels_gap(cfg))
+    return fail(RAYCA_ERR_UNSUPPORTED, std::string("RaycaConfig.") + field + ": " + what + " runs on the generation kernels only (Flat; Pathtracer with NEE or no direct sampler, cosine or hemisphere bounces, no roulette, one light sample where it bounces)");
+  return RAYCA_OK;
+}
+// The scene, behind the empty batch.
+int32_t ray_fed_scene(const RaycaScene* s, const RaycaConfig& cfg) {
+  if (const int32_t rc = refuse_empty_scene(s); rc != RAYCA_OK) return rc;
+  if (nee_meets_directional_light(s, cfg)) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaConfig.direct_sampler: a directional light under NEE is a todo!() of the reference (nee.rs:178)");
+  return RAYCA_OK;
+}
+// The Frame of `count` fed rays, up to frame_begin: a one-sample frame of the wavefront engine, one row of `count` pixels; none of
+// the camera's terms is read by a queue-fed kernel.
+void ray_fed_frame(Frame& f, RaycaScene* s, const RaycaConfig& cfg, const RaycaRenderOptions& o, const RayFeed* feed, uint32_t count) {
+  f.s = s;
+  f.cfg = cfg;
+  f.cfg.samples_per_pixel = 1;   // (not read from the caller's: a call is one sample of every ray)
+  f.opts = o;
+  f.rays = feed;
+  const bool flat = cfg.integrator == RAYCA_INTEGRATOR_FLAT;
+  f.plan = LaunchPlan{flat ? kModeFlat : kModePath, true, o.collect_stats != 0, true, flat ? 1u : cfg.max_depth};
+  FrameParams& fp = f.fp;
+  fp.width = count; fp.height = 1; fp.rows = 1;
+  fp.part = 0; fp.parts = 1; fp.band = 1;
+}
+
+}  // namespace
+
+extern "C" {
+
 // Radiance along the caller's rays: a one-sample frame of the wavefront engine, run by the frame driver (frame_begin, frame_run,
 // frame_finish) as render_body's is.  What is its own are the driver's three differences, all behind f.rays: generation 0 reads
 // its rays from a queue that k_enqueue_rays (wavefront.inc) fills -- queue 1, the queue generation 1 writes over once generation
@@ -1884,41 +1962,108 @@ int32_t rayca_hip_radiance_device(RaycaScene* s, const RaycaConfig* cfg_in, cons
   if (!rr.rays) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.rays: null rays");
   if (!rr.rgba32f_out && !rr.rgba8_out) return fail(RAYCA_ERR_BAD_ARG, "no output: RaycaRadiance.rgba32f_out and rgba8_out are both null");
   if (reinterpret_cast<uintptr_t>(rr.rgba32f_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaRadiance.rgba32f_out must be 16-byte aligned");
-  if (cfg.integrator > RAYCA_INTEGRATOR_PATHTRACER) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.integrator: unknown integrator");
-  if (cfg.direct_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.direct_sampler: unknown sampler");
-  if (cfg.indirect_sampler > RAYCA_SAMPLER_MIS) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.indirect_sampler: unknown sampler");
-  if (cfg.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.light_samples must be > 0");
-  int32_t rc = pass_options(o, "a radiance query", kOptTraversal | kOptCollectStats);
+  int32_t rc = ray_fed_config_args(cfg);
   if (rc != RAYCA_OK) return rc;
-  // what the queue-fed generation kernels do not cover (the per-pixel stack machine and the exhaustive instantiations have no
-  // queue-fed form)
-  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: a radiance query has no exhaustive form");
-  if (const char* field = generation_kernels_gap(cfg))
-    return fail(RAYCA_ERR_UNSUPPORTED, std::string("RaycaConfig.") + field + ": a radiance query runs on the generation kernels only (Flat; Pathtracer with NEE or no direct sampler, cosine or hemisphere bounces, no roulette, one light sample where it bounces)");
+  if ((rc = pass_options(o, "a radiance query", kOptTraversal | kOptCollectStats)) != RAYCA_OK) return rc;
+  if ((rc = ray_fed_unsupported(o, cfg, "a radiance query")) != RAYCA_OK) return rc;
   if (rr.count == 0) {
     if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
     return RAYCA_OK;
   }
-  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
-  if (nee_meets_directional_light(s, cfg)) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaConfig.direct_sampler: a directional light under NEE is a todo!() of the reference (nee.rs:178)");
+  if ((rc = ray_fed_scene(s, cfg)) != RAYCA_OK) return rc;
 
   std::lock_guard<std::mutex> lock(s->ctx[o.context].mu);
   Frame f{};
-  f.s = s;
-  f.cfg = cfg;
-  f.cfg.samples_per_pixel = 1;   // (not read from the caller's: a call is one sample of every ray)
-  f.opts = o;
-  f.rays = rin;
-  const bool flat = cfg.integrator == RAYCA_INTEGRATOR_FLAT;
-  f.plan = LaunchPlan{flat ? kModeFlat : kModePath, true, o.collect_stats != 0, true, flat ? 1u : cfg.max_depth};
-  // the "frame" is one row of `count` pixels; none of the camera's terms is read by a queue-fed kernel
-  FrameParams& fp = f.fp;
-  fp.width = rr.count; fp.height = 1; fp.rows = 1;
-  fp.part = 0; fp.parts = 1; fp.band = 1;
+  const RayFeed feed{static_cast<const float*>(rr.rays), nullptr, rr.first_index, rr.sample};
+  ray_fed_frame(f, s, cfg, o, &feed, rr.count);
   ContextPass pass{};
   if ((rc = pass_acquire(s, o, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
   if ((rc = frame_begin(f, pass, rr.rgba8_out, rr.rgba32f_out)) != RAYCA_OK || (rc = frame_run(f)) != RAYCA_OK) return rc;
   return frame_finish(f, pass, stats_out, false);
+}
+
+// Irradiance at points (gather.inc): the call's points in internal frames of whole points, each a radiance query's frame whose
+// generation 0 is fed by k_enqueue_gather -- ambient.inc's rays, made in registers -- and whose records k_gather_fold folds
+// behind k_resolve, on the same stream.  Each internal frame is a pass of its own on the context (so the statistics of each are a
+// frame's, and are summed); the caller's wait_event goes in front of the first, its record_event behind the last.  The records live
+// in samples_out or in the context's gather_samples, sized by the largest frame: the first.
+int32_t rayca_hip_gather_device(RaycaScene* s, const RaycaConfig* cfg_in, const RaycaRenderOptions* opts_in, const RaycaGather* gin,
+                                RaycaStats* stats_out) {
+  if (!s || !cfg_in || !gin) return fail(RAYCA_ERR_BAD_ARG, "null scene, config or RaycaGather");
+  const RaycaGather& rg = *gin;
+  const RaycaConfig& cfg = *cfg_in;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (!rg.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.points: null points");
+  if (!rg.normals) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.normals: null normals");
+  if (!rg.dirs) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.dirs: null dirs");
+  if (rg.samples == 0 || rg.samples > 64) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.samples: 1 .. 64 samples a point");
+  if (rg.dir_first > rg.dir_count || rg.samples > rg.dir_count - rg.dir_first)
+    return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.dir_first + samples exceeds dir_count");
+  if (rg.reserved[0] != 0 || rg.reserved[1] != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.reserved must be zero");
+  if (!rg.irradiance_out && !rg.sh_out && !rg.kept_out && !rg.samples_out) return fail(RAYCA_ERR_BAD_ARG, "no output for a gather call");
+  if (reinterpret_cast<uintptr_t>(rg.irradiance_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.irradiance_out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rg.sh_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.sh_out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rg.samples_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.samples_out must be 16-byte aligned");
+  if (!std::isfinite(rg.bias)) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.bias is not finite");
+  const uint64_t total = (uint64_t)rg.count * rg.samples;
+  if ((uint64_t)rg.first_index + total > (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.first_index + count x samples exceeds 2^32");
+  if (total > (1ull << 31)) return fail(RAYCA_ERR_BAD_ARG, "RaycaGather.count x samples exceeds 2^31");
+  int32_t rc = ray_fed_config_args(cfg);
+  if (rc != RAYCA_OK) return rc;
+  if ((rc = pass_options(o, "a gather call", kOptTraversal | kOptCollectStats)) != RAYCA_OK) return rc;
+  if ((rc = ray_fed_unsupported(o, cfg, "a gather call")) != RAYCA_OK) return rc;
+  if (!(cfg.gamma == 1.0f)) return fail(RAYCA_ERR_UNSUPPORTED, "RaycaConfig.gamma: a gather call folds linear radiance: gamma must be exactly 1");
+  if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+  if (rg.count == 0) return RAYCA_OK;
+  if ((rc = ray_fed_scene(s, cfg)) != RAYCA_OK) return rc;
+
+  const uint32_t samples = rg.samples;
+  uint32_t per_frame = std::max(1u, kGatherFrameRays / samples);
+  if (rg.chunk_points != 0 && rg.chunk_points < per_frame) per_frame = rg.chunk_points;
+  const bool sh = rg.sh_out != nullptr, weights = rg.weights != nullptr, rot = rg.rotations != nullptr;
+  std::lock_guard<std::mutex> lock(s->ctx[o.context].mu);
+  for (uint32_t first = 0; first < rg.count;) {
+    const uint32_t points = std::min(per_frame, rg.count - first), rays = points * samples;
+    const size_t ray0 = (size_t)first * samples;
+    RaycaRenderOptions of = o;
+    if (first != 0) of.wait_event = nullptr;
+    if (first + points != rg.count) of.record_event = nullptr;
+    GatherIo io{};
+    io.a.points = static_cast<const float*>(rg.points) + 3ull * first;
+    io.a.normals = static_cast<const float*>(rg.normals) + 3ull * first;
+    io.a.rotations = rot ? static_cast<const float*>(rg.rotations) + 2ull * first : nullptr;
+    io.a.dirs = static_cast<const float*>(rg.dirs) + 3ull * rg.dir_first;
+    io.a.radius_all = INFINITY;   // (ambient_point's radius: not read by either kernel)
+    io.a.bias = rg.bias;
+    io.a.count = points;
+    io.a.samples = samples;
+    io.weights = weights ? static_cast<const float*>(rg.weights) + rg.dir_first : nullptr;
+    io.first_index = rg.first_index + (uint32_t)ray0;
+    io.irradiance_out = rg.irradiance_out ? static_cast<float4*>(rg.irradiance_out) + first : nullptr;
+    io.sh_out = sh ? static_cast<float4*>(rg.sh_out) + 9ull * first : nullptr;
+    io.kept_out = rg.kept_out ? static_cast<uint32_t*>(rg.kept_out) + first : nullptr;
+    io.samples_out = rg.samples_out ? static_cast<float4*>(rg.samples_out) + ray0 : nullptr;
+    Frame f{};
+    const RayFeed feed{nullptr, &io, io.first_index, rg.sample};
+    ray_fed_frame(f, s, cfg, of, &feed, rays);
+    ContextPass pass{};
+    if ((rc = pass_acquire(s, of, stats_out != nullptr, pass)) != RAYCA_OK) return rc;
+    if (!io.samples_out && (rc = grow_behind_pass(pass.c, pass.c->gather_samples, (size_t)rays * sizeof(float4))) != RAYCA_OK) return rc;
+    io.samples = io.samples_out ? io.samples_out : static_cast<float4*>(pass.c->gather_samples.ptr);
+    if ((rc = frame_begin(f, pass, nullptr, io.samples)) != RAYCA_OK || (rc = frame_run(f)) != RAYCA_OK) return rc;
+    rc = timed_launch(f.log, f.stream, RAYCA_KERNEL_OTHER, f.timing, false, [&] {
+      hipLaunchKernelGGL(pick_gather_fold(sh, weights, rot), dim3((points + kGatherFoldBlock - 1u) / kGatherFoldBlock), dim3(kGatherFoldBlock), 0, f.stream, io);
+      return RAYCA_OK;
+    });
+    if (rc != RAYCA_OK) return rc;
+    RaycaStats st{};
+    if ((rc = frame_finish(f, pass, stats_out ? &st : nullptr, false)) != RAYCA_OK) return rc;
+    if (stats_out) stats_add(*stats_out, st);
+    first += points;
+  }
+  return RAYCA_OK;
 }
 
 }  // extern "C"

@@ -144,6 +144,20 @@ struct AmbientIo {
   float* bent_out;
 };
 
+// one internal frame of rayca_hip_gather_device: `a.count` whole points (every array of `a` starts at the frame's first point, the
+// table at dir_first; radius, mask and the ambient outputs are not used), their a.count x a.samples radiance records, and where
+// the fold writes -- all in DEVICE memory, the outputs from the frame's first point on
+struct GatherIo {
+  AmbientIo a;
+  const float* weights;    // samples weights from dir_first on, or nullptr: no weighting
+  uint32_t first_index;    // "pixel" index of the frame's ray 0: RaycaGather.first_index + (the frame's first point) x samples
+  float4* samples;         // a.count x a.samples records the frame driver writes and the fold reads: samples_out, or the context's scratch
+  float4* irradiance_out;  // what k_gather_fold writes: any may be nullptr
+  float4* sh_out;
+  uint32_t* kept_out;
+  float4* samples_out;     // == samples when given: the fold clears the rows of inactive points
+};
+
 // per generation, per pixel record used to fold the path back in the reference's evaluation order
 enum : uint32_t { kVertexNone = 0, kVertexLit = 1, kVertexEmissive = 2, kVertexLitNoIndirect = 3 };
 

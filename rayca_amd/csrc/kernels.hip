@@ -23,6 +23,9 @@
 //   k_ambient_rays,   hemisphere visibility at points: occlusion rays made in registers, one per lane, and the fold of a point's
 //   k_ambient_finish  mask word into hits, openness and the bent normal (ambient.inc: rayca_hip_ambient_device; the lane-refill
 //                     form is refill.hip k_ambient_refill).
+//   k_enqueue_gather, irradiance at points: the same rays written straight into the frame driver's generation-0 queue, and the
+//   k_gather_fold     fold of their radiance into irradiance and nine spherical-harmonic coefficients per point
+//                     (gather.inc: rayca_hip_gather_device).
 //   tile_pixel, ...   what the image-space passes below share: the 64 x 4 tile prologue, the guide terms of a tap, luminance,
 //                     albedo (de)modulation and the output stage (image_pass.inc; their entry points are in post.inc).
 //   k_atrous,         the edge-avoiding a-trous denoiser on a frame and its G-buffer in device memory
@@ -454,6 +457,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "nearest.inc"
 #include "hits.inc"
 #include "ambient.inc"
+#include "gather.inc"
 RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "image_pass.inc"
 #include "denoise.inc"

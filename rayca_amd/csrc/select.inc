@@ -104,6 +104,20 @@ AmbientFinishKernel pick_ambient_finish(bool bent, bool rot) {
   return with_flags([](auto BENT, auto ROT) -> AmbientFinishKernel { return k_ambient_finish<BENT, BENT && ROT>; }, bent, rot);
 }
 
+// k_enqueue_gather, k_gather_fold (gather.inc, rayca_hip_gather_device): flags only.  The fold makes directions only for sh_out, so
+// without it the rotation is not read
+using GatherEnqueueKernel = void (*)(GatherIo, uint32_t, uint32_t, QueuedRay*, uint32_t*);
+GatherEnqueueKernel pick_gather_enqueue(bool rot) {
+  return with_flags([](auto ROT) -> GatherEnqueueKernel { return k_enqueue_gather<ROT>; }, rot);
+}
+using GatherFoldKernel = void (*)(GatherIo);
+GatherFoldKernel pick_gather_fold(bool sh, bool weights, bool rot) {
+  return with_flags([](auto SH, auto WEIGHTS, auto ROT) -> GatherFoldKernel { return k_gather_fold<SH, WEIGHTS, SH && ROT>; }, sh, weights, rot);
+}
+// The rays of one internal frame of rayca_hip_gather_device (whole points; a point of 64 samples always fits): 2^22 rays are 128 MiB
+// of queue entries and 64 MiB of radiance records, and enough work for every CU at any depth.
+constexpr uint32_t kGatherFrameRays = 1u << 22;
+
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
 // else 24 entries + a global spill area for the rest
 #ifndef RAYCA_MAX_LDS_ENTRIES
@@ -478,6 +492,9 @@ int32_t selftest_kernel_selection(std::string& err) {
       {"pick_ambient_kernel(fast, sph, stats, rot)", none, 4, [&](Trav, uint32_t i) { return P(pick_ambient_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); }, every},
       {"pick_ambient_finish(bent, rot)", none, 2, [&](Trav, uint32_t i) { return P(pick_ambient_finish(b(i, 0), b(i, 1))); },
        [&](Trav, uint32_t i) { return b(i, 0) ? i : 0u; }},   // without bent_out no direction is made: rot is not read
+      {"pick_gather_enqueue(rot)", none, 1, [&](Trav, uint32_t i) { return P(pick_gather_enqueue(b(i, 0))); }, every},
+      {"pick_gather_fold(sh, weights, rot)", none, 3, [&](Trav, uint32_t i) { return P(pick_gather_fold(b(i, 0), b(i, 1), b(i, 2))); },
+       [&](Trav, uint32_t i) { return b(i, 0) ? i : i & 3u; }},   // without sh_out no direction is made: rot is not read
       {"flat_refill_kernel(trav; sph, stats)", fast, 2, [&](Trav t, uint32_t i) { return flat_refill_kernel(RefillFlavour{t, b(i, 0), b(i, 1)}); }, every},
       {"queue_refill_kernel(sph, stats, slack)", none, 3, [&](Trav, uint32_t i) { return queue_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"query_refill_kernel(occluded, sph, stats)", none, 3, [&](Trav, uint32_t i) { return query_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},

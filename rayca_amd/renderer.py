@@ -567,6 +567,102 @@ class DeviceScene:
             stats = abi.RaycaStats().as_dict()
         return _asked_for(out, out8, stats)
 
+    # ---- irradiance at points: radiance over a hemisphere of rays, folded (rayca_hip_gather_device) ----
+    GATHER_OUTPUTS = {"irradiance": ("float32", lambda n, s: (n, 4)), "sh": ("float32", lambda n, s: (n, 9, 4)),
+                      "kept": ("int32", lambda n, s: (n,)), "samples": ("float32", lambda n, s: (n, s, 4))}
+
+    def gather(self, points, normals, config: Config, *, samples, dirs=None, weights=None, rotations=None, dir_first=0, bias=0.0,
+               sample=0, first_index=0, chunk_points=0, outputs=("irradiance",), stream=None, context=0, out=None, want_stats=False,
+               collect_stats=False):
+        """rayca_hip_gather_device: the light that arrives at points in device memory -- `samples` rays over the hemisphere of each
+        normal, ambient()'s rays made on the device, the radiance() of `config` along each, folded per point in a fixed order --
+        asynchronously.
+
+        points, normals, dirs, dir_first, rotations, bias: as for ambient() (a zero normal or a value that is not finite marks an
+        inactive point: zeros); `samples` (1..64) has no default, bias is 0 unless given.  weights: (M,) float32, one per direction of dirs, multiplied into the samples (None: none).
+        config: a Config radiance() serves, with gamma 1.  Ray j of point i is "pixel" first_index + i * samples + j of a
+        radiance() call with the same `sample`.  chunk_points: at most this many points per internal frame (0: the library's
+        choice); the results do not depend on it.  Returns a dict with one tensor per name in `outputs`: "irradiance" (N, 4) float32
+        (the mean r, g, b of the samples that are finite, and the fraction that are), "sh" (N, 9, 4) float32 (the mean of
+        sample x Y_k(direction), k = 0..8, in r, g, b), "kept" (N,) int32 (the number of finite samples), "samples" (N, samples, 4)
+        float32 (the radiance itself).  With cosine_directions and no weights, irradiance is the irradiance / pi.  `out`: a dict of
+        tensors to write instead of new ones.  Stream handling as query(); `want_stats` / `collect_stats` wait and add "stats"."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        outputs = tuple(outputs)
+        unknown = [w for w in outputs if w not in self.GATHER_OUTPUTS]
+        if unknown or not outputs or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs: a non-empty selection without repeats of {tuple(self.GATHER_OUTPUTS)}, not {outputs!r}")
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+        n = points.shape[0]
+        if not 1 <= samples <= 64:
+            raise ValueError(f"samples: {samples}, expected 1..64")
+        if n * samples > 1 << 31 or first_index < 0 or first_index + n * samples > 1 << 32:
+            raise ValueError("points: points x samples must stay within 2**31, and first_index + points x samples within 2**32")
+        if dirs is None:
+            dirs, dir_first = self._ambient_table(call, samples), 0
+        if not isinstance(dirs, torch.Tensor):
+            raise TypeError(f"dirs: a torch tensor on {call.dev} is expected, not {type(dirs).__name__}")
+        if dirs.dim() != 2 or dirs.shape[1] != 3:
+            raise ValueError(f"dirs: shape {tuple(dirs.shape)}, expected (M, 3)")
+        m = dirs.shape[0]
+        if dir_first < 0 or dir_first + samples > m:
+            raise ValueError(f"dir_first: {dir_first} + samples {samples} exceeds the {m} directions of dirs")
+        if chunk_points < 0:
+            raise ValueError(f"chunk_points: {chunk_points}, expected 0 or a positive number of points")
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in outputs]
+        if stray:
+            raise ValueError(f"out: {stray} not in outputs")
+        g = abi.RaycaGather()
+        g.count, g.samples, g.dir_count, g.dir_first, g.bias = n, samples, m, dir_first, float(bias)
+        g.sample, g.first_index, g.chunk_points = sample, first_index, min(chunk_points, 0xFFFFFFFF)
+        result = {}
+        for name in outputs:
+            dtype, shape = self.GATHER_OUTPUTS[name]
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), shape(n, samples))
+            setattr(g, name + "_out", result[name].data_ptr() or None)
+        g.points = call.input(points, "points", torch.float32, (n, 3)).data_ptr()
+        g.normals = call.input(normals, "normals", torch.float32, (n, 3)).data_ptr()
+        g.dirs = call.input(dirs, "dirs", torch.float32, (m, 3)).data_ptr()
+        if weights is not None:
+            g.weights = call.input(weights, "weights", torch.float32, (m,)).data_ptr()
+        if rotations is not None:
+            g.rotations = call.input(rotations, "rotations", torch.float32, (n, 2)).data_ptr()
+        cfg = config.to_abi()
+        fn = self._lib.rayca_hip_gather_device
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(lambda handle, o, args, st: fn(handle, C.byref(cfg), o, args, st), g, context=context,
+                             want_stats=want_stats or collect_stats, collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
+    def render_irradiance(self, config: Config, width: int, height: int, *, samples, bias, rotate=True, sample=0,
+                          outputs=("irradiance",), stream=None, context=0):
+        """The light that arrives at the surface under every pixel, without a render call: gbuffer() -> gather() on one stream,
+        nothing waited for in between.  Returns gather()'s dict with every tensor shaped (height, width, ...); a pixel whose
+        camera ray misses is all zeros (its normal is zero: an inactive point).  bias, in world units, lifts the origins off the
+        surface; `rotate` turns the direction table per pixel (pixel_rotations).  `samples` and `bias` have no defaults: both
+        decide what the picture means."""
+        call = _DeviceCall(self, stream)
+        g = self.gbuffer(config, width, height, want=("point", "normal"), stream=stream, context=context)
+        rotations = None
+        if rotate:
+            from .ambient import pixel_rotations
+            rotations = call.torch.from_numpy(pixel_rotations(width, height).reshape(-1, 2)).to(call.dev)
+        r = self.gather(g["point"].reshape(-1, 3), g["normal"].reshape(-1, 3), config, samples=samples, bias=bias, rotations=rotations,
+                        sample=sample, outputs=outputs, stream=stream, context=context)
+        return {k: v.reshape(height, width, *v.shape[1:]) for k, v in r.items()}
+
     # ---- the denoiser: an edge-avoiding a-trous filter on a frame and its G-buffer (rayca_hip_denoise_device) ----
     def denoise(self, color, *, albedo=None, normal=None, point=None, id=None, iterations=5, sigma_color=4.0, sigma_plane=None,
                 normal_power_log2=7, gamma=1.0, out=None, rgba8=False, stream=None, context=0, want_stats=False):
