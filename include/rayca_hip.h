@@ -52,7 +52,8 @@ extern "C" {
                                   multi-hit ray queries: RaycaHits, rayca_hip_hits_device, RAYCA_HITS_;
                                   adaptive sampling: RaycaSamplePlan, rayca_hip_sample_plan_device, RaycaFilmFold,
                                   rayca_hip_film_fold_device;
-                                  irradiance gathering: RaycaGather, rayca_hip_gather_device */
+                                  irradiance gathering: RaycaGather, rayca_hip_gather_device;
+                                 irradiance volumes: RaycaProbeLookup, rayca_hip_probe_lookup_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -1031,6 +1032,94 @@ struct RaycaGather {
 typedef struct RaycaGather RaycaGather;
 int32_t rayca_hip_gather_device(RaycaScene* scene, const RaycaConfig* cfg, const RaycaRenderOptions* opts, const RaycaGather* gather,
                                 RaycaStats* stats_out);
+
+/* Irradiance volumes on DEVICE memory: the diffuse light at `count` caller-supplied points from a regular grid of SH9 probes -- the
+ * nine-coefficient records rayca_hip_gather_device writes to sh_out for points at the probes' centres.  The eight probes of a
+ * point's cell are blended by trilinear weight, by a wrapped normal term and, when asked for, by one short occlusion ray per probe,
+ * so that light does not leak through walls; the blend is evaluated as the irradiance at the point's normal (Ramamoorthi and
+ * Hanrahan 2001).  The rays are made in registers inside the traversal kernel: no ray buffer.  Asynchronous on the caller's stream.
+ *
+ * The specification, in f32 with every operation rounded on its own: + - * /, floor, min, max (maxNum), |x|, comparisons, selects
+ * and integers; no square root, no trigonometry.
+ *   Grid.  origin g (3 f32, finite), cell h (3 f32, finite, > 0), dims (nx, ny, nz), each >= 1, product <= 2^24.  Probe (ix, iy, iz)
+ *   has index m = (iz * ny + iy) * nx + ix and centre c = g + float(i) * h per axis: one multiply, one add.  sh: M x 9 x 4 f32,
+ *   exactly RaycaGather.sh_out's layout; .w is ignored.  kept: M u32 (RaycaGather.kept_out) or NULL; a probe with kept[m] == 0 is
+ *   invalid.  Non-finite coefficients of a valid probe are the caller's business and propagate.
+ *   Points.  points and normals are RaycaAmbient's, with the same inactive rule: n.x == 0 && n.y == 0 && n.z == 0, or any of the six
+ *   values not finite.  Unit normals are expected and not checked.
+ *   Cell, per axis a:
+ *     f  = (p.a - g.a) / h.a
+ *     f  = min(max(f, 0), float(dim_a - 1))
+ *     i0 = min(uint(floor(f)), dim_a >= 2 ? dim_a - 2 : 0)
+ *     t  = f - float(i0)
+ *     i1 = min(i0 + 1, dim_a - 1)
+ *   A point outside the grid takes the nearest boundary cell.
+ *   Corners.  k = 0 .. 7 with bits bx = k & 1, by = (k >> 1) & 1, bz = (k >> 2) & 1.  The index on an axis is b ? i1 : i0, the axis
+ *   weight b ? t : 1 - t;  wt_k = (wx * wy) * wz.  Corner k is a candidate iff wt_k > 0 and its probe is valid.
+ *   Visibility (flags & RAYCA_PROBE_VISIBILITY).
+ *     o = p + n * bias,  d = c_k - o            componentwise
+ *   A candidate corner is occluded iff rayca_hip_query_device(RAYCA_QUERY_OCCLUDED) reports 1 for the ray (o, d) with tmax = 1: the
+ *   same traversal, the same strict t < tmax.  Corners that are not candidates trace nothing.
+ *   Normal term (flags & RAYCA_PROBE_NORMAL_TERM).
+ *     v  = c_k - p
+ *     s  = (v.x * n.x + v.y * n.y) + v.z * n.z
+ *     l2 = (v.x * v.x + v.y * v.y) + v.z * v.z
+ *     q  = l2 > 0 ? (s * |s|) / l2 : 1
+ *     wb = (q + 1) * 0.5
+ *     wb = wb * wb + 0.0625f
+ *   A signed squared cosine, wrapped.  Without the flag the term is absent and no operation is performed.
+ *   Blend, for k ascending.  w_k = wt_k, times wb when the normal term is on.  A corner counts iff it is a candidate, is not
+ *   occluded, and w_k > 0 (a NaN weight fails the comparison).  For a counting corner:
+ *     wsum = wsum + w_k;  H[j] = H[j] + w_k * sh[m_k][j]    j = 0 .. 8, per r, g, b       (wsum and H from 0)
+ *   Fallback.  If wsum is not > 0 and either flag is on: the blend is run again from wsum = 0, H = 0 over the candidates with
+ *   w_k = wt_k alone, and the point is marked as a fallback (also when it has no candidate at all).
+ *   If wsum > 0 after either pass: H[j] = H[j] / wsum.  Otherwise H = 0 and wsum = 0.
+ *   Evaluate.  b_j = A_l(j) * Y_j(n), Y_j written exactly as in RaycaGather's comment with d = n; A = 3.1415927f for j = 0,
+ *   2.0943952f for j = 1 .. 3, 0.7853982f for j = 4 .. 8.
+ *     E = 0;  E = E + b_j * H[j]  for j ascending, per channel;  then E = max(E, 0)
+ *   Outputs (any may be NULL, not all), per point:
+ *     irradiance_out  4 x f32      (E.r, E.g, E.b, wsum)
+ *     sh_out          9 x 4 x f32  the blended H, w = 0
+ *     mask_out        u32          bits 0..7 the candidate corners, bits 8..15 the occluded corners, bit 16 the fallback
+ *     radiance_out    4 x f32      L = albedo * (E * 0.31830987f) per r, g, b, then + base when given; alpha = base.a, or 1
+ *   radiance_out needs albedo (count x 4 f32: a surface call's color or diffuse output) and optionally base (a direct-light frame).
+ *   An inactive point gives zeros; its radiance_out is base's pixel, or (0, 0, 0, 1) without base.
+ *   Order-free results: the trace kernel only ORs bit 8 + k of the point's mask word, with a 32-bit atomic; everything else is
+ *   made from the finished word, in k order.
+ * opts (may be NULL), ordering and statistics as for rayca_hip_ambient_device: stream, context, wait_event, record_event and
+ * collect_stats; traversal must be RAYCA_TRAVERSAL_ORDERED; tile, engine and camera_rays must be zero.  Without mask_out the mask
+ * words live in the context's work buffers.  With stats_out the call waits: rays_shadow = count x 8 with RAYCA_PROBE_VISIBILITY and
+ * 0 without, the time and the launches (the trace kernel with visibility, and the fold) under RAYCA_KERNEL_OTHER, boxes_tested and
+ * triangles_tested under collect_stats.  Nothing outside [0, count) of an output is written.  Scenes with spheres are served.
+ * Refusals, before any GPU work and before the scene is looked at, in this order.  RAYCA_ERR_BAD_ARG: NULL scene / struct; NULL
+ * points, normals, sh; unknown flag bits; a zero dim; dims product > 2^24; cell not finite or not > 0; origin not finite; bias not
+ * finite; non-zero reserved; no output; radiance_out without albedo; irradiance_out, sh_out, radiance_out, albedo, base or sh not
+ * 16-byte aligned, mask_out not 4-byte aligned; count x 8 >= 2^32; then context > 7, a non-zero field of opts that does not apply.
+ * Then RAYCA_ERR_UNSUPPORTED for EXHAUSTIVE.  count == 0 is then RAYCA_OK and launches nothing.  Then, only with
+ * RAYCA_PROBE_VISIBILITY, RAYCA_ERR_EMPTY_SCENE as the query: without the flag the scene is not read and an empty scene is no error. */
+enum { RAYCA_PROBE_VISIBILITY = 1, RAYCA_PROBE_NORMAL_TERM = 2 };
+struct RaycaProbeLookup {
+  uint32_t count;         /* points */
+  uint32_t flags;         /* RAYCA_PROBE_* */
+  float origin[3];        /* g: the centre of probe (0, 0, 0); finite */
+  float cell[3];          /* h: the spacing per axis; finite, > 0 */
+  uint32_t dims[3];       /* nx, ny, nz: each >= 1, product <= 2^24 */
+  float bias;             /* o = p + n * bias; finite */
+  uint32_t reserved[2];   /* must be zero */
+  const void* points;     /* DEVICE: count x 3 f32 */
+  const void* normals;    /* DEVICE: count x 3 f32; (0, 0, 0) marks an inactive point (a G-buffer's miss) */
+  const void* sh;         /* DEVICE: M x 9 x 4 f32, 16-byte aligned: RaycaGather.sh_out of the probes */
+  const void* kept;       /* DEVICE: M u32 (RaycaGather.kept_out), or NULL => every probe is valid */
+  const void* albedo;     /* DEVICE: count x 4 f32, 16-byte aligned, or NULL; required by radiance_out */
+  const void* base;       /* DEVICE: count x 4 f32, 16-byte aligned, or NULL */
+  void* irradiance_out;   /* DEVICE: count x 4 f32, 16-byte aligned, or NULL */
+  void* sh_out;           /* DEVICE: count x 9 x 4 f32, 16-byte aligned, or NULL */
+  void* mask_out;         /* DEVICE: count u32, or NULL */
+  void* radiance_out;     /* DEVICE: count x 4 f32, 16-byte aligned, or NULL */
+};
+typedef struct RaycaProbeLookup RaycaProbeLookup;
+int32_t rayca_hip_probe_lookup_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaProbeLookup* lookup,
+                                      RaycaStats* stats_out);
 
 /* The edge-avoiding a-trous wavelet denoiser, on a frame and its G-buffer in DEVICE memory: what rayca_hip_render_device wrote to
  * d_rgba32f_out (rendered with gamma 1) and what rayca_hip_surface_device wrote for the frame's camera rays go in, the filtered

@@ -79,6 +79,8 @@ pub const RAYCA_NEAREST_WITHIN: u32 = 1;
 // RaycaHits.faces, and the largest RaycaHits.k
 pub const RAYCA_HITS_FRONT: u32 = 0;
 pub const RAYCA_HITS_BOTH: u32 = 1;
+pub const RAYCA_PROBE_VISIBILITY: u32 = 1;
+pub const RAYCA_PROBE_NORMAL_TERM: u32 = 2;
 pub const RAYCA_HITS_MAX: u32 = 16;
 // RaycaTonemap.op
 pub const RAYCA_TONEMAP_LINEAR: u32 = 0;
@@ -425,6 +427,29 @@ pub struct RaycaGather {
     pub samples_out: *mut c_void,
 }
 
+// rayca_hip_probe_lookup_device: points, normals and a grid of SH9 probes in, the blended light per point out, all in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaProbeLookup {
+    pub count: u32,
+    pub flags: u32,
+    pub origin: [f32; 3],
+    pub cell: [f32; 3],
+    pub dims: [u32; 3],
+    pub bias: f32,
+    pub reserved: [u32; 2],
+    pub points: *const c_void,
+    pub normals: *const c_void,
+    pub sh: *const c_void,
+    pub kept: *const c_void,
+    pub albedo: *const c_void,
+    pub base: *const c_void,
+    pub irradiance_out: *mut c_void,
+    pub sh_out: *mut c_void,
+    pub mask_out: *mut c_void,
+    pub radiance_out: *mut c_void,
+}
+
 // rayca_hip_denoise_device: the a-trous filter on a frame and its G-buffer, all in DEVICE memory
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -699,6 +724,7 @@ extern "C" {
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;
     pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_gather_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, gather: *const RaycaGather, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_probe_lookup_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, lookup: *const RaycaProbeLookup, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;

@@ -45,6 +45,7 @@ GATHER_RCCL, GATHER_PEER_COPY = 0, 1
 QUERY_CLOSEST, QUERY_OCCLUDED = 0, 1   # RaycaQuery.kind
 NEAREST_CLOSEST, NEAREST_WITHIN = 0, 1   # RaycaNearest.kind
 HITS_FRONT, HITS_BOTH = 0, 1   # RaycaHits.faces
+PROBE_VISIBILITY, PROBE_NORMAL_TERM = 1, 2   # RaycaProbeLookup.flags
 HITS_MAX = 16   # RAYCA_HITS_MAX: the largest RaycaHits.k
 TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
 TONEMAP_NAMES = ("linear", "reinhard", "aces")
@@ -382,6 +383,29 @@ class RaycaGather(C.Structure):
         ("sh_out", C.c_void_p),
         ("kept_out", C.c_void_p),
         ("samples_out", C.c_void_p),
+    ]
+
+
+class RaycaProbeLookup(C.Structure):
+    """rayca_hip_probe_lookup_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("origin", C.c_float * 3),
+        ("cell", C.c_float * 3),
+        ("dims", C.c_uint32 * 3),
+        ("bias", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+        ("points", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("sh", C.c_void_p),
+        ("kept", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("base", C.c_void_p),
+        ("irradiance_out", C.c_void_p),
+        ("sh_out", C.c_void_p),
+        ("mask_out", C.c_void_p),
+        ("radiance_out", C.c_void_p),
     ]
 
 
@@ -746,6 +770,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_radiance_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaRadiance), P(RaycaStats)]
     lib.rayca_hip_gather_device.restype = C.c_int32
     lib.rayca_hip_gather_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaGather), P(RaycaStats)]
+    lib.rayca_hip_probe_lookup_device.restype = C.c_int32
+    lib.rayca_hip_probe_lookup_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaProbeLookup), P(RaycaStats)]
     lib.rayca_hip_denoise_device.restype = C.c_int32
     lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
     lib.rayca_hip_scene_camera.restype = C.c_int32
@@ -786,7 +812,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device", "rayca_hip_hits_device",
     "rayca_hip_ambient_device",
-    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_denoise_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_probe_lookup_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device", "rayca_hip_sample_plan_device", "rayca_hip_film_fold_device",
     "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",

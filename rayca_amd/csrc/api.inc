@@ -83,6 +83,7 @@ struct FrameCtx {
   DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
   DeviceBuffer denoise_var[2];        // rayca_hip_denoise_variance_device: the two variance planes that go with them (4 B a pixel)
   DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
+  DeviceBuffer probe_mask;            // rayca_hip_probe_lookup_device with visibility and without mask_out: the same, 4 B a point
   DeviceBuffer plan_weight;           // rayca_hip_sample_plan_device without weight_out: the weights its offsets kernel reads back (4 B a pixel)
   DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment)
   DeviceBuffer gather_samples;        // rayca_hip_gather_device without samples_out: the radiance records of one internal frame (16 B a ray)
@@ -97,7 +98,7 @@ struct FrameCtx {
   // and made its device current.  (A buffer this list forgets is not leaked: its own destructor frees it, with the context.)
   void release() {
     for (DeviceBuffer* b : {&path_direct, &path_brdf, &path_state, &accum, &queue[0], &queue[1], &out8, &out32, &ray_io, &stack_spill, &frames, &mis_samples,
-                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask, &plan_weight, &plan_sums, &gather_samples})
+                            &wf_hits, &wf_sh_ray, &wf_sh_x, &denoise[0], &denoise[1], &denoise_var[0], &denoise_var[1], &ambient_mask, &plan_weight, &plan_sums, &gather_samples, &probe_mask})
       b->release();
     if (heads_alloc) (void)hipFree(heads_alloc);
     if (counters) (void)hipFree(counters);
@@ -1810,6 +1811,130 @@ int32_t rayca_hip_ambient_device(RaycaScene* s, const RaycaRenderOptions* opts_i
       });
   if (rc != RAYCA_OK || !stats_out) return rc;
   stats_out->rays_shadow = total;
+  stats_out->boxes_tested = tc.boxes;
+  stats_out->triangles_tested = tc.tris;
+  stats_out->wave_box_slots = tc.box_slots;
+  stats_out->wave_triangle_slots = tc.tri_slots;
+  stats_out->node_format = node_format;
+  return RAYCA_OK;
+}
+
+// Irradiance volumes (probes.inc, refill.hip k_probe_refill): with RAYCA_PROBE_VISIBILITY count x 8 occlusion rays made in registers,
+// one mask word per point, then k_probe_fold; without it the fold alone, and the scene is not read.  The trace kernel is chosen
+// exactly as rayca_hip_ambient_device chooses its own.  The mask words live in mask_out, or in the context's scratch (grown before
+// the pass queues its waits); they are cleared on the launch stream in front of the trace kernel.  A pass on its context (run_pass).
+int32_t rayca_hip_probe_lookup_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaProbeLookup* pin, RaycaStats* stats_out) {
+  if (!s || !pin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaProbeLookup");
+  const RaycaProbeLookup& rp = *pin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (!rp.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.points: null points");
+  if (!rp.normals) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.normals: null normals");
+  if (!rp.sh) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.sh: null sh");
+  if (rp.flags & ~(uint32_t)(RAYCA_PROBE_VISIBILITY | RAYCA_PROBE_NORMAL_TERM)) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.flags: unknown flag bits");
+  if (rp.dims[0] == 0 || rp.dims[1] == 0 || rp.dims[2] == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.dims: a zero dim (each axis has at least one probe)");
+  if ((uint64_t)rp.dims[0] * rp.dims[1] > (1ull << 24) || (uint64_t)rp.dims[0] * rp.dims[1] * rp.dims[2] > (1ull << 24))
+    return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.dims: more than 2^24 probes");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(rp.cell[a]) || !(rp.cell[a] > 0.0f)) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.cell is not finite and > 0");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(rp.origin[a])) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.origin is not finite");
+  if (!std::isfinite(rp.bias)) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.bias is not finite");
+  if (rp.reserved[0] != 0 || rp.reserved[1] != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.reserved must be zero");
+  if (!rp.irradiance_out && !rp.sh_out && !rp.mask_out && !rp.radiance_out) return fail(RAYCA_ERR_BAD_ARG, "no output for a probe lookup");
+  if (rp.radiance_out && !rp.albedo) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.radiance_out needs albedo");
+  const struct { const void* p; const char* name; } aligned[] = {{rp.irradiance_out, "irradiance_out"}, {rp.sh_out, "sh_out"}, {rp.radiance_out, "radiance_out"},
+                                                                 {rp.albedo, "albedo"}, {rp.base, "base"}, {rp.sh, "sh"}};
+  for (const auto& a : aligned)
+    if (reinterpret_cast<uintptr_t>(a.p) & 15u) return fail(RAYCA_ERR_BAD_ARG, std::string("RaycaProbeLookup.") + a.name + " must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rp.mask_out) & 3u) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.mask_out must be 4-byte aligned");
+  if ((uint64_t)rp.count * 8u >= (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaProbeLookup.count x 8 must stay below 2^32");
+  int32_t rc = pass_options(o, "a probe lookup", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE)
+    return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: an occlusion ray ends at its first hit: there is no exhaustive form");
+  if (rp.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  const bool vis = (rp.flags & RAYCA_PROBE_VISIBILITY) != 0, normal = (rp.flags & RAYCA_PROBE_NORMAL_TERM) != 0;
+  if (vis && (rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  ProbeIo io{};
+  io.points = static_cast<const float*>(rp.points);
+  io.normals = static_cast<const float*>(rp.normals);
+  io.sh = static_cast<const float4*>(rp.sh);
+  io.kept = static_cast<const uint32_t*>(rp.kept);
+  io.albedo = static_cast<const float4*>(rp.albedo);
+  io.base = static_cast<const float4*>(rp.base);
+  for (int a = 0; a < 3; ++a) {
+    io.origin[a] = rp.origin[a];
+    io.cell[a] = rp.cell[a];
+    io.dims[a] = rp.dims[a];
+  }
+  io.bias = rp.bias;
+  io.count = rp.count;
+  io.irradiance_out = static_cast<float4*>(rp.irradiance_out);
+  io.sh_out = static_cast<float4*>(rp.sh_out);
+  io.mask_out = static_cast<uint32_t*>(rp.mask_out);
+  io.radiance_out = static_cast<float4*>(rp.radiance_out);
+  const bool stats = o.collect_stats != 0;
+  const uint32_t total = rp.count * 8u, batches = (total + 63u) / 64u;
+  const size_t mask_bytes = (size_t)rp.count * sizeof(uint32_t);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  uint32_t node_format = 0;
+  rc = run_pass(
+      s, o, stats_out,
+      [&](FrameCtx* ctx) -> int32_t {
+        if (!vis || io.mask_out) return RAYCA_OK;
+        HIP_TRY(hipSetDevice(s->device));
+        return grow_behind_pass(ctx, ctx->probe_mask, mask_bytes);
+      },
+      [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+        if (vis) {
+          const bool sph = s->host.sphere_count != 0;
+          io.mask = io.mask_out ? io.mask_out : static_cast<uint32_t*>(c->probe_mask.ptr);
+          const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+          const bool all_formats = formats_ready(s);
+          const bool refill = fast && all_formats;           // (rayca_hip_ambient_device's rule)
+          uint32_t grid = (batches + 3u) / 4u;               // one ray per lane; the persistent grid below replaces it
+          StackPlan sp{};
+          node_format = all_formats ? 0u : 2048u;
+          if (refill) {
+            sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
+            const uint32_t in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
+            if (const int32_t grc = persistent_grid(s, probe_refill_kernel(sph, stats), sp.lds_bytes, batches, true, in_flight, 0u, grid); grc != RAYCA_OK) return grc;
+            node_format |= (RAYCA_WF_BOUNCE_WIDE ? 1u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 4u : 0u);
+          } else {
+            sp = plan_stack(s->host.max_depth);
+            if (fast && RAYCA_NODE_CH && RAYCA_NODE_CH48 && s->dev.nodes_ch) node_format |= 4096u;
+          }
+          TraceLaunch tl{};
+          if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+          if (stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+          HIP_TRY(hipMemsetAsync(io.mask, 0, mask_bytes, stream));
+          if (refill) {
+            tl.ticket = 1u;
+            HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
+            c->heads_clean = false;   // the next frame of this context clears them for itself
+            launch_probe_refill(sph, stats, grid, sp.lds_bytes, stream, s->dev_full, io, c->heads, c->counters, tl);
+          } else {
+            hipLaunchKernelGGL(pick_probe_kernel(fast, sph, stats), dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, io, c->counters,
+                               tl);
+          }
+          HIP_TRY(hipGetLastError());
+          ++launches;
+        }
+        hipLaunchKernelGGL(pick_probe_fold(vis, normal, io.kept != nullptr), dim3((rp.count + kProbeFoldBlock - 1u) / kProbeFoldBlock), dim3(kProbeFoldBlock), 0, stream, io);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+        if (vis && stats && stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+        return RAYCA_OK;
+      });
+  if (rc != RAYCA_OK || !stats_out) return rc;
+  stats_out->rays_shadow = vis ? total : 0u;
   stats_out->boxes_tested = tc.boxes;
   stats_out->triangles_tested = tc.tris;
   stats_out->wave_box_slots = tc.box_slots;

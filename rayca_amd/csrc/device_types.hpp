@@ -158,6 +158,25 @@ struct GatherIo {
   float4* samples_out;     // == samples when given: the fold clears the rows of inactive points
 };
 
+// points, normals and a grid of SH9 probes in, the blended light per point out, all in DEVICE memory (rayca_hip_probe_lookup_device)
+struct ProbeIo {
+  const float* points;     // count x 3
+  const float* normals;    // count x 3
+  const float4* sh;        // M x 9 records (r, g, b, ignored): rayca_hip_gather_device's sh_out of the probes
+  const uint32_t* kept;    // M, or nullptr: every probe is valid
+  const float4* albedo;    // count, or nullptr (required by radiance_out)
+  const float4* base;      // count, or nullptr
+  float origin[3], cell[3];
+  uint32_t dims[3];
+  float bias;
+  uint32_t count;
+  uint32_t* mask;          // count words the trace kernels OR bits 8..15 into (cleared in front of them): mask_out, or the context's scratch
+  float4* irradiance_out;  // what k_probe_fold writes: any may be nullptr
+  float4* sh_out;
+  uint32_t* mask_out;
+  float4* radiance_out;
+};
+
 // per generation, per pixel record used to fold the path back in the reference's evaluation order
 enum : uint32_t { kVertexNone = 0, kVertexLit = 1, kVertexEmissive = 2, kVertexLitNoIndirect = 3 };
 

@@ -23,6 +23,9 @@
 //   k_ambient_rays,   hemisphere visibility at points: occlusion rays made in registers, one per lane, and the fold of a point's
 //   k_ambient_finish  mask word into hits, openness and the bent normal (ambient.inc: rayca_hip_ambient_device; the lane-refill
 //                     form is refill.hip k_ambient_refill).
+//   k_probe_rays,     irradiance volumes: the occlusion rays from a point to the eight probes of its grid cell, one per lane, and the
+//   k_probe_fold      blend of those probes' SH9 records into the light at the point (probes.inc: rayca_hip_probe_lookup_device; the
+//                     lane-refill form is refill.hip k_probe_refill).
 //   k_enqueue_gather, irradiance at points: the same rays written straight into the frame driver's generation-0 queue, and the
 //   k_gather_fold     fold of their radiance into irradiance and nine spherical-harmonic coefficients per point
 //                     (gather.inc: rayca_hip_gather_device).
@@ -457,6 +460,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "nearest.inc"
 #include "hits.inc"
 #include "ambient.inc"
+#include "probes.inc"
 #include "gather.inc"
 RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "image_pass.inc"

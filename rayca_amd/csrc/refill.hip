@@ -26,6 +26,7 @@ namespace {
 RAYCA_NO_PK_BEGIN
 #include "trace_core.inc"
 #include "ambient.inc"   // ambient_point, ambient_ray: what k_ambient_refill makes its rays with
+#include "probes.inc"    // probe_point, probe_cell, probe_corner, probe_ray: what k_probe_refill makes its rays with
 
 #ifndef RAYCA_REFILL_THRESHOLD
 #define RAYCA_REFILL_THRESHOLD 44
@@ -654,6 +655,112 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_ambient_refill(
   }
 }
 
+// ---- probe visibility at points (rayca_hip_probe_lookup_device) with lane refill --------------------------------------------------
+// k_ambient_refill's sibling, written beside it so that the existing listings stay what they are: the same work counters,
+// threshold and leave-K, node_step / test_leaf, stack plan and persistent grid, on the same 4-wide fp16 nodes.  Item = i * 8 + k,
+// corner k of point i's cell: a lane that takes an item reads the point's 24 B, computes cell and corner in registers (probes.inc)
+// and makes the ray from the lifted point to the probe's centre, t_stop = 1; a batch of 64 items is the eight rays of eight
+// neighbouring points, whose origins coincide per point.  An item whose corner is no candidate (no weight, or an invalid probe)
+// and the items of an inactive point retire at once.  A retiring lane whose ray was occluded ORs bit 8 + k into the point's word.
+template <bool SPH, bool STATS>
+__global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_probe_refill(DevScene sc, ProbeIo a, uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
+  constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_query_refill)
+  extern __shared__ uint32_t lds_stack[];
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t lane = __lane_id();
+  const uint32_t home = xcc_id();
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  const uint32_t count = a.count * 8u, n_batches = (count + 63u) >> 6;   // (the host refuses count x 8 >= 2^32)
+  const bool kept = a.kept != nullptr;
+  constexpr float t_stop = 1.0f;
+  WorkCursor wc{};
+  LaneCounters cnt{};
+  bool has = false;
+  uint32_t cur = kTerminated, item = 0;
+  DRay ray{};
+  FastRay fr{};
+  DHit hit{};
+  float limit = INFINITY;
+  uint32_t pool_next = 0, pool_end = 0;
+  bool dry = false;
+  for (;;) {
+    const uint32_t n_active = (uint32_t)__popcll(__ballot(cur != kTerminated));
+    if (n_active <= (dry ? 0u : (uint32_t)RAYCA_QREFILL_THRESHOLD)) {
+      if (has && cur == kTerminated) {  // retire: bit 8 + k of point i, iff the ray was occluded (i < count: nothing else is ever written)
+        if (query_found(hit, t_stop)) atomicOr(&a.mask[item >> 3], 1u << (8u + (item & 7u)));
+        has = false;
+      }
+      if (dry && n_active == 0u) break;  // every lane reaches this: n_active and dry are wave-uniform
+      while (!dry) {
+        const unsigned long long idle = __ballot(!has);
+        if (idle == 0ull) break;
+        if (pool_next == pool_end) {
+          const uint32_t batch = next_batch(heads, n_batches, home, wc, tl.ticket);
+          if (batch == RAYCA_NONE) {
+            dry = true;
+            break;
+          }
+          pool_next = batch * 64u;
+          pool_end = min(pool_next + 64u, count);
+        }
+        const uint32_t avail = pool_end - pool_next;
+        const uint32_t rank = (uint32_t)__popcll(idle & lanes_below);
+        if (!has && rank < avail) {
+          item = pool_next + rank;
+          const ProbePoint pt = probe_point(a, item >> 3);
+          if (pt.active) {   // (an item that traces nothing is skipped: the lane asks again)
+            const ProbeCorner pc = probe_corner(a, probe_cell(a, pt.p), item & 7u, kept);
+            if (pc.candidate) {
+              const AmbientRay pr = probe_ray(pt, pc.c, a.bias);
+              ray = make_ray(pr.o, pr.d);
+              fr = make_fast(sc, ray, HALF);   // prologue of trace(): the root box first (blas.rs:136-139)
+              hit.t = INFINITY;
+              hit.prim = RAYCA_NONE;
+              hit.u = hit.v = 0.0f;
+              limit = cull_limit<true>(sc, fr, t_stop);
+              stack.clear();
+              float tmin;
+              if (STATS) cnt.boxes++;
+              cur = slab(sc.root_min[0], sc.root_min[1], sc.root_min[2], sc.root_max[0], sc.root_max[1], sc.root_max[2], ray, tmin)
+                        ? (WIDE ? sc.root_ref4 : (!HALF && RAYCA_NODE_CH ? sc.root_ref_ch : sc.root_ref))
+                        : kTerminated;
+              has = true;
+            }
+          }
+        }
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        pool_next += n_idle < avail ? n_idle : avail;
+      }
+    }
+    for (;;) {  // (RAYCA_REFILL_SCHED 0 of k_flat_refill)
+      const bool searching = !(cur & kLeafFlag) && cur != kTerminated;
+      const uint32_t n = (uint32_t)__popcll(__ballot(searching));
+      if (n == 0u) break;
+      if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
+    }
+    if (cur & kLeafFlag) {
+      test_leaf<true, SPH, STATS>(sc, ray, fr, cur, t_stop, hit, limit, cnt);
+      cur = query_found(hit, t_stop) ? kTerminated : stack.pop();
+    }
+  }
+  if (STATS) {
+    unsigned long long b = cnt.boxes, t = cnt.tris, sb = cnt.slot_boxes, stt = cnt.slot_tris;
+    for (int off = 32; off > 0; off >>= 1) {
+      b += __shfl_down(b, off);
+      t += __shfl_down(t, off);
+      sb += __shfl_down(sb, off);
+      stt += __shfl_down(stt, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&counters->boxes, b);
+      atomicAdd(&counters->tris, t);
+      atomicAdd(&counters->box_slots, sb);
+      atomicAdd(&counters->tri_slots, stt);
+    }
+  }
+}
+
 // The pickers: flags only, but for k_flat_refill, which reads WIDE, SPILL and HALF of a flavour -- of the six kTravFast* in
 // production; the 4-wide forms always have the spill path, and the other flavours have no form of their own.
 using QueryRefillKernel = void (*)(DevScene, QueryIo, uint32_t*, TraceCounters*, TraceLaunch);
@@ -664,6 +771,11 @@ QueryRefillKernel pick_query(bool occluded, bool sph, bool stats) {
 using AmbientRefillKernel = void (*)(DevScene, AmbientIo, uint32_t*, TraceCounters*, TraceLaunch);
 AmbientRefillKernel pick_ambient(bool rot, bool sph, bool stats) {
   return with_flags([](auto ROT, auto SPH, auto STATS) -> AmbientRefillKernel { return k_ambient_refill<ROT, SPH, STATS>; }, rot, sph, stats);
+}
+
+using ProbeRefillKernel = void (*)(DevScene, ProbeIo, uint32_t*, TraceCounters*, TraceLaunch);
+ProbeRefillKernel pick_probe(bool sph, bool stats) {
+  return with_flags([](auto SPH, auto STATS) -> ProbeRefillKernel { return k_probe_refill<SPH, STATS>; }, sph, stats);
 }
 
 using ShadowRefillKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, uint32_t*, TraceCounters*, TraceLaunch);
@@ -714,6 +826,15 @@ const void* ambient_refill_kernel(bool rot, bool sph, bool stats) {
 void launch_ambient_refill(bool rot, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const AmbientIo& a,
                            uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl) {
   hipLaunchKernelGGL(pick_ambient(rot, sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, a, heads, counters, tl);
+}
+
+const void* probe_refill_kernel(bool sph, bool stats) {
+  return reinterpret_cast<const void*>(pick_probe(sph, stats));
+}
+
+void launch_probe_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const ProbeIo& a, uint32_t* heads,
+                         TraceCounters* counters, const TraceLaunch& tl) {
+  hipLaunchKernelGGL(pick_probe(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, a, heads, counters, tl);
 }
 
 const void* shadow_refill_kernel(bool gen0, bool sph, bool stats) {

@@ -33,6 +33,12 @@ const void* ambient_refill_kernel(bool rot, bool sph, bool stats);
 void launch_ambient_refill(bool rot, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const AmbientIo& a,
                            uint32_t* heads, TraceCounters* counters, const TraceLaunch& tl);
 
+// the same for the eight corner rays of rayca_hip_probe_lookup_device: made in registers from a point and its cell of the probe grid,
+// one bit of the point's mask word per occluded ray
+const void* probe_refill_kernel(bool sph, bool stats);
+void launch_probe_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const ProbeIo& a, uint32_t* heads,
+                         TraceCounters* counters, const TraceLaunch& tl);
+
 // and for the shadow-ray pass of a generation (k_wf_shadow's work)
 struct ShadowRefillArgs {
   float4* sh_ray;

@@ -118,6 +118,17 @@ GatherFoldKernel pick_gather_fold(bool sh, bool weights, bool rot) {
 // of queue entries and 64 MiB of radiance records, and enough work for every CU at any depth.
 constexpr uint32_t kGatherFrameRays = 1u << 22;
 
+// k_probe_rays (probes.inc, rayca_hip_probe_lookup_device where k_probe_refill of refill.hip cannot run): as pick_ambient_kernel
+using ProbeKernel = void (*)(DevScene, ProbeIo, TraceCounters*, TraceLaunch);
+ProbeKernel pick_probe_kernel(bool fast, bool sph, bool stats) {
+  return with_flags([](auto FAST, auto SPH, auto STATS) -> ProbeKernel { return k_probe_rays<FAST, SPH, STATS>; }, fast, sph, stats);
+}
+// k_probe_fold: the call's two flags, and whether it has a kept array
+using ProbeFoldKernel = void (*)(ProbeIo);
+ProbeFoldKernel pick_probe_fold(bool vis, bool normal, bool kept) {
+  return with_flags([](auto VIS, auto NORMAL, auto KEPT) -> ProbeFoldKernel { return k_probe_fold<VIS, NORMAL, KEPT>; }, vis, normal, kept);
+}
+
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
 // else 24 entries + a global spill area for the rest
 #ifndef RAYCA_MAX_LDS_ENTRIES
@@ -495,10 +506,13 @@ int32_t selftest_kernel_selection(std::string& err) {
       {"pick_gather_enqueue(rot)", none, 1, [&](Trav, uint32_t i) { return P(pick_gather_enqueue(b(i, 0))); }, every},
       {"pick_gather_fold(sh, weights, rot)", none, 3, [&](Trav, uint32_t i) { return P(pick_gather_fold(b(i, 0), b(i, 1), b(i, 2))); },
        [&](Trav, uint32_t i) { return b(i, 0) ? i : i & 3u; }},   // without sh_out no direction is made: rot is not read
+      {"pick_probe_kernel(fast, sph, stats)", none, 3, [&](Trav, uint32_t i) { return P(pick_probe_kernel(b(i, 0), b(i, 1), b(i, 2))); }, every},
+      {"pick_probe_fold(vis, normal, kept)", none, 3, [&](Trav, uint32_t i) { return P(pick_probe_fold(b(i, 0), b(i, 1), b(i, 2))); }, every},
       {"flat_refill_kernel(trav; sph, stats)", fast, 2, [&](Trav t, uint32_t i) { return flat_refill_kernel(RefillFlavour{t, b(i, 0), b(i, 1)}); }, every},
       {"queue_refill_kernel(sph, stats, slack)", none, 3, [&](Trav, uint32_t i) { return queue_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"query_refill_kernel(occluded, sph, stats)", none, 3, [&](Trav, uint32_t i) { return query_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"ambient_refill_kernel(rot, sph, stats)", none, 3, [&](Trav, uint32_t i) { return ambient_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
+      {"probe_refill_kernel(sph, stats)", none, 2, [&](Trav, uint32_t i) { return probe_refill_kernel(b(i, 0), b(i, 1)); }, every},
       {"shadow_refill_kernel(gen0, sph, stats)", none, 3, [&](Trav, uint32_t i) { return shadow_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
   };
   for (const PickerFamily& f : families)

@@ -663,6 +663,93 @@ class DeviceScene:
                         sample=sample, outputs=outputs, stream=stream, context=context)
         return {k: v.reshape(height, width, *v.shape[1:]) for k, v in r.items()}
 
+    # ---- irradiance volumes: the light at points from a grid of SH9 probes (rayca_hip_probe_lookup_device) ----
+    PROBE_OUTPUTS = {"irradiance": ("float32", lambda n: (n, 4)), "sh": ("float32", lambda n: (n, 9, 4)), "mask": ("int32", lambda n: (n,)),
+                     "radiance": ("float32", lambda n: (n, 4))}
+
+    def probe_lookup(self, points, normals, grid, sh, *, kept=None, visibility=True, normal_term=True, bias=0.0, albedo=None, base=None,
+                     outputs=("irradiance",), stream=None, context=0, out=None, want_stats=False, collect_stats=False):
+        """rayca_hip_probe_lookup_device: the diffuse light at points in device memory from a grid of SH9 probes -- the eight probes
+        of each point's cell blended by trilinear weight, the normal term and one short occlusion ray per probe -- asynchronously.
+
+        points, normals: as for ambient() (a zero normal or a value that is not finite marks an inactive point: zeros).  grid: a
+        probes.ProbeGrid (origin, cell, dims).  sh: (M, 9, 4) float32, M = the grid's probe count: gather()'s "sh" at the probes'
+        centres (ProbeGrid.bake).  kept: (M,) int32, gather()'s "kept", or None; a probe with kept 0 is left out.  visibility: trace
+        the corner rays (from point + normal * bias to each probe's centre); normal_term: weigh probes in front of the surface
+        higher.  albedo, base: (N, 4) float32; "radiance" = albedo * irradiance / pi + base needs albedo.  Returns a dict with one
+        tensor per name in `outputs`: "irradiance" (N, 4) float32 (r, g, b, the weight sum), "sh" (N, 9, 4) float32 (the blended
+        coefficients), "mask" (N,) int32 (bits 0..7 the candidate corners, 8..15 the occluded ones, bit 16 the fallback), "radiance"
+        (N, 4) float32.  `out`: a dict of tensors to write instead of new ones.  Stream handling as query(); `want_stats` /
+        `collect_stats` wait and add "stats"."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        outputs = tuple(outputs)
+        unknown = [w for w in outputs if w not in self.PROBE_OUTPUTS]
+        if unknown or not outputs or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs: a non-empty selection without repeats of {tuple(self.PROBE_OUTPUTS)}, not {outputs!r}")
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+        n = points.shape[0]
+        if n * 8 >= 1 << 32:
+            raise ValueError("points: the number of points x 8 must stay below 2**32")
+        dims = tuple(int(d) for d in grid.dims)
+        if len(dims) != 3 or min(dims) < 1 or dims[0] * dims[1] * dims[2] > 1 << 24:
+            raise ValueError(f"grid.dims: {dims}, expected three counts >= 1 with a product of at most 2**24")
+        m = dims[0] * dims[1] * dims[2]
+        if "radiance" in outputs and albedo is None:
+            raise ValueError('outputs: "radiance" needs albedo')
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in outputs]
+        if stray:
+            raise ValueError(f"out: {stray} not in outputs")
+        a = abi.RaycaProbeLookup()
+        a.count, a.bias = n, float(bias)
+        a.flags = (abi.PROBE_VISIBILITY if visibility else 0) | (abi.PROBE_NORMAL_TERM if normal_term else 0)
+        for k in range(3):
+            a.origin[k], a.cell[k], a.dims[k] = float(grid.origin[k]), float(grid.cell[k]), dims[k]
+        result = {}
+        for name in outputs:
+            dtype, shape = self.PROBE_OUTPUTS[name]
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), shape(n))
+            setattr(a, name + "_out", result[name].data_ptr() or None)
+        a.points = call.input(points, "points", torch.float32, (n, 3)).data_ptr()
+        a.normals = call.input(normals, "normals", torch.float32, (n, 3)).data_ptr()
+        a.sh = call.input(sh, "sh", torch.float32, (m, 9, 4)).data_ptr()
+        if kept is not None:
+            a.kept = call.input(kept, "kept", torch.int32, (m,)).data_ptr()
+        if albedo is not None:
+            a.albedo = call.input(albedo, "albedo", torch.float32, (n, 4)).data_ptr()
+        if base is not None:
+            a.base = call.input(base, "base", torch.float32, (n, 4)).data_ptr()
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_probe_lookup_device, a, context=context, want_stats=want_stats or collect_stats,
+                             collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
+    def render_probe_lit(self, width: int, height: int, grid, sh, *, config: Optional[Config] = None, kept=None, visibility=True,
+                         normal_term=True, bias=1e-3, albedo="color", base=None, stream=None, context=0):
+        """A frame lit by a probe grid, without a render call: gbuffer() -> probe_lookup() on one stream, nothing waited for in
+        between.  Returns the (height, width, 4) float32 radiance: the surface's `albedo` output ("color" or "diffuse") x the
+        blended irradiance / pi, plus `base` (an (height, width, 4) direct-light frame) when given; a pixel whose camera ray misses
+        is base's pixel, or (0, 0, 0, 1).  config: the camera rays' Config (None: Config()).  bias, in world units, lifts the
+        origins of the corner rays off the surface."""
+        if albedo not in ("color", "diffuse"):
+            raise ValueError(f'albedo: {albedo!r}, expected "color" or "diffuse"')
+        g = self.gbuffer(config if config is not None else Config(), width, height, want=("point", "normal", albedo), stream=stream, context=context)
+        r = self.probe_lookup(g["point"].reshape(-1, 3), g["normal"].reshape(-1, 3), grid, sh, kept=kept, visibility=visibility,
+                              normal_term=normal_term, bias=bias, albedo=g[albedo].reshape(-1, 4),
+                              base=base.reshape(-1, 4) if base is not None else None, outputs=("radiance",), stream=stream, context=context)
+        return r["radiance"].reshape(height, width, 4)
+
     # ---- the denoiser: an edge-avoiding a-trous filter on a frame and its G-buffer (rayca_hip_denoise_device) ----
     def denoise(self, color, *, albedo=None, normal=None, point=None, id=None, iterations=5, sigma_color=4.0, sigma_plane=None,
                 normal_power_log2=7, gamma=1.0, out=None, rgba8=False, stream=None, context=0, want_stats=False):
