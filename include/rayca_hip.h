@@ -195,7 +195,12 @@ typedef struct RaycaTexture {
   uint32_t image;
 } RaycaTexture;
 
-/* Image payload (image.rs:26-36): `color_type` texels, row-major, at `byte_offset` of image_bytes. */
+/* Image payload (image.rs:26-36): `color_type` texels, row-major, at `byte_offset` of image_bytes.
+ * Every image of a descriptor, referenced by a texture or not, is checked when the descriptor is taken; RAYCA_ERR_BAD_ARG
+ * with a message naming the image unless
+ *   - color_type is one of RAYCA_COLOR_RGB8 (3 bytes a texel), RAYCA_COLOR_RGBA8 (4) and RAYCA_COLOR_RGBA32F (16);
+ *   - byte_offset + width x height x texel size <= image_byte_count (evaluated without overflow);
+ *   - an RGBA32F image's byte_offset is a multiple of 4: its texels are read as floats. */
 typedef struct RaycaImage {
   uint32_t width;
   uint32_t height;

@@ -1631,7 +1631,17 @@ int32_t oracle_scene_create(const RaycaSceneDesc* d, const RaycaConfig* cfg, con
   if (d->abi_version != RAYCA_ABI_VERSION) return fail(RAYCA_ERR_BAD_ARG, "abi version mismatch");
   if (d->node_count && !d->nodes) return fail(RAYCA_ERR_BAD_ARG, "nodes is null");
   if (d->vertex_count && !d->positions) return fail(RAYCA_ERR_BAD_ARG, "positions is null");
-  OracleScene* s = (OracleScene*)calloc(1, sizeof *s);
+  if (d->image_count && !d->images) return fail(RAYCA_ERR_BAD_ARG, "images is null");
+  if (d->image_byte_count && !d->image_bytes) return fail(RAYCA_ERR_BAD_ARG, "image_bytes is null");
+  for (uint32_t i = 0; i < d->image_count; ++i) { /* the RaycaImage rules of include/rayca_hip.h: sample_texture reads no byte outside image_bytes */
+    const RaycaImage* im = &d->images[i];
+    if (im->color_type > RAYCA_COLOR_RGBA32F) return fail(RAYCA_ERR_BAD_ARG, "image %u: unknown color_type %u", i, im->color_type);
+    uint64_t texel = im->color_type == RAYCA_COLOR_RGB8 ? 3u : im->color_type == RAYCA_COLOR_RGBA8 ? 4u : 16u;
+    if (im->byte_offset > d->image_byte_count || (uint64_t)im->width * im->height > (d->image_byte_count - im->byte_offset) / texel)
+      return fail(RAYCA_ERR_BAD_ARG, "image %u: texels end beyond image_byte_count", i);
+    if (im->color_type == RAYCA_COLOR_RGBA32F && im->byte_offset % 4u) return fail(RAYCA_ERR_BAD_ARG, "image %u: RGBA32F byte_offset is not a multiple of 4", i);
+  }
+  OracleScene* s =(OracleScene*)calloc(1, sizeof *s);
   if (opts) s->opts = *opts;
   if (s->opts.threads == 0) s->opts.threads = online_cores();
   const uint32_t use_bvh = cfg ? cfg->bvh : 1u; /* Config::default(): bvh = true  config.rs:12-13 */
@@ -1843,25 +1853,28 @@ typedef struct {
   int unsupported;
 } Job;
 
-static void render_pixel(Ctx* cx, const Job* job, uint32_t x, uint32_t y, uint32_t out_row) {
-  const RaycaConfig* cfg = job->cfg;
-  const OracleScene* s = job->s;
-  float width = (float)job->width, height = (float)job->height;
+/* the ray of sub-sample i of pixel (x, y)  scene.rs:117-141 */
+static Ray camera_ray(const OracleScene* s, const RaycaConfig* cfg, uint32_t w, uint32_t h, uint32_t x, uint32_t y, uint32_t i) {
+  float width = (float)w, height = (float)h;
   float inv_width = 1.0f / width, inv_height = 1.0f / height;
   float aspectratio = width / height;
   float angle = tanf(s->camera_yfov * 0.5f); /* Camera::get_angle  camera.rs:74-76 */
   const Trs* camera_trs = &s->world_trs[s->camera_node];
-  Col color = COL_BLACK;
   float strate_count = sqrtf((float)cfg->samples_per_pixel);
   float offset = 0.5f / strate_count;
   float step = 1.0f / strate_count;
+  float ix = (float)(i % (uint32_t)strate_count);
+  float iy = (float)(i / (uint32_t)strate_count);
+  float xx = (2.0f * (((float)x + ix * step + offset) * inv_width) - 1.0f) * angle * aspectratio;
+  float yy = (1.0f - 2.0f * (((float)y + iy * step + offset) * inv_height)) * angle;
+  V4 dir = vnormalize(vec3(xx, yy, -1.0f));
+  return trs_ray(camera_trs, ray_new(point3(0, 0, 0), dir));
+}
+static void render_pixel(Ctx* cx, const Job* job, uint32_t x, uint32_t y, uint32_t out_row) {
+  const RaycaConfig* cfg = job->cfg;
+  Col color = COL_BLACK;
   for (uint32_t i = 0; i < cfg->samples_per_pixel; ++i) {
-    float ix = (float)(i % (uint32_t)strate_count);
-    float iy = (float)(i / (uint32_t)strate_count);
-    float xx = (2.0f * (((float)x + ix * step + offset) * inv_width) - 1.0f) * angle * aspectratio;
-    float yy = (1.0f - 2.0f * (((float)y + iy * step + offset) * inv_height)) * angle;
-    V4 dir = vnormalize(vec3(xx, yy, -1.0f));
-    Ray ray = trs_ray(camera_trs, ray_new(point3(0, 0, 0), dir));
+    Ray ray = camera_ray(job->s, cfg, job->width, job->height, x, y, i);
     Col c;
     uint32_t key = oracle_rng_root(cfg->seed, y * job->width + x, i);
     if (!trace(cx, ray, 0, key, &c)) c = COL_BLACK; /* draw_pixel  scene.rs:80-86 */
@@ -1976,6 +1989,78 @@ int32_t oracle_trace_rays(OracleScene* s, uint32_t count, const float* rays, flo
     }
   }
   if (stats_out) { memset(stats_out, 0, sizeof *stats_out); stats_out->rays_primary = count; stats_out->boxes_tested = tc.boxes; stats_out->triangles_tested = tc.tris; }
+  return RAYCA_OK;
+}
+/* the rays oracle_render traces: sub-sample `sample` of every pixel, row-major, 6 floats each (origin, direction) */
+int32_t oracle_camera_rays(OracleScene* s, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample, float* rays_out) {
+  if (!s || !cfg || !rays_out) return fail(RAYCA_ERR_BAD_ARG, "null argument");
+  if (!s->has_camera) return fail(RAYCA_ERR_NO_CAMERA, "scene has no camera (scene.rs:109)");
+  if (width == 0 || height == 0 || sample >= cfg->samples_per_pixel) return fail(RAYCA_ERR_BAD_ARG, "empty image or no such sample");
+  for (uint32_t y = 0; y < height; ++y)
+    for (uint32_t x = 0; x < width; ++x) {
+      Ray r = camera_ray(s, cfg, width, height, x, y, sample);
+      float* o = rays_out + 6 * ((size_t)y * width + x);
+      o[0] = r.origin.x; o[1] = r.origin.y; o[2] = r.origin.z; o[3] = r.dir.x; o[4] = r.dir.y; o[5] = r.dir.z;
+    }
+  return RAYCA_OK;
+}
+/* HitInfo at caller-supplied hit records (the RaycaSurfaceQuery contract of include/rayca_hip.h): the Hit is filled from the
+ * record as the intersection routines above fill it, and every value comes from the hi_* functions the render path calls. */
+int32_t oracle_surface(OracleScene* s, uint32_t count, const float* rays, const float* t, const uint32_t* prim, const float* uv,
+                       float* point_out, float* normal_out, float* color_out, float* diffuse_out, float* specular_out,
+                       float* rough_out, uint32_t* material_out, uint32_t* flags_out) {
+  if (!s || (count && (!t || !prim || !uv))) return fail(RAYCA_ERR_BAD_ARG, "null argument");
+  if (!point_out && !normal_out && !color_out && !diffuse_out && !specular_out && !rough_out && !material_out && !flags_out)
+    return fail(RAYCA_ERR_BAD_ARG, "no output");
+  if (!rays && (point_out || normal_out)) return fail(RAYCA_ERR_BAD_ARG, "point and normal need the rays");
+  for (uint32_t i = 0; i < count; ++i) {
+    const size_t k = i;
+    V4 point = v4(0, 0, 0, 0), normal = v4(0, 0, 0, 0);
+    Col zero = col(0, 0, 0, 0), color = zero, diffuse = zero, specular = zero;
+    float roughness = 0.0f, shininess = 0.0f;
+    uint32_t material = RAYCA_NONE, flags = 0;
+    if (prim[k] != RAYCA_NONE && prim[k] < s->prim_total) {
+      HitInfo hi;
+      memset(&hi, 0, sizeof hi);
+      hi.scene = s;
+      uint32_t b = 0;
+      while (b + 1 < s->blas_count && s->blas_prim_base[b + 1] <= prim[k]) ++b;
+      hi.hit.blas = b;
+      hi.hit.primitive = prim[k] - s->blas_prim_base[b];
+      const Prim* pr = hi_primitive(&hi);
+      Ray ray = rays ? ray_new(point3(rays[6 * k], rays[6 * k + 1], rays[6 * k + 2]), vec3(rays[6 * k + 3], rays[6 * k + 4], rays[6 * k + 5]))
+                     : ray_new(point3(0, 0, 0), vec3(0, 0, 1)); /* (read by point and normal alone, which need the rays) */
+      hi.hit.depth = t[k];
+      if (pr->kind == RAYCA_GEOMETRY_TRIANGLE_MESH) { /* triangle_intersects_world: ray.clone(), origin + dir * t, (u, v) */
+        hi.hit.ray = ray;
+        hi.hit.point = add4(ray.origin, vscale(ray.dir, t[k]));
+        hi.hit.uv = v2(uv[2 * k], uv[2 * k + 1]);
+      } else { /* sphere_intersects: the Hit of the inverse-transformed ray, its point taken back to the world */
+        const Trs* trs = &s->world_trs[pr->node];
+        Ray inv = inv_trs_ray(trs, ray);
+        hi.hit.ray = inv;
+        hi.hit.point = trs_point(trs, add4(inv.origin, vscale(inv.dir, t[k])));
+        hi.hit.uv = v2(0.0f, 0.0f);
+      }
+      const RaycaMaterial* m = prim_material(s, pr);
+      point = hi.hit.point;
+      if (normal_out) normal = hi_normal(&hi);
+      if (color_out) color = hi_color(&hi);
+      if (diffuse_out) diffuse = hi_diffuse(&hi);
+      if (specular_out) specular = hi_specular(&hi);
+      if (rough_out) { roughness = hi_roughness(&hi); shininess = m->shininess; }
+      material = m == &MATERIAL_DEFAULT ? RAYCA_NONE : pr->material;
+      flags = (m->kind & 3u) | (hi_is_emissive(&hi) ? 4u : 0u) | (pr->kind == RAYCA_GEOMETRY_SPHERE ? 8u : 0u) | 0x80000000u;
+    }
+    if (point_out) { point_out[3 * k] = point.x; point_out[3 * k + 1] = point.y; point_out[3 * k + 2] = point.z; }
+    if (normal_out) { normal_out[3 * k] = normal.x; normal_out[3 * k + 1] = normal.y; normal_out[3 * k + 2] = normal.z; }
+    if (color_out) { color_out[4 * k] = color.r; color_out[4 * k + 1] = color.g; color_out[4 * k + 2] = color.b; color_out[4 * k + 3] = color.a; }
+    if (diffuse_out) { diffuse_out[4 * k] = diffuse.r; diffuse_out[4 * k + 1] = diffuse.g; diffuse_out[4 * k + 2] = diffuse.b; diffuse_out[4 * k + 3] = diffuse.a; }
+    if (specular_out) { specular_out[4 * k] = specular.r; specular_out[4 * k + 1] = specular.g; specular_out[4 * k + 2] = specular.b; specular_out[4 * k + 3] = specular.a; }
+    if (rough_out) { rough_out[2 * k] = roughness; rough_out[2 * k + 1] = shininess; }
+    if (material_out) material_out[k] = material;
+    if (flags_out) flags_out[k] = flags;
+  }
   return RAYCA_OK;
 }
 

@@ -76,6 +76,18 @@ int32_t oracle_render_rows(OracleScene* s, const RaycaConfig* cfg, uint32_t widt
 /* Tlas::intersects for caller-supplied rays; prim_out in global post-build order */
 int32_t oracle_trace_rays(OracleScene* s, uint32_t count, const float* rays, float* t_out,
                           uint32_t* prim_out, float* uv_out, RaycaStats* stats_out);
+/* The camera rays oracle_render traces: sub-sample `sample` (< cfg->samples_per_pixel) of every pixel, row-major, 6 floats each */
+int32_t oracle_camera_rays(OracleScene* s, const RaycaConfig* cfg, uint32_t width, uint32_t height, uint32_t sample,
+                           float* rays_out);
+/* HitInfo at caller-supplied hit records -- the reference for rayca_hip_surface_device, under the RaycaSurfaceQuery contract of
+ * include/rayca_hip.h.  rays: count x 6 or NULL (needed for point_out / normal_out); prim in global post-build order, as
+ * oracle_trace_rays returns it; a prim of RAYCA_NONE or >= the primitive count is a miss (zeros, material RAYCA_NONE, flags 0).
+ * Each record's Hit is rebuilt as Triangle::intersects / Sphere::intersects build it (a sphere's from the inverse-transformed
+ * ray and t) and handed to the HitInfo getters the render path uses.  rough_out = (roughness, the material's shininess);
+ * flags: bits 0-1 material kind, bit 2 emissive, bit 3 sphere, bit 31 hit.  Any output may be NULL, not all. */
+int32_t oracle_surface(OracleScene* s, uint32_t count, const float* rays, const float* t, const uint32_t* prim,
+                       const float* uv, float* point_out, float* normal_out, float* color_out, float* diffuse_out,
+                       float* specular_out, float* rough_out, uint32_t* material_out, uint32_t* flags_out);
 
 /* ---- known-answer hooks for the restated unit tests (tests/test_oracle_kat.py) -------------- */
 void oracle_vec3_rotate(const float v[3], const float q[4], float out[3]);

@@ -1193,6 +1193,27 @@ int32_t desc_validate(const RaycaSceneDesc& d, std::string& err) {
     for (const uint32_t t : {m.albedo_texture, m.normal_texture, m.metallic_roughness_texture})
       if (t != RAYCA_NONE && t >= d.texture_count) { err = "material " + std::to_string(i) + ": texture index out of range"; return RAYCA_ERR_BAD_ARG; }
   }
+  // every image, referenced by a texture or not: a known texel format, all texels inside image_bytes, floats on a word.
+  // width x height fits 64 bits, width x height x 16 need not: the texel count is compared with the bytes left divided by the texel size.
+  for (uint32_t i = 0; i < d.image_count; ++i) {
+    const RaycaImage& im = d.images[i];
+    const std::string which = "image " + std::to_string(i);
+    if (im.color_type != RAYCA_COLOR_RGB8 && im.color_type != RAYCA_COLOR_RGBA8 && im.color_type != RAYCA_COLOR_RGBA32F) {
+      err = which + ": color_type " + std::to_string(im.color_type) + " is none of RGB8, RGBA8, RGBA32F";
+      return RAYCA_ERR_BAD_ARG;
+    }
+    const uint64_t texel = im.color_type == RAYCA_COLOR_RGB8 ? 3u : im.color_type == RAYCA_COLOR_RGBA8 ? 4u : 16u;
+    const uint64_t texels = (uint64_t)im.width * im.height;   // (two 32-bit factors: no overflow)
+    if (im.byte_offset > d.image_byte_count || texels > (d.image_byte_count - im.byte_offset) / texel) {
+      err = which + ": " + std::to_string(im.width) + " x " + std::to_string(im.height) + " texels of " + std::to_string(texel) + " bytes at byte_offset " +
+            std::to_string(im.byte_offset) + " end beyond image_byte_count " + std::to_string(d.image_byte_count);
+      return RAYCA_ERR_BAD_ARG;
+    }
+    if (im.color_type == RAYCA_COLOR_RGBA32F && im.byte_offset % 4u != 0u) {
+      err = which + ": an RGBA32F image's byte_offset " + std::to_string(im.byte_offset) + " is not a multiple of 4";
+      return RAYCA_ERR_BAD_ARG;
+    }
+  }
   return RAYCA_OK;
 }
 

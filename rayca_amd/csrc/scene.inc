@@ -515,6 +515,9 @@ extern "C" {
 int32_t rayca_hip_scene_create(const RaycaSceneDesc* desc, const RaycaConfig* cfg, const RaycaBuildOptions* opts, RaycaScene** out) {
   if (!desc || !out) return fail(RAYCA_ERR_BAD_ARG, "null argument");
   *out = nullptr;
+  // what no scene may hold, refused before any device call: a kernel samples a texture with nothing but `% width` between a UV and an
+  // address, so an image whose texels end beyond image_bytes would be read past the allocation
+  if (std::string err; desc_validate(*desc, err) != RAYCA_OK) return fail(RAYCA_ERR_BAD_ARG, err);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(RAYCA_ERR_NO_DEVICE, "no HIP device visible: librayca_hip has no CPU fallback");

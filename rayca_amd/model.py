@@ -322,6 +322,10 @@ def flatten(scene: Scene) -> abi.SceneDesc:
         base = dict(mesh=len(meshes), material=len(materials), texture=len(textures), image=len(images),
                     camera=len(cameras), light=len(lights))
         for im in model.images:
+            pad = (-image_off) % 4   # an RGBA32F image is read through a float pointer; every image starts on a word
+            if pad:
+                image_chunks.append(np.zeros(pad, np.uint8))
+                image_off += pad
             r = abi.RaycaImage()
             r.width, r.height, r.color_type, r.byte_offset = im.width, im.height, im.color_type, image_off
             raw = np.ascontiguousarray(im.data).view(np.uint8).reshape(-1)

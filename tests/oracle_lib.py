@@ -70,6 +70,10 @@ def load():
     lib.oracle_trace_rays.restype = C.c_int32
     lib.oracle_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       P(abi.RaycaStats)]
+    lib.oracle_camera_rays.restype = C.c_int32
+    lib.oracle_camera_rays.argtypes = [C.c_void_p, P(abi.RaycaConfig), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.oracle_surface.restype = C.c_int32
+    lib.oracle_surface.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 12
     F3, F4 = C.c_float * 3, C.c_float * 4
     lib.oracle_vec3_dot.restype = C.c_float
     lib.oracle_aabb_intersects.restype = C.c_float
@@ -205,3 +209,27 @@ class OracleScene:
         _check(self.lib.oracle_trace_rays(self.handle, n, rays.ctypes.data, t.ctypes.data, prim.ctypes.data,
                                           uv.ctypes.data, C.byref(st)))
         return t, prim, uv, st.as_dict()
+
+    def camera_rays(self, config, width, height, sample=0):
+        cfg = config.to_abi()
+        rays = np.zeros((width * height, 6), np.float32)
+        _check(self.lib.oracle_camera_rays(self.handle, C.byref(cfg), width, height, sample, rays.ctypes.data))
+        return rays
+
+    SURFACE_OUTPUTS = {"point": (np.float32, 3), "normal": (np.float32, 3), "color": (np.float32, 4), "diffuse": (np.float32, 4),
+                       "specular": (np.float32, 4), "rough": (np.float32, 2), "material": (np.uint32, 0), "flags": (np.uint32, 0)}
+
+    def surface(self, rays, t, prim, uv, want=tuple(SURFACE_OUTPUTS)):
+        """oracle_surface: HitInfo at hit records (prim in global post-build order); {name: array} of the outputs in `want`,
+        shaped as DeviceScene.surface shapes them.  `rays` may be None unless point or normal is wanted."""
+        t = np.ascontiguousarray(t, np.float32).reshape(-1)
+        n = t.shape[0]
+        prim = np.ascontiguousarray(prim).view(np.uint32).reshape(n)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+        if rays is not None:
+            rays = np.ascontiguousarray(rays, np.float32).reshape(n, 6)
+        out = {k: np.full((n, w) if w else (n,), 0x5A, dt) for k, (dt, w) in self.SURFACE_OUTPUTS.items() if k in want}
+        ptr = [out[k].ctypes.data if k in out else None for k in self.SURFACE_OUTPUTS]
+        _check(self.lib.oracle_surface(self.handle, n, rays.ctypes.data if rays is not None else None, t.ctypes.data,
+                                       prim.ctypes.data, uv.ctypes.data, *ptr))
+        return out

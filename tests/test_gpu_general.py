@@ -75,7 +75,8 @@ def sphere_scenes(with_boxes):
 
 
 def textured_scene():
-    """A quad with an albedo + normal texture in front of the box: HitInfo's texture paths under the stack machine."""
+    """A quad with an albedo texture (and no other) and the default camera and lights: HitInfo's albedo path under the stack
+    machine.  The normal-map and metallic-roughness paths are test_gpu_surface_oracle.py's, on the zoo of surface_cases.py."""
     import test_gpu_parity as P
     return P._textured_quad_scene()
 
