@@ -53,7 +53,8 @@ extern "C" {
                                   adaptive sampling: RaycaSamplePlan, rayca_hip_sample_plan_device, RaycaFilmFold,
                                   rayca_hip_film_fold_device;
                                   irradiance gathering: RaycaGather, rayca_hip_gather_device;
-                                 irradiance volumes: RaycaProbeLookup, rayca_hip_probe_lookup_device */
+                                 irradiance volumes: RaycaProbeLookup, rayca_hip_probe_lookup_device;
+                                  signed distance and occupancy: RaycaSigned, rayca_hip_signed_device, RAYCA_SIGNED_ */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -790,6 +791,81 @@ struct RaycaHits {
 };
 typedef struct RaycaHits RaycaHits;
 int32_t rayca_hip_hits_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaHits* query, RaycaStats* stats_out);
+
+/* Signed distance and occupancy on DEVICE memory: for `count` points the nearest surface point of the scene's triangles and
+ * whether the point lies inside the surface -- signed distance fields, occupancy masks, voxelisation, collision and clearance
+ * tests, and a signed-distance volume on a regular grid without a point buffer.  One launch where the composition costs a nearest
+ * call, a ray buffer per direction (24 B per point and direction, written and read again), a crossing count per direction and a
+ * reduction.  The rays are made in registers; points and results stay on the device; asynchronous on the caller's stream.
+ *
+ * The specification.  Every operation is f32 and rounded on its own.
+ *   The points (source):
+ *     RAYCA_SIGNED_POINTS  point i is (points[3i], points[3i + 1], points[3i + 2]).
+ *     RAYCA_SIGNED_GRID    no point buffer is read.  With (nx, ny, nz) = grid_dims, point i has ix = i % nx, iy = (i / nx) % ny,
+ *                          iz = i / (nx * ny) -- x runs fastest -- and per axis p = origin + (float)index * step: convert,
+ *                          multiply, add.  count must equal nx * ny * nz (computed in 64 bits; at most 2^32 - 1).
+ *   The distance part (dist2_out, prim_out, point_out, uv_out): bit for bit what RAYCA_NEAREST_CLOSEST writes for the same point
+ *   and radius (radius / radius_all as in RaycaNearest) -- the candidates, the strict bound dist2 < radius * radius, the tie to
+ *   the lowest slot, the miss record (dist2 = FLT_MAX, prim = RAYCA_NONE, zeros elsewhere), and the dead-point rule: a radius
+ *   that is NaN or <= 0, or a coordinate that is not finite, gives a miss.  The search runs only if one of the four is given.
+ *   The sign part (inside_out, votes_out, cross_out) does not depend on radius.  For direction j < n_dirs the ray is
+ *   (p, dirs[j]), and its hits are those of rayca_hip_hits_device with RAYCA_HITS_BOTH, count_all and an unbounded tmax: the same
+ *   test, the same "seen by the reference's leaf box" rule, the same t < +inf rule.
+ *     front_j = the number of those hits with face 0, back_j = the number with face 1
+ *     RAYCA_SIGNED_PARITY   vote_j = (front_j + back_j) & 1
+ *     RAYCA_SIGNED_WINDING  vote_j = back_j > front_j.  A ray that leaves a closed, outward-wound solid exits it once more than it
+ *                           enters it, so a point in the union of overlapping solids is inside, where parity calls the overlap
+ *                           of two solids outside.
+ *     votes  = the OR of vote_j << j over j < n_dirs
+ *     inside = 2 * popcount(votes) > n_dirs ? 1 : 0                                        (a strict majority; n_dirs is odd)
+ *     cross_out[(i * n_dirs + j) * 2 + 0 / 1] = front_j / back_j
+ *   A point with a coordinate that is not finite has votes 0, inside 0 and every crossing 0.
+ *   Consequences (for points whose coordinates are finite):
+ *     front_j equals n_out of a multi-hit query with k = 0, count_all, RAYCA_HITS_FRONT and tmax_all = INFINITY on the ray
+ *     (p, dirs[j]); front_j + back_j equals n_out of the same call with RAYCA_HITS_BOTH.
+ *   What the sign is worth: it is only as good as the crossing counts.  It is meaningful for closed, consistently wound meshes.
+ *   The reference's triangle test drops a hit whose unnormalised |n.d| < FLT_EPSILON, so a mesh of very small triangles loses
+ *   crossings; a ray through an edge or a vertex may count both triangles or neither; points on or within rounding of a surface
+ *   can land on either side.  That is why several directions vote, and votes_out is how a caller sees them disagree.  No component
+ *   of a direction may be zero: the reference's box test gives an axis-aligned ray no hits at all.
+ * Any output may be NULL, but one of inside_out, votes_out, cross_out must be given: without them the call is
+ * rayca_hip_nearest_device.
+ * opts (may be NULL): stream, context, wait_event, record_event, collect_stats and traversal as for rayca_hip_nearest_device;
+ * RAYCA_TRAVERSAL_EXHAUSTIVE runs both searches without the cull and the ordering and gives the same results bit for bit; tile,
+ * engine and camera_rays must be zero.  Ordered on its context like a query.  With stats_out the call waits: kernel_launches = 1,
+ * rays_primary = count * n_dirs, the kernel's time under RAYCA_KERNEL_OTHER, and under collect_stats boxes_tested and
+ * triangles_tested summed over both searches.  count == 0 is RAYCA_OK and launches nothing; nothing outside [0, count) of an
+ * output ([0, count * n_dirs * 2) of cross_out) is written.
+ * RAYCA_ERR_BAD_ARG, before any GPU work and before the scene is looked at, in this order: NULL scene / query; unknown source;
+ * POINTS with NULL points; GRID with a zero dimension or nx * ny * nz != count; unknown rule; n_dirs not 1, 3 or 5; a component of
+ * one of the first n_dirs directions that is zero, NaN or infinite; non-zero reserved; none of the three sign outputs; then
+ * context > 7, a non-zero field of opts that does not apply.  Then (count != 0) RAYCA_ERR_EMPTY_SCENE as the query, and
+ * RAYCA_ERR_UNSUPPORTED for a scene with spheres, as rayca_hip_nearest_device. */
+enum { RAYCA_SIGNED_POINTS = 0, RAYCA_SIGNED_GRID = 1 };
+enum { RAYCA_SIGNED_PARITY = 0, RAYCA_SIGNED_WINDING = 1 };
+struct RaycaSigned {
+  uint32_t count;
+  uint32_t source;         /* RAYCA_SIGNED_POINTS / RAYCA_SIGNED_GRID */
+  const void* points;      /* POINTS, DEVICE: count x 3 f32 */
+  const void* radius;      /* DEVICE: count f32, or NULL => radius_all for every point */
+  float radius_all;
+  uint32_t rule;           /* RAYCA_SIGNED_PARITY / RAYCA_SIGNED_WINDING */
+  uint32_t n_dirs;         /* 1, 3 or 5 */
+  uint32_t reserved;       /* must be zero */
+  float grid_origin[3];    /* GRID: the point of index (0, 0, 0) */
+  float grid_step[3];      /* GRID: the spacing per axis */
+  uint32_t grid_dims[3];   /* GRID: (nx, ny, nz), x fastest */
+  float dirs[5][3];        /* the first n_dirs are used; no zero, NaN or infinite component */
+  void* dist2_out;         /* DEVICE: count f32, SQUARED distance, FLT_MAX on a miss */
+  void* prim_out;          /* DEVICE: count u32 slot (post-build primitive order), RAYCA_NONE on a miss */
+  void* point_out;         /* DEVICE: count x 3 f32, the nearest point, 0 on a miss */
+  void* uv_out;            /* DEVICE: count x 2 f32 in the convention of hit records, 0 on a miss */
+  void* inside_out;        /* DEVICE: count u8, 1 / 0 */
+  void* votes_out;         /* DEVICE: count u8, bit j = direction j's vote */
+  void* cross_out;         /* DEVICE: count x n_dirs x 2 u32, (front, back) per direction */
+};
+typedef struct RaycaSigned RaycaSigned;
+int32_t rayca_hip_signed_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaSigned* query, RaycaStats* stats_out);
 
 /* Ambient occlusion on DEVICE memory: how open the scene is at `count` caller-supplied points -- `samples` occlusion rays over the
  * hemisphere of each point's normal, folded into one record per point: ambient occlusion on a G-buffer, sky visibility, per-vertex

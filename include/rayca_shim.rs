@@ -82,6 +82,11 @@ pub const RAYCA_HITS_BOTH: u32 = 1;
 pub const RAYCA_PROBE_VISIBILITY: u32 = 1;
 pub const RAYCA_PROBE_NORMAL_TERM: u32 = 2;
 pub const RAYCA_HITS_MAX: u32 = 16;
+// RaycaSigned.source and RaycaSigned.rule
+pub const RAYCA_SIGNED_POINTS: u32 = 0;
+pub const RAYCA_SIGNED_GRID: u32 = 1;
+pub const RAYCA_SIGNED_PARITY: u32 = 0;
+pub const RAYCA_SIGNED_WINDING: u32 = 1;
 // RaycaTonemap.op
 pub const RAYCA_TONEMAP_LINEAR: u32 = 0;
 pub const RAYCA_TONEMAP_REINHARD: u32 = 1;
@@ -346,6 +351,31 @@ pub struct RaycaHits {
     pub uv_out: *mut c_void,
     pub face_out: *mut c_void,
     pub n_out: *mut c_void,
+}
+
+// rayca_hip_signed_device: points (or a grid held by value), radii and results in DEVICE memory; the directions by value
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaSigned {
+    pub count: u32,
+    pub source: u32,
+    pub points: *const c_void,
+    pub radius: *const c_void,
+    pub radius_all: f32,
+    pub rule: u32,
+    pub n_dirs: u32,
+    pub reserved: u32,
+    pub grid_origin: [f32; 3],
+    pub grid_step: [f32; 3],
+    pub grid_dims: [u32; 3],
+    pub dirs: [[f32; 3]; 5],
+    pub dist2_out: *mut c_void,
+    pub prim_out: *mut c_void,
+    pub point_out: *mut c_void,
+    pub uv_out: *mut c_void,
+    pub inside_out: *mut c_void,
+    pub votes_out: *mut c_void,
+    pub cross_out: *mut c_void,
 }
 
 // rayca_hip_ambient_device: points, normals and a direction table in, one record per point out, all in DEVICE memory
@@ -719,6 +749,7 @@ extern "C" {
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_nearest_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaNearest, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_hits_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaHits, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_signed_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSigned, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_ambient_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, ambient: *const RaycaAmbient, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_surface_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSurfaceQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_camera_rays_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, width: u32, height: u32, sample: u32, opts: *const RaycaRenderOptions, d_rays_out: *mut c_void) -> i32;

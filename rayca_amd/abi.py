@@ -47,6 +47,8 @@ NEAREST_CLOSEST, NEAREST_WITHIN = 0, 1   # RaycaNearest.kind
 HITS_FRONT, HITS_BOTH = 0, 1   # RaycaHits.faces
 PROBE_VISIBILITY, PROBE_NORMAL_TERM = 1, 2   # RaycaProbeLookup.flags
 HITS_MAX = 16   # RAYCA_HITS_MAX: the largest RaycaHits.k
+SIGNED_POINTS, SIGNED_GRID = 0, 1   # RaycaSigned.source
+SIGNED_PARITY, SIGNED_WINDING = 0, 1   # RaycaSigned.rule
 TONEMAP_LINEAR, TONEMAP_REINHARD, TONEMAP_ACES = 0, 1, 2   # RaycaTonemap.op
 TONEMAP_NAMES = ("linear", "reinhard", "aces")
 METER_WORDS, METER_COUNTED, METER_BLACK, METER_NOT_FINITE = 260, 256, 257, 258   # hist_out of rayca_hip_meter_device
@@ -337,6 +339,31 @@ class RaycaHits(C.Structure):
         ("uv_out", C.c_void_p),
         ("face_out", C.c_void_p),
         ("n_out", C.c_void_p),
+    ]
+
+
+class RaycaSigned(C.Structure):
+    """rayca_hip_signed_device: every pointer is DEVICE memory; the grid and the directions are held by value."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("source", C.c_uint32),
+        ("points", C.c_void_p),
+        ("radius", C.c_void_p),
+        ("radius_all", C.c_float),
+        ("rule", C.c_uint32),
+        ("n_dirs", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("grid_origin", C.c_float * 3),
+        ("grid_step", C.c_float * 3),
+        ("grid_dims", C.c_uint32 * 3),
+        ("dirs", (C.c_float * 3) * 5),
+        ("dist2_out", C.c_void_p),
+        ("prim_out", C.c_void_p),
+        ("point_out", C.c_void_p),
+        ("uv_out", C.c_void_p),
+        ("inside_out", C.c_void_p),
+        ("votes_out", C.c_void_p),
+        ("cross_out", C.c_void_p),
     ]
 
 
@@ -760,6 +787,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_nearest_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaNearest), P(RaycaStats)]
     lib.rayca_hip_hits_device.restype = C.c_int32
     lib.rayca_hip_hits_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaHits), P(RaycaStats)]
+    lib.rayca_hip_signed_device.restype = C.c_int32
+    lib.rayca_hip_signed_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSigned), P(RaycaStats)]
     lib.rayca_hip_ambient_device.restype = C.c_int32
     lib.rayca_hip_ambient_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaAmbient), P(RaycaStats)]
     lib.rayca_hip_surface_device.restype = C.c_int32
@@ -811,6 +840,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device", "rayca_hip_hits_device",
+    "rayca_hip_signed_device",
     "rayca_hip_ambient_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_probe_lookup_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",

@@ -1709,6 +1709,97 @@ int32_t rayca_hip_hits_device(RaycaScene* s, const RaycaRenderOptions* opts_in, 
   return RAYCA_OK;
 }
 
+// What RaycaSigned alone decides, in the header's order; the first rule broken is the one reported.  No scene, no device.
+int32_t check_signed(const RaycaSigned& rs) {
+  if (rs.source != RAYCA_SIGNED_POINTS && rs.source != RAYCA_SIGNED_GRID) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.source: unknown source");
+  if (rs.source == RAYCA_SIGNED_POINTS && !rs.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.points: null points");
+  if (rs.source == RAYCA_SIGNED_GRID) {
+    if (rs.grid_dims[0] == 0 || rs.grid_dims[1] == 0 || rs.grid_dims[2] == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.grid_dims: a dimension is zero");
+    const uint64_t plane = (uint64_t)rs.grid_dims[0] * rs.grid_dims[1];   // (< 2^64; the second product is checked by division)
+    if (plane > 0xFFFFFFFFull || plane * rs.grid_dims[2] != (uint64_t)rs.count)
+      return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.grid_dims: nx * ny * nz must equal count (at most 2^32 - 1 points)");
+  }
+  if (rs.rule != RAYCA_SIGNED_PARITY && rs.rule != RAYCA_SIGNED_WINDING) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.rule: unknown rule");
+  if (rs.n_dirs != 1u && rs.n_dirs != 3u && rs.n_dirs != 5u) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.n_dirs: 1, 3 or 5 directions");
+  for (uint32_t j = 0; j < rs.n_dirs; ++j)
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(rs.dirs[j][a]) || rs.dirs[j][a] == 0.0f)
+        return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.dirs: a component of a used direction is zero, NaN or infinite (an axis-aligned ray has no hits)");
+  if (rs.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSigned.reserved must be zero");
+  if (!rs.inside_out && !rs.votes_out && !rs.cross_out)
+    return fail(RAYCA_ERR_BAD_ARG, "no sign output for a signed query: without inside_out, votes_out and cross_out this is a nearest-point query");
+  return RAYCA_OK;
+}
+
+// Signed distance and occupancy (signed.inc k_signed): one point per lane on the binary f32 nodes, which every scene has from
+// scene_create on, so the call never waits for the formats thread.  One launch: the nearest search where a distance output is
+// asked for, then a crossing-count ray per direction.  A pass on its context (run_pass), which clears the work counters on the
+// launch stream when they are read.
+int32_t rayca_hip_signed_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSigned* sin, RaycaStats* stats_out) {
+  if (!s || !sin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaSigned");
+  const RaycaSigned& rs = *sin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  int32_t rc = check_signed(rs);
+  if (rc != RAYCA_OK) return rc;
+  if ((rc = pass_options(o, "a signed query", kOptTraversal | kOptCollectStats)) != RAYCA_OK) return rc;
+  if (rs.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  if (s->host.sphere_count != 0)
+    return fail(RAYCA_ERR_UNSUPPORTED, "a scene with spheres has no signed query: its distance part is a nearest-point query, which has no closed form on an ellipsoid");
+  const bool grid_source = rs.source == RAYCA_SIGNED_GRID;
+  SignedIo io{};
+  io.points = grid_source ? nullptr : static_cast<const float*>(rs.points);
+  io.radius = static_cast<const float*>(rs.radius);
+  io.radius_all = rs.radius_all;
+  io.count = rs.count;
+  for (int a = 0; a < 3; ++a) {
+    io.grid_origin[a] = rs.grid_origin[a];
+    io.grid_step[a] = rs.grid_step[a];
+    io.grid_dims[a] = grid_source ? rs.grid_dims[a] : 1u;
+  }
+  io.rule = rs.rule;
+  io.n_dirs = rs.n_dirs;
+  std::memcpy(io.dirs, rs.dirs, sizeof io.dirs);
+  io.dist2_out = static_cast<float*>(rs.dist2_out);
+  io.prim_out = static_cast<uint32_t*>(rs.prim_out);
+  io.point_out = static_cast<float*>(rs.point_out);
+  io.uv_out = static_cast<float*>(rs.uv_out);
+  io.inside_out = static_cast<uint8_t*>(rs.inside_out);
+  io.votes_out = static_cast<uint8_t*>(rs.votes_out);
+  io.cross_out = static_cast<uint32_t*>(rs.cross_out);
+  const bool near = io.dist2_out || io.prim_out || io.point_out || io.uv_out;
+  const bool stats = o.collect_stats != 0, cull = o.traversal != RAYCA_TRAVERSAL_EXHAUSTIVE;
+  const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+  const StackPlan sp = plan_stack(s->host.max_depth);   // (one pending sibling per level in either phase)
+  const uint32_t grid = (uint32_t)(((uint64_t)rs.count + kBlock - 1u) / kBlock);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  rc = run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    TraceLaunch tl{};
+    if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+    if (stats) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+    hipLaunchKernelGGL(pick_signed_kernel(near, cull, grid_source, fast, stats), dim3(grid), dim3(kBlock), sp.lds_bytes, stream,
+                       formats_ready(s) ? s->dev_full : s->dev, io, c->counters, tl);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+    if (stats && stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+    return RAYCA_OK;
+  });
+  if (rc != RAYCA_OK || !stats_out) return rc;
+  stats_out->rays_primary = (uint64_t)rs.count * rs.n_dirs;
+  if (stats) {
+    stats_out->boxes_tested = tc.boxes;
+    stats_out->triangles_tested = tc.tris;
+  }
+  return RAYCA_OK;
+}
+
 // Hemisphere visibility at points (ambient.inc, refill.hip k_ambient_refill): count x samples occlusion rays made in registers, one
 // mask word per point, folded by k_ambient_finish.  The trace kernel is chosen as rayca_hip_query_device chooses an OCCLUDED query's:
 // the lane-refill form on the 4-wide fp16 nodes for a RAYCA_BUILDER_SAH scene whose formats are there, else one ray per lane on

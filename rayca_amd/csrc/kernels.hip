@@ -20,6 +20,8 @@
 //                     (nearest.inc: rayca_hip_nearest_device).
 //   k_hits            multi-hit ray queries: the first k hits along rays in device memory, in order, or their number
 //                     (hits.inc: rayca_hip_hits_device).
+//   k_signed          signed distance and occupancy: the nearest surface point of points or grid points in device memory and a
+//                     vote of crossing-count rays on the side they lie on (signed.inc: rayca_hip_signed_device).
 //   k_ambient_rays,   hemisphere visibility at points: occlusion rays made in registers, one per lane, and the fold of a point's
 //   k_ambient_finish  mask word into hits, openness and the bent normal (ambient.inc: rayca_hip_ambient_device; the lane-refill
 //                     form is refill.hip k_ambient_refill).
@@ -459,6 +461,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "surface.inc"
 #include "nearest.inc"
 #include "hits.inc"
+#include "signed.inc"
 #include "ambient.inc"
 #include "probes.inc"
 #include "gather.inc"

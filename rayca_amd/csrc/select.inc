@@ -92,6 +92,14 @@ HitsKernel pick_hits_kernel(Trav t, bool sph, bool stats, bool both, bool count_
   }, t, sph, stats, both, count_all);
 }
 
+// k_signed (signed.inc): flags only -- NEAR: a distance output is asked for (the nearest phase is compiled in), CULL: the ordered and
+// culled searches, GRID: the points are made from a grid, FAST: the scene's reference-leaf filter; the rule and the number of
+// directions are run-time values
+using SignedKernel = void (*)(DevScene, SignedIo, TraceCounters*, TraceLaunch);
+SignedKernel pick_signed_kernel(bool near, bool cull, bool grid, bool fast, bool stats) {
+  return with_flags([](auto NEAR, auto CULL, auto GRID, auto FAST, auto STATS) -> SignedKernel { return k_signed<NEAR, CULL, GRID, FAST, STATS>; }, near, cull, grid, fast, stats);
+}
+
 // k_ambient_rays (ambient.inc, rayca_hip_ambient_device where k_ambient_refill of refill.hip cannot run): ordered, binary f32 nodes
 // with the spill path, as pick_query_kernel's OCCLUDED forms -- so kTravFastSpill or kTravExact: the scene's FAST alone; flags only
 using AmbientKernel = void (*)(DevScene, AmbientIo, TraceCounters*, TraceLaunch);
@@ -500,6 +508,8 @@ int32_t selftest_kernel_selection(std::string& err) {
        [&](Trav, uint32_t i) { return b(i, 1) ? i : i & ~1u; }},   // the exhaustive form does not read within
       {"pick_hits_kernel(trav; sph, stats, both, count_all)", all, 4, [&](Trav t, uint32_t i) { return P(pick_hits_kernel(t, b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
        [&](Trav t, uint32_t i) { return (uint32_t)query_of(t) << 8 | i; }},
+      {"pick_signed_kernel(near, cull, grid, fast, stats)", none, 5,
+       [&](Trav, uint32_t i) { return P(pick_signed_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3), b(i, 4))); }, every},
       {"pick_ambient_kernel(fast, sph, stats, rot)", none, 4, [&](Trav, uint32_t i) { return P(pick_ambient_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); }, every},
       {"pick_ambient_finish(bent, rot)", none, 2, [&](Trav, uint32_t i) { return P(pick_ambient_finish(b(i, 0), b(i, 1))); },
        [&](Trav, uint32_t i) { return b(i, 0) ? i : 0u; }},   // without bent_out no direction is made: rot is not read

@@ -348,8 +348,113 @@ class DeviceScene:
             result["stats"] = stats
         return result
 
+    # ---- signed distance and occupancy: the nearest point plus a vote of crossing-count rays (rayca_hip_signed_device) ----
+    SIGNED_OUTPUTS = {"dist2": ("float32", ()), "prim": ("int32", ()), "point": ("float32", (3,)), "uv": ("float32", (2,)),
+                      "inside": ("uint8", ()), "votes": ("uint8", ()), "cross": ("int32", None)}
+    SIGNED_RULES = {"parity": abi.SIGNED_PARITY, "winding": abi.SIGNED_WINDING}
+
+    def signed(self, points=None, *, grid=None, radius=None, dirs=3, rule="parity",
+               outputs=("dist2", "prim", "point", "uv", "inside", "votes", "cross"), stream=None, context=0, out=None, want_stats=False,
+               traversal=abi.TRAVERSAL_ORDERED, collect_stats=False):
+        """rayca_hip_signed_device: the nearest surface point of points in device memory and the side of the surface they lie
+        on, in one launch, asynchronously.
+
+        points: torch tensor (N, 3) float32 on this scene's device -- or grid=(origin, step, dims): the N = nx * ny * nz points
+        origin + index * step of a regular grid, x running fastest, made inside the kernel (signed.grid_points restates them).
+        radius: as for nearest(); it bounds the distance part only.  dirs: 1, 3 or 5 -- that many of signed.sign_directions() --
+        or an (n, 3) array of directions without a zero component.  rule: "parity" (an odd number of crossings is inside) or
+        "winding" (more exits than entries is inside: the union of overlapping closed meshes).  Returns a dict with one tensor
+        per name in `outputs`: dist2, prim, point, uv as nearest() returns them; inside (N,) uint8, the majority of the
+        directions' votes; votes (N,) uint8, bit j the vote of direction j; cross (N, n, 2) int32, the (front, back) crossing
+        counts of each direction.  At least one of inside, votes, cross must be asked for; without a distance output the
+        nearest search is left out.  The sign is meaningful for closed, consistently wound meshes.  `out`: a dict of tensors
+        to write instead of new ones.  Stream handling and statistics as query(): `want_stats` / `collect_stats` wait and add
+        "stats".  Scenes with spheres are refused (ERR_UNSUPPORTED)."""
+        from .signed import checked_directions, checked_grid
+        if rule not in self.SIGNED_RULES:
+            raise ValueError(f"rule must be 'parity' or 'winding', not {rule!r}")
+        outputs = tuple(outputs)
+        unknown = [w for w in outputs if w not in self.SIGNED_OUTPUTS]
+        if unknown or not outputs or len(set(outputs)) != len(outputs):
+            raise ValueError(f"outputs: a non-empty selection without repeats of {tuple(self.SIGNED_OUTPUTS)}, not {outputs!r}")
+        if not {"inside", "votes", "cross"} & set(outputs):
+            raise ValueError("outputs: one of 'inside', 'votes', 'cross' must be asked for (the distance outputs alone are nearest())")
+        if (points is None) == (grid is None):
+            raise ValueError("either points or grid=(origin, step, dims) is expected")
+        d = checked_directions(dirs)
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        q = abi.RaycaSigned()
+        if grid is not None:
+            origin, step, dims, n = checked_grid(grid)
+            q.source = abi.SIGNED_GRID
+            for a in range(3):
+                q.grid_origin[a], q.grid_step[a], q.grid_dims[a] = float(origin[a]), float(step[a]), dims[a]
+        else:
+            if not isinstance(points, torch.Tensor):
+                raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+            if points.dim() != 2 or points.shape[1] != 3:
+                raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+            n = points.shape[0]
+            if n > 0xFFFFFFFF:
+                raise ValueError("points: more than 2**32 - 1 points")
+            q.source = abi.SIGNED_POINTS
+        q.count, q.rule, q.n_dirs = n, self.SIGNED_RULES[rule], d.shape[0]
+        for j in range(d.shape[0]):
+            for a in range(3):
+                q.dirs[j][a] = float(d[j, a])
+        out = dict(out) if out is not None else {}
+        stray = [w for w in out if w not in outputs]
+        if stray:
+            raise ValueError(f"out: {stray} not in outputs")
+        result = {}
+        for name in outputs:
+            dtype, tail = self.SIGNED_OUTPUTS[name]
+            shape = (n, d.shape[0], 2) if tail is None else (n, *tail)
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), shape)
+            setattr(q, name + "_out", result[name].data_ptr() or None)
+        if grid is None:
+            q.points = call.input(points, "points", torch.float32, (n, 3)).data_ptr()
+        if radius is None:
+            q.radius_all = float("inf")
+        elif isinstance(radius, torch.Tensor):
+            q.radius = call.input(radius, "radius", torch.float32, (n,)).data_ptr()
+        else:
+            q.radius_all = float(radius)
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_signed_device, q, context=context, want_stats=want_stats or collect_stats,
+                             traversal=traversal, collect_stats=collect_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats or collect_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
+    def signed_distance(self, points=None, *, grid=None, **kw):
+        """The signed distance to the surface, float32 (N,): sqrt(dist2) of signed(), negated where `inside`.  The square root is
+        torch's, on the stream of the call; the kernel's own contract stays free of it.  A point without a surface point within
+        `radius` has the square root of FLT_MAX.  Keywords as signed() without `outputs` and `out`."""
+        call = _DeviceCall(self, kw.get("stream"))
+        r = self.signed(points, grid=grid, outputs=("dist2", "inside"), **kw)
+        torch = call.torch
+        # (a raw handle is wrapped; without a stream the call has waited, and torch's current stream will do)
+        stream = call.stream if hasattr(call.stream, "cuda_stream") else (torch.cuda.ExternalStream(call.handle, device=call.dev) if call.handle else None)
+        with torch.cuda.stream(stream):
+            d = torch.sqrt(r["dist2"])
+            return torch.where(r["inside"] != 0, -d, d)
+
+    def occupancy(self, points=None, *, grid=None, **kw):
+        """The inside mask of signed(), uint8 (N,).  No distance output is asked for, so the nearest search is not run.  Keywords
+        as signed() without `outputs`; `out`: the tensor to write."""
+        if "out" in kw:
+            kw["out"] = {"inside": kw["out"]} if kw["out"] is not None else None
+        return self.signed(points, grid=grid, outputs=("inside",), **kw)["inside"]
+
     # ---- surface queries: what is at a hit (rayca_hip_surface_device), and the rays of a frame (rayca_hip_camera_rays_device) ----
-    SURFACE_OUTPUTS = {"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
+    SURFACE_OUTPUTS ={"point": ("float32", 3), "normal": ("float32", 3), "color": ("float32", 4), "diffuse": ("float32", 4),
                        "specular": ("float32", 4), "rough": ("float32", 2), "material": ("int32", 0), "flags": ("int32", 0)}
 
     def stream_handle(self, stream=None) -> int:
