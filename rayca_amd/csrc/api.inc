@@ -777,17 +777,21 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   // waves per SIMD, so that a wave holds 7 680 B and twenty waves per CU -- what their 96 registers admit -- fit 160 KiB whether LDS
   // is handed out in granules of 512 B or of 1 280 B (8 192 B would round to 8 960 B under the second: eighteen waves); twelve rows
   // for the counting and the sphere instantiations, which stay at four waves (sixteen of 9 728 B fit).  Deeper entries go to the
-  // (cold) spill area.  (-DRAYCA_CTX_COMPACT=0: 7 KiB + twelve rows, sixteen waves of 10 KiB.)
+  // (cold) spill area.  (-DRAYCA_CTX_COMPACT=0: 7 KiB + twelve rows, sixteen waves of 10 KiB.)  What is parked is read back in two
+  // parts: the context by every NEE sample that is prepared and by the bounce behind them, the direct sum by the vertex's record.  A
+  // generation on the last-vertex form (last_form, select.inc: no vertex of it bounces) reads the sum alone behind its samples; the
+  // layout and the allocation are the same for both forms -- its NEE samples still need the context.
   const bool park = RAYCA_PARK_CTX && f.plan.mode == kModePath;
   const bool sph = s->host.sphere_count != 0;
+  const bool last = last_form(f.plan.mode, f.cfg, g);
   const TravPlan tp = plan_traversal(s, f.plan.ordered, g, ch.format, park ? path_lds_entries(path_waves(f.plan.stats, sph)) : kMaxLdsEntries);
   f.node_format |= (traits(tp.trav).wide ? (g == 0 ? 1u : 2u) : 0u) | (traits(tp.trav).half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
-                   (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u);
+                   (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u) | (last && g < 16u ? 65536u << g : 0u);
   const StackPlan sp = tp.stack;
   // (k_generation runs as workgroups of kGenBlock threads, k_flat_refill as 256-thread blocks: rows and quads per thread of the workgroup)
   const uint32_t block = ch.refill ? (uint32_t)kBlock : (uint32_t)kGenBlock;
   const size_t lds_bytes = ((size_t)sp.lds_entries * 4u + (park ? (size_t)kCtxBytes : 0u)) * block;
-  GenKernel k = pick_kernel(f.plan.mode, g == 0, f.fused, tp.trav, sph, f.plan.stats);
+  GenKernel k = pick_kernel(f.plan.mode, g == 0, f.fused, tp.trav, sph, f.plan.stats, last);
   const RefillFlavour rf{tp.trav, sph, f.plan.stats};   // (launched only where choose_generation allows it: one of the kTravFast*)
   const uint32_t batches = g == 0 ? f.fp.tile_count : (f.pb.npix + 63u) / 64u;
   const uint32_t grid_mult = knobs().grid_mult;

@@ -94,7 +94,12 @@ struct GenArgs {
 #else
 #define GEN_COLD(member) (a.member)
 #endif
-template <int MODE, bool GEN0, bool ORDERED, bool FUSED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF>
+// LAST (Path only; Flat does not read it): the generation behind which no vertex samples a bounce -- `depth >= limit` of the tail
+// below holds for every vertex, which the host knows from the Config (last_form, select.inc).  The tail then takes the direct sum
+// back from LDS and writes the vertex's record; the bounce sampler with its double-precision libm_exact functions, surf_brdf, the
+// factor record, push_ray, the bounce counter and the fetch of the parked context are not compiled in.  The records are those the
+// general form writes for such a vertex: the same direct sum, kVertexLitNoIndirect, pb.brdf untouched.
+template <int MODE, bool GEN0, bool ORDERED, bool FUSED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF, bool LAST>
 __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : path_waves(STATS, SPH)) void k_generation(GenArgs a) {
   const TraceLaunch& tl = a.tl;
   uint32_t* const heads = a.heads;
@@ -253,6 +258,15 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
     }
     if (FUSED) {
       if (has_pixel) finalize_pixel(GEN_COLD(fp), direct, p, GEN_COLD(rgba8), GEN_COLD(rgba32f));
+    } else if (MODE == kModePath && LAST) {
+      // the last vertex of a path: its direct sum is its record (pathtracer.rs:89-93 with depth >= limit); the context stays parked
+      if (tail) {
+        const PathBuffers& pb = GEN_COLD(pb);
+        if (PARK) direct = unpark_sum<kGenBlock>(ctx_slot);
+        pb.direct[slot] = as_f4(direct);
+        pb.state[slot] = kVertexLitNoIndirect;
+      }
+      n_shadow += (uint32_t)__popcll(__ballot(tail)) * nee_lights * GEN_COLD(fp).light_samples;
     } else if (MODE == kModePath) {
       const FrameParams& fp = GEN_COLD(fp);
       const PathBuffers& pb = GEN_COLD(pb);
@@ -336,7 +350,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
     if (lane == 0 && (s2 | b2)) {
       TraceCounters* const counters = GEN_COLD(counters);
       atomicAdd(&counters->shadow, s2);
-      atomicAdd(&counters->bounce, b2);
+      if (!LAST) atomicAdd(&counters->bounce, b2);
     }
   }
 }

@@ -19,13 +19,14 @@ struct LaunchPlan {
 // the traversal loop (measured: +15 % frame time on the depth-1 path kernel), so production launches
 // use the instantiation without them
 
-// k_generation: every flavour; Flat is generation 0, fused (the kernel writes the pixel) or not; Path is never fused
+// k_generation: every flavour; Flat is generation 0, fused (the kernel writes the pixel) or not; Path is never fused, and has a
+// last-vertex form (`last`: last_form below), which Flat does not read
 using GenKernel = void (*)(GenArgs);
-GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats) {
+GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats, bool last) {
   const bool flat = mode == kModeFlat;
-  return with_flavour([](auto T, auto FLAT, auto A, auto SPH, auto STATS) -> GenKernel {   // A: fused (Flat) / generation 0 (Path)
-    return k_generation<FLAT ? kModeFlat : kModePath, FLAT || A, T.ORDERED, FLAT && A, T.FAST, SPH, T.WIDE, T.SPILL, STATS, T.HALF>;
-  }, t, flat, flat ? fused : gen0, sph, stats);
+  return with_flavour([](auto T, auto FLAT, auto A, auto SPH, auto STATS, auto LAST) -> GenKernel {   // A: fused (Flat) / generation 0 (Path)
+    return k_generation<FLAT ? kModeFlat : kModePath, FLAT || A, T.ORDERED, FLAT && A, T.FAST, SPH, T.WIDE, T.SPILL, STATS, T.HALF, !FLAT && LAST>;
+  }, t, flat, flat ? fused : gen0, sph, stats, last);
 }
 
 // k_trace_rays: ignores HALF (caller-supplied rays traverse the f32 nodes): six distinct traversals
@@ -195,6 +196,7 @@ struct Knobs {
   uint32_t grid_mult;         // RAYCA_GRID_MULT: blocks per CU of the fused engine's persistent grids (experiments); 0 = what the kernel admits
   uint32_t ticket;            // RAYCA_TICKET: batches per work ticket of the fused engine; 0 = by the size of the frame
   uint32_t path_lds_entries;  // RAYCA_PATH_LDS_ENTRIES: LDS part of a path frame's node stack, clamped to 4..kMaxLdsEntries; 0 = by the kernel's waves
+  bool last_form;             // RAYCA_LAST_FORM=0: every generation of a path frame on k_generation's general form (A/B runs and tests); nothing else hangs on it
 };
 const Knobs& knobs() {
   static const Knobs k = [] {
@@ -208,6 +210,7 @@ const Knobs& knobs() {
     n.grid_mult = (uint32_t)env("RAYCA_GRID_MULT", 0);
     n.ticket = (uint32_t)env("RAYCA_TICKET", 0);
     n.path_lds_entries = getenv("RAYCA_PATH_LDS_ENTRIES") ? std::min(std::max((uint32_t)env("RAYCA_PATH_LDS_ENTRIES", 0), 4u), kMaxLdsEntries) : 0u;
+    n.last_form = env("RAYCA_LAST_FORM", 1) != 0;
     return n;
   }();
   return k;
@@ -232,6 +235,16 @@ uint32_t path_lds_entries(int waves_per_simd) {
   if (const uint32_t forced = knobs().path_lds_entries) return forced;
   return std::min(std::max((uint32_t)(waves_per_simd >= 5 ? RAYCA_PATH_LDS_ENTRIES : RAYCA_PATH_LDS_ENTRIES_FOUR_WAVES), 4u), kMaxLdsEntries);
 }
+
+// Does generation g of a frame run k_generation's last-vertex form (LAST, kernels.hip)?  Exactly when the test of the kernel's tail,
+// `depth < limit`, is false for every vertex of the generation: a path frame's generations from `limit` on.  Under NEE that is the
+// frame's last generation (max_depth 1: generation 0, the bench frame); with direct_sampler NONE the limit is max_depth and no
+// generation of a frame reaches it.  last_form_rule is the arithmetic alone (rayca_hip_selftest checks it), last_form adds the knob.
+bool last_form_rule(int mode, uint32_t direct_sampler, uint32_t max_depth, uint32_t g) {
+  const uint32_t limit = direct_sampler != RAYCA_SAMPLER_NONE ? (max_depth ? max_depth - 1u : 0u) : max_depth;
+  return mode == kModePath && g >= limit;
+}
+bool last_form(int mode, const RaycaConfig& c, uint32_t g) { return knobs().last_form && last_form_rule(mode, c.direct_sampler, c.max_depth, g); }
 
 // What plan_traversal reads of a scene.
 struct TreeFacts {
@@ -491,9 +504,9 @@ int32_t selftest_kernel_selection(std::string& err) {
   const auto exhaustive = [](Trav t) { return t == kTravExactAll || t == kTravFastAll; };
   const auto every = [](Trav t, uint32_t i) { return (uint32_t)t << 8 | i; };   // no narrowing: every tuple its own kernel
   const PickerFamily families[] = {
-      {"pick_kernel(trav; sph, stats, flat, gen0, fused)", all, 5,
-       [&](Trav t, uint32_t i) { return P(pick_kernel(mode(b(i, 2)), b(i, 3), b(i, 4), t, b(i, 0), b(i, 1))); },
-       [&](Trav t, uint32_t i) { return (uint32_t)t << 8 | (i & 7u) | ((b(i, 2) ? b(i, 4) : b(i, 3)) ? 8u : 0u); }},   // Flat does not read gen0, Path not fused
+      {"pick_kernel(trav; sph, stats, flat, gen0, fused, last)", all, 6,
+       [&](Trav t, uint32_t i) { return P(pick_kernel(mode(b(i, 2)), b(i, 3), b(i, 4), t, b(i, 0), b(i, 1), b(i, 5))); },
+       [&](Trav t, uint32_t i) { return (uint32_t)t << 8 | (i & 7u) | ((b(i, 2) ? b(i, 4) : b(i, 3)) ? 8u : 0u) | (!b(i, 2) && b(i, 5) ? 16u : 0u); }},   // Flat reads neither gen0 nor last, Path not fused
       {"pick_trace_kernel(trav; sph, stats)", all, 2, [&](Trav t, uint32_t i) { return P(pick_trace_kernel(t, b(i, 0), b(i, 1))); },
        [&](Trav t, uint32_t i) { return (uint32_t)f32_of(t) << 8 | i; }},
       {"pick_query_kernel(trav; sph, stats, occluded)", all, 3, [&](Trav t, uint32_t i) { return P(pick_query_kernel(t, b(i, 0), b(i, 1), b(i, 2))); },
@@ -549,5 +562,23 @@ int32_t selftest_kernel_selection(std::string& err) {
           return RAYCA_ERR_BAD_ARG;
         }
       }
+  // last_form_rule: the generations of a frame on the last-vertex form, as a bit mask
+  struct LastCase { int mode; uint32_t direct_sampler, max_depth, generations, mask; const char* what; };
+  const LastCase last_cases[] = {
+      {kModePath, RAYCA_SAMPLER_NEE, 1u, 1u, 1u, "max_depth 1 under NEE: generation 0"},
+      {kModePath, RAYCA_SAMPLER_NEE, 2u, 2u, 2u, "max_depth 2 under NEE: generation 1 only"},
+      {kModePath, RAYCA_SAMPLER_NEE, 3u, 3u, 4u, "max_depth 3 under NEE: generation 2 only"},
+      {kModePath, RAYCA_SAMPLER_NONE, 1u, 1u, 0u, "max_depth 1 without a direct sampler: none"},
+      {kModePath, RAYCA_SAMPLER_NONE, 3u, 3u, 0u, "max_depth 3 without a direct sampler: none"},
+      {kModeFlat, RAYCA_SAMPLER_NEE, 1u, 1u, 0u, "a Flat frame: none"},
+  };
+  for (const LastCase& c : last_cases) {
+    uint32_t mask = 0;
+    for (uint32_t g = 0; g < c.generations; ++g) mask |= last_form_rule(c.mode, c.direct_sampler, c.max_depth, g) ? 1u << g : 0u;
+    if (mask != c.mask) {
+      err = std::string("last_form_rule: ") + c.what + ", got generations " + std::to_string(mask) + " (a bit each)";
+      return RAYCA_ERR_BAD_ARG;
+    }
+  }
   return RAYCA_OK;
 }
