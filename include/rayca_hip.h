@@ -401,7 +401,9 @@ typedef struct RaycaStats {
    * issued (a thread started by rayca_hip_scene_create encodes and uploads them; until then frames traverse the binary
    * f32 nodes and nothing is timed -- same pixels either way), bit 12 = where "binary f32" nodes are traversed by the
    * conservative (RAYCA_BUILDER_SAH) kernels they are read as 48-B centre / half-extent records (three 16-B loads per
-   * node instead of four; 0: 64-B min / max nodes), bit 16 + g (g < 16) = generation g of a fused-engine path frame ran
+   * node instead of four; 0: 64-B min / max nodes), bit 13 = a fused-engine path frame whose one generation kernel wrote the
+   * pixel itself: one sample per pixel, max_depth 1 under NEE, not a counting frame -- one launch, no k_resolve
+   * (RAYCA_FUSE_RESOLVE=0 in the environment keeps the two launches -- same pixels either way), bit 16 + g (g < 16) = generation g of a fused-engine path frame ran
    * the generation kernel's last-vertex form, the one without the bounce code (no vertex of that generation samples a
    * bounce; RAYCA_LAST_FORM=0 in the environment keeps every generation on the general form -- same pixels either way).
    * Wavefront-engine frames report the formats their kernels are compiled for (bits 0-3). */

@@ -88,8 +88,11 @@ struct FrameCtx {
   DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment)
   DeviceBuffer gather_samples;        // rayca_hip_gather_device without samples_out: the radiance records of one internal frame (16 B a ray)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-  bool heads_clean = false;           // both work-counter sets and the queue counters are known to be zero (k_resolve of the
-                                      // previous frame cleared them): generation 0 needs no memset launch
+  // Which of the context's counters are known to be zero, a bit each: the first work-counter set, the second, the two queue
+  // counters.  A launch that draws from one clears its bit; k_resolve zeroes all three behind a frame, and a fused k_generation
+  // launch the set it does not draw from (GenArgs.clear), so that the next frame finds what it needs clean and issues no memset.
+  enum : uint32_t { kCleanHeads = 1u, kCleanHeadsB = 2u, kCleanQueues = 4u, kCleanAll = 7u };
+  uint32_t heads_clean = 0u;
   hipEvent_t ev_done = nullptr;       // recorded behind the last kernel of every frame of this context
   bool frame_pending = false;         // ev_done has been recorded at least once
   std::vector<hipEvent_t> ev_trace;   // pairs around the timed launches of a frame (LaunchLog)
@@ -113,7 +116,8 @@ struct FrameCtx {
     ev_trace.clear();
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
-    ready = frame_pending = heads_clean = false;
+    ready = frame_pending = false;
+    heads_clean = 0u;
   }
   ~FrameCtx() { release(); }
 };
@@ -767,6 +771,10 @@ GenChoice choose_generation(Frame& f, uint32_t g) {
   return ch;
 }
 
+// A fused camera frame of the fused engine is one k_generation (or k_flat_refill) launch, which looks after the work counters itself
+// (fused_generation); every other frame has them cleared by frame_run.
+bool own_counters(const Frame& f) { return f.fused && !f.plan.wavefront && !f.rays; }
+
 // One generation of the fused engine: one k_generation (or k_flat_refill) launch.
 int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   RaycaScene* s = f.s;
@@ -786,7 +794,8 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   const bool last = last_form(f.plan.mode, f.cfg, g);
   const TravPlan tp = plan_traversal(s, f.plan.ordered, g, ch.format, park ? path_lds_entries(path_waves(f.plan.stats, sph)) : kMaxLdsEntries);
   f.node_format |= (traits(tp.trav).wide ? (g == 0 ? 1u : 2u) : 0u) | (traits(tp.trav).half ? (g == 0 ? 4u : 8u) : 0u) | (ch.calibrating ? 256u : 0u) |
-                   (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u) | (last && g < 16u ? 65536u << g : 0u);
+                   (ch.refill_cal ? 512u : 0u) | (ch.refill ? 1024u : 0u) | (last && g < 16u ? 65536u << g : 0u) |
+                   (f.fused && f.plan.mode == kModePath ? 8192u : 0u);
   const StackPlan sp = tp.stack;
   // (k_generation runs as workgroups of kGenBlock threads, k_flat_refill as 256-thread blocks: rows and quads per thread of the workgroup)
   const uint32_t block = ch.refill ? (uint32_t)kBlock : (uint32_t)kGenBlock;
@@ -801,13 +810,38 @@ int32_t fused_generation(Frame& f, uint32_t g, const GenQueues& q) {
   if (rc != RAYCA_OK || (rc = bind_stack(c, sp, grid, tl, block)) != RAYCA_OK) return rc;
   const uint32_t ticket_forced = knobs().ticket;
   tl.ticket = ticket_forced ? ticket_forced : ticket_policy(batches, grid, block / 64u);
+  // The work counters.  A generation of a frame with several launches finds them cleared by frame_run.  A fused camera frame is this
+  // one launch, and frame_run leaves the counters to it: k_generation draws from whichever of the context's two sets is known to be
+  // zero and zeroes the other one itself (GenArgs.clear), so the next such frame of the context swaps them and neither issues a fill
+  // launch -- in the steady state a fused Flat or depth-1 path frame is exactly one launch.  Nothing of this launch reads the set it
+  // clears, and whatever drew from that set before has retired: the passes of one context are ordered by the context-pass protocol,
+  // which is what k_resolve's clear relies on too.  Only when neither set is known clean (the context's first frame, or behind
+  // launches that dirtied both) does a memset go first.  k_flat_refill keeps its own memset of the first set: its frames are
+  // milliseconds long.
+  uint32_t* heads = c->heads;
+  uint32_t* clear = nullptr;
+  if (own_counters(f)) {
+    if (ch.refill) {
+      if (!(c->heads_clean & FrameCtx::kCleanHeads)) HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), f.stream));
+      c->heads_clean &= ~FrameCtx::kCleanHeads;
+    } else {
+      if (!(c->heads_clean & (FrameCtx::kCleanHeads | FrameCtx::kCleanHeadsB))) {
+        HIP_TRY(hipMemsetAsync(c->heads_b, 0, 17 * kHeadStride * sizeof(uint32_t), f.stream));
+        c->heads_clean = FrameCtx::kCleanAll;
+      }
+      const bool first = (c->heads_clean & FrameCtx::kCleanHeads) != 0u;
+      heads = first ? c->heads : c->heads_b;
+      clear = first ? c->heads_b : c->heads;
+      c->heads_clean = (c->heads_clean & FrameCtx::kCleanQueues) | (first ? FrameCtx::kCleanHeadsB : FrameCtx::kCleanHeads);
+    }
+  }
   size_t ev = 0;
   rc = timed_launch(f.log, f.stream, ch.refill ? RAYCA_KERNEL_FLAT_REFILL : RAYCA_KERNEL_GENERATION, f.timing || ch.calibrating || ch.refill_cal, true, [&] {
     if (ch.refill)
       launch_flat_refill(rf, grid, lds_bytes, f.stream, *f.dscene, f.fp, c->heads, f.rgba8, f.rgba32f, c->counters, tl);
     else
       hipLaunchKernelGGL(k, dim3(grid), dim3(kGenBlock), lds_bytes, f.stream,
-                         GenArgs{*f.dscene, f.fp, c->heads, q.in, q.in_count, q.out, q.out_count, f.pb, g, f.rgba8, f.rgba32f, c->counters, tl});
+                         GenArgs{*f.dscene, f.fp, heads, q.in, q.in_count, q.out, q.out_count, f.pb, g, f.rgba8, f.rgba32f, c->counters, tl, clear});
     return RAYCA_OK;
   }, &ev);
   if (rc != RAYCA_OK) return rc;
@@ -844,7 +878,7 @@ int32_t stack_machine(Frame& f) {
   TraceLaunch tl{};
   if ((rc = bind_stack(c, sp, grid, tl)) != RAYCA_OK) return rc;
   tl.ticket = f.fp.tile_count >= 16u * grid ? 2u : 1u;
-  c->heads_clean = false;
+  c->heads_clean &= ~FrameCtx::kCleanHeads;
   return timed_launch(f.log, f.stream, RAYCA_KERNEL_OTHER, f.timing, true, [&]() -> int32_t {
     HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), f.stream));
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), sp.lds_bytes, f.stream, s->dev, f.fp, c->heads, f.pb, store, c->counters, tl);
@@ -873,7 +907,7 @@ int32_t resolve(Frame& f) {
                        static_cast<float4*>(c->accum.ptr), f.rgba8, f.rgba32f, general ? nullptr : c->heads_b, 17u * kHeadStride);
     return RAYCA_OK;
   });
-  if (rc == RAYCA_OK && !general) c->heads_clean = true;
+  if (rc == RAYCA_OK && !general) c->heads_clean = FrameCtx::kCleanAll;
   return rc;
 }
 
@@ -1058,9 +1092,11 @@ int32_t frame_begin(Frame& f, const ContextPass& pass, void* d_rgba8, void* d_rg
   f.node_format = (f.all_formats ? 0u : 2048u) | (RAYCA_NODE_CH && RAYCA_NODE_CH48 && f.dscene->nodes_ch ? 4096u : 0u);
   f.rgba8 = static_cast<uint8_t*>(d_rgba8);
   f.rgba32f = static_cast<float4*>(d_rgba32f);
-  // Flat, one sample: the generation kernel writes the pixel itself.  Path frames always resolve in their own pass: the same
-  // fusion for the depth-1 path frame was measured twice and lost twice (DESIGN.md, the k_generation table).
-  f.fused = f.cfg.samples_per_pixel == 1 && plan.mode == kModeFlat;
+  // Flat, one sample: the generation kernel writes the pixel itself.  So does the one-sample depth-1 path frame of the fused engine
+  // (fuse_resolve, select.inc), since its generation runs the last-vertex form: that fusion was measured and lost twice while the
+  // kernel carried the direct sum through trace() and spilled; the third measurement is in DESIGN.md (the k_generation table).
+  // Every other path frame resolves in a pass of its own.
+  f.fused = (f.cfg.samples_per_pixel == 1 && plan.mode == kModeFlat) || fuse_resolve(plan, f.cfg, f.rays != nullptr);
   config_frame_params(f, f.fp);
 
   // One record per pixel and depth; the two queues where a path bounces, queue 1 also where generation 0 reads the caller's rays.
@@ -1102,10 +1138,12 @@ int32_t frame_run(Frame& f) {
       // generation 0 clears the work counters and both queue counters in one go (unless k_resolve of the previous frame
       // left them clean); later generations must keep the input queue's counter.  One memset clears both counter sets (the
       // second one is only used by the wavefront engine), in whole lines: a size that is not a multiple of the fill
-      // kernel's granule costs a second fill launch, ~5 us.
-      if (!(g == 0 && c->heads_clean))
-        HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
-      c->heads_clean = false;
+      // kernel's granule costs a second fill launch, ~5 us.  (Not for a fused camera frame of the fused engine: own_counters.)
+      if (!own_counters(f)) {
+        if (!(g == 0 && c->heads_clean == FrameCtx::kCleanAll))
+          HIP_TRY(hipMemsetAsync(c->heads_b, 0, (16 * kHeadStride + (g == 0 ? kHeadStride : 0)) * sizeof(uint32_t), stream));
+        c->heads_clean = 0u;
+      }
       // generation g reads what generation g - 1 wrote; generation 0 the caller's rays in queue 1, which generation 1 writes
       // over once they are read, or nothing (the camera)
       const int in = g ? (int)((g - 1) & 1) : (f.rays ? 1 : -1);
@@ -1561,7 +1599,7 @@ int32_t rayca_hip_query_device(RaycaScene* s, const RaycaRenderOptions* opts_in,
   if (refill) {
     tl.ticket = 1u;
     HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
-    c->heads_clean = false;   // the next frame of this context clears them for itself
+    c->heads_clean &= ~FrameCtx::kCleanHeads;   // the next frame of this context clears them for itself
   }
   if (pass.timing) HIP_TRY(hipEventRecord(c->ev_begin, stream));
   if (refill) launch_query_refill(occluded, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, q, c->heads, c->counters, tl);
@@ -1887,7 +1925,7 @@ int32_t rayca_hip_ambient_device(RaycaScene* s, const RaycaRenderOptions* opts_i
         if (refill) {
           tl.ticket = 1u;
           HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
-          c->heads_clean = false;   // the next frame of this context clears them for itself
+          c->heads_clean &= ~FrameCtx::kCleanHeads;   // the next frame of this context clears them for itself
           launch_ambient_refill(rot, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, io, c->heads, c->counters, tl);
         } else {
           hipLaunchKernelGGL(pick_ambient_kernel(fast, sph, stats, rot), dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, io,
@@ -2012,7 +2050,7 @@ int32_t rayca_hip_probe_lookup_device(RaycaScene* s, const RaycaRenderOptions* o
           if (refill) {
             tl.ticket = 1u;
             HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
-            c->heads_clean = false;   // the next frame of this context clears them for itself
+            c->heads_clean &= ~FrameCtx::kCleanHeads;   // the next frame of this context clears them for itself
             launch_probe_refill(sph, stats, grid, sp.lds_bytes, stream, s->dev_full, io, c->heads, c->counters, tl);
           } else {
             hipLaunchKernelGGL(pick_probe_kernel(fast, sph, stats), dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, io, c->counters,

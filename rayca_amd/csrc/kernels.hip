@@ -88,6 +88,7 @@ struct GenArgs {
   float4* rgba32f;
   TraceCounters* counters;
   TraceLaunch tl;
+  uint32_t* clear;   // FUSED: the work-counter set this launch does not draw from (kCounterSetWords dwords), zeroed by block 0; or null
 };
 #if RAYCA_COLD_ARGS
 #define GEN_COLD(member) cold_arg<decltype(GenArgs::member)>((uint32_t)offsetof(GenArgs, member))
@@ -99,8 +100,17 @@ struct GenArgs {
 // back from LDS and writes the vertex's record; the bounce sampler with its double-precision libm_exact functions, surf_brdf, the
 // factor record, push_ray, the bounce counter and the fetch of the parked context are not compiled in.  The records are those the
 // general form writes for such a vertex: the same direct sum, kVertexLitNoIndirect, pb.brdf untouched.
+// FUSED: the kernel writes the pixel and no record -- `pb` is not read.  Flat (generation 0), and Path with GEN0 && LAST: the one-sample
+// depth-1 path frame, whose every lane ends in this launch.  A lane that finishes leaves the sum k_resolve would have folded for one
+// depth and sample 0 -- miss: black() + black(); emissive hit: black() + color; a vertex with all its samples in:
+// black() + (direct + black()), the `+ black()` terms being the reference's evaluation order (k_resolve) -- and the gamma + quantise +
+// store tail runs once per batch behind the loop, with the wave reconverged: whole 8 x 8 tile stores.  Path keeps that sum in the
+// parked direct sum's slot (park_sum_set), which a lane that ends without samples does not need: as a loop-carried value it would be
+// three more registers over trace().  The same launch zeroes the work-counter set it does not draw from (GenArgs.clear), for the
+// context's next frame: what k_resolve's clear did for a frame that has a k_resolve.
 template <int MODE, bool GEN0, bool ORDERED, bool FUSED, bool FAST, bool SPH, bool WIDE, bool SPILL, bool STATS, bool HALF, bool LAST>
 __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT : path_waves(STATS, SPH)) void k_generation(GenArgs a) {
+  static_assert(!FUSED || MODE == kModeFlat || (MODE == kModePath && GEN0 && LAST && !STATS), "FUSED: Flat, or the path frame's only generation on the last-vertex form");
   const TraceLaunch& tl = a.tl;
   uint32_t* const heads = a.heads;
   const uint32_t depth = a.depth;
@@ -118,6 +128,12 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
   uint32_t n_shaded = 0, n_shadow = 0, n_bounce = 0;
   const bool collect_emissive = GEN0 ? true : (GEN_COLD(fp).direct_sampler == RAYCA_SAMPLER_NONE);
   const uint32_t nee_lights = (MODE == kModePath && GEN_COLD(fp).direct_sampler == RAYCA_SAMPLER_NEE) ? GEN_COLD(sc).light_count : 0u;
+  if (FUSED && rc_bid() == 0) {
+    // the other counter set of the context: no wave of this launch reads it, and the passes of one context are ordered (the
+    // context-pass protocol), so whoever drew from it has retired and the next frame finds it zero without a fill launch
+    if (uint32_t* const clear = GEN_COLD(clear))
+      for (uint32_t i = rc_tid(); i < kCounterSetWords; i += kGenBlock) clear[i] = 0u;
+  }
 
   for (;;) {
     const uint32_t batch = next_batch(heads, total, home, wc, tl.ticket);
@@ -146,7 +162,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
         key = q.key;
       }
     }
-    const size_t slot = (size_t)depth * GEN_COLD(pb).npix + p;
+    const size_t slot = FUSED ? 0 : (size_t)depth * GEN_COLD(pb).npix + p;
     bool in_shadow = false;
     // shadow rays: the any-hit bound.  A point light's is its distance (a finite square root, never FLT_MAX); FLT_MAX
     // means "closest hit wanted": camera and bounce rays, and the shadow ray of a quad light (NeeSample.quad)
@@ -155,8 +171,8 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
     Color ns_x = black();  // the pending NEE sample's contribution if its light turns out to be visible   (PARK: park_sample)
     Color direct = black();  // sum of the direct samples so far                                           (PARK: park_sum_add)
     uint32_t li = 0, k = 0, dim = 0;
-    // FUSED (Flat only): a lane that finishes leaves its pixel sum in `direct`; the gamma + quantise + store tail runs
-    // once per batch with the wave reconverged, not inside the divergent state machine
+    // FUSED: a lane that finishes leaves its pixel sum in `direct` (Flat) or in the parked sum's slot (Path); the gamma + quantise +
+    // store tail runs once per batch with the wave reconverged, not inside the divergent state machine
     const bool has_pixel = live;
     // Path: a vertex whose direct samples are all in leaves the loop with `tail` set; its record, the bounce sample and the
     // next generation's ray are made behind the loop, with the wave reconverged -- so the bounce ray is not a loop-carried
@@ -170,7 +186,8 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
       const bool found = trace<ORDERED, FAST, SPH, WIDE, SPILL, STATS, HALF, kLeaveK, kSlackForm>(a.sc, ray, t_stop, stack, hit, cnt);
       if (!in_shadow) {
         if (!found) {
-          if (FUSED) direct = black() + black();  // unwrap_or(BLACK), color += it
+          if (FUSED && PARK) park_sum_reset<kGenBlock>(ctx_slot);  // black() + black(): +0.0f thrice and alpha 1, black()'s own bits
+          else if (FUSED) direct = black() + black();  // unwrap_or(BLACK), color += it
           else GEN_COLD(pb).state[slot] = kVertexNone;
           live = false;
         } else {
@@ -187,8 +204,12 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
             }
             live = false;
           } else if (collect_emissive && emissive) {  // pathtracer.rs:83-87
-            pb.direct[slot] = as_f4(color);
-            pb.state[slot] = kVertexEmissive;
+            if (FUSED && PARK) park_sum_set<kGenBlock>(ctx_slot, black() + color);
+            else if (FUSED) direct = black() + color;
+            else {
+              pb.direct[slot] = as_f4(color);
+              pb.state[slot] = kVertexEmissive;
+            }
             live = false;
           } else {
             in_shadow = true;  // enter the NEE loop (possibly empty)
@@ -257,7 +278,13 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
       }
     }
     if (FUSED) {
-      if (has_pixel) finalize_pixel(GEN_COLD(fp), direct, p, GEN_COLD(rgba8), GEN_COLD(rgba32f));
+      if (has_pixel) {
+        if (PARK) direct = unpark_sum<kGenBlock>(ctx_slot);
+        // the last vertex of a path (pathtracer.rs:89-93 with depth >= limit), folded as k_resolve folds one depth
+        if (MODE == kModePath && tail) direct = black() + (direct + black());
+        finalize_pixel(GEN_COLD(fp), direct, p, GEN_COLD(rgba8), GEN_COLD(rgba32f));
+      }
+      if (MODE == kModePath) n_shadow += (uint32_t)__popcll(__ballot(tail)) * nee_lights * GEN_COLD(fp).light_samples;
     } else if (MODE == kModePath && LAST) {
       // the last vertex of a path: its direct sum is its record (pathtracer.rs:89-93 with depth >= limit); the context stays parked
       if (tail) {
@@ -347,7 +374,7 @@ __global__ __launch_bounds__(kGenBlock, MODE == kModeFlat ? RAYCA_MIN_WAVES_FLAT
   }
   if (MODE == kModePath) {
     const unsigned long long s2 = n_shadow, b2 = n_bounce;  // already whole-wave sums
-    if (lane == 0 && (s2 | b2)) {
+    if ((FUSED ? lane_now() : lane) == 0 && (s2 | b2)) {
       TraceCounters* const counters = GEN_COLD(counters);
       atomicAdd(&counters->shadow, s2);
       if (!LAST) atomicAdd(&counters->bounce, b2);

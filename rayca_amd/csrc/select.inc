@@ -19,14 +19,16 @@ struct LaunchPlan {
 // the traversal loop (measured: +15 % frame time on the depth-1 path kernel), so production launches
 // use the instantiation without them
 
-// k_generation: every flavour; Flat is generation 0, fused (the kernel writes the pixel) or not; Path is never fused, and has a
-// last-vertex form (`last`: last_form below), which Flat does not read
+// k_generation: every flavour; Flat is generation 0, fused (the kernel writes the pixel) or not; Path has a last-vertex form
+// (`last`: last_form below), which Flat does not read, and is fused only as generation 0 on that form without the counters
+// (fuse_resolve below: the frame's only generation) -- every other Path tuple does not read `fused`
 using GenKernel = void (*)(GenArgs);
 GenKernel pick_kernel(int mode, bool gen0, bool fused, Trav t, bool sph, bool stats, bool last) {
   const bool flat = mode == kModeFlat;
-  return with_flavour([](auto T, auto FLAT, auto A, auto SPH, auto STATS, auto LAST) -> GenKernel {   // A: fused (Flat) / generation 0 (Path)
-    return k_generation<FLAT ? kModeFlat : kModePath, FLAT || A, T.ORDERED, FLAT && A, T.FAST, SPH, T.WIDE, T.SPILL, STATS, T.HALF, !FLAT && LAST>;
-  }, t, flat, flat ? fused : gen0, sph, stats, last);
+  return with_flavour([](auto T, auto FLAT, auto A, auto SPH, auto STATS, auto LAST, auto PF) -> GenKernel {   // A: fused (Flat) / generation 0 (Path); PF: fused (Path)
+    return k_generation<FLAT ? kModeFlat : kModePath, FLAT || A, T.ORDERED, (FLAT && A) || (!FLAT && A && LAST && !STATS && PF), T.FAST, SPH, T.WIDE, T.SPILL, STATS,
+                        T.HALF, !FLAT && LAST>;
+  }, t, flat, flat ? fused : gen0, sph, stats, last, !flat && fused);
 }
 
 // k_trace_rays: ignores HALF (caller-supplied rays traverse the f32 nodes): six distinct traversals
@@ -196,7 +198,8 @@ struct Knobs {
   uint32_t grid_mult;         // RAYCA_GRID_MULT: blocks per CU of the fused engine's persistent grids (experiments); 0 = what the kernel admits
   uint32_t ticket;            // RAYCA_TICKET: batches per work ticket of the fused engine; 0 = by the size of the frame
   uint32_t path_lds_entries;  // RAYCA_PATH_LDS_ENTRIES: LDS part of a path frame's node stack, clamped to 4..kMaxLdsEntries; 0 = by the kernel's waves
-  bool last_form;             // RAYCA_LAST_FORM=0: every generation of a path frame on k_generation's general form (A/B runs and tests); nothing else hangs on it
+  bool last_form;             // RAYCA_LAST_FORM=0: every generation of a path frame on k_generation's general form (A/B runs and tests); implies fuse_resolve off
+  bool fuse_resolve;          // RAYCA_FUSE_RESOLVE=0: the one-sample depth-1 path frame stays generation + k_resolve, two launches (A/B runs and tests)
 };
 const Knobs& knobs() {
   static const Knobs k = [] {
@@ -211,6 +214,7 @@ const Knobs& knobs() {
     n.ticket = (uint32_t)env("RAYCA_TICKET", 0);
     n.path_lds_entries = getenv("RAYCA_PATH_LDS_ENTRIES") ? std::min(std::max((uint32_t)env("RAYCA_PATH_LDS_ENTRIES", 0), 4u), kMaxLdsEntries) : 0u;
     n.last_form = env("RAYCA_LAST_FORM", 1) != 0;
+    n.fuse_resolve = n.last_form && env("RAYCA_FUSE_RESOLVE", 1) != 0;
     return n;
   }();
   return k;
@@ -245,6 +249,20 @@ bool last_form_rule(int mode, uint32_t direct_sampler, uint32_t max_depth, uint3
   return mode == kModePath && g >= limit;
 }
 bool last_form(int mode, const RaycaConfig& c, uint32_t g) { return knobs().last_form && last_form_rule(mode, c.direct_sampler, c.max_depth, g); }
+
+// Does a path frame's generation kernel write the pixel itself (k_generation's FUSED with GEN0 && LAST, kernels.hip), with no record
+// and no k_resolve?  A camera frame of the fused engine with one sample per pixel and one generation, that generation on the
+// last-vertex form, and not a counting frame: every lane's path then ends inside the one launch, and k_resolve would only read each
+// record once.  Counting frames keep the two launches (their instantiation is the one with the counters), and so do caller-supplied
+// rays, more samples, deeper paths, paths without a direct sampler, and the other engines.  fuse_resolve_rule is the arithmetic alone
+// (rayca_hip_selftest checks it), fuse_resolve adds the knobs.
+bool fuse_resolve_rule(int mode, bool wavefront, bool caller_rays, bool stats, uint32_t spp, uint32_t generations, uint32_t direct_sampler, uint32_t max_depth) {
+  return mode == kModePath && !wavefront && !caller_rays && !stats && spp == 1u && generations == 1u && last_form_rule(mode, direct_sampler, max_depth, 0u);
+}
+bool fuse_resolve(const LaunchPlan& plan, const RaycaConfig& c, bool caller_rays) {
+  return knobs().fuse_resolve && knobs().last_form &&
+         fuse_resolve_rule(plan.mode, plan.wavefront, caller_rays, plan.stats, c.samples_per_pixel, plan.generations, c.direct_sampler, c.max_depth);
+}
 
 // What plan_traversal reads of a scene.
 struct TreeFacts {
@@ -506,7 +524,10 @@ int32_t selftest_kernel_selection(std::string& err) {
   const PickerFamily families[] = {
       {"pick_kernel(trav; sph, stats, flat, gen0, fused, last)", all, 6,
        [&](Trav t, uint32_t i) { return P(pick_kernel(mode(b(i, 2)), b(i, 3), b(i, 4), t, b(i, 0), b(i, 1), b(i, 5))); },
-       [&](Trav t, uint32_t i) { return (uint32_t)t << 8 | (i & 7u) | ((b(i, 2) ? b(i, 4) : b(i, 3)) ? 8u : 0u) | (!b(i, 2) && b(i, 5) ? 16u : 0u); }},   // Flat reads neither gen0 nor last, Path not fused
+       [&](Trav t, uint32_t i) {   // Flat reads neither gen0 nor last; Path reads fused only as generation 0 on the last-vertex form without the counters
+         return (uint32_t)t << 8 | (i & 7u) | ((b(i, 2) ? b(i, 4) : b(i, 3)) ? 8u : 0u) | (!b(i, 2) && b(i, 5) ? 16u : 0u) |
+                (!b(i, 2) && b(i, 3) && b(i, 5) && !b(i, 1) && b(i, 4) ? 32u : 0u);
+       }},
       {"pick_trace_kernel(trav; sph, stats)", all, 2, [&](Trav t, uint32_t i) { return P(pick_trace_kernel(t, b(i, 0), b(i, 1))); },
        [&](Trav t, uint32_t i) { return (uint32_t)f32_of(t) << 8 | i; }},
       {"pick_query_kernel(trav; sph, stats, occluded)", all, 3, [&](Trav t, uint32_t i) { return P(pick_query_kernel(t, b(i, 0), b(i, 1), b(i, 2))); },
@@ -580,5 +601,24 @@ int32_t selftest_kernel_selection(std::string& err) {
       return RAYCA_ERR_BAD_ARG;
     }
   }
+  // fuse_resolve_rule: the path frames whose one launch writes the pixel
+  struct FuseCase { int mode; bool wavefront, caller_rays, stats; uint32_t spp, generations, direct_sampler, max_depth; bool fused; const char* what; };
+  const FuseCase fuse_cases[] = {
+      {kModePath, false, false, false, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, true, "the one-sample depth-1 frame under NEE (the bench frame)"},
+      {kModePath, false, false, true, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "a counting frame"},
+      {kModePath, false, false, false, 4u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "four samples per pixel"},
+      {kModePath, false, false, false, 1u, 2u, RAYCA_SAMPLER_NEE, 2u, false, "max_depth 2"},
+      {kModePath, false, false, false, 1u, 3u, RAYCA_SAMPLER_NEE, 3u, false, "max_depth 3"},
+      {kModePath, false, false, false, 1u, 1u, RAYCA_SAMPLER_NONE, 1u, false, "no direct sampler: generation 0 is on the general form"},
+      {kModePath, true, false, false, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "the wavefront engine"},
+      {kModePath, false, true, false, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "a caller's rays"},
+      {kModeGeneral, false, false, false, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "the stack machine"},
+      {kModeFlat, false, false, false, 1u, 1u, RAYCA_SAMPLER_NEE, 1u, false, "a Flat frame (fused by its own rule)"},
+  };
+  for (const FuseCase& c : fuse_cases)
+    if (fuse_resolve_rule(c.mode, c.wavefront, c.caller_rays, c.stats, c.spp, c.generations, c.direct_sampler, c.max_depth) != c.fused) {
+      err = std::string("fuse_resolve_rule: ") + c.what + (c.fused ? " must be fused" : " must not be fused");
+      return RAYCA_ERR_BAD_ARG;
+    }
   return RAYCA_OK;
 }

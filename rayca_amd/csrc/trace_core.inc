@@ -929,6 +929,13 @@ __device__ __forceinline__ uint32_t ctx_tid() {
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
   return l;
 }
+// The lane's number made where it is read, the same way: __lane_id() at the kernel's entry is one value for the whole kernel, which
+// the fused path form, with its pixel tail behind the loop, kept in scratch from the entry to the last counter's `lane == 0`.
+__device__ __forceinline__ uint32_t lane_now() {
+  uint32_t l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
 template <int STRIDE>
 __device__ __forceinline__ float4* ctx_quads(const CtxSlot& s) { return reinterpret_cast<float4*>(s.base) + ctx_tid<STRIDE>(); }
 template <int STRIDE>
@@ -985,6 +992,18 @@ __device__ __forceinline__ void park_sum_reset(const CtxSlot& s) {
   words[5 * STRIDE] = zero;
 #else
   ctx_quads<STRIDE>(s)[6 * STRIDE] = make_float4(zero, zero, zero, 1.0f);
+#endif
+}
+// park_sum_set: the sum = c, whose alpha is 1 (black() + x): the fused path frame's pixel sum of a lane that ends without samples
+template <int STRIDE = kBlock>
+__device__ __forceinline__ void park_sum_set(const CtxSlot& s, Color c) {
+#if RAYCA_CTX_COMPACT
+  float* const words = ctx_words<STRIDE>(s);
+  words[3 * STRIDE] = c.r;
+  words[4 * STRIDE] = c.g;
+  words[5 * STRIDE] = c.b;
+#else
+  ctx_quads<STRIDE>(s)[6 * STRIDE] = make_float4(c.r, c.g, c.b, c.a);
 #endif
 }
 // park_sample: the contribution the pending sample makes if its light turns out to be visible
@@ -1198,6 +1217,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 // when there are fewer batches than resident waves (a rank's share of a frame on eight GPUs): pairs would then
 // leave half the waves without work and double the time of the others.
 constexpr uint32_t kHeadStride = 64;
+constexpr uint32_t kCounterSetWords = 8u * kHeadStride;   // one set of work counters: what a fused k_generation launch zeroes of the other set
 struct WorkCursor {   // (an aggregate: `WorkCursor wc{};`)
   uint32_t exhausted;  // partitions found empty so far
   uint32_t next, end;  // batches of the current ticket still to do
