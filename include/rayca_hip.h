@@ -54,7 +54,9 @@ extern "C" {
                                   rayca_hip_film_fold_device;
                                   irradiance gathering: RaycaGather, rayca_hip_gather_device;
                                  irradiance volumes: RaycaProbeLookup, rayca_hip_probe_lookup_device;
-                                  signed distance and occupancy: RaycaSigned, rayca_hip_signed_device, RAYCA_SIGNED_ */
+                                  signed distance and occupancy: RaycaSigned, rayca_hip_signed_device, RAYCA_SIGNED_;
+                                  surface sampling: RaycaSurfaceCdf, rayca_hip_surface_cdf_device, RaycaSurfaceSample,
+                                  rayca_hip_surface_sample_device */
 #define RAYCA_NONE 0xFFFFFFFFu /* Handle::NONE, rayca-util/src/pack.rs:61-64 */
 
 /* ---- status codes -------------------------------------------------------------------------- */
@@ -727,6 +729,97 @@ struct RaycaNearest {
 typedef struct RaycaNearest RaycaNearest;
 int32_t rayca_hip_nearest_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaNearest* query,
                                  RaycaStats* stats_out);
+
+/* Surface sampling on DEVICE memory: area-weighted random points on the scene's triangles -- training points for distance
+ * fields (perturbed, into rayca_hip_signed_device), point clouds for Chamfer and Hausdorff distances (into
+ * rayca_hip_nearest_device), the points and normals an occlusion or irradiance bake runs over (rayca_hip_ambient_device,
+ * rayca_hip_gather_device), probe placement.  Two calls: rayca_hip_surface_cdf_device turns the slots' areas into a table of
+ * exact integer prefix sums, rayca_hip_surface_sample_device draws from such a table.  A handle's geometry never changes
+ * (rayca_hip_scene_update refuses every edit that moves it), so a table stays valid for as long as its handle lives.  No
+ * reference counterpart.  Neither call traverses anything; tables, seeds' samples and results stay on the device and both
+ * calls are asynchronous on the caller's stream.
+ *
+ * The specification, in f32 with every operation rounded on its own and in the association written here; behind the weight
+ * everything is integer arithmetic, and no result depends on an order of execution, so a literal restatement
+ * (tests/sample_literal.py) gives the same words.  T = the number of triangle slots.
+ *   Candidates: every triangle slot of the scene (post-build primitive order; the two triangles of a quad light count, as they
+ *   do for nearest points).  A scene with spheres is refused: RAYCA_ERR_UNSUPPORTED.
+ *   Area of slot i, with a, b, c = the slot's world-space vertices 0, 1, 2:
+ *     ab = b - a, ac = c - a                                                             (componentwise)
+ *     n = (ab.y*ac.z - ab.z*ac.y, ab.z*ac.x - ab.x*ac.z, ab.x*ac.y - ab.y*ac.x)
+ *     a2 = (n.x*n.x + n.y*n.y) + n.z*n.z
+ *     area_i = sqrt(a2), correctly rounded: the build's sqrtf, which the compiler lowers to its correctly rounded f32 square
+ *     root (its default for HIP; __fsqrt_rn of this toolchain is the approximate native instruction and is NOT used).  This is
+ *     twice the triangle's area; the common factor changes no share.
+ *     area_i counts as 0 if it is NaN or +inf (vertices whose products overflow), and if include[i] == 0.
+ *   Weights: amax = the largest area_i, found as an integer maximum over the floats' bits (non-negative floats order as their
+ *   bits do) -- the only atomic in either call.  With amax = m * 2^e, 0.5 <= m < 1:
+ *     w_i = (uint32) floor(area_i * 2^(32 - e)).  The factor is an f32: an area that counts is the root of an a2 >= 2^-149, so
+ *     2^-75 <= amax <= FLT_MAX and -96 <= 32 - e <= 106 (the kernel applies it as an exponent shift, ldexpf: the same product).
+ *     area_i <= amax < 2^e, so w_i < 2^32.  The product is exact unless it underflows, and then the
+ *     result is below 1 and w_i = 0: A TRIANGLE WHOSE AREA IS BELOW 2^-32 OF THE LARGEST HAS WEIGHT 0 AND IS NEVER DRAWN; every
+ *     other weight is its area's share of amax to 2^-32 absolute.  amax = 0 (no area counts) makes every weight 0.
+ *   Table: cdf_out[0] = 0, cdf_out[i + 1] = cdf_out[i] + w_i as uint64 -- an exact prefix sum in slot order, formed without
+ *   atomics.  T <= 2^25 slots of weights below 2^32: every entry is below 2^57.
+ *   Sample j (0 <= j < count) of a table cdf, with W(key, d) = the 32-bit hash word rng_f32 takes its mantissa from
+ *   (rayca_math.hpp rng_word):
+ *     key = rng_root(seed, (first_index + j) mod 2^32, sample)       the stream RaycaRadiance names the same way
+ *     r = W(key, 0) * 2^32 + W(key, 1), total = cdf[T]
+ *     target = floor(r * total / 2^64)                               the high half of the 128-bit product; < total
+ *     prim = the slot i with cdf[i] <= target < cdf[i + 1]: it exists and is unique when total > 0, and its weight is not 0
+ *     s0 = rng_f32(key, 2), t0 = rng_f32(key, 3)                     multiples of 2^-23 in [0, 1)
+ *     if s0 + t0 > 1: s = 1 - s0, t = 1 - t0; else s = s0, t = t0
+ *     Every one of these operations is exact: s0 + t0 is a multiple of 2^-23 below 2 and 1 - s0 one in (0, 1], each of at most
+ *     24 significant bits; so is (1 - s) - t below, which lies in [0, 1] because s + t <= 1.  Hence s, t >= 0, s + t <= 1, and
+ *     the fold maps the upper half of the unit square onto the lower: (s, t) is uniform over the triangle's 2^-23 lattice.
+ *     prim_out[j]   = prim
+ *     uv_out[j]     = ((1 - s) - t, s): the weights of vertex 0 and vertex 1, the convention of hit records, so that prim_out /
+ *                     uv_out go to rayca_hip_surface_device as they are (colour, material, flags; no rays needed)
+ *     point_out[j]  = (a + ab*s) + ac*t componentwise, as rayca_hip_nearest_device forms q
+ *     normal_out[j] = (n.x / l, n.y / l, n.z / l), l = sqrt(a2): the geometric normal in winding order (a drawn slot has
+ *                     0 < l < +inf)
+ *     total == 0 makes every sample a miss: prim = RAYCA_NONE, zeros elsewhere.
+ *   Consequences: sample j does not depend on count; any split of a sample set into consecutive calls, each with the
+ *   first_index of its first sample, writes what one call writes.
+ *   `cdf` need not come from rayca_hip_surface_cdf_device: any T + 1 non-decreasing uint64 with cdf[0] = 0 weighs the slots
+ *   (per material, by a texture's importance); with an entry that decreases the slot drawn is unspecified but in range.
+ * Not offered: stratified or systematic draws (target = (j + xi) * total / count needs a 128-bit quotient per sample, and the
+ * draws are no longer independent of count); a table per model (include masks do that: one byte per slot); spheres.
+ * opts (may be NULL) for both calls: stream (NULL => the context's own stream, and the call waits for it), context,
+ * wait_event, record_event as for rayca_hip_nearest_device; collect_stats is accepted and counts nothing; traversal, tile,
+ * engine and camera_rays must be zero.  Ordered on their context like a query.  With stats_out the call waits: the kernels'
+ * time under RAYCA_KERNEL_OTHER, kernel_launches = 3 for the table (the maximum, the weights, the one-block scan) and 1 for a
+ * draw, every rays_* field 0.  The table call keeps one scratch word on its context.  count == 0 is RAYCA_OK and launches
+ * nothing; nothing outside [0, count) of an output, or [0, T] of cdf_out, is written.
+ * RAYCA_ERR_BAD_ARG, before any GPU work and before the scene is looked at, in this order --
+ *   table: NULL scene / arguments, non-zero reserved, non-zero flags, NULL cdf_out, cdf_out not 8-byte aligned;
+ *   draw:  NULL scene / arguments, non-zero reserved, NULL cdf, cdf not 8-byte aligned, no output;
+ * then context > 7, a non-zero field of opts that does not apply.  Then (the draw: for count != 0) RAYCA_ERR_EMPTY_SCENE as the
+ * query, and last RAYCA_ERR_UNSUPPORTED for a scene with spheres. */
+struct RaycaSurfaceCdf {
+  const void* include;  /* DEVICE: T u8, 0 = the slot has area 0; or NULL => every slot */
+  void* cdf_out;        /* DEVICE: (T + 1) u64, 8-byte aligned, required */
+  uint32_t flags;       /* must be zero */
+  uint32_t reserved;    /* must be zero */
+};
+typedef struct RaycaSurfaceCdf RaycaSurfaceCdf;
+int32_t rayca_hip_surface_cdf_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaSurfaceCdf* table,
+                                     RaycaStats* stats_out);
+struct RaycaSurfaceSample {
+  uint32_t count;
+  uint32_t seed;         /* as RaycaConfig.seed */
+  uint32_t sample;       /* RNG stream of the draws, as RaycaRadiance.sample */
+  uint32_t first_index;  /* the index of sample 0; first_index + j wraps at 2^32 */
+  const void* cdf;       /* DEVICE: (T + 1) u64, 8-byte aligned, required */
+  void* prim_out;        /* DEVICE: count u32 slot (post-build primitive order), RAYCA_NONE on a miss; any of the four may be NULL, not all */
+  void* uv_out;          /* DEVICE: count x 2 f32 in the convention of hit records, 0 on a miss */
+  void* point_out;       /* DEVICE: count x 3 f32, 0 on a miss */
+  void* normal_out;      /* DEVICE: count x 3 f32, unit length, 0 on a miss */
+  uint32_t reserved;     /* must be zero (4 bytes of padding follow) */
+};
+typedef struct RaycaSurfaceSample RaycaSurfaceSample;
+int32_t rayca_hip_surface_sample_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaSurfaceSample* draw,
+                                        RaycaStats* stats_out);
 
 /* Multi-hit ray queries on DEVICE memory: for `count` caller-supplied rays the first k hits along each ray, in order, or the
  * number of all of them -- thickness and transmission through layers, crossing counts, picking through a surface, x-ray and

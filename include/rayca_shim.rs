@@ -334,6 +334,32 @@ pub struct RaycaNearest {
     pub within_out: *mut c_void,
 }
 
+// rayca_hip_surface_cdf_device: the mask and the table in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaSurfaceCdf {
+    pub include: *const c_void,
+    pub cdf_out: *mut c_void,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+// rayca_hip_surface_sample_device: the table and the results in DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaSurfaceSample {
+    pub count: u32,
+    pub seed: u32,
+    pub sample: u32,
+    pub first_index: u32,
+    pub cdf: *const c_void,
+    pub prim_out: *mut c_void,
+    pub uv_out: *mut c_void,
+    pub point_out: *mut c_void,
+    pub normal_out: *mut c_void,
+    pub reserved: u32,
+}
+
 // rayca_hip_hits_device: rays, bounds and results in DEVICE memory; entry j of ray i at index i * k + j
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -748,6 +774,8 @@ extern "C" {
     pub fn rayca_hip_trace_rays(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, count: u32, rays: *const f32, t_out: *mut f32, prim_out: *mut u32, uv_out: *mut f32, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_query_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaQuery, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_nearest_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaNearest, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_surface_cdf_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, table: *const RaycaSurfaceCdf, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_surface_sample_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, draw: *const RaycaSurfaceSample, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_hits_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaHits, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_signed_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, query: *const RaycaSigned, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_ambient_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, ambient: *const RaycaAmbient, stats_out: *mut RaycaStats) -> i32;

@@ -323,6 +323,32 @@ class RaycaNearest(C.Structure):
     ]
 
 
+class RaycaSurfaceCdf(C.Structure):
+    """rayca_hip_surface_cdf_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("include", C.c_void_p),
+        ("cdf_out", C.c_void_p),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class RaycaSurfaceSample(C.Structure):
+    """rayca_hip_surface_sample_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("seed", C.c_uint32),
+        ("sample", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("cdf", C.c_void_p),
+        ("prim_out", C.c_void_p),
+        ("uv_out", C.c_void_p),
+        ("point_out", C.c_void_p),
+        ("normal_out", C.c_void_p),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class RaycaHits(C.Structure):
     """rayca_hip_hits_device: every pointer is DEVICE memory."""
     _fields_ = [
@@ -785,6 +811,10 @@ def bind_product_signatures(lib):
     lib.rayca_hip_query_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaQuery), P(RaycaStats)]
     lib.rayca_hip_nearest_device.restype = C.c_int32
     lib.rayca_hip_nearest_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaNearest), P(RaycaStats)]
+    lib.rayca_hip_surface_cdf_device.restype = C.c_int32
+    lib.rayca_hip_surface_cdf_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceCdf), P(RaycaStats)]
+    lib.rayca_hip_surface_sample_device.restype = C.c_int32
+    lib.rayca_hip_surface_sample_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaSurfaceSample), P(RaycaStats)]
     lib.rayca_hip_hits_device.restype = C.c_int32
     lib.rayca_hip_hits_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaHits), P(RaycaStats)]
     lib.rayca_hip_signed_device.restype = C.c_int32
@@ -840,6 +870,7 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_scene_create", "rayca_hip_scene_destroy", "rayca_hip_scene_reap", "rayca_hip_scene_info", "rayca_hip_scene_finish", "rayca_hip_scene_update",
     "rayca_hip_render",
     "rayca_hip_render_device", "rayca_hip_tile_rows", "rayca_hip_trace_rays", "rayca_hip_query_device", "rayca_hip_nearest_device", "rayca_hip_hits_device",
+    "rayca_hip_surface_cdf_device", "rayca_hip_surface_sample_device",
     "rayca_hip_signed_device",
     "rayca_hip_ambient_device",
     "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_probe_lookup_device", "rayca_hip_denoise_device",

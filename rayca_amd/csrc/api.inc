@@ -85,7 +85,7 @@ struct FrameCtx {
   DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
   DeviceBuffer probe_mask;            // rayca_hip_probe_lookup_device with visibility and without mask_out: the same, 4 B a point
   DeviceBuffer plan_weight;           // rayca_hip_sample_plan_device without weight_out: the weights its offsets kernel reads back (4 B a pixel)
-  DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment)
+  DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment); rayca_hip_surface_cdf_device: its first word is the largest area's bits
   DeviceBuffer gather_samples;        // rayca_hip_gather_device without samples_out: the radiance records of one internal frame (16 B a ray)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   // Which of the context's counters are known to be zero, a bit each: the first work-counter set, the second, the two queue
@@ -1679,6 +1679,97 @@ int32_t rayca_hip_nearest_device(RaycaScene* s, const RaycaRenderOptions* opts_i
   stats_out->boxes_tested = tc.boxes;
   stats_out->triangles_tested = tc.tris;
   return RAYCA_OK;
+}
+
+// What a surface-sampling call refuses of a scene, behind everything its structs decide: nothing to sample, or spheres.
+int32_t refuse_unsampled_scene(const RaycaScene* s) {
+  if (const int32_t rc = refuse_empty_scene(s); rc != RAYCA_OK) return rc;
+  if (s->host.sphere_count != 0)
+    return fail(RAYCA_ERR_UNSUPPORTED, "a scene with spheres has no surface sampling: the table weighs triangle slots, and the area of a sphere under a non-uniform scale has no closed form");
+  return RAYCA_OK;
+}
+
+// The cumulative area table of a scene's slots (sample.inc): k_cdf_amax -> k_cdf_weights -> k_cdf_scan (one block), each behind
+// the other on the pass's stream.  The one scratch word -- the largest area's bits -- is the first of the context's plan_sums,
+// cleared on the launch stream in front of the first kernel.  Only the primitive records are read, which every scene has from
+// scene_create on, so the call never waits for the formats thread.
+int32_t rayca_hip_surface_cdf_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSurfaceCdf* cin, RaycaStats* stats_out) {
+  if (!s || !cin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaSurfaceCdf");
+  const RaycaSurfaceCdf& a = *cin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceCdf.reserved must be zero");
+  if (a.flags != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceCdf.flags must be zero");
+  if (!a.cdf_out) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceCdf.cdf_out: null cdf_out");
+  if (reinterpret_cast<uintptr_t>(a.cdf_out) & 7u) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceCdf.cdf_out: alignment: the table is written 8 bytes an entry");
+  int32_t rc = pass_options(o, "a surface-table call", kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  if ((rc = refuse_unsampled_scene(s)) != RAYCA_OK) return rc;
+  SurfaceCdfIo io{};
+  io.include = static_cast<const uint8_t*>(a.include);
+  io.cdf = static_cast<unsigned long long*>(a.cdf_out);
+  const uint32_t slots = s->prim_count, grid = (slots + kBlock - 1u) / kBlock;   // (slots <= 2^25)
+  return run_pass(
+      s, o, stats_out,
+      [&](FrameCtx* c) -> int32_t {
+        HIP_TRY(hipSetDevice(s->device));
+        return grow_behind_pass(c, c->plan_sums, sizeof(uint32_t));
+      },
+      [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+        io.amax = static_cast<uint32_t*>(s->ctx[o.context].plan_sums.ptr);
+        const DevScene& dev = formats_ready(s) ? s->dev_full : s->dev;
+        HIP_TRY(hipMemsetAsync(io.amax, 0, sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_cdf_amax, dim3(grid), dim3(kBlock), 0, stream, dev, io);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        hipLaunchKernelGGL(k_cdf_weights, dim3(grid), dim3(kBlock), 0, stream, dev, io);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        hipLaunchKernelGGL(k_cdf_scan, dim3(1), dim3(kCdfScanBlock), 0, stream, io.cdf + 1, slots);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        return RAYCA_OK;
+      });
+}
+
+// Samples drawn from such a table (sample.inc k_sample_surface): one sample per lane, one launch, no scratch.
+int32_t rayca_hip_surface_sample_device(RaycaScene* s, const RaycaRenderOptions* opts_in, const RaycaSurfaceSample* sin, RaycaStats* stats_out) {
+  if (!s || !sin) return fail(RAYCA_ERR_BAD_ARG, "null scene or RaycaSurfaceSample");
+  const RaycaSurfaceSample& a = *sin;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (a.reserved != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceSample.reserved must be zero");
+  if (!a.cdf) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceSample.cdf: null cdf");
+  if (reinterpret_cast<uintptr_t>(a.cdf) & 7u) return fail(RAYCA_ERR_BAD_ARG, "RaycaSurfaceSample.cdf: alignment: the table is read 8 bytes an entry");
+  if (!a.prim_out && !a.uv_out && !a.point_out && !a.normal_out)
+    return fail(RAYCA_ERR_BAD_ARG, "no output for this surface-sampling call: RaycaSurfaceSample.prim_out, uv_out, point_out and normal_out are all null");
+  int32_t rc = pass_options(o, "a surface-sampling call", kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  if (a.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_unsampled_scene(s)) != RAYCA_OK) return rc;
+  SurfaceSampleIo io{};
+  io.cdf = static_cast<const unsigned long long*>(a.cdf);
+  io.count = a.count;
+  io.seed = a.seed;
+  io.sample = a.sample;
+  io.first_index = a.first_index;
+  io.prim_out = static_cast<uint32_t*>(a.prim_out);
+  io.uv_out = static_cast<float*>(a.uv_out);
+  io.point_out = static_cast<float*>(a.point_out);
+  io.normal_out = static_cast<float*>(a.normal_out);
+  const uint32_t grid = (uint32_t)(((uint64_t)a.count + kBlock - 1u) / kBlock);
+  return run_pass(s, o, stats_out, [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+    hipLaunchKernelGGL(pick_sample_kernel(io.point_out || io.normal_out), dim3(grid), dim3(kBlock), 0, stream,
+                       formats_ready(s) ? s->dev_full : s->dev, io);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    return RAYCA_OK;
+  });
 }
 
 // What RaycaHits alone decides, in the header's order; the first rule broken is the one reported.  No scene, no device.

@@ -18,6 +18,9 @@
 //   k_camera_rays     (surface.inc: rayca_hip_surface_device, rayca_hip_camera_rays_device).
 //   k_nearest         nearest-point queries: the closest surface point to points in device memory, within a radius
 //                     (nearest.inc: rayca_hip_nearest_device).
+//   k_cdf_*,          surface sampling: the slots' areas into integer weights and their exact prefix sums, and area-weighted points
+//   k_sample_surface  on the triangles drawn from that table (sample.inc: rayca_hip_surface_cdf_device,
+//                     rayca_hip_surface_sample_device).
 //   k_hits            multi-hit ray queries: the first k hits along rays in device memory, in order, or their number
 //                     (hits.inc: rayca_hip_hits_device).
 //   k_signed          signed distance and occupancy: the nearest surface point of points or grid points in device memory and a
@@ -501,6 +504,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "wavefront.inc"
 #include "surface.inc"
 #include "nearest.inc"
+#include "sample.inc"
 #include "hits.inc"
 #include "signed.inc"
 #include "ambient.inc"

@@ -259,8 +259,10 @@ RC_FN uint32_t rng_mix(uint32_t h) {
 RC_FN uint32_t rng_hash2(uint32_t a, uint32_t b) { return rng_mix(a * 0x9E3779B1u + rng_mix(b + 0x7F4A7C15u)); }
 RC_FN uint32_t rng_root(uint32_t seed, uint32_t pixel, uint32_t sample) { return rng_hash2(rng_hash2(seed, pixel), sample); }
 RC_FN uint32_t rng_child(uint32_t key, uint32_t k) { return rng_hash2(key, k + 1u); }
+// the 32-bit word of dimension `dim` of a key's stream: rng_f32 keeps its top 23 bits, the surface sampler two whole words
+RC_FN uint32_t rng_word(uint32_t key, uint32_t dim) { return rng_hash2(key ^ 0xA511E9B3u, dim); }
 RC_FN float rng_f32(uint32_t key, uint32_t dim) {
-  const uint32_t u = rng_hash2(key ^ 0xA511E9B3u, dim);
+  const uint32_t u = rng_word(key, dim);
   const uint32_t bits = 0x3F800000u | (u >> 9);
 #if defined(__HIP_DEVICE_COMPILE__)
   return __uint_as_float(bits) - 1.0f;

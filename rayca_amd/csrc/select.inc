@@ -86,6 +86,12 @@ NearestKernel pick_nearest_kernel(bool within, bool cull, bool spill, bool stats
   return with_flags([](auto WITHIN, auto CULL, auto SPILL, auto STATS) -> NearestKernel { return k_nearest<WITHIN && CULL, CULL, SPILL, STATS>; }, within, cull, spill, stats);
 }
 
+// k_sample_surface (sample.inc): no traversal.  geom: point_out or normal_out is given, the drawn slot's record is read
+using SampleKernel = void (*)(DevScene, SurfaceSampleIo);
+SampleKernel pick_sample_kernel(bool geom) {
+  return with_flags([](auto GEOM) -> SampleKernel { return k_sample_surface<GEOM>; }, geom);
+}
+
 // k_hits (hits.inc): ORDERED and FAST of the flavour on the binary f32 nodes with the spill path, as pick_query_kernel -- so
 // kTravExact, kTravExactAll and kTravFastAll have a form of their own and every other flavour is kTravFastSpill's
 using HitsKernel = void (*)(DevScene, HitsIo, TraceCounters*, TraceLaunch);
@@ -540,6 +546,7 @@ int32_t selftest_kernel_selection(std::string& err) {
       {"pick_surface_kernel(sph)", none, 1, [&](Trav, uint32_t i) { return P(pick_surface_kernel(b(i, 0))); }, every},
       {"pick_nearest_kernel(within, cull, spill, stats)", none, 4, [&](Trav, uint32_t i) { return P(pick_nearest_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
        [&](Trav, uint32_t i) { return b(i, 1) ? i : i & ~1u; }},   // the exhaustive form does not read within
+      {"pick_sample_kernel(geom)", none, 1, [&](Trav, uint32_t i) { return P(pick_sample_kernel(b(i, 0))); }, every},
       {"pick_hits_kernel(trav; sph, stats, both, count_all)", all, 4, [&](Trav t, uint32_t i) { return P(pick_hits_kernel(t, b(i, 0), b(i, 1), b(i, 2), b(i, 3))); },
        [&](Trav t, uint32_t i) { return (uint32_t)query_of(t) << 8 | i; }},
       {"pick_signed_kernel(near, cull, grid, fast, stats)", none, 5,

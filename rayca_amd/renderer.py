@@ -64,6 +64,7 @@ class DeviceScene:
         if getattr(self, "handle", None):
             self._lib.rayca_hip_scene_destroy(self.handle)
             self.handle = None
+            self._surface_cdf_all = None   # (sample_surface's table of all slots)
 
     __del__ = close
 
@@ -281,6 +282,91 @@ class DeviceScene:
         if stats is None:
             return result
         return (result, stats) if within else (*result, stats)
+
+    # ---- surface sampling: area-weighted points on the triangles (rayca_hip_surface_cdf_device, rayca_hip_surface_sample_device) ----
+    SAMPLE_OUTPUTS = {"prim": ("int32", 0), "uv": ("float32", 2), "point": ("float32", 3), "normal": ("float32", 3)}
+
+    def _slots(self) -> int:
+        """the number of primitive slots (fixed for the handle)"""
+        if "_slot_count" not in self.__dict__:
+            i = self.info()
+            self._slot_count = i["triangle_count"] + i["sphere_count"]
+        return self._slot_count
+
+    def surface_cdf(self, include=None, *, stream=None, context=0, out=None, want_stats=False):
+        """rayca_hip_surface_cdf_device: the cumulative area table sample_surface() draws from, in device memory, asynchronously.
+
+        include: None (every slot) or a (T,) uint8 / bool torch tensor on this scene's device, T the number of primitive slots;
+        a slot whose byte is 0 gets area 0 and is never drawn.  Returns an int64 (T + 1,) tensor: 0, then the running sums of the
+        slots' integer weights (the largest area weighs just under 2**32, every sum stays below 2**57); its last entry is 0 iff
+        nothing can be drawn.  The table depends on the handle's geometry alone, which never changes.  `out`: the tensor to
+        write instead of a new one.  Scenes with spheres are refused (ERR_UNSUPPORTED).  Stream handling as query();
+        `want_stats` waits and returns (table, stats)."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        slots = self._slots()
+        a = abi.RaycaSurfaceCdf()
+        table = call.output(out, "out", torch.int64, (slots + 1,))
+        a.cdf_out = table.data_ptr()
+        if include is not None:
+            if isinstance(include, torch.Tensor) and include.dtype == torch.bool:
+                include = include.view(torch.uint8)   # (one byte an element, 0 / 1)
+            a.include = call.input(include, "include", torch.uint8, (slots,)).data_ptr()
+        stats = call.run(self._lib.rayca_hip_surface_cdf_device, a, context=context, want_stats=want_stats)
+        return table if stats is None else (table, stats)
+
+    def sample_surface(self, n, *, cdf=None, seed=0, sample=0, first_index=0, want=("prim", "uv", "point", "normal"), out=None,
+                       stream=None, context=0, want_stats=False):
+        """rayca_hip_surface_sample_device: `n` area-weighted random points on the scene's triangles, in device memory,
+        asynchronously.
+
+        cdf: a table from surface_cdf() (or any int64 (T + 1,) tensor of non-decreasing sums that starts at 0); None uses the
+        table of all slots, which is made on first use -- that one call waits for it -- and kept on the handle.  Sample j draws
+        from the stream of (seed, first_index + j, sample), as radiance() names a ray's: it does not depend on n, and chunks with
+        the first_index of their first sample give what one call gives.  Returns a dict with one tensor per name in `want`: prim
+        (n,) int32 holding the u32 primitive slot (abi.NONE, i.e. -1, when the table's total is 0), uv (n, 2) float32 in the
+        convention of hit records -- prim and uv go to surface() as they are, rays=None -- point (n, 3) float32 and normal
+        (n, 3) float32, the unit geometric normal in winding order; zeros on a miss.  `out`: a dict of tensors to write instead
+        of new ones.  Scenes with spheres are refused (ERR_UNSUPPORTED).  Stream handling as query(); `want_stats` waits and
+        adds "stats"."""
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 0xFFFFFFFF:
+            raise ValueError(f"n: an int in 0 .. 2**32 - 1 is expected, not {n!r}")
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.SAMPLE_OUTPUTS]
+        if unknown or not want or len(set(want)) != len(want):
+            raise ValueError(f"want: a non-empty selection without repeats of {tuple(self.SAMPLE_OUTPUTS)}, not {want!r}")
+        for name, v in (("seed", seed), ("sample", sample), ("first_index", first_index)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"{name}: an int in 0 .. 2**32 - 1 is expected, not {v!r}")
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        slots = self._slots()
+        a = abi.RaycaSurfaceSample()
+        a.count, a.seed, a.sample, a.first_index = n, seed, sample, first_index
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in want]
+        if stray:
+            raise ValueError(f"out: {stray} not in want")
+        result = {}
+        for name in want:
+            dtype, width = self.SAMPLE_OUTPUTS[name]
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), (n, width) if width else (n,))
+            setattr(a, name + "_out", result[name].data_ptr() or None)
+        if cdf is None:
+            if self.__dict__.get("_surface_cdf_all") is None:   # (made once: the call waits, so every later stream may read it)
+                self._surface_cdf_all = self.surface_cdf(stream=stream, context=context, want_stats=True)[0]
+            cdf = self._surface_cdf_all
+        a.cdf = call.input(cdf, "cdf", torch.int64, (slots + 1,)).data_ptr()
+        stats = None
+        if n:   # (an empty batch has no device pointers to hand over; the native call would launch nothing either)
+            stats = call.run(self._lib.rayca_hip_surface_sample_device, a, context=context, want_stats=want_stats)
+        elif context >= 8:
+            raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+        elif want_stats:
+            stats = abi.RaycaStats().as_dict()
+        if stats is not None:
+            result["stats"] = stats
+        return result
 
     # ---- multi-hit queries: the first k hits along a ray, in order (rayca_hip_hits_device) ----
     HITS_OUTPUTS = {"t": ("float32", 0), "prim": ("int32", 0), "uv": ("float32", 2), "face": ("uint8", 0), "n": ("int32", None)}
