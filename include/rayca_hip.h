@@ -1299,6 +1299,98 @@ typedef struct RaycaProbeLookup RaycaProbeLookup;
 int32_t rayca_hip_probe_lookup_device(RaycaScene* scene, const RaycaRenderOptions* opts, const RaycaProbeLookup* lookup,
                                       RaycaStats* stats_out);
 
+/* Direct light at points on DEVICE memory: the light that arrives at `count` caller-supplied points straight from the scene's point
+ * and quad lights -- the next-event-estimation sum of a path vertex (sampler/nee.rs:72-166) with the BRDF taken out, for points
+ * that are no path vertices: the points of rayca_hip_surface_sample_device, mesh vertices, lightmap texels, the centres of a probe
+ * grid, a G-buffer.  rayca_hip_gather_device never sees a point light (a hemisphere ray hits surfaces, not points); this call is
+ * the other half of a bake.  The shadow rays are made in registers inside the traversal kernel: no ray buffer, no per-sample
+ * intermediate.  Asynchronous on the caller's stream.
+ *
+ * The specification, in f32 with every operation rounded on its own.  Vectors are (x, y, z); dot(a, b) is
+ * (((-0.0f + a.x * b.x) + a.y * b.y) + a.z * b.z) + 0.0f, the ordered four-lane sum of rayca-math with a zero w lane;
+ * |a|^2 = dot(a, a), |a| = sqrt(|a|^2); normalized(a) = a / |a| per component when |a| > 2^-10, else a itself.  A light is the
+ * record rayca_hip_scene_read_lights returns (position: the translation of the light's node-LOCAL transform, as the reference).
+ *   Samples.  Sample j = (li - light_first) * light_samples + k for li in [light_first, light_first + light_count) and
+ *   k < cfg->light_samples; N = light_count * light_samples must be 1 .. 64, one bit of the mask word each.  Callers with more
+ *   lights chunk over light ranges: a sample does not depend on the range it is asked in.
+ *   Modes.  With normals (hemisphere mode): o = p + n * bias per component (one multiply, one add); bias = 1e-4f, the reference's
+ *   ray bias, reproduces a path vertex.  A point is inactive iff n.x == 0 && n.y == 0 && n.z == 0, or any of the six values is not
+ *   finite (RaycaAmbient's rule).  Without normals (sphere mode): o = p, bias must be 0, and a point is inactive iff a coordinate
+ *   is not finite.
+ *   Point light (kind RAYCA_LIGHT_POINT), with x1 = position:
+ *     v      = x1 - p                        dist = |v|        omega = normalized(v)
+ *     w      = p - x1                        r2 = |w|^2        rr = sqrt(r2)
+ *     fallof = (((-0.0f + att[0] * 1.0f) + att[1] * rr) + att[2] * r2) + 0.0f
+ *     le     = (intensity * color.rgb) / fallof            alpha = color.a
+ *     d_omega = 1.0f / |v|^2
+ *   (le carries the reference's own 1 / fallof and d_omega its extra 1 / r^2).
+ *   Quad light (any other kind that is served), with key = rng_root(cfg->seed, (first_index + i) mod 2^32, sample) -- the stream
+ *   RaycaRadiance and RaycaSurfaceSample name -- and the random dimension D = 2 * (q(li) * light_samples + k), q(li) the number of
+ *   quad lights of the WHOLE scene with an index below li (where a path vertex's dimension stands: with first_index + i a pixel
+ *   index the draws are that pixel's generation-0 draws):
+ *     sc = float(strate_count)               strate_count = light_stratify ? uint(sqrt(float(light_samples))) : 1
+ *     u1 = rng_f32(key, D) / sc              u2 = rng_f32(key, D + 1) / sc
+ *     x1 = (position + u1 * ab) + u2 * ac
+ *     with light_stratify:  x1 = x1 + ((ab / sc) * float(k % strate_count) + (ac / sc) * float(k / strate_count))
+ *     v      = x1 - p                        omega = normalized(v)
+ *     le     = (intensity * color.rgb) * area              alpha = color.a
+ *     d_omega = dot(normal, omega) / |v|^2
+ *   (the reference's unnegated dot: the light counts from the side its normal points AWAY from, and negatively from the other).
+ *   Contribution.  Hemisphere mode: ndot = clamp(dot(n, omega), 0, 1) (a NaN stays NaN) and x = (le * ndot) * d_omega per r, g, b.
+ *   Sphere mode: x = le * d_omega.  y = x * alpha per r, g, b: what the reference's Color `+` adds.
+ *   Classes.  A sample is dropped iff a component of y is not finite (a point on the light, say): it is neither traced nor added --
+ *   a path vertex's pixel would be NaN; here "a NaN sample stays out", as in rayca_hip_gather_device.  A sample is void iff it is not
+ *   dropped and y.r == 0 && y.g == 0 && y.b == 0 (it faces away, the intensity is 0, it underflowed): not traced, never lit; adding
+ *   it would change no bit.  Every other sample is traced along the ray (o, omega).
+ *   Lit.  Point light: lit iff rayca_hip_query_device(RAYCA_QUERY_OCCLUDED) reports 0 for (o, omega) with tmax = dist.  Quad light:
+ *   lit iff RAYCA_QUERY_CLOSEST, unbounded, finds a hit whose material is emissive (bit 2 of rayca_hip_surface_device's flags): the
+ *   reference's "lit iff the closest hit is emissive" (nee.rs:103-104).  Scenes with spheres are served, as by both queries.
+ *   Fold, per point, j ascending over the lit samples, from zeros:
+ *     hemisphere mode   E = E + y
+ *     sphere mode       I = I + y;  with sh_out  H[k] = H[k] + y * Y_k(omega), k = 0 .. 8, Y_k exactly the nine expressions of
+ *                       RaycaGather's comment with d = omega.  There is no division by a count.
+ *   Outputs (any may be NULL, not all), per point:
+ *     irradiance_out  4 x f32      hemisphere mode (E.r, E.g, E.b, float(lit) / float(N)); sphere mode (I.r, I.g, I.b, the same)
+ *     sh_out          9 x 4 x f32  sphere mode only: [k] = (H[k].r, H[k].g, H[k].b, 0)
+ *     mask_out        u64          bit j = sample j was traced and lit
+ *     counts_out      u32          lit samples in the low 16 bits, dropped samples in the high 16
+ *   An inactive point gives zeros everywhere.  Nothing outside [0, count) of an output is written.
+ *   Units.  Hemisphere E is the irradiance (not / pi): a Lambert surface of albedo a radiates a * E / pi.  Sphere I is the incident
+ *   radiance times solid angle, and sh_out is the integral of L Y_k over the sphere of the direct light: the units of
+ *   rayca_hip_gather_device's sh_out under a uniform sphere table with weights of 4 pi, so the two add into one probe.
+ *   Order-free results: the trace kernel only ORs bit j of the point's mask word, with a 64-bit atomic; everything else is made
+ *   from the finished word, in j order.
+ * Of cfg only light_samples, light_stratify and seed are read.  opts (may be NULL), ordering and statistics as for
+ * rayca_hip_ambient_device: stream, context, wait_event, record_event and collect_stats; traversal must be RAYCA_TRAVERSAL_ORDERED;
+ * tile, engine and camera_rays must be zero.  Without mask_out the mask words live in the context's work buffers.  With stats_out
+ * the call waits: rays_shadow = the samples that were traced, the time and the launches (the trace kernel, and the fold unless
+ * mask_out is the only output) under RAYCA_KERNEL_OTHER, boxes_tested and triangles_tested under collect_stats.
+ * Refusals, before any GPU work and before the scene is looked at, in this order.  RAYCA_ERR_BAD_ARG: NULL scene / cfg / struct; NULL
+ * points; light_count == 0; cfg->light_samples == 0, or N > 64; non-zero reserved; no output; sh_out with normals; a non-zero bias
+ * without normals; irradiance_out or sh_out not 16-byte aligned, mask_out not 8-byte aligned, counts_out not 4-byte aligned; bias not
+ * finite; first_index + count above 2^32; count x N >= 2^32; then context > 7, a non-zero field of opts that does not apply.  Then
+ * RAYCA_ERR_UNSUPPORTED for EXHAUSTIVE.  count == 0 is then RAYCA_OK and launches nothing.  Then the scene: RAYCA_ERR_EMPTY_SCENE;
+ * RAYCA_ERR_BAD_ARG for light_first + light_count above the scene's lights; RAYCA_ERR_UNSUPPORTED for a directional light in the
+ * range (the reference's todo!() at nee.rs:178, as in the radiance call). */
+struct RaycaDirect {
+  uint32_t count;         /* points */
+  uint32_t light_first;   /* the first light of the range */
+  uint32_t light_count;   /* lights in the range: light_count * cfg->light_samples is 1 .. 64 */
+  uint32_t sample;        /* RNG stream of the quad-light draws, as RaycaRadiance.sample */
+  uint32_t first_index;   /* point i draws from the stream of "pixel" first_index + i */
+  float bias;             /* hemisphere mode: o = p + n * bias; finite; sphere mode: must be 0 */
+  uint32_t reserved[2];   /* must be zero */
+  const void* points;     /* DEVICE: count x 3 f32 */
+  const void* normals;    /* DEVICE: count x 3 f32, (0, 0, 0) marks an inactive point; or NULL => sphere mode */
+  void* irradiance_out;   /* DEVICE: count x 4 f32, 16-byte aligned, or NULL */
+  void* sh_out;           /* DEVICE: count x 9 x 4 f32, 16-byte aligned, or NULL; sphere mode only */
+  void* mask_out;         /* DEVICE: count u64, or NULL */
+  void* counts_out;       /* DEVICE: count u32, or NULL */
+};
+typedef struct RaycaDirect RaycaDirect;
+int32_t rayca_hip_direct_device(RaycaScene* scene, const RaycaConfig* cfg, const RaycaRenderOptions* opts, const RaycaDirect* direct,
+                                RaycaStats* stats_out);
+
 /* The edge-avoiding a-trous wavelet denoiser, on a frame and its G-buffer in DEVICE memory: what rayca_hip_render_device wrote to
  * d_rgba32f_out (rendered with gamma 1) and what rayca_hip_surface_device wrote for the frame's camera rays go in, the filtered
  * frame comes out as RGBA32F and / or RGBA8, through the gamma and the quantisation of a render call.  No reference counterpart.
@@ -1782,6 +1874,29 @@ int32_t rayca_hip_scene_primitive_order(const RaycaScene* scene, uint32_t* prim_
  * being the child record's byte offset, 48 x its index) -- node i of one is node i of the other.  `bytes_out` receives the array's size; with out == NULL only that.  RAYCA_ERR_BAD_ARG if the
  * scene has no such array or `capacity_bytes` is too small. */
 int32_t rayca_hip_scene_read_nodes(RaycaScene* scene, uint32_t which, void* out, uint64_t capacity_bytes, uint64_t* bytes_out);
+
+/* Light read-back (no reference counterpart): copies the scene's light records, as the kernels read them, to HOST memory -- in
+ * flatten order, the index rayca_hip_direct_device's light_first counts in; after a rayca_hip_scene_update the updated records.
+ * What a caller needs to reproduce a direct-light sample without restating the scene flatten: position is the translation of the
+ * light node's LOCAL transform (w = 1), as the reference's NEE reads it (nee.rs:133-134), not the node's world position; normal
+ * is normalized(ab x ac) and area the reference's own (1 - cos(ab, ac)) |ab| |ac| (|ab| |ac| for a rectangle) of a quad light,
+ * zeros otherwise; attenuation[3] is 0.  `count_out` receives the
+ * number of lights; with out == NULL only that.  RAYCA_ERR_BAD_ARG: NULL scene; out and count_out both NULL; `capacity` (in
+ * records) too small. */
+struct RaycaLightRecord {
+  uint32_t kind;         /* RAYCA_LIGHT_* */
+  uint32_t material;     /* a quad light's material, or RAYCA_NONE */
+  float intensity;
+  float area;
+  float color[4];
+  float attenuation[4];  /* constant, linear, quadratic, 0 */
+  float position[4];
+  float ab[4];
+  float ac[4];
+  float normal[4];
+};
+typedef struct RaycaLightRecord RaycaLightRecord;
+int32_t rayca_hip_scene_read_lights(RaycaScene* scene, RaycaLightRecord* out, uint32_t capacity, uint32_t* count_out);
 
 #ifdef __cplusplus
 }

@@ -506,6 +506,42 @@ pub struct RaycaProbeLookup {
     pub radiance_out: *mut c_void,
 }
 
+// rayca_hip_direct_device: points and optional normals in, the direct light of a range of the scene's lights per point out, all in
+// DEVICE memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaDirect {
+    pub count: u32,
+    pub light_first: u32,
+    pub light_count: u32,
+    pub sample: u32,
+    pub first_index: u32,
+    pub bias: f32,
+    pub reserved: [u32; 2],
+    pub points: *const c_void,
+    pub normals: *const c_void,
+    pub irradiance_out: *mut c_void,
+    pub sh_out: *mut c_void,
+    pub mask_out: *mut c_void,
+    pub counts_out: *mut c_void,
+}
+
+// rayca_hip_scene_read_lights: one light as the kernels read it, in HOST memory
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RaycaLightRecord {
+    pub kind: u32,
+    pub material: u32,
+    pub intensity: f32,
+    pub area: f32,
+    pub color: [f32; 4],
+    pub attenuation: [f32; 4],
+    pub position: [f32; 4],
+    pub ab: [f32; 4],
+    pub ac: [f32; 4],
+    pub normal: [f32; 4],
+}
+
 // rayca_hip_denoise_device: the a-trous filter on a frame and its G-buffer, all in DEVICE memory
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -784,6 +820,7 @@ extern "C" {
     pub fn rayca_hip_radiance_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, radiance: *const RaycaRadiance, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_gather_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, gather: *const RaycaGather, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_probe_lookup_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, lookup: *const RaycaProbeLookup, stats_out: *mut RaycaStats) -> i32;
+    pub fn rayca_hip_direct_device(scene: *mut RaycaScene, cfg: *const RaycaConfig, opts: *const RaycaRenderOptions, direct: *const RaycaDirect, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_denoise_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, d: *const RaycaDenoise, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_camera(scene: *const RaycaScene, out: *mut RaycaCameraPose) -> i32;
     pub fn rayca_hip_accumulate_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, a: *const RaycaAccumulate, stats_out: *mut RaycaStats) -> i32;
@@ -795,6 +832,7 @@ extern "C" {
     pub fn rayca_hip_film_fold_device(scene: *mut RaycaScene, opts: *const RaycaRenderOptions, fold: *const RaycaFilmFold, stats_out: *mut RaycaStats) -> i32;
     pub fn rayca_hip_scene_primitive_order(scene: *const RaycaScene, prim_order: *mut u32, capacity: u32) -> i32;
     pub fn rayca_hip_scene_read_nodes(scene: *mut RaycaScene, which: u32, out: *mut c_void, capacity_bytes: u64, bytes_out: *mut u64) -> i32;
+    pub fn rayca_hip_scene_read_lights(scene: *mut RaycaScene, out: *mut RaycaLightRecord, capacity: u32, count_out: *mut u32) -> i32;
 }
 
 // ---- Config -------------------------------------------------------------------------------------------------------------

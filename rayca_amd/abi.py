@@ -462,6 +462,41 @@ class RaycaProbeLookup(C.Structure):
     ]
 
 
+class RaycaDirect(C.Structure):
+    """rayca_hip_direct_device: every pointer is DEVICE memory."""
+    _fields_ = [
+        ("count", C.c_uint32),
+        ("light_first", C.c_uint32),
+        ("light_count", C.c_uint32),
+        ("sample", C.c_uint32),
+        ("first_index", C.c_uint32),
+        ("bias", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+        ("points", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("irradiance_out", C.c_void_p),
+        ("sh_out", C.c_void_p),
+        ("mask_out", C.c_void_p),
+        ("counts_out", C.c_void_p),
+    ]
+
+
+class RaycaLightRecord(C.Structure):
+    """rayca_hip_scene_read_lights: one light as the kernels read it (HOST memory)."""
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("material", C.c_uint32),
+        ("intensity", C.c_float),
+        ("area", C.c_float),
+        ("color", C.c_float * 4),
+        ("attenuation", C.c_float * 4),
+        ("position", C.c_float * 4),
+        ("ab", C.c_float * 4),
+        ("ac", C.c_float * 4),
+        ("normal", C.c_float * 4),
+    ]
+
+
 class RaycaSurfaceQuery(C.Structure):
     """rayca_hip_surface_device: every pointer is DEVICE memory."""
     _fields_ = [
@@ -831,6 +866,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_gather_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaGather), P(RaycaStats)]
     lib.rayca_hip_probe_lookup_device.restype = C.c_int32
     lib.rayca_hip_probe_lookup_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaProbeLookup), P(RaycaStats)]
+    lib.rayca_hip_direct_device.restype = C.c_int32
+    lib.rayca_hip_direct_device.argtypes = [C.c_void_p, P(RaycaConfig), P(RaycaRenderOptions), P(RaycaDirect), P(RaycaStats)]
     lib.rayca_hip_denoise_device.restype = C.c_int32
     lib.rayca_hip_denoise_device.argtypes = [C.c_void_p, P(RaycaRenderOptions), P(RaycaDenoise), P(RaycaStats)]
     lib.rayca_hip_scene_camera.restype = C.c_int32
@@ -853,6 +890,8 @@ def bind_product_signatures(lib):
     lib.rayca_hip_scene_primitive_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.rayca_hip_scene_read_nodes.restype = C.c_int32
     lib.rayca_hip_scene_read_nodes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.rayca_hip_scene_read_lights.restype = C.c_int32
+    lib.rayca_hip_scene_read_lights.argtypes = [C.c_void_p, P(RaycaLightRecord), C.c_uint32, C.POINTER(C.c_uint32)]
     lib.rayca_hip_rccl_status.restype = C.c_int32
     lib.rayca_hip_rccl_status.argtypes = []
     lib.rayca_hip_render_multi.restype = C.c_int32
@@ -873,10 +912,10 @@ PRODUCT_SYMBOLS = [
     "rayca_hip_surface_cdf_device", "rayca_hip_surface_sample_device",
     "rayca_hip_signed_device",
     "rayca_hip_ambient_device",
-    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_probe_lookup_device", "rayca_hip_denoise_device",
+    "rayca_hip_surface_device", "rayca_hip_camera_rays_device", "rayca_hip_radiance_device", "rayca_hip_gather_device", "rayca_hip_probe_lookup_device", "rayca_hip_direct_device", "rayca_hip_denoise_device",
     "rayca_hip_scene_camera", "rayca_hip_accumulate_device", "rayca_hip_denoise_variance_device", "rayca_hip_upsample_device",
     "rayca_hip_meter_device", "rayca_hip_tonemap_device", "rayca_hip_sample_plan_device", "rayca_hip_film_fold_device",
-    "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
+    "rayca_hip_scene_primitive_order", "rayca_hip_scene_read_nodes", "rayca_hip_scene_read_lights", "rayca_hip_render_multi", "rayca_hip_render_multi_issue", "rayca_hip_render_multi_wait",
     "rayca_hip_rccl_status",
     "rayca_hip_renderer_create", "rayca_hip_renderer_draw", "rayca_hip_renderer_last_draw", "rayca_hip_renderer_scene",
     "rayca_hip_renderer_invalidate", "rayca_hip_renderer_destroy", "rayca_hip_scene_desc_compare",

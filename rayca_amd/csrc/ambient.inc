@@ -64,6 +64,20 @@ __device__ __forceinline__ AmbientRay ambient_ray(F4 p, F4 n, float c, float s, 
   return r;
 }
 
+// The nine real spherical harmonics of bands 0 .. 2 at a direction, exactly the expressions of the header's comment on RaycaGather:
+// what the gather fold and the direct-light fold weigh a sample with.
+__device__ __forceinline__ void sh9_basis(F4 d, float (&y)[9]) {
+  y[0] = 0.2820948f;
+  y[1] = 0.4886025f * d.y;
+  y[2] = 0.4886025f * d.z;
+  y[3] = 0.4886025f * d.x;
+  y[4] = 1.0925484f * (d.x * d.y);
+  y[5] = 1.0925484f * (d.y * d.z);
+  y[6] = 0.3153916f * ((3.0f * (d.z * d.z)) - 1.0f);
+  y[7] = 1.0925484f * (d.x * d.z);
+  y[8] = 0.5462742f * ((d.x * d.x) - (d.y * d.y));
+}
+
 // k_query_rays<..., OCCLUDED>'s sibling: one ray per lane, item = i * S + j, on the binary f32 nodes with the spill path -- what
 // serves a RAYCA_BUILDER_REFERENCE scene and a SAH scene whose formats thread has not finished.  Same t_stop convention (an
 // unbounded ray gets the largest float below FLT_MAX, so that the early out is on for it too), same query_found.

@@ -82,7 +82,7 @@ struct FrameCtx {
   DeviceBuffer path_direct, path_brdf, path_state, accum, queue[2], out8, out32, ray_io, stack_spill, frames, mis_samples, wf_hits, wf_sh_ray, wf_sh_x;
   DeviceBuffer denoise[2];            // rayca_hip_denoise_device: the two images its iterations go back and forth between
   DeviceBuffer denoise_var[2];        // rayca_hip_denoise_variance_device: the two variance planes that go with them (4 B a pixel)
-  DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point)
+  DeviceBuffer ambient_mask;          // rayca_hip_ambient_device without mask_out: the mask words its trace kernel ORs into (8 B a point); rayca_hip_direct_device's likewise
   DeviceBuffer probe_mask;            // rayca_hip_probe_lookup_device with visibility and without mask_out: the same, 4 B a point
   DeviceBuffer plan_weight;           // rayca_hip_sample_plan_device without weight_out: the weights its offsets kernel reads back (4 B a pixel)
   DeviceBuffer plan_sums;             // ... and the sums of its 64-pixel row segments, their prefix sums once scanned (4 B a segment); rayca_hip_surface_cdf_device: its first word is the largest area's bits
@@ -2159,6 +2159,142 @@ int32_t rayca_hip_probe_lookup_device(RaycaScene* s, const RaycaRenderOptions* o
       });
   if (rc != RAYCA_OK || !stats_out) return rc;
   stats_out->rays_shadow = vis ? total : 0u;
+  stats_out->boxes_tested = tc.boxes;
+  stats_out->triangles_tested = tc.tris;
+  stats_out->wave_box_slots = tc.box_slots;
+  stats_out->wave_triangle_slots = tc.tri_slots;
+  stats_out->node_format = node_format;
+  return RAYCA_OK;
+}
+
+// Direct light at points (direct.inc, refill.hip k_direct_refill): count x N shadow rays made in registers from the points and the
+// scene's light records, one mask word per point, folded by k_direct_fold.  The trace kernel is chosen exactly as
+// rayca_hip_ambient_device chooses its own.  The mask words live in mask_out, or in the context's scratch (grown before the pass
+// queues its waits); they are cleared on the launch stream in front of the trace kernel.  A pass on its context (run_pass), so that
+// a rayca_hip_scene_update of lights never overwrites a table these kernels are still reading.
+int32_t rayca_hip_direct_device(RaycaScene* s, const RaycaConfig* cfg_in, const RaycaRenderOptions* opts_in, const RaycaDirect* din, RaycaStats* stats_out) {
+  if (!s || !cfg_in || !din) return fail(RAYCA_ERR_BAD_ARG, "null scene, config or RaycaDirect");
+  const RaycaDirect& rd = *din;
+  const RaycaConfig& cfg = *cfg_in;
+  RaycaRenderOptions o{};
+  if (opts_in) o = *opts_in;
+  // everything the structs alone decide, before the scene handle is looked at
+  if (!rd.points) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.points: null points");
+  if (rd.light_count == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.light_count: a range of no lights");
+  if (cfg.light_samples == 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaConfig.light_samples must be > 0");
+  if ((uint64_t)rd.light_count * cfg.light_samples > 64u)
+    return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.light_count x light_samples: 1 .. 64 samples (one bit of the mask word each); chunk over light ranges");
+  if (rd.reserved[0] != 0 || rd.reserved[1] != 0) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.reserved must be zero");
+  if (!rd.irradiance_out && !rd.sh_out && !rd.mask_out && !rd.counts_out) return fail(RAYCA_ERR_BAD_ARG, "no output for a direct-light call");
+  const bool sphere = rd.normals == nullptr;
+  if (!sphere && rd.sh_out) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.sh_out is a sphere-mode output: not with normals");
+  if (sphere && rd.bias != 0.0f) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.bias must be 0 without normals (sphere mode: o = p)");
+  if (reinterpret_cast<uintptr_t>(rd.irradiance_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.irradiance_out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rd.sh_out) & 15u) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.sh_out must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rd.mask_out) & 7u) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.mask_out must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(rd.counts_out) & 3u) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.counts_out must be 4-byte aligned");
+  if (!std::isfinite(rd.bias)) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.bias is not finite");
+  if ((uint64_t)rd.first_index + rd.count > (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.first_index + count exceeds 2^32");
+  const uint32_t samples = rd.light_count * cfg.light_samples;
+  if ((uint64_t)rd.count * samples >= (1ull << 32)) return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.count x light_count x light_samples must stay below 2^32");
+  int32_t rc = pass_options(o, "a direct-light call", kOptTraversal | kOptCollectStats);
+  if (rc != RAYCA_OK) return rc;
+  if (o.traversal == RAYCA_TRAVERSAL_EXHAUSTIVE)
+    return fail(RAYCA_ERR_UNSUPPORTED, "RaycaRenderOptions.traversal: a shadow ray ends at its first hit: there is no exhaustive form");
+  if (rd.count == 0) {
+    if (stats_out) std::memset(stats_out, 0, sizeof *stats_out);
+    return RAYCA_OK;
+  }
+  if ((rc = refuse_empty_scene(s)) != RAYCA_OK) return rc;
+  const std::vector<HostLight>& lights = s->host.lights;
+  if (rd.light_first > lights.size() || rd.light_count > lights.size() - rd.light_first)
+    return fail(RAYCA_ERR_BAD_ARG, "RaycaDirect.light_first + light_count exceeds the scene's " + std::to_string(lights.size()) + " lights");
+  DirectIo io{};
+  for (uint32_t li = 0; li < rd.light_first + rd.light_count; ++li) {
+    const uint32_t kind = lights[li].kind;
+    if (li < rd.light_first) {
+      if (kind != RAYCA_LIGHT_POINT) ++io.quad_base;   // (what nee_prepare's other branch serves: two dimensions a sample)
+      continue;
+    }
+    if (kind == RAYCA_LIGHT_DIRECTIONAL)
+      return fail(RAYCA_ERR_UNSUPPORTED, "light " + std::to_string(li) + " is directional: NEE has no sample for it (todo!() in the reference, nee.rs:178)");
+    if (kind != RAYCA_LIGHT_POINT) io.quad_bits |= 1ull << (li - rd.light_first);
+  }
+  io.points = static_cast<const float*>(rd.points);
+  io.normals = static_cast<const float*>(rd.normals);
+  io.bias = rd.bias;
+  io.count = rd.count;
+  io.samples = samples;
+  io.light_first = rd.light_first;
+  io.light_samples = cfg.light_samples;
+  io.light_stratify = cfg.light_stratify;
+  io.strate_count = cfg.light_stratify ? (uint32_t)sqrtf((float)cfg.light_samples) : 1u;  // config.rs:73-79, as frame_params
+  io.seed = cfg.seed;
+  io.sample = rd.sample;
+  io.first_index = rd.first_index;
+  io.count_traced = stats_out ? 1u : 0u;
+  io.irradiance_out = static_cast<float4*>(rd.irradiance_out);
+  io.sh_out = static_cast<float4*>(rd.sh_out);
+  io.mask_out = static_cast<unsigned long long*>(rd.mask_out);
+  io.counts_out = static_cast<uint32_t*>(rd.counts_out);
+  const bool stats = o.collect_stats != 0, sph = s->host.sphere_count != 0;
+  const bool fold = rd.irradiance_out || rd.sh_out || rd.counts_out;   // (mask_out alone is the trace kernel's own work)
+  const uint32_t total = rd.count * samples, batches = (total + 63u) / 64u;
+  const size_t mask_bytes = (size_t)rd.count * sizeof(unsigned long long);
+  FrameCtx* c = &s->ctx[o.context];
+  TraceCounters tc{};
+  uint32_t node_format = 0;
+  rc = run_pass(
+      s, o, stats_out,
+      [&](FrameCtx* ctx) -> int32_t {
+        if (io.mask_out) return RAYCA_OK;
+        HIP_TRY(hipSetDevice(s->device));
+        return grow_behind_pass(ctx, ctx->ambient_mask, mask_bytes);
+      },
+      [&](hipStream_t stream, uint32_t& launches) -> int32_t {
+        io.mask = io.mask_out ? io.mask_out : static_cast<unsigned long long*>(c->ambient_mask.ptr);
+        const bool fast = s->dev.ref_leaf_of != nullptr;   // the reference-leaf filter is present (RAYCA_BUILDER_SAH)
+        const bool all_formats = formats_ready(s);
+        const bool refill = fast && all_formats;           // (rayca_hip_ambient_device's rule)
+        uint32_t grid = (batches + 3u) / 4u;               // one sample per lane; the persistent grid below replaces it
+        StackPlan sp{};
+        node_format = all_formats ? 0u : 2048u;
+        if (refill) {
+          sp = plan_stack(std::max(s->host.max_depth, s->host.max_depth4), RAYCA_WF_LDS_ENTRIES);
+          const uint32_t in_flight = frames_in_flight_hint(s, o.context, o.stream != nullptr);
+          if (const int32_t grc = persistent_grid(s, direct_refill_kernel(sphere, sph, stats), sp.lds_bytes, batches, true, in_flight, 0u, grid); grc != RAYCA_OK) return grc;
+          node_format |= (RAYCA_WF_BOUNCE_WIDE ? 1u : 0u) | (RAYCA_WF_BOUNCE_HALF ? 4u : 0u);
+        } else {
+          sp = plan_stack(s->host.max_depth);
+          if (fast && RAYCA_NODE_CH && RAYCA_NODE_CH48 && s->dev.nodes_ch) node_format |= 4096u;
+        }
+        TraceLaunch tl{};
+        if (const int32_t brc = bind_stack(c, sp, grid, tl); brc != RAYCA_OK) return brc;
+        if (stats || io.count_traced) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(TraceCounters), stream));
+        HIP_TRY(hipMemsetAsync(io.mask, 0, mask_bytes, stream));
+        if (refill) {
+          tl.ticket = 1u;
+          HIP_TRY(hipMemsetAsync(c->heads, 0, 8 * kHeadStride * sizeof(uint32_t), stream));
+          c->heads_clean &= ~FrameCtx::kCleanHeads;   // the next frame of this context clears them for itself
+          launch_direct_refill(sphere, sph, stats, grid, sp.lds_bytes, stream, s->dev_full, io, c->heads, c->counters, tl);
+        } else {
+          hipLaunchKernelGGL(pick_direct_kernel(sphere, fast, sph, stats), dim3(grid), dim3(kBlock), sp.lds_bytes, stream, all_formats ? s->dev_full : s->dev, io,
+                             c->counters, tl);
+        }
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        if (fold) {
+          hipLaunchKernelGGL(pick_direct_fold(sphere, io.sh_out != nullptr), dim3((rd.count + kDirectFoldBlock - 1u) / kDirectFoldBlock), dim3(kDirectFoldBlock), 0, stream,
+                             s->dev.lights, io);
+          HIP_TRY(hipGetLastError());
+          ++launches;
+        }
+        // (read back inside the pass, under the context's lock: with stats_out the pass waits for the stream before it returns)
+        if (stats_out) HIP_TRY(hipMemcpyAsync(&tc, c->counters, sizeof tc, hipMemcpyDeviceToHost, stream));
+        return RAYCA_OK;
+      });
+  if (rc != RAYCA_OK || !stats_out) return rc;
+  stats_out->rays_shadow = tc.shadow;   // the samples that were traced: dropped and empty samples and inactive points cost no ray
   stats_out->boxes_tested = tc.boxes;
   stats_out->triangles_tested = tc.tris;
   stats_out->wave_box_slots = tc.box_slots;

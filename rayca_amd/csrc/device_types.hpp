@@ -177,6 +177,25 @@ struct ProbeIo {
   float4* radiance_out;
 };
 
+// points and optional normals in, the direct light of a range of the scene's lights per point out, all in DEVICE memory
+// (rayca_hip_direct_device).  Sample j = (li - light_first) * light_samples + k; samples = light_count * light_samples <= 64.
+struct DirectIo {
+  const float* points;     // count x 3
+  const float* normals;    // count x 3, or nullptr: sphere mode
+  float bias;
+  uint32_t count, samples;
+  uint32_t light_first, light_samples, light_stratify, strate_count;
+  uint32_t quad_base;            // quad lights of the whole scene with an index below light_first
+  unsigned long long quad_bits;  // bit b: light light_first + b is no point light (it draws two random dimensions a sample)
+  uint32_t seed, sample, first_index;
+  uint32_t count_traced;         // 1: the trace kernel adds its traced samples to TraceCounters::shadow
+  unsigned long long* mask;      // count words the trace kernels OR into (cleared in front of them): mask_out, or the context's scratch
+  float4* irradiance_out;        // what k_direct_fold writes: any may be nullptr
+  float4* sh_out;
+  unsigned long long* mask_out;
+  uint32_t* counts_out;
+};
+
 // per generation, per pixel record used to fold the path back in the reference's evaluation order
 enum : uint32_t { kVertexNone = 0, kVertexLit = 1, kVertexEmissive = 2, kVertexLitNoIndirect = 3 };
 

@@ -68,15 +68,7 @@ __global__ __launch_bounds__(kGatherFoldBlock) void k_gather_fold(GatherIo g) {
       if (SH) {
         const F4 d = ambient_ray<ROT>(pt.p, pt.n, pt.c, pt.s, g.a.dirs, j, g.a.bias).d;
         float y[9];
-        y[0] = 0.2820948f;
-        y[1] = 0.4886025f * d.y;
-        y[2] = 0.4886025f * d.z;
-        y[3] = 0.4886025f * d.x;
-        y[4] = 1.0925484f * (d.x * d.y);
-        y[5] = 1.0925484f * (d.y * d.z);
-        y[6] = 0.3153916f * ((3.0f * (d.z * d.z)) - 1.0f);
-        y[7] = 1.0925484f * (d.x * d.z);
-        y[8] = 0.5462742f * ((d.x * d.x) - (d.y * d.y));
+        sh9_basis(d, y);   // (ambient.inc: the header's nine expressions)
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
           hr[k] = hr[k] + cr * y[k];

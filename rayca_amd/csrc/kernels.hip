@@ -31,6 +31,9 @@
 //   k_probe_rays,     irradiance volumes: the occlusion rays from a point to the eight probes of its grid cell, one per lane, and the
 //   k_probe_fold      blend of those probes' SH9 records into the light at the point (probes.inc: rayca_hip_probe_lookup_device; the
 //                     lane-refill form is refill.hip k_probe_refill).
+//   k_direct_rays,    direct light at points: the shadow rays of a range of the scene's lights, made in registers, one per lane, and
+//   k_direct_fold     the sum of the lit samples in a fixed order (direct.inc: rayca_hip_direct_device; the lane-refill form is
+//                     refill.hip k_direct_refill).
 //   k_enqueue_gather, irradiance at points: the same rays written straight into the frame driver's generation-0 queue, and the
 //   k_gather_fold     fold of their radiance into irradiance and nine spherical-harmonic coefficients per point
 //                     (gather.inc: rayca_hip_gather_device).
@@ -510,6 +513,7 @@ __global__ __launch_bounds__(kBlock, RAYCA_TRACE_MIN_WAVES) void k_query_rays(De
 #include "ambient.inc"
 #include "probes.inc"
 #include "gather.inc"
+#include "direct.inc"
 RAYCA_NO_PK_END   // (the image-space passes below keep the packed forms: whole float4 pixels)
 #include "image_pass.inc"
 #include "denoise.inc"

@@ -27,6 +27,7 @@ RAYCA_NO_PK_BEGIN
 #include "trace_core.inc"
 #include "ambient.inc"   // ambient_point, ambient_ray: what k_ambient_refill makes its rays with
 #include "probes.inc"    // probe_point, probe_cell, probe_corner, probe_ray: what k_probe_refill makes its rays with
+#include "direct.inc"    // direct_point, direct_sample, direct_lit: what k_direct_refill makes and judges its samples with
 
 #ifndef RAYCA_REFILL_THRESHOLD
 #define RAYCA_REFILL_THRESHOLD 44
@@ -761,6 +762,122 @@ __global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_probe_refill(De
   }
 }
 
+// ---- direct light at points (rayca_hip_direct_device) with lane refill ----------------------------------------------------------
+// k_probe_refill's sibling, written beside it so that the existing listings stay what they are: the same work counters,
+// threshold and leave-K, node_step / test_leaf, stack plan and persistent grid, on the same 4-wide fp16 nodes.  Item = i * N + j,
+// sample j of point i: a lane that takes an item reads the point's 12 B (24 B with a normal) and the light's record and makes the
+// sample in registers (direct.inc direct_sample); a batch of 64 items is the full sample set of 64 / N neighbouring points.  An
+// item that traces nothing -- an inactive point, a dropped or an empty sample -- retires at once.  The search starts as
+// k_shadow_refill::start_ray starts it: any-hit with the cull bound for a point light (t_stop = its distance), closest hit for a
+// quad light (t_stop = FLT_MAX) -- with the slack of k_query_refill, since a caller's points lie anywhere.  A retiring lane whose
+// sample was lit ORs bit j into the point's word with one 64-bit atomic; an unlit one writes nothing.
+template <bool SPHERE, bool SPH, bool STATS>
+__global__ __launch_bounds__(kBlock, RAYCA_QREFILL_WAVES) void k_direct_refill(DevScene sc, DirectIo a, uint32_t* heads, TraceCounters* counters, TraceLaunch tl) {
+  constexpr bool WIDE = RAYCA_WF_BOUNCE_WIDE != 0, SPILL = true, HALF = RAYCA_WF_BOUNCE_HALF != 0;   // (as k_query_refill)
+  extern __shared__ uint32_t lds_stack[];
+  NodeStack<SPILL> stack = make_stack<SPILL>(lds_stack, tl, rc_bid() * kBlock + rc_tid());
+  const uint32_t lane = __lane_id();
+  const uint32_t home = xcc_id();
+  const unsigned long long lanes_below = (1ull << lane) - 1ull;
+  const uint32_t count = a.count * a.samples, n_batches = (count + 63u) >> 6;   // (the host refuses count x samples >= 2^32)
+  WorkCursor wc{};
+  LaneCounters cnt{};
+  uint32_t n_traced = 0;   // the wave's traced samples
+  bool has = false;
+  uint32_t cur = kTerminated, item = 0;
+  float t_stop = FLT_MAX;
+  DRay ray{};
+  FastRay fr{};
+  DHit hit{};
+  float limit = INFINITY;
+  uint32_t pool_next = 0, pool_end = 0;
+  bool dry = false;
+  for (;;) {
+    const uint32_t n_active = (uint32_t)__popcll(__ballot(cur != kTerminated));
+    if (n_active <= (dry ? 0u : (uint32_t)RAYCA_QREFILL_THRESHOLD)) {
+      if (has && cur == kTerminated) {  // retire: bit j of point i, iff the sample was lit (i < count: nothing else is ever written)
+        if (direct_lit(sc, hit, t_stop)) {
+          const uint32_t i = item / a.samples, j = item - i * a.samples;
+          atomicOr(&a.mask[i], 1ull << j);
+        }
+        has = false;
+      }
+      if (dry && n_active == 0u) break;  // every lane reaches this: n_active and dry are wave-uniform
+      while (!dry) {
+        const unsigned long long idle = __ballot(!has);
+        if (idle == 0ull) break;
+        if (pool_next == pool_end) {
+          const uint32_t batch = next_batch(heads, n_batches, home, wc, tl.ticket);
+          if (batch == RAYCA_NONE) {
+            dry = true;
+            break;
+          }
+          pool_next = batch * 64u;
+          pool_end = min(pool_next + 64u, count);
+        }
+        const uint32_t avail = pool_end - pool_next;
+        const uint32_t rank = (uint32_t)__popcll(idle & lanes_below);
+        bool started = false;
+        if (!has && rank < avail) {
+          item = pool_next + rank;
+          const uint32_t i = item / a.samples, j = item - i * a.samples;
+          const DirectPoint pt = direct_point<SPHERE>(a, i);
+          if (pt.active) {   // (an item that traces nothing is skipped: the lane asks again)
+            const DirectSample s = direct_sample<SPHERE>(sc.lights, a, pt, i, j);
+            if (!s.dropped && !s.empty) {
+              ray = make_ray(s.o, s.omega);
+              t_stop = s.t_stop;
+              fr = make_fast(sc, ray, HALF);   // prologue of trace(): the root box first (blas.rs:136-139)
+              hit.t = INFINITY;
+              hit.prim = RAYCA_NONE;
+              hit.u = hit.v = 0.0f;
+              limit = t_stop < FLT_MAX ? cull_limit<true>(sc, fr, t_stop) : INFINITY;
+              stack.clear();
+              float tmin;
+              if (STATS) cnt.boxes++;
+              started = true;
+              cur = slab(sc.root_min[0], sc.root_min[1], sc.root_min[2], sc.root_max[0], sc.root_max[1], sc.root_max[2], ray, tmin)
+                        ? (WIDE ? sc.root_ref4 : (!HALF && RAYCA_NODE_CH ? sc.root_ref_ch : sc.root_ref))
+                        : kTerminated;
+              has = true;
+            }
+          }
+        }
+        n_traced += (uint32_t)__popcll(__ballot(started));   // (wave-uniform: a scalar, not a lane's register)
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        pool_next += n_idle < avail ? n_idle : avail;
+      }
+    }
+    for (;;) {  // (RAYCA_REFILL_SCHED 0 of k_flat_refill)
+      const bool searching = !(cur & kLeafFlag) && cur != kTerminated;
+      const uint32_t n = (uint32_t)__popcll(__ballot(searching));
+      if (n == 0u) break;
+      if (n < (uint32_t)RAYCA_QREFILL_LEAVE_K && __ballot((cur & kLeafFlag) != 0u) != 0ull) break;
+      if (searching) cur = node_step<true, true, WIDE, SPILL, STATS, HALF>(sc, ray, fr, limit, cur, stack, cnt);
+    }
+    if (cur & kLeafFlag) {
+      test_leaf<true, SPH, STATS>(sc, ray, fr, cur, t_stop, hit, limit, cnt);
+      cur = (t_stop < FLT_MAX && query_found(hit, t_stop)) ? kTerminated : stack.pop();   // a point light: any hit in front of it ends the search
+    }
+  }
+  if (a.count_traced && lane == 0) atomicAdd(&counters->shadow, (unsigned long long)n_traced);
+  if (STATS) {
+    unsigned long long b = cnt.boxes, t = cnt.tris, sb = cnt.slot_boxes, stt = cnt.slot_tris;
+    for (int off = 32; off > 0; off >>= 1) {
+      b += __shfl_down(b, off);
+      t += __shfl_down(t, off);
+      sb += __shfl_down(sb, off);
+      stt += __shfl_down(stt, off);
+    }
+    if (lane == 0) {
+      atomicAdd(&counters->boxes, b);
+      atomicAdd(&counters->tris, t);
+      atomicAdd(&counters->box_slots, sb);
+      atomicAdd(&counters->tri_slots, stt);
+    }
+  }
+}
+
 // The pickers: flags only, but for k_flat_refill, which reads WIDE, SPILL and HALF of a flavour -- of the six kTravFast* in
 // production; the 4-wide forms always have the spill path, and the other flavours have no form of their own.
 using QueryRefillKernel = void (*)(DevScene, QueryIo, uint32_t*, TraceCounters*, TraceLaunch);
@@ -776,6 +893,11 @@ AmbientRefillKernel pick_ambient(bool rot, bool sph, bool stats) {
 using ProbeRefillKernel = void (*)(DevScene, ProbeIo, uint32_t*, TraceCounters*, TraceLaunch);
 ProbeRefillKernel pick_probe(bool sph, bool stats) {
   return with_flags([](auto SPH, auto STATS) -> ProbeRefillKernel { return k_probe_refill<SPH, STATS>; }, sph, stats);
+}
+
+using DirectRefillKernel = void (*)(DevScene, DirectIo, uint32_t*, TraceCounters*, TraceLaunch);
+DirectRefillKernel pick_direct(bool sphere, bool sph, bool stats) {
+  return with_flags([](auto SPHERE, auto SPH, auto STATS) -> DirectRefillKernel { return k_direct_refill<SPHERE, SPH, STATS>; }, sphere, sph, stats);
 }
 
 using ShadowRefillKernel = void (*)(DevScene, FrameParams, const QueuedRay*, const uint32_t*, WfBuffers, PathBuffers, uint32_t, uint32_t*, TraceCounters*, TraceLaunch);
@@ -835,6 +957,15 @@ const void* probe_refill_kernel(bool sph, bool stats) {
 void launch_probe_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const ProbeIo& a, uint32_t* heads,
                          TraceCounters* counters, const TraceLaunch& tl) {
   hipLaunchKernelGGL(pick_probe(sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, a, heads, counters, tl);
+}
+
+const void* direct_refill_kernel(bool sphere, bool sph, bool stats) {
+  return reinterpret_cast<const void*>(pick_direct(sphere, sph, stats));
+}
+
+void launch_direct_refill(bool sphere, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const DirectIo& a, uint32_t* heads,
+                          TraceCounters* counters, const TraceLaunch& tl) {
+  hipLaunchKernelGGL(pick_direct(sphere, sph, stats), dim3(grid), dim3(kBlock), lds_bytes, stream, sc, a, heads, counters, tl);
 }
 
 const void* shadow_refill_kernel(bool gen0, bool sph, bool stats) {

@@ -39,6 +39,12 @@ const void* probe_refill_kernel(bool sph, bool stats);
 void launch_probe_refill(bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const ProbeIo& a, uint32_t* heads,
                          TraceCounters* counters, const TraceLaunch& tl);
 
+// the same for the shadow rays of rayca_hip_direct_device: made in registers from a point, its optional normal and a light's record,
+// one bit of the point's mask word per lit sample.  sphere: the call has no normals
+const void* direct_refill_kernel(bool sphere, bool sph, bool stats);
+void launch_direct_refill(bool sphere, bool sph, bool stats, uint32_t grid, size_t lds_bytes, hipStream_t stream, const DevScene& sc, const DirectIo& a, uint32_t* heads,
+                          TraceCounters* counters, const TraceLaunch& tl);
+
 // and for the shadow-ray pass of a generation (k_wf_shadow's work)
 struct ShadowRefillArgs {
   float4* sh_ray;

@@ -828,4 +828,41 @@ int32_t rayca_hip_scene_read_nodes(RaycaScene* s, uint32_t which, void* out, uin
   return RAYCA_OK;
 }
 
+// The light table as the kernels read it, back from the device: what scene_create uploaded or the last rayca_hip_scene_update wrote.
+// Every context is locked for the copy, as the update locks them, so that the table is never read half written.
+int32_t rayca_hip_scene_read_lights(RaycaScene* s, RaycaLightRecord* out, uint32_t capacity, uint32_t* count_out) {
+  if (!s) return fail(RAYCA_ERR_BAD_ARG, "null scene");
+  if (!out && !count_out) return fail(RAYCA_ERR_BAD_ARG, "neither out nor count_out: nothing to read the lights into");
+  const uint32_t n = s->dev.light_count;
+  if (count_out) *count_out = n;
+  if (!out) return RAYCA_OK;
+  if (capacity < n) return fail(RAYCA_ERR_BAD_ARG, "capacity too small");
+  if (n == 0) return RAYCA_OK;
+  std::vector<DevLight> table(n);
+  {
+    std::unique_lock<std::mutex> ctx_locks[kMaxContexts];
+    for (uint32_t c = 0; c < kMaxContexts; ++c) ctx_locks[c] = std::unique_lock<std::mutex>(s->ctx[c].mu);
+    HIP_TRY(hipSetDevice(s->device));
+    StagedCopier back;   // (through page-locked blocks, like every other copy of the library: staging.hpp)
+    HIP_TRY(back.copy_back(table.data(), s->dev.lights, sizeof(DevLight) * n, nullptr));
+    back.finish();
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    const DevLight& d = table[i];
+    RaycaLightRecord& r = out[i];
+    std::memset(&r, 0, sizeof r);
+    r.kind = d.kind;
+    r.material = d.material;
+    r.intensity = d.intensity;
+    r.area = d.area;
+    std::memcpy(r.color, d.color, 16);
+    std::memcpy(r.attenuation, d.attenuation, 16);
+    std::memcpy(r.position, d.position, 16);
+    std::memcpy(r.ab, d.ab, 16);
+    std::memcpy(r.ac, d.ac, 16);
+    std::memcpy(r.normal, d.normal, 16);
+  }
+  return RAYCA_OK;
+}
+
 }  // extern "C"

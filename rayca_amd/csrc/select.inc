@@ -146,6 +146,18 @@ ProbeFoldKernel pick_probe_fold(bool vis, bool normal, bool kept) {
   return with_flags([](auto VIS, auto NORMAL, auto KEPT) -> ProbeFoldKernel { return k_probe_fold<VIS, NORMAL, KEPT>; }, vis, normal, kept);
 }
 
+// k_direct_rays (direct.inc, rayca_hip_direct_device where k_direct_refill of refill.hip cannot run): as pick_ambient_kernel;
+// sphere: the call has no normals
+using DirectKernel = void (*)(DevScene, DirectIo, TraceCounters*, TraceLaunch);
+DirectKernel pick_direct_kernel(bool sphere, bool fast, bool sph, bool stats) {
+  return with_flags([](auto SPHERE, auto FAST, auto SPH, auto STATS) -> DirectKernel { return k_direct_rays<SPHERE, FAST, SPH, STATS>; }, sphere, fast, sph, stats);
+}
+// k_direct_fold: the call's mode, and whether it has sh_out (sphere mode only: the host refuses sh_out with normals)
+using DirectFoldKernel = void (*)(const DevLight*, DirectIo);
+DirectFoldKernel pick_direct_fold(bool sphere, bool sh) {
+  return with_flags([](auto SPHERE, auto SH) -> DirectFoldKernel { return k_direct_fold<SPHERE, SPHERE && SH>; }, sphere, sh);
+}
+
 // LDS part of the node stack: enough for the whole tree if that fits 24 entries (24 KiB per block),
 // else 24 entries + a global spill area for the rest
 #ifndef RAYCA_MAX_LDS_ENTRIES
@@ -559,11 +571,15 @@ int32_t selftest_kernel_selection(std::string& err) {
        [&](Trav, uint32_t i) { return b(i, 0) ? i : i & 3u; }},   // without sh_out no direction is made: rot is not read
       {"pick_probe_kernel(fast, sph, stats)", none, 3, [&](Trav, uint32_t i) { return P(pick_probe_kernel(b(i, 0), b(i, 1), b(i, 2))); }, every},
       {"pick_probe_fold(vis, normal, kept)", none, 3, [&](Trav, uint32_t i) { return P(pick_probe_fold(b(i, 0), b(i, 1), b(i, 2))); }, every},
+      {"pick_direct_kernel(sphere, fast, sph, stats)", none, 4, [&](Trav, uint32_t i) { return P(pick_direct_kernel(b(i, 0), b(i, 1), b(i, 2), b(i, 3))); }, every},
+      {"pick_direct_fold(sphere, sh)", none, 2, [&](Trav, uint32_t i) { return P(pick_direct_fold(b(i, 0), b(i, 1))); },
+       [&](Trav, uint32_t i) { return b(i, 0) ? i : 0u; }},   // with normals there is no sh_out: sh is not read
       {"flat_refill_kernel(trav; sph, stats)", fast, 2, [&](Trav t, uint32_t i) { return flat_refill_kernel(RefillFlavour{t, b(i, 0), b(i, 1)}); }, every},
       {"queue_refill_kernel(sph, stats, slack)", none, 3, [&](Trav, uint32_t i) { return queue_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"query_refill_kernel(occluded, sph, stats)", none, 3, [&](Trav, uint32_t i) { return query_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"ambient_refill_kernel(rot, sph, stats)", none, 3, [&](Trav, uint32_t i) { return ambient_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"probe_refill_kernel(sph, stats)", none, 2, [&](Trav, uint32_t i) { return probe_refill_kernel(b(i, 0), b(i, 1)); }, every},
+      {"direct_refill_kernel(sphere, sph, stats)", none, 3, [&](Trav, uint32_t i) { return direct_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
       {"shadow_refill_kernel(gen0, sph, stats)", none, 3, [&](Trav, uint32_t i) { return shadow_refill_kernel(b(i, 0), b(i, 1), b(i, 2)); }, every},
   };
   for (const PickerFamily& f : families)

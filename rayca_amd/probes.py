@@ -42,10 +42,13 @@ class ProbeGrid:
         step = (i * self.cell).astype(np.float32)
         return (self.origin + step).astype(np.float32)
 
-    def bake(self, ds, config, samples=64, sample=0, *, stream=None, context=0):
+    def bake(self, ds, config, samples=64, sample=0, *, stream=None, context=0, direct=False):
         """(sh (M, 9, 4) float32, kept (M,) int32) on ds's device: DeviceScene.gather at the probes' centres with the normal
         (0, 0, 1), sphere_directions(samples) and weights of 4 pi -- the projections of the incoming radiance onto the nine basis
-        functions, which the lookup takes as they are.  A probe none of whose samples is finite has kept 0."""
+        functions, which the lookup takes as they are.  A probe none of whose samples is finite has kept 0.
+        direct: add the light that reaches the centres straight from the scene's lights -- DeviceScene.direct without normals,
+        its "sh", in the same units -- which no gather ray can find for a point light: sh = gather's sh + direct's sh, one
+        torch addition on the same stream.  kept stays gather's."""
         import torch
         dev = torch.device("cuda", ds.device)
         p = torch.from_numpy(self.positions()).to(dev)
@@ -54,4 +57,8 @@ class ProbeGrid:
         dirs = torch.from_numpy(sphere_directions(samples)).to(dev)
         weights = torch.full((samples,), float(np.float32(4.0 * np.pi)), dtype=torch.float32, device=dev)
         r = ds.gather(p, n, config, samples=samples, dirs=dirs, weights=weights, sample=sample, outputs=("sh", "kept"), stream=stream, context=context)
-        return r["sh"], r["kept"]
+        if not direct:
+            return r["sh"], r["kept"]
+        d = ds.direct(p, None, config, sample=sample, want=("sh",), stream=stream, context=context)
+        with torch.cuda.stream(ds.torch_stream(stream)):
+            return r["sh"] + d["sh"], r["kept"]

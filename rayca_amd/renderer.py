@@ -941,6 +941,134 @@ class DeviceScene:
                               base=base.reshape(-1, 4) if base is not None else None, outputs=("radiance",), stream=stream, context=context)
         return r["radiance"].reshape(height, width, 4)
 
+    # ---- direct light at points: the NEE sum of a path vertex without the BRDF (rayca_hip_direct_device) ----
+    DIRECT_OUTPUTS = {"irradiance": ("float32", lambda n: (n, 4)), "sh": ("float32", lambda n: (n, 9, 4)), "mask": ("int64", lambda n: (n,)),
+                      "counts": ("int32", lambda n: (n,))}
+
+    def lights(self) -> np.ndarray:
+        """rayca_hip_scene_read_lights: the scene's light records as the kernels read them (after update(): the updated ones), a
+        structured array with the fields of abi.RaycaLightRecord: kind, material, intensity, area, color, attenuation, position
+        (the translation of the light node's LOCAL transform), ab, ac, normal."""
+        n = C.c_uint32(0)
+        lib.check(self._lib.rayca_hip_scene_read_lights(self.handle, None, 0, C.byref(n)))
+        out = (abi.RaycaLightRecord * max(n.value, 1))()
+        if n.value:
+            lib.check(self._lib.rayca_hip_scene_read_lights(self.handle, out, n.value, None))
+        return np.ctypeslib.as_array(out)[:n.value].copy()
+
+    def torch_stream(self, stream=None):
+        """the torch stream object a device call with this `stream` argument runs on (for torch work queued behind it)"""
+        return _DeviceCall(self, stream).torch_stream()
+
+    def direct(self, points, normals, config: Config, *, light_first=0, light_count=None, sample=0, first_index=0, bias=0.0,
+               want=("irradiance",), out=None, stream=None, context=0, want_stats=False, collect_stats=False):
+        """rayca_hip_direct_device: the light that arrives at points in device memory straight from the scene's point and quad
+        lights -- the next-event-estimation sum of a path vertex with the BRDF taken out -- asynchronously.
+
+        points: (N, 3) float32.  normals: (N, 3) float32 -- hemisphere mode: the cosine-weighted irradiance E at a surface point
+        (a Lambert surface radiates albedo * E / pi), rays from point + normal * bias (bias = 1e-4 reproduces a path vertex), a
+        zero normal or a value that is not finite marks an inactive point -- or None -- sphere mode: the incident radiance times
+        solid angle, no cosine, bias must be 0, and "sh" is available: its SH9 projection, in the units of gather()'s "sh" under
+        sphere_directions with weights of 4 pi, so the two add.  config: its light_samples, light_stratify and seed are read.
+        Lights light_first .. light_first + light_count (None: to the scene's last).  Point i draws a quad light's points from
+        the stream of "pixel" first_index + i of a radiance() call with the same `sample`.
+        Returns a dict with one tensor per name in `want`: "irradiance" (N, 4) float32 (r, g, b, the lit fraction of the samples),
+        "sh" (N, 9, 4) float32, "mask" (N, C) int64 (one word per chunk of lights, C = 1 unless the range needs more than 64
+        samples; bit j of a word = sample j of that chunk was traced and lit), "counts"
+        (N,) int32 (lit samples in the low 16 bits, dropped ones -- a component that is not finite -- in the high 16).
+        One native call serves at most 64 samples (lights x light_samples).  A longer range is cut into chunks of whole lights;
+        irradiance, sh and counts are summed on the device, chunk by chunk, and "mask" holds one word per chunk.  Across chunk
+        borders that sum is not the single fold in sample order: equal to rounding, not to the bit.  `out`: a dict of tensors to
+        write instead of new ones.  Stream handling as query(); `want_stats` / `collect_stats` wait and add "stats" (summed)."""
+        call = _DeviceCall(self, stream)
+        torch = call.torch
+        want = tuple(want)
+        unknown = [w for w in want if w not in self.DIRECT_OUTPUTS]
+        if unknown or not want or len(set(want)) != len(want):
+            raise ValueError(f"want: a non-empty selection without repeats of {tuple(self.DIRECT_OUTPUTS)}, not {want!r}")
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"points: a torch tensor on {call.dev} is expected, not {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"points: shape {tuple(points.shape)}, expected (N, 3)")
+        n = points.shape[0]
+        if "sh" in want and normals is not None:
+            raise ValueError('want: "sh" is a sphere-mode output (normals=None)')
+        if first_index < 0 or first_index + n > 1 << 32:
+            raise ValueError("first_index + points must stay within 2**32")
+        ls = int(config.light_samples)
+        if not 1 <= ls <= 64:
+            raise ValueError(f"config.light_samples: {ls}, expected 1..64")
+        total = self.info()["light_count"]
+        if light_count is None:
+            light_count = total - light_first
+        if light_first < 0 or light_count < 1 or light_first + light_count > total:
+            raise ValueError(f"lights {light_first} .. {light_first + light_count}: the scene has {total}")
+        per = 64 // ls
+        chunks = [(a, min(per, light_first + light_count - a)) for a in range(light_first, light_first + light_count, per)]
+        out = dict(out) if out is not None else {}
+        stray = [k for k in out if k not in want]
+        if stray:
+            raise ValueError(f"out: {stray} not in want")
+        result = {}
+        for name in want:
+            dtype, shape = self.DIRECT_OUTPUTS[name]
+            shp = (n, len(chunks)) if name == "mask" else shape(n)
+            result[name] = call.output(out.get(name), f"out[{name!r}]", getattr(torch, dtype), shp)
+        p = call.input(points, "points", torch.float32, (n, 3))
+        nrm = call.input(normals, "normals", torch.float32, (n, 3)) if normals is not None else None
+        cfg = config.to_abi()
+        fn = self._lib.rayca_hip_direct_device
+        stats = None
+        if n == 0:
+            if context >= 8:
+                raise lib.RaycaError(abi.ERR_BAD_ARG, "context out of range")
+            if want_stats or collect_stats:
+                stats = abi.RaycaStats().as_dict()
+        for c, (first, cnt) in enumerate(chunks if n else ()):
+            d = abi.RaycaDirect()
+            d.count, d.light_first, d.light_count, d.sample, d.first_index, d.bias = n, first, cnt, sample, first_index, float(bias)
+            d.points, d.normals = p.data_ptr(), nrm.data_ptr() if nrm is not None else None
+            part = {}
+            for name in want:
+                if name == "mask":
+                    part[name] = result[name][:, 0] if len(chunks) == 1 else torch.empty((n,), dtype=torch.int64, device=call.dev)
+                elif c == 0:
+                    part[name] = result[name]
+                else:
+                    part[name] = torch.empty_like(result[name])
+                setattr(d, name + "_out", part[name].data_ptr() or None)
+            st = call.run(lambda handle, o, args, s_: fn(handle, C.byref(cfg), o, args, s_), d, context=context,
+                          want_stats=want_stats or collect_stats, collect_stats=collect_stats)
+            if st is not None:
+                if stats is None:
+                    stats = st
+                else:
+                    for k, v in st.items():
+                        if isinstance(v, (int, float)) and k != "node_format":
+                            stats[k] += v
+                        elif isinstance(v, list):
+                            stats[k] = [a + b for a, b in zip(stats[k], v)]
+            if len(chunks) > 1:
+                with torch.cuda.stream(call.torch_stream()):
+                    for name in want:
+                        if name == "mask":
+                            result[name][:, c] = part[name]
+                        elif c > 0 and name == "irradiance":   # (the lit fractions are re-weighted by their sample counts below)
+                            result[name][:, :3] += part[name][:, :3]
+                            result[name][:, 3] += part[name][:, 3] * float(cnt * ls)
+                        elif c > 0:
+                            result[name] += part[name]
+                        elif name == "irradiance":
+                            result[name][:, 3] *= float(cnt * ls)
+                    for x in part.values():
+                        x.record_stream(call.torch_stream())
+        if n and len(chunks) > 1 and "irradiance" in want:
+            with torch.cuda.stream(call.torch_stream()):
+                result["irradiance"][:, 3] /= float(light_count * ls)
+        if stats is not None:
+            result["stats"] = stats
+        return result
+
     # ---- the denoiser: an edge-avoiding a-trous filter on a frame and its G-buffer (rayca_hip_denoise_device) ----
     def denoise(self, color, *, albedo=None, normal=None, point=None, id=None, iterations=5, sigma_color=4.0, sigma_plane=None,
                 normal_power_log2=7, gamma=1.0, out=None, rgba8=False, stream=None, context=0, want_stats=False):
@@ -1408,6 +1536,10 @@ class _DeviceCall:
 
     def options(self, context, traversal=0, collect_stats=False, tile=None):
         return self.scene._opts(traversal, collect_stats, tile, self.handle or None, context=context)
+
+    def torch_stream(self):
+        """the call's stream as a torch stream object: for torch work that is to run behind the call"""
+        return self.stream if hasattr(self.stream, "cuda_stream") else self.torch.cuda.ExternalStream(self.handle, device=self.dev)
 
     def run(self, fn, args, *, context, want_stats=False, **options):
         """fn(scene, options, args, stats) through lib.check; returns the stats dict (the call has waited) or None"""
